@@ -2,12 +2,22 @@
 """bench.py — MCMF solve latency and arcs/s on Quincy-shaped cell graphs.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload full|incremental|batch]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line
+(metric, value, unit, ms_per_step, per-step latencies). ``--full`` adds what the
+headline figure does not need: the CPU baseline legs, the parity checks (golden,
+CPU oracles, the solves against each other; a mismatch exits 3), the roofline
+figures, the last solve's counters and, for N > 1 and the batch workload, the
+post-solve gather of the mappings. ``--dump-outputs DIR`` writes what the last
+timed step returned to its caller as DIR/<name>.npy (float64): cost, flow and the
+tasks placed per PU (dump_outputs below).
 
 * ``full`` (default, the headline line): config 3 (100k tasks × 10k machines),
   one full device re-solve per step. N > 1 runs under torch.distributed (one
   rank per GPU, RCCL): every rank solves its own independent cell graph
-  (seed + rank), the north star's sharding of independent graphs; the task→PU
-  mappings are gathered over RCCL after the timed region.
+  (seed + rank), the north star's sharding of independent graphs; with ``--full``
+  the task→PU mappings are gathered over RCCL after the timed region.
   ``value`` = Σ arcs over ranks ÷ max-rank time.
 * ``incremental``: config 4 — the config-3 cell under churn (5% completions +
   5% arrivals per round, pins, ageing, capacity refresh); a step is one round:
@@ -16,7 +26,7 @@
   round-robin over the ranks; each GPU solves its share as ONE device solve of
   their disjoint union (``--batch-mode union``, default) or as concurrent
   contexts (``--batch-mode streams``, ks_solve_many); a step solves every graph
-  once. Mappings are gathered over RCCL afterwards.
+  once. With ``--full`` the mappings are gathered over RCCL afterwards.
 
 Inputs are resident in HBM before timing (the first, untimed solve uploads).
 """
@@ -297,6 +307,31 @@ def full_opts(args) -> dict:
     return dict(opts_of(args), warm_start=0)
 
 
+def pu_load(pu_ids, M: int, R: int):
+    """Tasks placed on each machine's PU (PU node ids are 3 + R + M + k, gen.quincy;
+    0 = unscheduled), from a task→PU vector."""
+    pu = np.asarray(pu_ids).astype(np.int64)
+    return np.bincount(pu[pu > 0] - (3 + R + M), minlength=M)
+
+
+def dump_outputs(args, D, **arrays):
+    """--dump-outputs DIR: what the last timed step handed its caller, one float64
+    DIR/<name>.npy per array (rank r > 0 of an N > 1 run writes <name>.rank<r>.npy).
+    The counts, costs and flows are integers far below 2**53, so float64 holds them exactly.
+
+    A minimum-cost flow is not unique and the solver's race order picks among the
+    optimal ones, so the same build returns a different task→PU vector from run
+    to run (about one task in eight on config 3). The dump therefore holds what
+    two runs on the same input agree on: the solve's cost and flow, and the
+    mapping reduced to the number of tasks it places on each PU (pu_load)."""
+    if not args.dump_outputs:
+        return
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    sfx = f".rank{D.rank}" if D.rank else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(args.dump_outputs, f"{name}{sfx}.npy"), np.asarray(a).astype(np.float64))
+
+
 def base_line(args, D, value, ms_per_step, config, **extra):
     line = {"metric": METRIC, "value": round(value, 1), "unit": "arcs/s", "n_gpus": D.world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
@@ -335,6 +370,18 @@ def run_full(args, D):
     elapsed = D.max(time.perf_counter() - t0)
     ms_per_step = 1e3 * elapsed / max(1, args.steps)
     value = D.world * g.m / (ms_per_step / 1e3)
+    if results:
+        pu = dev_map.cpu().numpy() if dev_map is not None else ctx.task_mapping_arrays()[1]
+        dump_outputs(args, D, cost=[results[-1].cost], flow=[results[-1].flow], pu_load=pu_load(pu, M, R))
+    config = {"workload": f"{args.config}: Quincy-shaped cell graph T={T} M={M} R={R} J={J} "
+                          f"(n={g.n}, m={g.m}), step = full device re-solve + device task->PU extraction "
+                          f"(Solve() -> TaskMapping), one graph per GPU",
+              "tasks": T, "machines": M, "racks": R, "jobs": J, "seed": seed, "n": g.n, "m": g.m,
+              "parallelism": f"independent graphs x{D.world}"}
+    if not args.full:
+        ctx.close()
+        return base_line(args, D, value, ms_per_step, config, step_ms=[round(x, 2) for x in step_ms],
+                         latency=latency_stats(step_ms))
 
     gather = None
     if D.dist:       # RCCL gather of the task→PU mappings (int64 PU id per task, 0 = unscheduled)
@@ -379,11 +426,6 @@ def run_full(args, D):
     parity["match"] = not problems
     if problems:
         parity["problems"] = problems
-    config = {"workload": f"{args.config}: Quincy-shaped cell graph T={T} M={M} R={R} J={J} "
-                          f"(n={g.n}, m={g.m}), step = full device re-solve + device task->PU extraction "
-                          f"(Solve() -> TaskMapping), one graph per GPU",
-              "tasks": T, "machines": M, "racks": R, "jobs": J, "seed": seed, "n": g.n, "m": g.m,
-              "parallelism": f"independent graphs x{D.world}"}
     line = base_line(args, D, value, ms_per_step, config, step_ms=[round(x, 2) for x in step_ms],
                      roofline=roofline_of(results, args.config), cpu_baseline=cpu, parity=parity, gather=gather,
                      latency=latency_stats(step_ms), solve=dict(results[-1].raw))
@@ -414,7 +456,7 @@ def run_incremental(args, D):
     rounds, results = [], []
     t_total = 0.0
     problems = []
-    cpu_on = D.rank == 0 and D.world == 1 and args.cpu_baseline == "auto"
+    cpu_on = args.full and D.rank == 0 and D.world == 1 and args.cpu_baseline == "auto"
     inc = cold_ms = inc_ms = None
     if cpu_on:
         from oracle import ko
@@ -438,7 +480,6 @@ def run_incremental(args, D):
         te = time.perf_counter()
         D.sync()
         dt = D.max(time.perf_counter() - ts)
-        sst = ctx.store_stats()
         rec = {"round": i + 1, "timed": i >= args.warmup, "deltas": int(d.shape[0]), "ms": round(1e3 * dt, 3),
                "apply_ms": round(1e3 * (ta - ts), 3), "solve_ms": round(1e3 * (tb - ta), 3),
                "mapping_ms": round(1e3 * (te - tb), 3), "cost": r.cost, "flow": r.flow,
@@ -447,10 +488,13 @@ def run_incremental(args, D):
                "recoveries": r.raw["recoveries"],
                "solve_parts_ms": {k: round(v, 2) for k, v in r.raw["ms"].items()},
                "m": r.raw["n_arcs"], "running": int((cell.state == cell.RUN).sum()),
-               "rebuilt": r.raw["rebuilt"], "rebuilds_since_load": sst["rebuilds"],
-               "store": {k: sst[k] for k in ("inserted", "updated", "killed", "superseded")}}
-        if r.flow != cell.graph().supply[cell.graph().supply > 0].sum():
-            problems.append(f"round {i + 1}: flow {r.flow} short of the supply")
+               "rebuilt": r.raw["rebuilt"]}
+        if args.full:
+            sst = ctx.store_stats()
+            rec["rebuilds_since_load"] = sst["rebuilds"]
+            rec["store"] = {k: sst[k] for k in ("inserted", "updated", "killed", "superseded")}
+            if r.flow != cell.graph().supply[cell.graph().supply > 0].sum():
+                problems.append(f"round {i + 1}: flow {r.flow} short of the supply")
         if cpu_on:
             g = cell.graph()
             t0 = time.perf_counter()
@@ -476,6 +520,8 @@ def run_incremental(args, D):
     m_avg = sum(r.raw["n_arcs"] for r in results) / max(1, len(results))
     value = D.world * m_avg / (ms_per_step / 1e3)
     timed = [x for x in rounds if x["timed"]]
+    if results:   # every round builds on the mapping before it, so only the first rounds repeat run to run
+        dump_outputs(args, D, cost=[results[-1].cost], flow=[results[-1].flow], pu_load=pu_load(mp[1], M, R))
     parity = {"rounds_checked": len(rounds) if cpu_on else 0, "flows_checked": len(rounds),
               "match": not problems, "last_round_gpu_cost": rounds[-1]["cost"]}
     if problems:
@@ -514,6 +560,9 @@ def run_incremental(args, D):
               "round_ms": {"median": round(float(np.median([x["ms"] for x in timed])), 3),
                            "max": round(max(x["ms"] for x in timed), 3)},
               "parallelism": f"independent cells x{D.world}"}
+    if not args.full:
+        ctx.close()
+        return base_line(args, D, value, ms_per_step, config, latency=latency_stats([x["ms"] for x in timed]))
     line = base_line(args, D, value, ms_per_step, config, rounds=rounds, roofline=roofline_of(results, "config4"),
                      latency=latency_stats([x["ms"] for x in timed]),
                      cpu_baseline=cpu, parity=parity)
@@ -568,6 +617,24 @@ def run_batch(args, D):
     ms_per_step = 1e3 * elapsed / max(1, args.steps)
     arcs_all = num * gen.quincy_sizes(T, M, R, J)[1]
     value = arcs_all / (ms_per_step / 1e3)
+    if results:
+        last = results[-(len(results) // args.steps):]     # one result per device solve of the last step
+        dump_outputs(args, D, cost=[r.cost for r in last], flow=[r.flow for r in last])
+    mode = {"abi": "C-ABI batch (union per device, RCCL gather inside libksmcmf)",
+            "union": "one device solve of their disjoint union",
+            "streams": f"one context each, solved concurrently ({args.workers} workers/GPU)"}[args.batch_mode]
+    config = {"workload": f"config5: {num} independent config-2 graphs (T={T} M={M}, seeds 1000..{999 + num}) "
+                          f"round-robin over {D.world} GPU(s), {mode}; step = every graph solved once",
+              "graphs": num, "tasks": T, "machines": M, "graphs_per_gpu": len(mine), "mode": args.batch_mode,
+              "parallelism": f"graph sharding x{D.world}"}
+    if not args.full:
+        if args.batch_mode == "abi":
+            bt.close()
+        else:
+            for c in ctxs:
+                c.close()
+        return base_line(args, D, value, ms_per_step, config, step_ms=[round(x, 2) for x in step_ms],
+                         scaling="strong", latency=latency_stats(step_ms))
 
     # after the timed region: per-graph cost/flow and task→PU rows gathered to rank 0
     gather = None
@@ -644,13 +711,6 @@ def run_batch(args, D):
                                                                    zip(outs, per_graph, outs_s)))})
         if not parity["match"]:
             parity["problems"] = ["a graph's GPU cost differs from the CPU reference path"]
-    mode = {"abi": "C-ABI batch (union per device, RCCL gather inside libksmcmf)",
-            "union": "one device solve of their disjoint union",
-            "streams": f"one context each, solved concurrently ({args.workers} workers/GPU)"}[args.batch_mode]
-    config = {"workload": f"config5: {num} independent config-2 graphs (T={T} M={M}, seeds 1000..{999 + num}) "
-                          f"round-robin over {D.world} GPU(s), {mode}; step = every graph solved once",
-              "graphs": num, "tasks": T, "machines": M, "graphs_per_gpu": len(mine), "mode": args.batch_mode,
-              "parallelism": f"graph sharding x{D.world}"}
     line = base_line(args, D, value, ms_per_step, config, step_ms=[round(x, 2) for x in step_ms],
                      scaling="strong",   # a fixed 64 graphs shared by the ranks
                      roofline=roofline_of(results, "config5"), cpu_baseline=cpu, gather=gather, parity=parity,
@@ -680,7 +740,12 @@ def main():
     ap.add_argument("--batch-mode", default="abi", choices=["abi", "union", "streams"])
     ap.add_argument("--warm", type=int, default=None,
                     help="incremental workload: ks_opts.warm_start of the re-solves (default: the library's)")
-    ap.add_argument("--cpu-baseline", default="auto", choices=["auto", "off"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baselines, parity checks, roofline figures and the post-solve gather")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (cost, flow, tasks per PU) as DIR/<name>.npy")
+    ap.add_argument("--cpu-baseline", default="auto", choices=["auto", "off"],
+                    help="with --full: run the CPU baseline legs (auto) or leave them out (off)")
     ap.add_argument("--cpu-reps", type=int, default=5, help="CPU baseline: median of this many after 1 warm-up")
     ap.add_argument("--alpha", type=int, default=0)
     ap.add_argument("--gu-interval", type=int, default=0)

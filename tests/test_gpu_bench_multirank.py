@@ -26,7 +26,7 @@ def test_two_rank_bench_line(workload):
     env = dict(os.environ, KS_BENCH_REHEARSAL="1", OMP_NUM_THREADS="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr=127.0.0.1", f"--master-port={_port()}", os.path.join(ROOT, "bench.py"), "--gpus", "2",
-           "--workload", workload, "--steps", "1", "--warmup", "0", "--config", "config2", "--graphs", "4"]
+           "--full", "--workload", workload, "--steps", "1", "--warmup", "0", "--config", "config2", "--graphs", "4"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=110, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

@@ -17,7 +17,7 @@ for r in $(seq 1 "$ROUNDS"); do
         elif [ "$v" = default ]; then envs=""; lib=""
         else envs=""; lib="KS_LIB_VARIANT=$v"
         fi
-        timeout -k 10 120 env $envs $lib python -u bench.py --steps 10 --warmup 2 --cpu-baseline off ${AB_ARGS} \
+        timeout -k 10 120 env $envs $lib python -u bench.py --full --steps 10 --warmup 2 --cpu-baseline off ${AB_ARGS} \
             > "$OUT/$name.$r.json" 2> "$OUT/$name.$r.err" \
             || { echo "bench $v failed"; tail -20 "$OUT/$name.$r.err"; exit 1; }
         python - "$OUT/$name.$r.json" "$v" "$r" <<'PY'

@@ -21,7 +21,7 @@ PASSES=${3:-all}
 run_pass() {   # name, bench args, rocprofv3 args...
     local name=$1 bargs=$2; shift 2
     timeout -s KILL 150 rocprofv3 "$@" -f csv -d "$OUT/$name" -o run -- \
-        python -u bench.py $bargs --cpu-baseline off > "$OUT/$name.json" 2> "$OUT/$name.err" \
+        python -u bench.py --full $bargs --cpu-baseline off >"$OUT/$name.json" 2> "$OUT/$name.err" \
         || { echo "pass $name failed"; tail -20 "$OUT/$name.err"; exit 1; }
 }
 if [ "$PASSES" = all ]; then

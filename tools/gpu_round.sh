@@ -24,7 +24,7 @@ if [ "$WHAT" = suite ] || [ "$WHAT" = all ]; then
 fi
 bench() {   # name, bench args...
     local name=$1; shift
-    timeout -k 10 600 python -u bench.py "$@" > "$OUT/bench_$name.json" 2> "$OUT/bench_$name.err" \
+    timeout -k 10 600 python -u bench.py --full "$@" >"$OUT/bench_$name.json" 2> "$OUT/bench_$name.err" \
         || { echo "bench $name failed"; tail -20 "$OUT/bench_$name.err"; exit 1; }
     python - "$OUT/bench_$name.json" "$name" <<'PY'
 import json, sys
