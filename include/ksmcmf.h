@@ -26,6 +26,9 @@
  *   ks_get_task_mapping      parseFlowToMapping + addPUToSourceNodes
  *                            (placement/solver.go:183-269) → flowmanager.TaskMapping
  *                            (flowmanager/types.go:6)
+ *   ks_commit_schedule       TaskScheduled → pinTaskToNode and capacityFromResNodeToParent
+ *                            (flowmanager/graph_manager.go:454-460, 675-720, 662-667) and the
+ *                            change records they would log, generated and applied on device
  *   ks_last_error            the panics of solver.go:97-108, 148-153, 175-178, 223-225
  *                            become status codes + a message
  *
@@ -425,6 +428,59 @@ int ks_update_unsched_costs(ks_ctx* ctx, const uint64_t* unsched_ids, size_t k, 
 int ks_topology_stats(ks_ctx* ctx, uint64_t max_tasks_per_pu, const uint64_t* pu_ids,
                       const uint64_t* pu_running, size_t k, uint64_t* slots_below,
                       uint64_t* running_below, size_t cap, size_t* count);
+
+#define KS_COMMIT_RESOURCE_CAPS 1   /* also refresh resource-arc capacities (below) */
+
+typedef struct ks_commit_stats {
+    int64_t placed;            /* PLACE deltas pinned                                  */
+    int64_t arcs_removed;      /* task out-arcs deleted                                */
+    int64_t running_added;     /* new task→PU running arcs                             */
+    int64_t running_converted; /* existing task→PU arcs turned into running arcs       */
+    int64_t unsched_updates;   /* aggregator→sink arcs whose capacity changed          */
+    int64_t cap_updates;       /* resource arcs whose capacity changed                 */
+    int64_t records;           /* delta records generated on device and applied        */
+    int64_t reserved[5];
+} ks_commit_stats;
+
+/* The graph edit that follows applySchedulingDeltas with Preemption == false, on device:
+ * TaskScheduled → updateArcsForScheduledTask → pinTaskToNode (graph_manager.go:454-460,
+ * 855-859, 675-720), updateUnscheduledAggNode(−1) (:706, :1291-1305) and, with
+ * KS_COMMIT_RESOURCE_CAPS, capacityFromResNodeToParent (:662-667) after a
+ * ComputeTopologyStatistics pass. The records a host would export for it (about six
+ * per placed task) are generated in device memory and applied as ONE stream with the
+ * semantics of ks_apply_deltas (all or nothing, in place, store counters, warm-start
+ * bookkeeping; no (src, dst) twice, so superseded is 0); nothing but the deltas
+ * crosses PCIe.
+ *   - The deltas are those of ks_scheduling_deltas, written to out. out == NULL:
+ *     *count only, nothing changes; cap < count: KS_E_INVALID, nothing changes.
+ *   - Any PREEMPT or MIGRATE delta: KS_E_INVALID, nothing changes (pinned tasks carry
+ *     low = 1 and never move; an evicted task's arcs come from the host's cost model).
+ *   - Per PLACE t → p: every out-arc of t whose head is not p is deleted; the arc
+ *     t → p becomes (or is added as) the running arc — type 1, low 1, cap 1, cost
+ *     continuation_cost; t is bound to p.
+ *   - Each unscheduled aggregator (unsched_ids, k of them; NULL: every type-0 node
+ *     with an arc into the sink, as ks_update_unsched_costs) loses, on its arc into
+ *     the sink, one unit of capacity per task pinned by this call that had an arc
+ *     into it. Capacity 0 removes the arc.
+ *   - KS_COMMIT_RESOURCE_CAPS: the BFS and sums of ks_topology_stats, a PU's slots
+ *     being the capacity of its arc into the sink and its running count the running
+ *     arcs (type 1) into it, this call's included; every arc u → v with u not a task,
+ *     v not the sink and v a PU, machine, intermediate node or a type-0 node with
+ *     slots_below[v] > 0 is set to slots_below[v] − running_below[v] (0 removes it;
+ *     only changed arcs get a record). Type-0 heads count as resources exactly as
+ *     ks_topology_stats counts them (the coordinator, an equivalence class above
+ *     machines): a cost model with arcs between equivalence classes leaves the
+ *     flag off and sends those capacities itself.
+ *   - A capacity that would fall below its arc's lower bound: KS_E_VERIFY, nothing
+ *     changes.
+ * Requires a successful solve on the context (KS_E_INVALID otherwise) and, on
+ * success, invalidates it as ks_apply_deltas does: fetch the mapping or the flows
+ * before committing. A device failure leaves the store unusable until the next
+ * ks_load_graph, as for ks_apply_deltas. stats may be NULL. */
+int ks_commit_schedule(ks_ctx* ctx, int32_t flags, int64_t continuation_cost,
+                       const uint64_t* unsched_ids, size_t k,
+                       ks_sched_delta* out, size_t cap, size_t* count,
+                       ks_commit_stats* stats /* may be NULL */);
 
 /* ---- config 5: independent graphs sharded over GPUs (SURVEY §7 step 6, §8 row e) --
  * No reference counterpart (ksched solves one graph per round,

@@ -85,6 +85,11 @@ public:
                       std::string& err);
     int topology_stats(uint64_t mtpp, const uint64_t* pu_ids, const uint64_t* pu_running, size_t k, int64_t sink_slot,
                        uint64_t* slots_below, uint64_t* running_below, std::string& err);
+    // ks_commit_schedule: *out receives the deltas (cap: the caller's room for them);
+    // sink_slot < 0: no single sink. *dirty: device state was touched before a failure.
+    int commit_schedule(int flags, int64_t ccost, const uint64_t* ids, size_t k, int64_t sink_slot, int64_t n_tasks,
+                        size_t cap, std::vector<ks_sched_delta>* out, size_t* count, ks_commit_stats* stats,
+                        bool* dirty, std::string& err);
     int device() const;
 
 private:

@@ -652,6 +652,41 @@ int ks_topology_stats(ks_ctx* c, uint64_t max_tasks_per_pu, const uint64_t* pu_i
     return rc;
 }
 
+int ks_commit_schedule(ks_ctx* c, int32_t flags, int64_t continuation_cost, const uint64_t* ids, size_t k,
+                       ks_sched_delta* out, size_t cap, size_t* count, ks_commit_stats* stats) {
+    if (!c || !count) return KS_E_INVALID;
+    if (int g = store_guard(c)) return g;
+    if (!c->have_solution) return c->fail(KS_E_INVALID, "no successful solve on this context");
+    if (flags & ~KS_COMMIT_RESOURCE_CAPS) return c->fail(KS_E_INVALID, "unknown commit flag");
+    const int64_t lim = int64_t(1) << 40;
+    if (continuation_cost > lim || continuation_cost < -lim)
+        return c->fail(KS_E_RANGE, "cost outside the supported range");
+    for (size_t i = 0; ids && i < k; ++i)
+        if (!node_alive(c, ids[i])) return c->fail(KS_E_INVALID, "unscheduled aggregator " + std::to_string(ids[i]) +
+                                                                     " is not a live node");
+    if (!out) {   // count only
+        size_t n = 0;
+        const int rc = c->eng.sched_deltas(0, nullptr, &n, c->n_tasks, c->err);
+        *count = n;
+        return rc;
+    }
+    const int64_t sink = c->n_sinks == 1 ? (int64_t)c->sink_id - 1 : -1;
+    std::vector<ks_sched_delta> v;
+    bool dirty = false;
+    const int rc = c->eng.commit_schedule(flags, continuation_cost, ids, ids ? k : 0, sink, c->n_tasks, cap, &v, count,
+                                          stats, &dirty, c->err);
+    if (rc) {
+        if (dirty) c->store_bad = true;   // the stream may be half applied: reload first
+        return rc;
+    }
+    if (!v.empty()) std::memcpy(out, v.data(), v.size() * sizeof(ks_sched_delta));
+    *count = v.size();
+    c->have_solution = false;   // as after ks_apply_deltas
+    c->map_fresh = false;
+    c->flows_fresh = false;
+    return KS_OK;
+}
+
 int ks_get_graph(ks_ctx* c, ks_node* nodes, size_t ncap, size_t* n, ks_arc* arcs, size_t acap, size_t* m) {
     if (!c || !n || !m) return KS_E_INVALID;
     if (int g = store_guard(c)) return g;

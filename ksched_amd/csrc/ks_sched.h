@@ -25,9 +25,12 @@ struct SchedDev {
     const unsigned char* a_type;
     const int* a_src;
     const int* a_dst;
+    const long long* a_low;
+    const long long* a_cap;
     long long* a_cost;
     const int* fwd;
     const int* first;              // residual CSR (internal ids)
+    const int* used;               // positions handed out in each segment
     Pos* pos;                      // residual positions (ks_pos.h)
     const int* ent;
     long long mult;
@@ -41,10 +44,71 @@ hipError_t sched_delta_emit(const SchedDev& d, const int* rank, const unsigned l
                             int commit, hipStream_t st);
 hipError_t sched_running_counts(const SchedDev& d, const unsigned long long* ids, const unsigned long long* vals,
                                 int k, unsigned long long* cnt, hipStream_t st);
+// pu_slots: per node slot, the slots of a PU (ks_commit_schedule: the capacity of its
+// arc into the sink); nullptr: every PU has mtpp slots (ks_topology_stats).
 hipError_t sched_topo_level(const SchedDev& d, const int* front, int nfront, int level, int* lvl, int* next,
-                            int* nnext, unsigned long long mtpp, const unsigned long long* pu_running,
-                            unsigned long long* slots, unsigned long long* running, hipStream_t st);
+                            int* nnext, unsigned long long mtpp, const unsigned long long* pu_slots,
+                            const unsigned long long* pu_running, unsigned long long* slots,
+                            unsigned long long* running, hipStream_t st);
 hipError_t sched_unsched_costs(const SchedDev& d, const unsigned long long* ids, int k, unsigned char* flags, int mode,
                                long long ucost, long long ccost, int* changed, hipStream_t st);
+
+
+// ---- ks_commit_schedule: the pin of every placed task (pinTaskToNode,
+// graph_manager.go:675-720), the unscheduled aggregators' capacities (:1291-1305) and
+// the resource arcs' (:662-667) as ks_delta records generated in device memory.
+// Device counters of one commit; the host reads them in one copy.
+struct CommitCtl {
+    int rec_pin;      // records of the placed tasks' existing out-arcs (deletes + conversions)
+    int rec_add;      // new running arcs
+    int rec_arc;      // aggregator and resource-arc capacity records
+    int unsched;      // of those, aggregator → sink arcs
+    int caps;         // of those, resource arcs
+    int bad;          // a capacity would fall below its arc's lower bound
+    int _pad[2];
+};
+
+// Scratch of one commit (device pointers; np placed tasks, ni_max chunk items at most).
+struct CommitDev {
+    int np;                        // PLACE deltas
+    int ni_max;                    // upper bound of the chunk items (np + residual positions / 64)
+    int* pl_task;                  // [np] task node slot, in delta order
+    int* pl_pu;                    // [np] PU node slot
+    int* pl_has;                   // [np + 1] 1: the arc task → PU exists (it is converted)
+    int* pl_noarc;                 // [np + 1] 1 − pl_has, and its exclusive scan add_off
+    int* add_off;                  // [np + 1]
+    int* nch;                      // [np + 1] 64-position chunks of the task's segment; ch_off its scan
+    int* ch_off;                   // [np + 1]
+    int* icnt;                     // [ni_max + 1] records of one chunk item; i_off its scan
+    int* i_off;                    // [ni_max + 1]
+    int* aflag;                    // [hi + 1] arc slot emits a capacity record; a_off its scan
+    int* a_off;                    // [hi + 1]
+    unsigned char* fl;             // per node slot: 1 unscheduled aggregator, 2 placed by this call
+    unsigned long long* agg_cnt;   // per node slot: pinned tasks that had an arc into the aggregator
+    unsigned long long* pu_slots;  // per node slot: capacity of the PU → sink arc
+    unsigned long long* pu_run;    // per node slot: running arcs into the PU after the commit
+    unsigned long long* slots;     // per node slot: slots_below (resource caps)
+    unsigned long long* running;   // per node slot: running_below
+    CommitCtl* ctl;
+};
+
+// The places of the delta kinds (sched_delta_kinds) in delta order, their chunk counts,
+// and the aggregator flags (ids: k node ids, or nullptr for every type-0 node with an
+// arc into the sink).
+hipError_t sched_commit_places(const SchedDev& d, const CommitDev& c, const int* rank, const unsigned long long* newpu,
+                               const int* other, const int* other_pos, const unsigned long long* ids, int k,
+                               hipStream_t st);
+// Count pass over the chunk items (after the scan nch → ch_off).
+hipError_t sched_commit_count(const SchedDev& d, const CommitDev& c, hipStream_t st);
+// PU slots and running counts for the resource capacities (before the level BFS).
+hipError_t sched_commit_pu_counts(const SchedDev& d, const CommitDev& c, hipStream_t st);
+// Arc slots that emit a capacity record (aflag), resource_caps != 0: also the resource arcs.
+hipError_t sched_commit_arc_flags(const SchedDev& d, const CommitDev& c, int resource_caps, hipStream_t st);
+// Record totals into c.ctl (after the scans icnt → i_off, pl_noarc → add_off, aflag → a_off).
+hipError_t sched_commit_totals(const SchedDev& d, const CommitDev& c, hipStream_t st);
+// Emit pass: the records into recs (pins, then new running arcs, then capacities) and the
+// bindings of the placed tasks.
+hipError_t sched_commit_emit(const SchedDev& d, const CommitDev& c, long long ccost, int resource_caps, ks_delta* recs,
+                             hipStream_t st);
 
 }  // namespace ks

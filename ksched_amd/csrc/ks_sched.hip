@@ -15,6 +15,11 @@
 //                       every task's arc into its unscheduled aggregator re-costed
 //                       in place (residual pair included), running tasks' running
 //                       arcs set to the continuation cost
+//   commit schedule     TaskScheduled → pinTaskToNode (graph_manager.go:454-460, 675-720),
+//                       updateUnscheduledAggNode(−1) (:706) and
+//                       capacityFromResNodeToParent (:662-667): the records a host
+//                       would export for them, generated in device memory for
+//                       store_apply (ks_store.hip)
 #include "ks_sched.h"
 
 namespace ks {
@@ -83,6 +88,7 @@ __device__ __forceinline__ bool accum(unsigned char t) {
 
 __global__ void k_topo_level(SchedDev d, const int* __restrict__ front, int nfront, int level, int* __restrict__ lvl,
                              int* __restrict__ next, int* __restrict__ nnext, unsigned long long mtpp,
+                             const unsigned long long* __restrict__ pu_slots,
                              const unsigned long long* __restrict__ pu_running, unsigned long long* __restrict__ slots,
                              unsigned long long* __restrict__ running) {
     const int lane = threadIdx.x & 63;
@@ -105,7 +111,7 @@ __global__ void k_topo_level(SchedDev d, const int* __restrict__ front, int nfro
             if (cur_sink) {
                 if (tu == KS_NODE_PU) {
                     running[us] = pu_running[us];
-                    slots[us] = mtpp;
+                    slots[us] = pu_slots ? pu_slots[us] : mtpp;
                 }
             } else if (cur_res) {
                 atomicAdd(&running[us], running[v]);
@@ -184,6 +190,225 @@ __global__ void k_unsched_costs(SchedDev d, int hi, const unsigned char* __restr
     }
 }
 
+// ------------------------------------------------------------ commit schedule ---
+// pinTaskToNode (graph_manager.go:675-720) for every PLACE of the last solve, with
+// updateUnscheduledAggNode(−1) (:706, :1291-1305) and capacityFromResNodeToParent
+// (:662-667), as ks_delta records written in device memory for store_apply. Three
+// record families, disjoint in (src, dst): a placed task's out-arcs (the tail is a
+// task), aggregator → sink arcs (the head is the sink), resource arcs (neither).
+//
+// A placed task's out-arcs are found in its residual segment, one wave per
+// 64-position chunk of it (the chunk items of k_bf_round, built here on device:
+// nch → ch_off by a scan, the item's place by bisection): no lane walks a segment.
+
+// One atomicAdd per distinct idx among the pred lanes of a wave (hundreds of tasks
+// placed on one PU hit one word: same-word atomics serialise at ~10 ns each).
+// Every lane of the wave calls it.
+__device__ __forceinline__ void wave_add_distinct(unsigned long long* base, int idx, bool pred) {
+    const int me = (int)__lane_id();
+    unsigned long long rem = __ballot(pred);
+    while (rem) {
+        const int l = __ffsll((long long)rem) - 1;
+        const int il = __shfl(idx, l);
+        const unsigned long long same = __ballot(pred && idx == il) & rem;
+        if (me == l) atomicAdd(&base[il], (unsigned long long)__popcll(same));
+        rem &= ~same;
+    }
+}
+
+__device__ __forceinline__ void wave_count(int* ctr, bool pred) {
+    const unsigned long long m = __ballot(pred);
+    if (m && (int)__lane_id() == __ffsll((long long)m) - 1) atomicAdd(ctr, __popcll(m));
+}
+
+__global__ void k_commit_places(SchedDev d, CommitDev c, const int* __restrict__ rank,
+                                const unsigned long long* __restrict__ newpu, const int* __restrict__ other,
+                                const int* __restrict__ other_pos) {
+    for (long long v = blockIdx.x * (long long)SB + threadIdx.x; v < d.ncap; v += (long long)gridDim.x * SB) {
+        if (other[v] != 1) continue;
+        const int i = other_pos[v];
+        if (i < 0 || i >= c.np) continue;
+        c.pl_task[i] = (int)v;
+        c.pl_pu[i] = (int)newpu[rank[v]] - 1;
+        const int x = d.perm[v];
+        int len = 0;
+        if (x >= 0) len = min(d.used[x], d.first[x + 1] - d.first[x]);
+        c.nch[i] = (max(len, 0) + 63) >> 6;
+        c.fl[v] |= 2;
+    }
+}
+
+// Chunk item w → its place i (ch_off[i] ≤ w < ch_off[i + 1]) and the position this lane reads.
+__device__ __forceinline__ int commit_item(const SchedDev& d, const CommitDev& c, int w, int lane, int* place) {
+    int lo = 0, hi = c.np - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (c.ch_off[mid] <= w) lo = mid;
+        else hi = mid - 1;
+    }
+    *place = lo;
+    const int x = d.perm[c.pl_task[lo]];
+    const int b = d.first[x];
+    const int len = min(d.used[x], d.first[x + 1] - b);
+    const int p = b + ((w - c.ch_off[lo]) << 6) + lane;
+    return p < b + len ? p : -1;
+}
+
+__global__ void k_commit_count(SchedDev d, CommitDev c) {
+    const int lane = threadIdx.x & 63;
+    const int wave = (blockIdx.x * SB + threadIdx.x) >> 6;
+    const int nwaves = (gridDim.x * SB) >> 6;
+    const int ni = min(c.ch_off[c.np], c.ni_max);
+    for (int w = wave; w < ni; w += nwaves) {
+        int i;
+        const int p = commit_item(d, c, w, lane, &i);
+        const int e = p >= 0 ? d.ent[p] : -1;
+        const bool live = e >= 0 && !(e & 1);   // forward positions: the task's out-arcs
+        if (live) {
+            const int dst = d.a_dst[e >> 1];
+            if (dst == c.pl_pu[i]) c.pl_has[i] = 1;
+            // (one task per wave and one arc per (src, dst): the lanes' aggregators are distinct words)
+            if (c.fl[dst] & 1) atomicAdd(&c.agg_cnt[dst], 1ULL);
+        }
+        const unsigned long long m = __ballot(live);
+        if (lane == 0) c.icnt[w] = __popcll(m);
+    }
+}
+
+__global__ void k_commit_noarc(CommitDev c) {
+    for (long long i = blockIdx.x * (long long)SB + threadIdx.x; i <= c.np; i += (long long)gridDim.x * SB)
+        c.pl_noarc[i] = i < c.np ? 1 - c.pl_has[i] : 0;
+}
+
+// A PU's slots are the capacity of its arc into the sink; its running count the
+// running arcs (type 1) into it that stay — a placed task's own arcs go or are
+// converted — plus the tasks this call places on it.
+__global__ void k_commit_pu_arcs(SchedDev d, CommitDev c) {
+    for (long long s0 = blockIdx.x * (long long)SB; s0 < d.hi; s0 += (long long)gridDim.x * SB) {   // (uniform per workgroup)
+        const long long s = s0 + threadIdx.x;
+        bool run = false;
+        int dst = 0;
+        if (s < d.hi && d.a_alive[s]) {
+            const int src = d.a_src[s];
+            dst = d.a_dst[s];
+            if (d.n_type[dst] == KS_NODE_SINK && d.n_type[src] == KS_NODE_PU) c.pu_slots[src] = (unsigned long long)d.a_cap[s];
+            run = d.a_type[s] == 1 && !(c.fl[src] & 2);
+        }
+        wave_add_distinct(c.pu_run, dst, run);
+    }
+}
+
+__global__ void k_commit_pu_places(CommitDev c) {
+    for (long long i0 = blockIdx.x * (long long)SB; i0 < c.np; i0 += (long long)gridDim.x * SB) {
+        const long long i = i0 + threadIdx.x;
+        wave_add_distinct(c.pu_run, i < c.np ? c.pl_pu[i] : 0, i < c.np);
+    }
+}
+
+// The capacity arc slot s gets from this commit: 1 an aggregator → sink arc (minus
+// the tasks pinned out of it), 2 a resource arc (slots − running below its head), 0
+// none or unchanged.
+__device__ __forceinline__ int commit_arc_cap(const SchedDev& d, const CommitDev& c, int resource_caps, int s,
+                                              long long* cap) {
+    if (!d.a_alive[s]) return 0;
+    const int u = d.a_src[s], v = d.a_dst[s];
+    const unsigned char tu = d.n_type[u], tv = d.n_type[v];
+    if (tv == KS_NODE_SINK) {
+        if (!(c.fl[u] & 1) || c.agg_cnt[u] == 0) return 0;
+        *cap = d.a_cap[s] - (long long)c.agg_cnt[u];
+        return 1;
+    }
+    if (!resource_caps || tu == KS_NODE_TASK) return 0;
+    const bool res = tv == KS_NODE_PU || tv == KS_NODE_MACHINE || tv == KS_NODE_INTERMEDIATE ||
+                     (tv == KS_NODE_OTHER && c.slots[v] > 0);
+    if (!res) return 0;
+    *cap = (long long)c.slots[v] - (long long)c.running[v];
+    return *cap != d.a_cap[s] ? 2 : 0;
+}
+
+__global__ void k_commit_arc_flags(SchedDev d, CommitDev c, int resource_caps) {
+    for (long long s0 = blockIdx.x * (long long)SB; s0 <= d.hi; s0 += (long long)gridDim.x * SB) {
+        const long long s = s0 + threadIdx.x;
+        int kind = 0;
+        if (s < d.hi) {
+            long long cap = 0;
+            kind = commit_arc_cap(d, c, resource_caps, (int)s, &cap);
+            if (kind && cap < d.a_low[s]) atomicOr(&c.ctl->bad, 1);
+        }
+        if (s <= d.hi) c.aflag[s] = kind != 0;
+        wave_count(&c.ctl->unsched, kind == 1);
+        wave_count(&c.ctl->caps, kind == 2);
+    }
+}
+
+__global__ void k_commit_totals(SchedDev d, CommitDev c) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        c.ctl->rec_pin = c.i_off[c.ni_max];
+        c.ctl->rec_add = c.add_off[c.np];
+        c.ctl->rec_arc = c.a_off[d.hi];
+    }
+}
+
+__device__ __forceinline__ ks_delta arc_record(int kind, int type, int src, int dst, long long low, long long cap,
+                                               long long cost, long long old_cost) {
+    ks_delta r{};
+    r.kind = kind;
+    r.type = type;
+    r.src = (uint64_t)src + 1;
+    r.dst = (uint64_t)dst + 1;
+    r.low = (uint64_t)low;
+    r.cap = (uint64_t)cap;
+    r.cost = cost;
+    r.old_cost = old_cost;
+    return r;
+}
+
+// Per out-arc of a placed task: the arc into its PU becomes the running arc (type 1,
+// low 1, cap 1, the continuation cost), every other one is deleted (DeleteArc's
+// "x src dst 0 0", graph_change_manager.go:184-193).
+__global__ void k_commit_emit_pins(SchedDev d, CommitDev c, long long ccost, ks_delta* __restrict__ recs) {
+    const int lane = threadIdx.x & 63;
+    const int wave = (blockIdx.x * SB + threadIdx.x) >> 6;
+    const int nwaves = (gridDim.x * SB) >> 6;
+    const int ni = min(c.ch_off[c.np], c.ni_max);
+    for (int w = wave; w < ni; w += nwaves) {
+        int i;
+        const int p = commit_item(d, c, w, lane, &i);
+        const int e = p >= 0 ? d.ent[p] : -1;
+        const bool live = e >= 0 && !(e & 1);
+        const unsigned long long m = __ballot(live);
+        if (!live) continue;
+        const int s = e >> 1, t = c.pl_task[i], dst = d.a_dst[s];
+        const int r = c.i_off[w] + __popcll(m & ((1ULL << lane) - 1));
+        const long long co = d.a_cost[s];
+        recs[r] = dst == c.pl_pu[i] ? arc_record(KS_UPDATE_ARC, 1, t, dst, 1, 1, ccost, co)
+                                    : arc_record(KS_UPDATE_ARC, d.a_type[s], t, dst, 0, 0, co, co);
+    }
+}
+
+// A placed task without an arc into its PU gets the running arc; every placed task its binding.
+__global__ void k_commit_emit_adds(SchedDev d, CommitDev c, long long ccost, ks_delta* __restrict__ recs) {
+    const int base = c.ctl->rec_pin;
+    for (long long i = blockIdx.x * (long long)SB + threadIdx.x; i < c.np; i += (long long)gridDim.x * SB) {
+        const int t = c.pl_task[i], pu = c.pl_pu[i];
+        d.n_bind[t] = (unsigned long long)pu + 1;
+        if (!c.pl_has[i]) recs[base + c.add_off[i]] = arc_record(KS_ADD_ARC, 1, t, pu, 1, 1, ccost, 0);
+    }
+}
+
+__global__ void k_commit_emit_arcs(SchedDev d, CommitDev c, int resource_caps, ks_delta* __restrict__ recs) {
+    const int base = c.ctl->rec_pin + c.ctl->rec_add;
+    for (long long s = blockIdx.x * (long long)SB + threadIdx.x; s < d.hi; s += (long long)gridDim.x * SB) {
+        if (!c.aflag[s]) continue;
+        long long cap = 0;
+        if (!commit_arc_cap(d, c, resource_caps, (int)s, &cap)) continue;
+        // capacity 0 removes the arc (the store's low == cap == 0 rule; cap ≥ low was checked)
+        const long long co = d.a_cost[s];
+        recs[base + c.a_off[s]] = arc_record(KS_UPDATE_ARC, d.a_type[s], d.a_src[s], d.a_dst[s], cap ? d.a_low[s] : 0,
+                                             cap, co, co);
+    }
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------ launchers ---
@@ -214,11 +439,58 @@ hipError_t sched_running_counts(const SchedDev& d, const unsigned long long* ids
 }
 
 hipError_t sched_topo_level(const SchedDev& d, const int* front, int nfront, int level, int* lvl, int* next,
-                            int* nnext, unsigned long long mtpp, const unsigned long long* pu_running,
-                            unsigned long long* slots, unsigned long long* running, hipStream_t st) {
+                            int* nnext, unsigned long long mtpp, const unsigned long long* pu_slots,
+                            const unsigned long long* pu_running, unsigned long long* slots,
+                            unsigned long long* running, hipStream_t st) {
     const int blocks = std::max(1, std::min(4096, (nfront + 3) / 4));
     hipLaunchKernelGGL(k_topo_level, dim3(blocks), dim3(SB), 0, st, d, front, nfront, level, lvl, next, nnext, mtpp,
-                       pu_running, slots, running);
+                       pu_slots, pu_running, slots, running);
+    return hipGetLastError();
+}
+
+hipError_t sched_commit_places(const SchedDev& d, const CommitDev& c, const int* rank, const unsigned long long* newpu,
+                               const int* other, const int* other_pos, const unsigned long long* ids, int k,
+                               hipStream_t st) {
+    // the aggregators as ks_update_unsched_costs finds them, then the places (fl bit 2)
+    if (ids) {
+        if (k) hipLaunchKernelGGL(k_mark_ids, dim3(grid(k)), dim3(SB), 0, st, k, ids, c.fl);
+    } else if (d.hi) {
+        hipLaunchKernelGGL(k_mark_unsched_auto, dim3(grid(d.hi)), dim3(SB), 0, st, d.hi, d.a_alive, d.a_src, d.a_dst,
+                           d.n_type, c.fl);
+    }
+    if (c.np) hipLaunchKernelGGL(k_commit_places, dim3(grid(d.ncap)), dim3(SB), 0, st, d, c, rank, newpu, other, other_pos);
+    return hipGetLastError();
+}
+
+hipError_t sched_commit_count(const SchedDev& d, const CommitDev& c, hipStream_t st) {
+    if (c.np) hipLaunchKernelGGL(k_commit_count, dim3(grid(64LL * c.ni_max)), dim3(SB), 0, st, d, c);
+    hipLaunchKernelGGL(k_commit_noarc, dim3(grid(c.np + 1)), dim3(SB), 0, st, c);
+    return hipGetLastError();
+}
+
+hipError_t sched_commit_pu_counts(const SchedDev& d, const CommitDev& c, hipStream_t st) {
+    if (d.hi) hipLaunchKernelGGL(k_commit_pu_arcs, dim3(grid(d.hi)), dim3(SB), 0, st, d, c);
+    if (c.np) hipLaunchKernelGGL(k_commit_pu_places, dim3(grid(c.np)), dim3(SB), 0, st, c);
+    return hipGetLastError();
+}
+
+hipError_t sched_commit_arc_flags(const SchedDev& d, const CommitDev& c, int resource_caps, hipStream_t st) {
+    hipLaunchKernelGGL(k_commit_arc_flags, dim3(grid(d.hi + 1)), dim3(SB), 0, st, d, c, resource_caps);
+    return hipGetLastError();
+}
+
+hipError_t sched_commit_totals(const SchedDev& d, const CommitDev& c, hipStream_t st) {
+    hipLaunchKernelGGL(k_commit_totals, dim3(1), dim3(64), 0, st, d, c);
+    return hipGetLastError();
+}
+
+hipError_t sched_commit_emit(const SchedDev& d, const CommitDev& c, long long ccost, int resource_caps, ks_delta* recs,
+                             hipStream_t st) {
+    if (c.np) {
+        hipLaunchKernelGGL(k_commit_emit_pins, dim3(grid(64LL * c.ni_max)), dim3(SB), 0, st, d, c, ccost, recs);
+        hipLaunchKernelGGL(k_commit_emit_adds, dim3(grid(c.np)), dim3(SB), 0, st, d, c, ccost, recs);
+    }
+    if (d.hi) hipLaunchKernelGGL(k_commit_emit_arcs, dim3(grid(d.hi)), dim3(SB), 0, st, d, c, resource_caps, recs);
     return hipGetLastError();
 }
 

@@ -20,7 +20,7 @@ EXPORTED_SYMBOLS = (
     "ks_abi_version", "ks_default_opts", "ks_create", "ks_destroy", "ks_last_error", "ks_load_graph",
     "ks_apply_deltas", "ks_solve", "ks_get_flows", "ks_get_task_mapping", "ks_get_task_pu_device", "ks_solve_many",
     "ks_coalesce_deltas", "ks_get_store_stats", "ks_set_bindings", "ks_scheduling_deltas",
-    "ks_update_unsched_costs", "ks_topology_stats", "ks_get_graph",
+    "ks_update_unsched_costs", "ks_topology_stats", "ks_get_graph", "ks_commit_schedule",
     "ks_batch_create", "ks_batch_create_rank", "ks_batch_unique_id", "ks_batch_destroy", "ks_batch_last_error",
     "ks_batch_load", "ks_batch_solve", "ks_batch_gather",
     "ks_batch_slots", "ks_batch_owner", "ks_batch_block_len", "ks_batch_unpack",
@@ -28,6 +28,7 @@ EXPORTED_SYMBOLS = (
 ABI_VERSION = 5
 KS_DELTA_PLACE, KS_DELTA_PREEMPT, KS_DELTA_MIGRATE, KS_DELTA_NOOP = 0, 1, 2, 3
 KS_COST_SET, KS_COST_ADD = 0, 1
+KS_COMMIT_RESOURCE_CAPS = 1
 
 NODE_DT = np.dtype({"names": ["id", "excess", "type", "_pad"],
                     "formats": ["<u8", "<i8", "<i4", "<i4"], "offsets": [0, 8, 16, 20], "itemsize": 24})
@@ -83,6 +84,16 @@ class KsStoreStats(C.Structure):
     _fields_ = [("live_arcs", C.c_int64), ("inserted", C.c_int64), ("updated", C.c_int64),
                 ("killed", C.c_int64), ("superseded", C.c_int64), ("rebuilds", C.c_int64),
                 ("residual_slots", C.c_int64), ("reserved", C.c_int64 * 4)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class KsCommitStats(C.Structure):
+    """ks_commit_stats: what one ks_commit_schedule generated on device."""
+    _fields_ = [("placed", C.c_int64), ("arcs_removed", C.c_int64), ("running_added", C.c_int64),
+                ("running_converted", C.c_int64), ("unsched_updates", C.c_int64), ("cap_updates", C.c_int64),
+                ("records", C.c_int64), ("reserved", C.c_int64 * 5)]
 
     def as_dict(self) -> dict:
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
@@ -179,6 +190,8 @@ def _bind(path: str):
     L.ks_scheduling_deltas.argtypes = [V, C.c_int, V, C.c_size_t, P(C.c_size_t)]
     L.ks_update_unsched_costs.argtypes = [V, V, C.c_size_t, C.c_int32, C.c_int64, C.c_int64, P(C.c_size_t)]
     L.ks_topology_stats.argtypes = [V, C.c_uint64, V, V, C.c_size_t, V, V, C.c_size_t, P(C.c_size_t)]
+    L.ks_commit_schedule.argtypes = [V, C.c_int32, C.c_int64, V, C.c_size_t, V, C.c_size_t, P(C.c_size_t),
+                                     P(KsCommitStats)]
     return L
 
 
@@ -334,6 +347,23 @@ class Context:
                                               None if vals is None else vals.ctypes.data, k, sl.ctypes.data,
                                               rn.ctypes.data, cnt.value, C.byref(cnt)))
         return sl, rn
+
+    def commit_schedule(self, continuation: int = 0, resource_caps: bool = True, unsched_ids=None):
+        """ks_commit_schedule: pin every task the last solve placed, on device (the
+        running arcs, the unscheduled aggregators' capacities and, with
+        resource_caps, the resource arcs'). → (deltas SCHED_DELTA_DT, stats dict).
+        Invalidates the solution: fetch the mapping first."""
+        ids = None if unsched_ids is None else np.ascontiguousarray(unsched_ids, np.uint64)
+        pid = None if ids is None else ids.ctypes.data
+        k = 0 if ids is None else ids.shape[0]
+        flags = KS_COMMIT_RESOURCE_CAPS if resource_caps else 0
+        cnt = C.c_size_t()
+        self._check(self._L.ks_commit_schedule(self._h, flags, continuation, pid, k, None, 0, C.byref(cnt), None))
+        out = np.zeros(max(cnt.value, 1), SCHED_DELTA_DT)
+        st = KsCommitStats()
+        self._check(self._L.ks_commit_schedule(self._h, flags, continuation, pid, k, out.ctypes.data, cnt.value,
+                                               C.byref(cnt), C.byref(st)))
+        return out[:cnt.value], st.as_dict()
 
     def task_pu_device(self, dev_ptr: int, cap: int) -> int:
         cnt = C.c_size_t()
