@@ -58,6 +58,10 @@ constexpr long long CELL_MAX_CAP = (1LL << 24) - 1;         // capacities the ce
                                                             // admissible sum then fits int32) and |cost|
 constexpr long long CELL_MAX_COST = (1LL << 31) - 2;        // |scaled cost| (CELL_DEAD = 2^31 − 1 marks inert)
 
+// The cycle-cancelling finish of both solvers finds cycles of up to 2^CYC_LOG arcs
+// (the doubling steps of a full parent-graph search; CellArgs::cyc_lg).
+constexpr int CYC_LOG = 10;
+
 enum CellStatus { CS_OK = 0, CS_INFEASIBLE = 1, CS_NOCONV = 2, CS_TIMEOUT = 3, CS_RANGE = 4 };
 
 // Written by the cell's workgroup when it finishes.

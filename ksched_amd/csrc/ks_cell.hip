@@ -56,7 +56,6 @@ constexpr long long DNEG = -(1LL << 30);   // price refinement below this: treat
 constexpr long long INF64 = 0x3fffffffffffffffLL;
 constexpr int BXC = 256;                   // updates with at most this many excess nodes are bounded
 // cycle-cancelling finish (cyc_search)
-constexpr int CYC_LOG = 10;                 // cycles of up to 1,024 arcs
 constexpr int CYC_WALK = 1 << CYC_LOG;
 constexpr int CYC_EVERY = 16;               // refinement rounds between searches (8 and 32: no better)
 constexpr int CYC_IDB = 15;                 // bits of a local node id in the packed word (cells ≤ 32k nodes)

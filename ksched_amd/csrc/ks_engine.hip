@@ -1,4 +1,8 @@
-// ks_engine.hip — gfx950 ε-scaling push-relabel min-cost flow engine.
+// ks_engine.hip — gfx950 ε-scaling push-relabel min-cost flow engine: the solve
+// (Engine::solve → SolveRun) and every kernel it launches. The engine's other sources:
+// ks_engine_build.hip (the residual CSR and the cold reset), ks_engine_io.hip (store
+// glue, the task → PU mapping and the other outputs), ks_engine_sched.hip (scheduler
+// glue); what they share is in ks_engine_impl.h.
 //
 // Replaces the Flowlessly solve behind ksched's placement.Solver
 // (scheduling/flow/placement/solver.go:30-34, 60-90). Algorithm and data
@@ -64,7 +68,6 @@
 // All in-kernel cross-workgroup communication uses device-scope RMW atomics or
 // idempotent flag stores; everything else is handed over at kernel boundaries.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <chrono>
@@ -73,174 +76,10 @@
 #include <cstring>
 #include <vector>
 
-#include "ks_cell.h"
-#include "ks_engine.h"
-#include "ks_sched.h"
+#include "ks_engine_impl.h"
 
 namespace ks {
 namespace {
-
-constexpr int BLK = 256;
-constexpr int WAVE = 64;
-constexpr int WPB = BLK / WAVE;
-constexpr int NGC = 6;             // group classes: 4, 8, 16, 32, 64 lanes; 64 lanes × several chunks
-constexpr int HEAVY_MIN = 4096;    // degree > 4096: hub, chunked over workgroups
-constexpr int CHUNK = 1024;        // heavy hubs: 1024 residual arcs per workgroup
-constexpr int PER_T = CHUNK / 256; // arcs per thread in a hub chunk
-constexpr int HSPLIT = 4;          // Bellman-Ford: workgroups per hub chunk (one arc per thread at 4)
-constexpr int BF_PER_T = PER_T / HSPLIT;
-static_assert(PER_T % HSPLIT == 0, "a hub chunk splits into whole arcs per thread");
-constexpr int WPW = 2;             // windows per wave in sparse (grid-stride) passes
-constexpr int SHARDS = 16;         // inbox shards per heavy hub
-constexpr int MAXB = 64;           // max sweeps per cycle
-constexpr int HUB_LDS = 16;        // hubs whose Bellman-Ford minima are reduced in LDS
-constexpr int CYC_SLOTS = 2;       // control snapshots / timing events rotate over two cycles
-constexpr int NCTR = 10;
-constexpr int CTR_SHARDS = 64;
-constexpr long long INF64 = 0x3fffffffffffffffLL;
-constexpr long long LEN_CAP = 1LL << 40;   // global-update arc length clamp
-constexpr double kSolveWallLimitS = 120.0; // host-side guard against a non-converging solve
-constexpr double kCellLimitS = 20.0;       // the cell solver's in-kernel wall-clock limit (every workgroup exits)
-
-enum { C_SCAN = 0, C_VISIT = 1, C_PUSH = 2, C_RELABEL = 3, C_GUSCAN = 4, C_BFROUND = 5, C_AUGWALK = 6, C_AUGHOP = 7,
-       C_FSSCAN = 8, C_GULEAF = 9 };
-constexpr int AUG_KMAX = 4096;     // most excess nodes a tail's walkers start from (ks_opts.tail_nodes)
-constexpr int BX_CAP = 64;         // global updates with at most this many excess nodes are bounded
-// Forward tail update: a node's search key (in its record's dist slot) packs the
-// distance from the excess nodes above the position of the arc that set it.
-constexpr int FS_PB = 26;
-constexpr long long FS_NONE = (1LL << FS_PB) - 1;    // no parent (an excess node)
-constexpr long long FS_DMAX = 1LL << 36;             // distances beyond are not searched
-constexpr int FDEF_CAP = 64;       // deficits one forward update traces paths to
-constexpr int FS_LIST_BLOCKS = 128;
-constexpr int FWD_UPD = 4;         // forward updates per cycle once a search finished within its rounds (2: ~1 ms slower on config 4)
-
-struct Ctl {
-    long long eps;
-    long long gu_L;        // max finite distance of the current global update
-    long long gu_X;        // max distance of a node holding excess (−1: none)
-    int infeasible;
-    int bf_done;           // Bellman-Ford frontier drained (update converged)
-    int verify_bad;
-    int cp_bad;            // k_pack_pos: a value the 16-B record cannot hold (the solve reads Pos)
-    int cyc_done;          // cycle-cancelling refinement: cycles cancelled
-    int cyc_rej;           //   marked nodes k_cyc_check found with other than one member pointing at them
-    int bf_count;          // Bellman-Ford rounds that did work (whole solve)
-    int bfa[3];            // Bellman-Ford flag buffer k holds at least one flag
-    int apply_act;         // the global-update apply seeded a non-empty frontier
-    int sweep_act[MAXB];   // sweep pos left a non-empty frontier
-    int gu_pending;        // the last cycle's update did not converge: the next cycle continues it
-    int n_exc;             // nodes the last apply found holding excess
-    int bf_r0;             // bf_count when the running update started
-    int bf_seq0;           // sequence number of the running update's first (dense) round
-    int aug_reached;       // walks of this cycle that reached a deficit / stopped short
-    int aug_short;
-    int n_xl2;             // nodes fed by this cycle's hub distribution
-    int dbg_x[4];          // diagnostics (KS_CYCLE_LOG): the first listed excess nodes, their excess at the apply
-    int dbg_e[4];
-    int n_bx;              // excess nodes k_gu_init listed for the distance bound (> BX_CAP: no bound)
-    long long bf_bound;    // Bellman-Ford prune bound: max tentative distance of the listed excess nodes
-    long long gu_B;        // the converged bounded update's cap: max distance of the listed excess nodes
-    // forward tail update (k_fs_*): a search from the excess nodes
-    long long fs_D;        // least distance of a deficit found by the running search (INF64: none yet)
-    int fs_cnt[3];         // frontier list lengths (rotating like the flag buffers)
-    int fs_done;           // the search's frontier drained
-    int fs_fail;           // list overflow or no deficit in range: the next cycle is a backward update
-    int fs_pending;        // a search is running: the next init continues it (set by its first round)
-    int fs_rounds;         // rounds of the running search that had a frontier
-    int n_fdef;            // deficits at distance D listed for the trace
-    int fs_moved;          // units the trace moved
-    long long u_exc;       // excess units the last apply (backward) / init (forward) found
-    int fs_maxcnt;         // the running search's widest frontier (nodes; hubs count 1024 each)
-    int n_exc_rep;         // excess nodes / units the last completed forward update's init found
-    long long u_exc_rep;
-    int fs_completed;      // forward updates completed (whole solve)
-    int fs_moved_cyc;      // units the traces of this cycle moved
-    // device-clock timing (s_memrealtime, 100 MHz) where a HIP event between two
-    // kernels would cost a ~5.7 µs gap of its own (profiles/r06_*_gaps):
-    unsigned long long t_sw0;       // the cycle's first sweep started
-    unsigned long long t_end;       // k_cycle_end started (= the last sweep ended)
-    unsigned long long t_srch;      // the finish's running parent-graph search started (0: none)
-    unsigned long long srch_ticks;  // the finish's searches so far (subtracted from its batches' spans)
-};
-
-struct HItem {
-    int node, hid, begin, end;
-};
-
-__host__ __device__ constexpr int class_lanes(int c) { return c < 4 ? (4 << c) : 64; }
-__host__ __device__ inline int degree_class(int d) {
-    return d <= 4 ? 0 : d <= 8 ? 1 : d <= 16 ? 2 : d <= 32 ? 3 : d <= 64 ? 4 : d <= HEAVY_MIN ? 5 : NGC;
-}
-constexpr int CCLS = 5;            // chunked class: Bellman-Ford splits its nodes into 64-arc waves
-
-struct CItem {                     // one 64-arc chunk of a chunked-class node
-    int node, begin, end, lead;    // lead = 1 for the node's first chunk
-};
-// A wave owns one window: win_batches(c) batches of 64/G consecutive node ids.
-// classes below 4 (≤ 16 lanes per node) own two batches per window, the rest one
-__host__ __device__ constexpr int win_batches(int c) { return c < 4 ? 2 : 1; }
-static_assert(NGC == 6, "KS_BY_CLASS dispatches six classes");
-__host__ __device__ constexpr int win_slots(int c) { return win_batches(c) * (64 / class_lanes(c)); }
-
-// One frontier buffer: a flag byte per (non-hub) node, a flag per hub.
-struct Front {
-    unsigned char* flag;   // [hub_base]
-    int* hub;              // [nheavy]
-};
-
-struct DG {
-    int n;                 // internal node ids: [0, hub_base) grouped nodes, then hubs
-    int m;
-    int hub_base;
-    int expand;            // Bellman-Ford: relax low-degree targets two hops per round
-    const int* first;
-    Pos* pos;              // residual positions: cost, rcap, ucap = rcap(a) + rcap(rev a), head, rev
-    CPos* cp;              // compact solve: 16-B copies of the positions (nullptr: the solve reads pos)
-    int* crev;             // compact solve: reverse position of each position
-    long long* excess;
-    long long* p0;         // node records (stride 4, index with ni()): p0 at +0, dist at +1, p1 at +2
-    long long* p1;
-    long long* dist;
-    long long* inbox;
-    int wbeg[NGC + 1];     // windows of class c: [wbeg[c], wbeg[c+1])
-    int obeg[NGC + 1];     // first node id of class c
-    int oend[NGC];         // one past the last real node of class c
-    const HItem* hitems;
-    int nhitems;
-    int nheavy;
-    const CItem* citems;   // chunks of the chunked class
-    int ncitems;
-    int ncls_c;            // nodes of the chunked class
-    int sw_clsb;           // sweep blocks striding the class windows (after the hub blocks)
-    const int* hnchunks;
-    int* xl;               // excess nodes listed by the last apply (the first aug_k)
-    int aug_k;             // a phase's tail: ≤ aug_k excess nodes (ks_opts.tail_nodes)
-    int* xl2;              // nodes fed by k_aug_hub (the first AUG_K2)
-    int* bx;               // excess nodes of the running update (the first BX_CAP; k_gu_init)
-    int* fl;               // forward search: 3 rotating frontier lists of fl_cap node ids
-    int fl_cap;
-    int fs_wide;           // a forward frontier wider than this fails its search as wide
-    int npos;              // residual positions (m2cap)
-    int* fdef;             // forward search: deficits at the found distance (FDEF_CAP)
-    int bound;             // 1: prune Bellman-Ford offers at ctl->bf_bound (ks_opts.bf_bound >= 0)
-    long long* aug_req;    // per hub: excess claimed by its k_aug_hub chunks
-    long long* q_req;      // claim slots: hubs [0, nheavy), then chunked nodes
-    long long* q_taken;
-    long long* q_min;
-    int* q_unsat;
-    int* q_arrive;
-    Front sf[3];   // sweep frontiers
-    Front bf[3];   // Bellman-Ford frontiers
-    Ctl* ctl;
-    unsigned long long* ctr;
-};
-
-// Node records: p0, dist, p1 and the node's segment bounds (first[x], first[x+1]
-// packed) share one 32-B record, so a Bellman-Ford tail gather (price, distance,
-// and a leaf's segment) or a sweep's node load (price, segment) is one cache line.
-__host__ __device__ __forceinline__ size_t ni(long long x) { return 4 * (size_t)x; }
-constexpr int ND_SEG = 3;   // record slot of the packed segment bounds
 
 __device__ __forceinline__ void seg_of(const long long* nd, int x, int& b0, int& b1) {
     const unsigned long long w = (unsigned long long)nd[ni(x) + ND_SEG];
@@ -249,9 +88,6 @@ __device__ __forceinline__ void seg_of(const long long* nd, int x, int& b0, int&
 }
 
 // ---------------------------------------------------------------- atomics ---
-__device__ __forceinline__ void atom_add(long long* p, long long v) {
-    __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 __device__ __forceinline__ long long atom_add_ret(long long* p, long long v) {
     return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -594,194 +430,6 @@ __device__ __forceinline__ int wave_index_in_grid(int first_block) {
     return ((int)blockIdx.x - first_block) * WPB + ((int)threadIdx.x >> 6);
 }
 
-// ===================================================================== build ===
-// The residual CSR is built on device from the arc table of the store
-// (ks_store.h). Every node owns a segment of CAPACITY positions: its live arcs
-// (forward arcs and reverses of its in-arcs), plus slack once the graph is
-// edited incrementally, so later inserts land in place. Internal ids group the
-// nodes by the degree class of their capacity, hubs last; dead positions are
-// inert (no capacity, head = owner, cost DEAD_COST).
-__global__ void k_degree(int hi, const unsigned char* __restrict__ alive, const int* __restrict__ src,
-                         const int* __restrict__ dst, int* __restrict__ deg) {
-    for (long long s = blockIdx.x * (long long)BLK + threadIdx.x; s < hi; s += (long long)gridDim.x * BLK)
-        if (alive[s]) {
-            atomicAdd(&deg[src[s]], 1);
-            atomicAdd(&deg[dst[s]], 1);
-        }
-}
-
-// Segment capacity of a node slot. Tight after a load (its degree). Once the
-// graph is edited incrementally: tasks (≤ 8 arcs: preferences, or one running
-// arc after the pin) one 8-lane group — a removed task's segment is reused
-// whole by the task that takes over its id (flowgraph/graph.go:169-182), and
-// so are dead and spare slots; other nodes their degree +50 % (at least 4)
-// rounded up to a lane group (≤ 64) or a 64-arc chunk, never less than what
-// they had before (hint) unless that is 4× their need — an aggregator whose
-// degree fell after the pins keeps room for the next arrivals — and twice that
-// when an insert overflowed them since the last build.
-__host__ __device__ inline int seg_capacity(int deg, bool alive, bool task, int slack) {
-    if (!slack) return deg;
-    if ((!alive || task) && deg <= 8) return 8;
-    const int c = deg + (deg / 2 > 4 ? deg / 2 : 4);
-    if (c <= 64) {
-        int g = 4;
-        while (g < c) g <<= 1;
-        return g;
-    }
-    return (c + 63) / 64 * 64;
-}
-
-__global__ void k_capacity(int ncap, int nstore, const int* __restrict__ deg, const unsigned char* __restrict__ alive,
-                           const unsigned char* __restrict__ type, int slack, int* __restrict__ hint,
-                           unsigned char* __restrict__ grow, int* __restrict__ capv, unsigned char* __restrict__ cls) {
-    for (long long v = blockIdx.x * (long long)BLK + threadIdx.x; v < ncap; v += (long long)gridDim.x * BLK) {
-        const int d = v < nstore ? deg[v] : 0;
-        const bool a = v < nstore && alive[v];
-        int c = seg_capacity(d, a, a && type[v] == KS_NODE_TASK, slack);
-        if (slack && v < nstore) {
-            const int h = hint[v];
-            if (grow[v]) c = max(c, 2 * max(h, 4));
-            else if (h <= 4 * c) c = max(c, h);
-            else c = max(c, h / 2);
-            if (c > 64) c = (c + 63) / 64 * 64;
-            grow[v] = 0;
-        }
-        if (v < nstore) hint[v] = c;
-        capv[v] = c;
-        cls[v] = (unsigned char)degree_class(c);
-    }
-}
-
-// perm[list[i]] = base + i (one class, or the hubs).
-__global__ void k_make_perm(int cnt, int base, const int* __restrict__ list, int* __restrict__ perm) {
-    for (long long i = blockIdx.x * (long long)BLK + threadIdx.x; i < cnt; i += (long long)gridDim.x * BLK)
-        perm[list[i]] = base + (int)i;
-}
-
-__global__ void k_capi(int ncap, const int* __restrict__ perm, const int* __restrict__ capv, int* __restrict__ capi,
-                       int* __restrict__ iperm) {
-    for (long long v = blockIdx.x * (long long)BLK + threadIdx.x; v < ncap; v += (long long)gridDim.x * BLK) {
-        capi[perm[v]] = capv[v];
-        iperm[perm[v]] = (int)v;
-    }
-}
-
-// Sort keys: the tail (internal id) of every residual arc; dead slots sort last.
-__global__ void k_pos_keys(int hi, int sentinel, const unsigned char* __restrict__ alive, const int* __restrict__ src,
-                           const int* __restrict__ dst, const int* __restrict__ perm, unsigned* __restrict__ keys,
-                           int* __restrict__ vals) {
-    for (long long s = blockIdx.x * (long long)BLK + threadIdx.x; s < hi; s += (long long)gridDim.x * BLK) {
-        const bool a = alive[s];
-        keys[2 * s] = a ? (unsigned)perm[src[s]] : (unsigned)sentinel;
-        keys[2 * s + 1] = a ? (unsigned)perm[dst[s]] : (unsigned)sentinel;
-        vals[2 * s] = (int)(2 * s);
-        vals[2 * s + 1] = (int)(2 * s + 1);
-    }
-}
-
-// rs[v] = lower bound of v in the sorted keys, v ∈ [0, nn].
-__global__ void k_first(int nn, long long m2, const unsigned* __restrict__ keys, int* __restrict__ rs) {
-    for (long long v = blockIdx.x * (long long)BLK + threadIdx.x; v <= nn; v += (long long)gridDim.x * BLK) {
-        long long lo = 0, hi = m2;
-        while (lo < hi) {
-            const long long mid = (lo + hi) >> 1;
-            if (keys[mid] < (unsigned)v) lo = mid + 1; else hi = mid;
-        }
-        rs[v] = (int)lo;
-    }
-}
-
-// Every position inert, owned by the node whose segment holds it.
-__global__ void k_inert_all(long long m2cap, int nn, const int* __restrict__ first, Pos* __restrict__ pos,
-                            int* __restrict__ ent) {
-    for (long long p = blockIdx.x * (long long)BLK + threadIdx.x; p < m2cap; p += (long long)gridDim.x * BLK) {
-        int lo = 0, hi = nn;   // owner: the last v with first[v] <= p
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (first[mid] <= p) lo = mid; else hi = mid;
-        }
-        pos[p] = Pos{DEAD_COST, 0, 0, lo, (int)p};
-        ent[p] = -1;
-    }
-}
-
-__global__ void k_fill_csr(long long m2, int nn, const unsigned* __restrict__ keys, const int* __restrict__ vals,
-                           const int* __restrict__ rs, const int* __restrict__ first, const int* __restrict__ perm,
-                           const int* __restrict__ src, const int* __restrict__ dst, const long long* __restrict__ low,
-                           const long long* __restrict__ cap, const long long* __restrict__ cost, long long mult,
-                           Pos* __restrict__ pos, int* __restrict__ ent, int* __restrict__ fwd,
-                           int* __restrict__ pos_of) {
-    for (long long i = blockIdx.x * (long long)BLK + threadIdx.x; i < m2; i += (long long)gridDim.x * BLK) {
-        const int v = (int)keys[i];
-        if (v >= nn) continue;
-        const int p = first[v] + (int)(i - rs[v]);
-        const int val = vals[i];
-        const int s = val >> 1;
-        const bool r = val & 1;
-        pos_of[val] = p;
-        const long long u = cap[s] - low[s];
-        pos[p].head = perm[r ? src[s] : dst[s]];
-        pos[p].rcap = r ? 0 : u;
-        pos[p].ucap = u;
-        pos[p].cost = (r ? -cost[s] : cost[s]) * mult;
-        ent[p] = val;
-        if (!r) fwd[s] = p;
-    }
-}
-
-__global__ void k_fill_rev(long long m2, int nn, const unsigned* __restrict__ keys, const int* __restrict__ vals,
-                           const int* __restrict__ pos_of, Pos* __restrict__ pos) {
-    for (long long i = blockIdx.x * (long long)BLK + threadIdx.x; i < m2; i += (long long)gridDim.x * BLK) {
-        if ((int)keys[i] >= nn) continue;
-        const int val = vals[i];
-        pos[pos_of[val]].rev = pos_of[val ^ 1];
-    }
-}
-
-__global__ void k_used(int nn, const int* __restrict__ rs, int* __restrict__ used) {
-    for (long long v = blockIdx.x * (long long)BLK + threadIdx.x; v < nn; v += (long long)gridDim.x * BLK)
-        used[v] = rs[v + 1] - rs[v];
-}
-
-// ------------------------------------------------------------ cold reset ---
-// Zero flow: forward residual = u, reverse 0; excess = supply with the
-// lower-bound transform; prices 0. Runs before every cold solve (no rebuild).
-__global__ void k_reset_pos(long long m2cap, const int* __restrict__ ent, Pos* __restrict__ pos) {
-    for (long long p = blockIdx.x * (long long)BLK + threadIdx.x; p < m2cap; p += (long long)gridDim.x * BLK) {
-        const int e = ent[p];
-        if (e >= 0) pos[p].rcap = (e & 1) ? 0 : pos[p].ucap;
-    }
-}
-
-// Segment bounds into the node records (the CSR's first[] is fixed per build).
-__global__ void k_node_bounds(int nn, const int* __restrict__ first, long long* __restrict__ nd) {
-    for (long long x = blockIdx.x * (long long)BLK + threadIdx.x; x < nn; x += (long long)gridDim.x * BLK)
-        nd[ni(x) + ND_SEG] = (long long)(((unsigned long long)(unsigned)first[x + 1] << 32) | (unsigned)first[x]);
-}
-
-__global__ void k_reset_nodes(int nn, int ncap, const int* __restrict__ iperm, const unsigned char* __restrict__ alive,
-                              const long long* __restrict__ supply, long long* __restrict__ excess,
-                              long long* __restrict__ p0, long long* __restrict__ p1) {
-    for (long long x = blockIdx.x * (long long)BLK + threadIdx.x; x < nn; x += (long long)gridDim.x * BLK) {
-        const int v = iperm[x];
-        excess[x] = (v >= 0 && v < ncap && alive[v]) ? supply[v] : 0;
-        p0[ni(x)] = 0;
-        p1[ni(x)] = 0;
-    }
-}
-
-__global__ void k_reset_low(int hi, const unsigned char* __restrict__ alive, const int* __restrict__ src,
-                            const int* __restrict__ dst, const int* __restrict__ perm,
-                            const long long* __restrict__ low, long long* __restrict__ excess) {
-    for (long long s = blockIdx.x * (long long)BLK + threadIdx.x; s < hi; s += (long long)gridDim.x * BLK) {
-        const long long l = low[s];
-        if (alive[s] && l) {
-            atom_add(&excess[perm[src[s]]], -l);
-            atom_add(&excess[perm[dst[s]]], l);
-        }
-    }
-}
-
 // max |cost| over live arcs → *out (the first phase's ε).
 __global__ void k_max_cost(int hi, const unsigned char* __restrict__ alive, const long long* __restrict__ cost,
                            long long* __restrict__ out) {
@@ -825,12 +473,6 @@ __global__ void k_unpack_pos(long long m2, const CPos* __restrict__ cp, Pos* __r
     for (long long p = blockIdx.x * (long long)BLK + threadIdx.x; p < m2; p += (long long)gridDim.x * BLK)
         pos[p].rcap = cp[p].rcap;
 }
-
-struct ClassIs {
-    const unsigned char* cls;
-    unsigned char c;
-    __host__ __device__ bool operator()(const int& v) const { return cls[v] == c; }
-};
 
 // ================================================= saturate (phase start) ===
 // Push the full residual capacity of every arc with negative reduced cost
@@ -2617,7 +2259,6 @@ __global__ void k_pr_apply(DG g, int packed) {
 // pushes its bottleneck around in parallel; the cycle's nodes rejoin the frontier.
 // The refinement then continues; once its frontier drains, every residual arc
 // meets d(u) ≤ d(v) + len(u, v): the prices p − d certify the flow optimal.
-constexpr int CYC_LOG = 10;      // cycles up to 1,024 arcs are found
 [[maybe_unused]] constexpr int CYC_WALK = 1 << CYC_LOG;
 constexpr int CYC_SHORT = 7;              // a short search's doubling steps
 // refinement rounds between parent-graph searches: 4 where the whole
@@ -3119,504 +2760,16 @@ __global__ void k_max_viol(DG g, long long m2) {
     if (lane_id() == 0 && mx > 0) __hip_atomic_fetch_max(&g.ctl->gu_L, mx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// ================================================ task → PU mapping ===
-// Path decomposition of the solved flow on device (replaces parseFlowToMapping,
-// placement/solver.go:183-269). Flow units are numbered per node: the units
-// leaving x are numbered along x's forward arcs in segment order (out prefix), the
-// units entering y along y's reverse arcs (in prefix); unit k entering y leaves
-// on y's k-th outgoing unit. A task's single unit is followed until it reaches a
-// node without outflow (the sink); the last PU on the way is its placement.
-__global__ void k_unit_vals(long long m2cap, const int* __restrict__ ent, const long long* __restrict__ flows,
-                            long long* __restrict__ outv, long long* __restrict__ inv) {
-    for (long long p = blockIdx.x * (long long)BLK + threadIdx.x; p < m2cap; p += (long long)gridDim.x * BLK) {
-        const int e = ent[p];
-        const long long f = e >= 0 ? flows[e >> 1] : 0;
-        outv[p] = (e >= 0 && !(e & 1)) ? f : 0;
-        inv[p] = (e >= 0 && (e & 1)) ? f : 0;
-    }
-}
-
-__global__ void k_node_meta(int ncap, const int* __restrict__ perm, const unsigned char* __restrict__ type,
-                            const unsigned char* __restrict__ alive, unsigned char* __restrict__ itype,
-                            int* __restrict__ is_task) {
-    for (long long v = blockIdx.x * (long long)BLK + threadIdx.x; v < ncap; v += (long long)gridDim.x * BLK) {
-        const unsigned char t = alive[v] ? type[v] : 0;
-        itype[perm[v]] = t;
-        is_task[v] = t == KS_NODE_TASK ? 1 : 0;
-    }
-}
-
-// smallest position p in [lo, hi) with pre[p] + val[p] > k (pre is the inclusive-
-// exclusive pair of a scan: pre[p] = units before p within the segment)
-__device__ __forceinline__ int find_unit(const long long* __restrict__ scan, const long long* __restrict__ val,
-                                         int lo, int hi, long long base, long long k) {
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (scan[mid] - base + val[mid] <= k) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
-__global__ void k_task_paths(int ncap, int nn, const int* __restrict__ perm, const int* __restrict__ first,
-                             const Pos* __restrict__ pos,
-                             const long long* __restrict__ outv, const long long* __restrict__ outs,
-                             const long long* __restrict__ inv, const long long* __restrict__ ins,
-                             const int* __restrict__ iperm, const unsigned char* __restrict__ itype,
-                             const int* __restrict__ rank, const int* __restrict__ is_task, long long cap,
-                             unsigned long long* __restrict__ out) {
-    for (long long v = blockIdx.x * (long long)BLK + threadIdx.x; v < ncap; v += (long long)gridDim.x * BLK) {
-        if (!is_task[v]) continue;
-        int x = perm[v];
-        long long k = 0;   // unit index among x's outgoing units
-        int last_pu = -1;
-        for (int step = 0; step <= nn; ++step) {
-            const int lo = first[x], hi = first[x + 1];
-            if (lo >= hi) break;
-            const long long obase = outs[lo];
-            const long long otot = outs[hi - 1] + outv[hi - 1] - obase;
-            if (k >= otot) break;   // absorbed here (no outflow left)
-            const int p = find_unit(outs, outv, lo, hi, obase, k);
-            const long long off = k - (outs[p] - obase);
-            const int y = pos[p].head;
-            if (itype[y] == KS_NODE_PU) last_pu = y;
-            const int q = pos[p].rev;
-            k = ins[q] - ins[first[y]] + off;
-            x = y;
-        }
-        if (rank[v] < cap) out[rank[v]] = last_pu >= 0 ? (unsigned long long)iperm[last_pu] + 1 : 0ULL;
-    }
-}
-
-// Per-partition cost and flow value of a disjoint union (k ≤ 1024 parts; one LDS
-// accumulator per part and block, one atomic per part and block).
-constexpr int MAX_CELLS = 1024;
-__global__ void k_cell_sums(int hi, int k, const long long* __restrict__ off, const unsigned char* __restrict__ alive,
-                            const int* __restrict__ src, const int* __restrict__ dst,
-                            const long long* __restrict__ supply, const long long* __restrict__ cost,
-                            const long long* __restrict__ flows, long long* __restrict__ out_cost,
-                            long long* __restrict__ out_flow) {
-    __shared__ long long sc[MAX_CELLS], sf[MAX_CELLS];
-    for (int i = threadIdx.x; i < k; i += BLK) sc[i] = sf[i] = 0;
-    __syncthreads();
-    for (long long s = blockIdx.x * (long long)BLK + threadIdx.x; s < hi; s += (long long)gridDim.x * BLK) {
-        if (!alive[s]) continue;
-        const long long f = flows[s];
-        if (!f) continue;
-        const long long id = (long long)src[s] + 1;
-        int lo = 0, hh = k;   // the part j with off[j] < id <= off[j+1]
-        while (hh - lo > 1) {
-            const int mid = (lo + hh) >> 1;
-            if (off[mid] < id) lo = mid; else hh = mid;
-        }
-        __hip_atomic_fetch_add(&sc[lo], f * cost[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        long long fv = 0;
-        if (supply[dst[s]] < 0) fv += f;
-        if (supply[src[s]] < 0) fv -= f;
-        if (fv) __hip_atomic_fetch_add(&sf[lo], fv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < k; i += BLK) {
-        if (sc[i]) atom_add(&out_cost[i], sc[i]);
-        if (sf[i]) atom_add(&out_flow[i], sf[i]);
-    }
-}
-
-struct SlotAlive {
-    const unsigned char* alive;
-    __host__ __device__ bool operator()(const int& s) const { return alive[s] != 0; }
-};
-
-__global__ void k_arc_records(int cnt, const int* __restrict__ sel, const int* __restrict__ src,
-                              const int* __restrict__ dst, const long long* __restrict__ low,
-                              const long long* __restrict__ cap, const long long* __restrict__ cost,
-                              const unsigned char* __restrict__ type, ks_arc* __restrict__ out) {
-    for (long long i = blockIdx.x * (long long)BLK + threadIdx.x; i < cnt; i += (long long)gridDim.x * BLK) {
-        const int s = sel[i];
-        ks_arc a;
-        a.src = (uint64_t)src[s] + 1;
-        a.dst = (uint64_t)dst[s] + 1;
-        a.low = (uint64_t)low[s];
-        a.cap = (uint64_t)cap[s];
-        a.cost = cost[s];
-        a.type = type[s];
-        a._pad = 0;
-        out[i] = a;
-    }
-}
-
-// positive-flow arcs of the last solve as "f" records (ks_flow), slot order
-struct FlowPositive {
-    const unsigned char* alive;
-    const long long* flows;
-    __host__ __device__ bool operator()(const int& s) const { return alive[s] && flows[s] > 0; }
-};
-
-__global__ void k_flow_records(int cnt, const int* __restrict__ sel, const int* __restrict__ src,
-                               const int* __restrict__ dst, const long long* __restrict__ flows,
-                               ks_flow* __restrict__ out) {
-    for (long long i = blockIdx.x * (long long)BLK + threadIdx.x; i < cnt; i += (long long)gridDim.x * BLK) {
-        const int s = sel[i];
-        out[i] = ks_flow{(uint64_t)src[s] + 1, (uint64_t)dst[s] + 1, flows[s]};
-    }
-}
-
-// ============================================================ host helpers ===
-inline int grid_for(long long n, int cap = 4096) {
-    long long b = (n + BLK - 1) / BLK;
-    if (b < 1) b = 1;
-    return (int)std::min<long long>(b, cap);
-}
-
-template <typename T>
-struct DBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    hipError_t ensure(size_t k) {
-        if (k <= n && p) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-        size_t want = std::max<size_t>(k, 1);
-        hipError_t e = hipMalloc(&p, want * sizeof(T));
-        if (e == hipSuccess) n = want;
-        return e;
-    }
-    // grow to ≥ k elements keeping the first `keep` ones; new tail bytes = fill
-    hipError_t grow(size_t k, size_t keep, int fill, hipStream_t st) {
-        if (k <= n && p) return hipSuccess;
-        const size_t want = std::max<size_t>(k, 1);
-        T* q = nullptr;
-        hipError_t e = hipMalloc(&q, want * sizeof(T));
-        if (e != hipSuccess) return e;
-        keep = std::min(keep, n);
-        if (keep && p) e = hipMemcpyAsync(q, p, keep * sizeof(T), hipMemcpyDeviceToDevice, st);
-        if (e == hipSuccess) e = hipMemsetAsync(q + keep, fill, (want - keep) * sizeof(T), st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (p) (void)hipFree(p);
-        p = q;
-        n = want;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-};
-
 }  // namespace
 
-struct EngineImpl {
-    int device = 0;
-    ks_opts opts{};
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[8] = {};
-    hipEvent_t kev[4] = {};   // kernel-batch timing (price refinement)
-    hipEvent_t fin_ev[4] = {};      // the finish's pipelined batches: [3] its start, [b % 3] batch b's end
-    // per-cycle timing, each kind's span bracketing exactly its kernels: [0] before the
-    // first Bellman-Ford round, [1] after the last, [2] before the first sweep, [3] after
-    // the last sweep; forward cycles: [0]/[1] around each update's search rounds (fev)
-    hipEvent_t cev[CYC_SLOTS][4] = {};
-    hipEvent_t fev[CYC_SLOTS][8] = {};
-    hipEvent_t cdone[CYC_SLOTS] = {};   // a cycle's control snapshot has landed (timed: cycle end)
-    hipEvent_t cstart = nullptr;        // start of a phase's first cycle
-    Ctl* h_cyc[CYC_SLOTS] = {};         // pinned control snapshots of the cycles in flight
-    Ctl* d_cyc[CYC_SLOTS] = {};         // their device-side addresses (written by k_cycle_end)
-
-    // ---- node store (by slot = id − 1)
-    int64_t nstore = 0;       // allocated slots
-    int64_t nslots = 0;       // slots in use (max id)
-    DBuf<long long> n_supply;
-    DBuf<unsigned char> n_type, n_alive, n_fresh;
-    DBuf<unsigned long long> n_cshift;   // per slot: cost rise on a flow-carrying out-arc (warm start)
-    DBuf<int> n_lastrm;
-    DBuf<int> n_hint;         // per slot: segment capacity of the last build
-    DBuf<unsigned char> n_grow;
-    DBuf<unsigned long long> n_bind;   // per slot: bound PU (scheduling deltas)
-    // ---- arc table (by slot) and its hash index
-    int64_t acap = 0;
-    DBuf<int> a_src, a_dst, fwd, free_stack;
-    DBuf<long long> a_low, a_cap, a_cost;
-    DBuf<unsigned char> a_alive, a_type;
-    int64_t hcap = 0;
-    DBuf<unsigned long long> hkey;
-    DBuf<int> hval, hlast;
-    DBuf<StoreCtl> sctl;
-    StoreCtl* h_sctl = nullptr;   // pinned mirror
-    DBuf<ks_delta> d_recs;
-    DBuf<NodeEdit> d_edits;
-    DBuf<int> rec_ent;
-    // ---- residual CSR built from the table (internal ids)
-    bool csr_valid = false;   // CSR matches the table (deltas applied in place)
-    bool incremental = false; // deltas seen since the load: rebuild with slack
-    int64_t rebuilds = 0;     // CSR builds since the load
-    int64_t ncap = 0;         // node slots covered by the build
-    long long mult = 1;       // cost multiplier (ncap + 1)
-    int64_t m2cap = 0;        // residual positions (Σ segment capacities)
-    DBuf<int> first, ent, used, scur, perm, iperm;
-    DBuf<Pos> pos;
-    DBuf<CPos> cpos;               // the compact solve's 16-B positions (k_pack_pos)
-    DBuf<int> crev;
-    DBuf<int> cyc;                 // cycle-cancelling refinement: parents, doubling buffers, marks, arcs
-    DBuf<long long> cyc64;         //   and per-group cost sums and bottlenecks
-    DBuf<long long> excess;
-    DBuf<long long> nd;            // node records [p0, dist, p1, pad] × nn
-    DBuf<unsigned> keys_in, keys_out;
-    DBuf<int> vals_in, vals_out, pos_of, deg, capv, capi, rs;
-    DBuf<unsigned char> sort_tmp, cls;
-    DBuf<int> nsel;
-    DBuf<int> cls_list[NGC + 1];   // node slots of each degree class; [NGC] = heavy hubs
-    DBuf<unsigned char> sel_tmp;
-    DBuf<HItem> hitems;
-    DBuf<CItem> citems;
-    DBuf<int> hnchunks, q_unsat, q_arrive;
-    DBuf<long long> q_req, q_taken, q_min, inbox, part, flows;
-    DBuf<long long> vbal;               // verification: per-node balance of the arc flows (input slots)
-    DBuf<unsigned char> flags;   // 6 frontier buffers × hub_base
-    DBuf<int> hubflags;          // 6 × nheavy
-    DBuf<unsigned long long> ctr;
-    DBuf<int> xl, xl2;                 // walker start nodes (k_augment)
-    DBuf<int> bx;                      // excess nodes of the running update (distance bound)
-    DBuf<int> fl, fdef;                // forward tail update: frontier lists, traced deficits
-    DBuf<long long> aug_req;           // per hub claim counter (k_aug_hub)
-    DBuf<Ctl> ctl;
-    Ctl* h_ctl = nullptr;        // pinned host mirror
-    long long* h_scr = nullptr;  // pinned scratch: [0] eps, [1] max |cost|
-    int ncls[NGC + 1] = {0};
-    int nheavy = 0, nhitems = 0, ncitems = 0;
-    int hub_base = 0, nn = 0;    // grouped node ids [0, hub_base), hubs after: nn ids
-    int obeg[NGC + 1] = {0}, oend[NGC] = {0}, wbeg[NGC + 1] = {0};
-    // ---- solution
-    bool solved = false;         // flows/prices of the current graph are optimal
-    bool has_prev = false;       // a solution exists in place (warm start possible)
-    int64_t n_tasks = 0;
-    DBuf<long long> saved_flows, p_slot;
-    DBuf<long long> map_outv, map_inv, map_outs, map_ins;
-    DBuf<int> map_rank, map_is_task, flow_sel, flow_cnt;
-    DBuf<unsigned char> map_itype, map_tmp;
-    DBuf<uint64_t> map_scratch;  // device vector behind ks_get_task_mapping
-    DBuf<ks_flow> flow_recs;
-    // ---- cell solver (ks_cell.h): one workgroup per small graph
-    bool cell_layout = false;           // the CSR was built cell-major (the cell solver's node order)
-    std::vector<int64_t> cell_off;      // node-id partition into independent cells (ks_batch); empty: one
-    std::vector<CellDesc> h_cells;      // per cell: its class bounds in internal ids
-    int cell_max = 0;                   // largest cell (node slots)
-    DBuf<CellDesc> cells;
-    DBuf<int> cl_lists, cl_rln;
-    DBuf<long long> cl_rlp;
-    DBuf<CellOut> cl_out;
-    DBuf<CellPos> cl_pos;               // compact positions (k_cell_pack / k_cell_unpack)
-    DBuf<int> cl_bad;
-    bool cell_refused = false;          // the graph's values do not fit the compact record: engine until reload
-    size_t lds_limit = 0;               // the device's opt-in LDS per workgroup (sizes the cells)
-    bool fb_active = false;             // a per-cell fallback solve is running (engine order, failing cells cold)
-    std::vector<int> fb_cells;          // the cells it re-solves
-    DBuf<long long> fb_rng;             // their node-slot ranges on the device
-    DBuf<unsigned long long> fb_cnt;    // arc + node slots k_fb_reset restarted cold
-    std::vector<CellOut> h_cell_out;
-    // ---- scheduler-side sweeps (ks_sched.hip)
-    DBuf<int> sched_i;                  // int scratch
-    DBuf<unsigned long long> sched_u;   // u64 scratch
-    DBuf<unsigned char> sched_b;        // byte scratch
-    DBuf<ks_sched_delta> sched_d;
-    DBuf<int> cm_i;                     // ks_commit_schedule: places, chunk items, arc flags and their scans
-    DBuf<unsigned long long> cm_u;      //   per node slot: aggregator / PU counts, slots and running below
-    DBuf<unsigned char> cm_b;           //   per node slot: aggregator / placed flags
-    DBuf<CommitCtl> cm_ctl;
-
-    SchedDev schd() const {
-        SchedDev d{};
-        d.ncap = (int)ncap;
-        d.nstore = nstore;
-        d.perm = perm.p;
-        d.iperm = iperm.p;
-        d.n_alive = n_alive.p;
-        d.n_type = n_type.p;
-        d.n_bind = n_bind.p;
-        d.hi = h_sctl ? h_sctl->hi : 0;
-        d.a_alive = a_alive.p;
-        d.a_type = a_type.p;
-        d.a_src = a_src.p;
-        d.a_dst = a_dst.p;
-        d.a_low = a_low.p;
-        d.a_cap = a_cap.p;
-        d.a_cost = a_cost.p;
-        d.fwd = fwd.p;
-        d.first = first.p;
-        d.used = used.p;
-        d.pos = pos.p;
-        d.ent = ent.p;
-        d.mult = mult;
-        d.csr_valid = csr_valid ? 1 : 0;
-        return d;
-    }
-
-    ~EngineImpl() {
-        if (stream) {
-            (void)hipSetDevice(device);
-            (void)hipStreamSynchronize(stream);
-        }
-        n_supply.release(); n_type.release(); n_alive.release(); n_fresh.release(); n_cshift.release(); n_lastrm.release();
-        n_hint.release(); n_grow.release(); n_bind.release(); a_type.release(); sched_i.release(); sched_u.release();
-        sched_b.release(); sched_d.release(); cm_i.release(); cm_u.release(); cm_b.release(); cm_ctl.release();
-        a_src.release(); a_dst.release(); fwd.release(); free_stack.release(); a_low.release(); a_cap.release();
-        a_cost.release(); a_alive.release(); hkey.release(); hval.release(); hlast.release(); sctl.release();
-        d_recs.release(); d_edits.release(); rec_ent.release();
-        first.release(); pos.release(); ent.release(); used.release(); scur.release(); perm.release(); iperm.release();
-        excess.release(); nd.release(); cpos.release(); crev.release(); cyc.release(); cyc64.release();
-        keys_in.release(); keys_out.release(); vals_in.release(); vals_out.release(); pos_of.release(); deg.release();
-        capv.release(); capi.release(); rs.release(); sort_tmp.release(); cls.release(); nsel.release();
-        for (auto& b : cls_list) b.release();
-        sel_tmp.release(); hitems.release(); citems.release(); hnchunks.release(); q_unsat.release(); q_arrive.release();
-        q_req.release(); q_taken.release(); q_min.release(); inbox.release(); part.release(); flows.release(); vbal.release();
-        flags.release(); hubflags.release(); ctr.release(); xl.release(); xl2.release(); bx.release(); fl.release(); fdef.release(); aug_req.release(); ctl.release(); saved_flows.release(); p_slot.release();
-        map_outv.release(); map_inv.release(); map_outs.release(); map_ins.release(); map_rank.release();
-        map_is_task.release(); flow_sel.release(); flow_cnt.release(); map_itype.release(); map_tmp.release();
-        map_scratch.release(); flow_recs.release();
-        cells.release(); cl_lists.release(); cl_rln.release(); cl_rlp.release(); cl_out.release(); cl_pos.release();
-        cl_bad.release(); fb_rng.release();
-        if (h_ctl) (void)hipHostFree(h_ctl);
-        for (auto* h : h_cyc)
-            if (h) (void)hipHostFree(h);
-        for (auto& c : cev)
-            for (auto& e : c)
-                if (e) (void)hipEventDestroy(e);
-        for (auto& c : fev)
-            for (auto& e : c)
-                if (e) (void)hipEventDestroy(e);
-        for (auto& e : cdone)
-            if (e) (void)hipEventDestroy(e);
-        if (cstart) (void)hipEventDestroy(cstart);
-        if (h_scr) (void)hipHostFree(h_scr);
-        if (h_sctl) (void)hipHostFree(h_sctl);
-        for (auto& e : ev)
-            if (e) (void)hipEventDestroy(e);
-        for (auto& e : kev)
-            if (e) (void)hipEventDestroy(e);
-        for (auto& e : fin_ev)
-            if (e) (void)hipEventDestroy(e);
-        fb_cnt.release();
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-
-    StoreDev sd() const {
-        StoreDev d{};
-        d.ncap = (int)ncap;
-        d.n_supply = n_supply.p;
-        d.n_type = n_type.p;
-        d.n_alive = n_alive.p;
-        d.n_fresh = n_fresh.p;
-        d.n_cshift = n_cshift.p;
-        d.n_lastrm = n_lastrm.p;
-        d.n_grow = n_grow.p;
-        d.n_bind = n_bind.p;
-        d.perm = perm.p;
-        d.acap = (int)acap;
-        d.a_src = a_src.p;
-        d.a_dst = a_dst.p;
-        d.a_low = a_low.p;
-        d.a_cap = a_cap.p;
-        d.a_cost = a_cost.p;
-        d.a_type = a_type.p;
-        d.a_alive = a_alive.p;
-        d.fwd = fwd.p;
-        d.free_stack = free_stack.p;
-        d.hmask = (int)(hcap - 1);
-        d.hkey = hkey.p;
-        d.hval = hval.p;
-        d.hlast = hlast.p;
-        d.nn = nn;
-        d.first = first.p;
-        d.used = used.p;
-        d.scur = scur.p;
-        d.pos = pos.p;
-        d.ent = ent.p;
-        d.excess = excess.p;
-        d.mult = mult;
-        d.csr_valid = csr_valid ? 1 : 0;
-        d.ctl = sctl.p;
-        return d;
-    }
-
-    DG dg() const {
-        DG g{};
-        g.n = nn;
-        g.m = 0;
-        g.hub_base = hub_base;
-        g.first = first.p;
-        g.pos = pos.p;
-        g.excess = excess.p;
-        g.p0 = nd.p;
-        g.p1 = nd.p ? nd.p + 2 : nullptr;
-        g.dist = nd.p ? nd.p + 1 : nullptr;
-        g.inbox = inbox.p;
-        for (int c = 0; c <= NGC; ++c) {
-            g.obeg[c] = obeg[c];
-            g.wbeg[c] = wbeg[c];
-        }
-        for (int c = 0; c < NGC; ++c) g.oend[c] = oend[c];
-        g.hitems = hitems.p;
-        g.nhitems = nhitems;
-        g.citems = citems.p;
-        g.ncitems = ncitems;
-        g.ncls_c = ncls[CCLS];
-        g.sw_clsb = sweep_cls_blocks();
-        g.nheavy = nheavy;
-        g.hnchunks = hnchunks.p;
-        g.xl = xl.p;
-        g.xl2 = xl2.p;
-        g.bx = bx.p;
-        g.fl = fl.p;
-        g.fl_cap = (int)(fl.n / 3);
-        g.fdef = fdef.p;
-        g.npos = (int)m2cap;
-        g.aug_req = aug_req.p;
-        g.q_req = q_req.p;
-        g.q_taken = q_taken.p;
-        g.q_min = q_min.p;
-        g.q_unsat = q_unsat.p;
-        g.q_arrive = q_arrive.p;
-        const int hs = std::max(1, nheavy);
-        const size_t fs = std::max(1, hub_base);
-        for (int k = 0; k < 6; ++k) {
-            Front f{flags.p + k * fs, hubflags.p + (size_t)k * hs};
-            if (k < 3) g.sf[k] = f;
-            else g.bf[k - 3] = f;
-        }
-        g.ctl = ctl.p;
-        g.ctr = ctr.p;
-        return g;
-    }
-    int window_grid() const { return nhitems + std::max(1, (wbeg[NGC] + WPB - 1) / WPB); }
-    // Bellman-Ford rounds: HSPLIT workgroups per hub chunk, then the windows / chunk items
-    int dense_grid() const { return nhitems * HSPLIT + std::max(1, (wbeg[CCLS] + ncitems + WPB - 1) / WPB); }
-    int sweep_cls_blocks() const { return std::max(1, (wbeg[CCLS] + WPW * WPB - 1) / (WPW * WPB)); }
-    // sweeps: hub chunks, class-window blocks, one wave per chunked-class node
-    int sweep_grid() const {
-        return nhitems + sweep_cls_blocks() + ncls[CCLS];
-    }
-    int sparse_grid() const {
-        return nhitems * HSPLIT + std::max(1, (wbeg[CCLS] + ncitems + WPW * WPB - 1) / (WPW * WPB));
-    }
-    int hi() const { return h_sctl->hi; }
-};
-
-#define KS_CHECK(expr)                                                   \
-    do {                                                                 \
-        hipError_t _e = (expr);                                          \
-        if (_e != hipSuccess) {                                          \
-            err = std::string(#expr) + ": " + hipGetErrorString(_e);     \
-            return KS_E_DEVICE;                                          \
-        }                                                                \
-    } while (0)
-
-// A hot kernel of the solve in the record layout the solve reads.
-#define KS_HOT(CPV, K, GRID, BLKS, ST, ...)                                                     \
+// A hot kernel of the solve in the record layout the solve reads;
+// KS_HOT_LDS: with LDS bytes of dynamic shared memory.
+#define KS_HOT_LDS(CPV, K, GRID, BLKS, LDS, ST, ...)                                            \
     do {                                                                                        \
-        if (CPV) K<true><<<dim3(GRID), dim3(BLKS), 0, ST>>>(__VA_ARGS__);                      \
-        else K<false><<<dim3(GRID), dim3(BLKS), 0, ST>>>(__VA_ARGS__);                         \
+        if (CPV) K<true><<<dim3(GRID), dim3(BLKS), LDS, ST>>>(__VA_ARGS__);                    \
+        else K<false><<<dim3(GRID), dim3(BLKS), LDS, ST>>>(__VA_ARGS__);                       \
     } while (0)
+#define KS_HOT(CPV, K, GRID, BLKS, ST, ...) KS_HOT_LDS(CPV, K, GRID, BLKS, 0, ST, __VA_ARGS__)
 
 Engine::Engine() : p_(new EngineImpl) {}
 Engine::~Engine() { delete p_; }
@@ -3648,7 +2801,6 @@ int Engine::init(int device, const ks_opts& opts, std::string& err) {
     for (auto& c : s.fev)
         for (auto& e : c) KS_CHECK(hipEventCreate(&e));
     for (auto& e : s.cdone) KS_CHECK(hipEventCreate(&e));
-    KS_CHECK(hipEventCreate(&s.cstart));
     for (int i = 0; i < CYC_SLOTS; ++i) {
         KS_CHECK(hipHostMalloc(&s.h_cyc[i], sizeof(Ctl), hipHostMallocCoherent | hipHostMallocMapped));
         std::memset(s.h_cyc[i], 0, sizeof(Ctl));
@@ -3663,483 +2815,8 @@ int Engine::init(int device, const ks_opts& opts, std::string& err) {
     KS_CHECK(s.sctl.ensure(1));
     KS_CHECK(hipMemset(s.sctl.p, 0, sizeof(StoreCtl)));
     KS_CHECK(hipHostMalloc(&s.h_ctl, sizeof(Ctl)));
-    KS_CHECK(hipHostMalloc(&s.h_scr, 4 * sizeof(long long)));
     KS_CHECK(hipHostMalloc(&s.h_sctl, sizeof(StoreCtl)));
     std::memset(s.h_sctl, 0, sizeof(StoreCtl));
-    return KS_OK;
-}
-
-// ------------------------------------------------------------------ store ---
-static int read_sctl(EngineImpl& s, std::string& err) {
-    KS_CHECK(hipMemcpyAsync(s.h_sctl, s.sctl.p, sizeof(StoreCtl), hipMemcpyDeviceToHost, s.stream));
-    KS_CHECK(hipStreamSynchronize(s.stream));
-    return KS_OK;
-}
-
-// Node store covers slots [0, need).
-static int ensure_nodes(EngineImpl& s, int64_t need, std::string& err) {
-    if (need <= s.nstore) return KS_OK;
-    const int64_t cap = std::max<int64_t>(need + need / 8 + 64, 1024);
-    hipStream_t st = s.stream;
-    KS_CHECK(s.n_supply.grow(cap, s.nstore, 0, st));
-    KS_CHECK(s.n_type.grow(cap, s.nstore, 0, st));
-    KS_CHECK(s.n_alive.grow(cap, s.nstore, 0, st));
-    KS_CHECK(s.n_fresh.grow(cap, s.nstore, 0, st));
-    KS_CHECK(s.n_cshift.grow(cap, s.nstore, 0, st));
-    KS_CHECK(s.n_lastrm.grow(cap, s.nstore, 0xff, st));
-    KS_CHECK(s.n_hint.grow(cap, s.nstore, 0, st));
-    KS_CHECK(s.n_grow.grow(cap, s.nstore, 0, st));
-    KS_CHECK(s.n_bind.grow(cap, s.nstore, 0, st));
-    s.nstore = cap;
-    return KS_OK;
-}
-
-// Arc table holds slots [0, need).
-static int ensure_arcs(EngineImpl& s, int64_t need, std::string& err) {
-    if (need <= s.acap) return KS_OK;
-    if (need >= (1LL << 30)) {
-        err = "arc table beyond 2^30 slots";
-        return KS_E_RANGE;
-    }
-    const int64_t cap = std::max<int64_t>(need + need / 4 + 64, 4096);
-    hipStream_t st = s.stream;
-    const int64_t keep = s.acap;
-    KS_CHECK(s.a_src.grow(cap, keep, 0, st));
-    KS_CHECK(s.a_dst.grow(cap, keep, 0, st));
-    KS_CHECK(s.a_low.grow(cap, keep, 0, st));
-    KS_CHECK(s.a_cap.grow(cap, keep, 0, st));
-    KS_CHECK(s.a_cost.grow(cap, keep, 0, st));
-    KS_CHECK(s.a_alive.grow(cap, keep, 0, st));
-    KS_CHECK(s.a_type.grow(cap, keep, 0, st));
-    KS_CHECK(s.fwd.grow(cap, keep, 0xff, st));
-    KS_CHECK(s.free_stack.grow(cap, keep, 0, st));
-    KS_CHECK(s.flows.grow(cap, keep, 0, st));
-    s.acap = cap;
-    return KS_OK;
-}
-
-// Hash index with room for `extra` more keys at load ≤ 1/2 (tombstones count).
-static int ensure_hash(EngineImpl& s, int64_t extra, std::string& err) {
-    const int64_t live = s.h_sctl->live, tombs = s.h_sctl->tombs;
-    if (s.hcap && 2 * (live + tombs + extra) <= s.hcap) return KS_OK;
-    int64_t cap = s.hcap ? s.hcap : 1024;
-    while (cap < 4 * (live + extra) + 1024) cap <<= 1;
-    if (cap > (1LL << 31)) {
-        err = "hash index beyond 2^31 entries";
-        return KS_E_RANGE;
-    }
-    KS_CHECK(s.hkey.ensure(cap));
-    KS_CHECK(s.hval.ensure(cap));
-    KS_CHECK(s.hlast.ensure(cap));
-    s.hcap = cap;
-    KS_CHECK(store_rehash(s.sd(), s.stream));
-    return read_sctl(s, err);
-}
-
-// After store_apply and read_sctl: the store's overflow word.
-static int applied(EngineImpl& s, std::string& err) {
-    if (s.h_sctl->overflow & 12) {
-        err = "store index or table exhausted";
-        return KS_E_DEVICE;
-    }
-    if (s.h_sctl->overflow) {   // a full segment or a node beyond the build: rebuild from the table
-        s.csr_valid = false;
-        KS_CHECK(hipMemsetAsync(&s.sctl.p->overflow, 0, sizeof(int), s.stream));
-        s.h_sctl->overflow = 0;
-    }
-    return KS_OK;
-}
-
-static int run_apply(EngineImpl& s, const NodeEdit* edits, size_t ne, const ks_delta* recs, size_t k,
-                     std::string& err) {
-    hipStream_t st = s.stream;
-    size_t narc = 0;
-    for (size_t i = 0; i < k; ++i) narc += recs[i].kind == KS_ADD_ARC || recs[i].kind == KS_UPDATE_ARC;
-    int rc = ensure_arcs(s, (int64_t)s.hi() + (int64_t)narc, err);
-    if (rc == KS_OK) rc = ensure_hash(s, (int64_t)narc, err);
-    if (rc) return rc;
-    KS_CHECK(s.d_recs.ensure(std::max<size_t>(k, 1)));
-    KS_CHECK(s.rec_ent.ensure(std::max<size_t>(k, 1)));
-    KS_CHECK(s.d_edits.ensure(std::max<size_t>(ne, 1)));
-    const auto t0 = std::chrono::steady_clock::now();
-    if (k) KS_CHECK(hipMemcpyAsync(s.d_recs.p, recs, k * sizeof(ks_delta), hipMemcpyHostToDevice, st));
-    if (ne) KS_CHECK(hipMemcpyAsync(s.d_edits.p, edits, ne * sizeof(NodeEdit), hipMemcpyHostToDevice, st));
-    const auto t1 = std::chrono::steady_clock::now();
-    KS_CHECK(store_apply(s.sd(), s.d_recs.p, (int)k, s.rec_ent.p, s.d_edits.p, (int)ne, st));
-    rc = read_sctl(s, err);
-    if (rc) return rc;
-    if (s.opts.log_cycles) {
-        const auto t2 = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "apply: upload call %.3f ms (%.1f MB), store kernels + wait %.3f ms\n",
-                     std::chrono::duration<double, std::milli>(t1 - t0).count(),
-                     1e-6 * (double)(k * sizeof(ks_delta) + ne * sizeof(NodeEdit)),
-                     std::chrono::duration<double, std::milli>(t2 - t1).count());
-    }
-    rc = applied(s, err);
-    if (rc) return rc;
-    if (k || ne) s.solved = false;
-    return KS_OK;
-}
-
-int Engine::load(int64_t nslots, const int64_t* supply, const uint8_t* type, const uint8_t* alive, const ks_arc* arcs,
-                 size_t m, std::string& err) {
-    EngineImpl& s = *p_;
-    KS_CHECK(hipSetDevice(s.device));
-    hipStream_t st = s.stream;
-    if (nslots >= (1LL << 30) || m >= (1ULL << 29)) {
-        err = "graph too large for 32-bit CSR indices";
-        return KS_E_RANGE;
-    }
-    int rc = ensure_nodes(s, std::max<int64_t>(nslots, 1), err);
-    if (rc) return rc;
-    s.nslots = nslots;
-    // empty store
-    KS_CHECK(hipMemsetAsync(s.n_alive.p, 0, s.nstore, st));
-    KS_CHECK(hipMemsetAsync(s.n_supply.p, 0, s.nstore * sizeof(long long), st));
-    KS_CHECK(hipMemsetAsync(s.n_type.p, 0, s.nstore, st));
-    KS_CHECK(hipMemsetAsync(s.n_fresh.p, 0, s.nstore, st));
-    KS_CHECK(hipMemsetAsync(s.n_cshift.p, 0, s.nstore * sizeof(unsigned long long), st));
-    KS_CHECK(hipMemsetAsync(s.n_hint.p, 0, s.nstore * sizeof(int), st));
-    KS_CHECK(hipMemsetAsync(s.n_grow.p, 0, s.nstore, st));
-    KS_CHECK(hipMemsetAsync(s.n_bind.p, 0, s.nstore * sizeof(unsigned long long), st));
-    if (nslots) {
-        KS_CHECK(hipMemcpyAsync(s.n_supply.p, supply, nslots * sizeof(long long), hipMemcpyHostToDevice, st));
-        KS_CHECK(hipMemcpyAsync(s.n_type.p, type, nslots, hipMemcpyHostToDevice, st));
-        KS_CHECK(hipMemcpyAsync(s.n_alive.p, alive, nslots, hipMemcpyHostToDevice, st));
-    }
-    if (s.acap) {
-        KS_CHECK(hipMemsetAsync(s.a_alive.p, 0, s.acap, st));
-        KS_CHECK(hipMemsetAsync(s.fwd.p, 0xff, s.acap * sizeof(int), st));
-        KS_CHECK(hipMemsetAsync(s.a_low.p, 0, s.acap * sizeof(long long), st));
-    }
-    KS_CHECK(hipMemsetAsync(s.sctl.p, 0, sizeof(StoreCtl), st));
-    std::memset(s.h_sctl, 0, sizeof(StoreCtl));
-    s.csr_valid = false;
-    s.incremental = false;
-    s.rebuilds = 0;
-    s.solved = false;
-    s.has_prev = false;
-    s.cell_refused = false;
-    rc = ensure_arcs(s, (int64_t)m, err);
-    if (rc) return rc;
-    if (s.hcap) {   // clear the index (keeps its size)
-        KS_CHECK(hipMemsetAsync(s.hkey.p, 0, s.hcap * sizeof(unsigned long long), st));
-        KS_CHECK(hipMemsetAsync(s.hval.p, 0xff, s.hcap * sizeof(int), st));
-        KS_CHECK(hipMemsetAsync(s.hlast.p, 0xff, s.hcap * sizeof(int), st));
-    }
-    // the arcs enter as ADD_ARC records of one stream (duplicates: the last wins)
-    std::vector<ks_delta> recs(m);
-    for (size_t i = 0; i < m; ++i) {
-        ks_delta& d = recs[i];
-        std::memset(&d, 0, sizeof(d));
-        d.kind = KS_ADD_ARC;
-        d.type = arcs[i].type;
-        d.src = arcs[i].src;
-        d.dst = arcs[i].dst;
-        d.low = arcs[i].low;
-        d.cap = arcs[i].cap;
-        d.cost = arcs[i].cost;
-    }
-    return run_apply(s, nullptr, 0, recs.data(), m, err);
-}
-
-int Engine::apply(const NodeEdit* edits, size_t ne, const ks_delta* recs, size_t k, int64_t nslots,
-                  std::string& err) {
-    EngineImpl& s = *p_;
-    KS_CHECK(hipSetDevice(s.device));
-    int rc = ensure_nodes(s, std::max<int64_t>(nslots, 1), err);
-    if (rc) return rc;
-    s.nslots = std::max(s.nslots, nslots);
-    s.incremental = true;
-    return run_apply(s, edits, ne, recs, k, err);
-}
-
-int64_t Engine::live_arcs() const { return p_->h_sctl ? p_->h_sctl->live : 0; }
-bool Engine::solved() const { return p_->solved; }
-
-void Engine::store_stats(ks_store_stats* o) const {
-    const EngineImpl& s = *p_;
-    std::memset(o, 0, sizeof(*o));
-    if (!s.h_sctl) return;
-    o->live_arcs = s.h_sctl->live;
-    o->inserted = s.h_sctl->inserted;
-    o->updated = s.h_sctl->updated;
-    o->killed = s.h_sctl->killed;
-    o->superseded = s.h_sctl->superseded;
-    o->rebuilds = s.rebuilds;
-    o->residual_slots = s.m2cap;
-}
-
-// Cell-major internal ids for the cell solver (ks_cell.h): every cell (a ks_batch
-// graph, or the whole graph) is one contiguous id range, its nodes grouped by the
-// cell solver's degree classes (cell_class of the segment capacity). Slots past the
-// partition belong to the last cell. Computed on the host from the capacities.
-static int cell_order(EngineImpl& s, int64_t ncap, std::string& err) {
-    hipStream_t st = s.stream;
-    std::vector<int> capv(ncap);
-    if (ncap) KS_CHECK(hipMemcpyAsync(capv.data(), s.capv.p, ncap * sizeof(int), hipMemcpyDeviceToHost, st));
-    KS_CHECK(hipStreamSynchronize(st));
-    const size_t k = s.cell_off.size() >= 2 ? s.cell_off.size() - 1 : 1;
-    std::vector<int64_t> bound(k + 1, 0);   // slot bounds of each cell
-    for (size_t i = 1; i < k; ++i) bound[i] = std::min<int64_t>(ncap, std::max<int64_t>(0, s.cell_off[i]));
-    bound[k] = ncap;
-    std::vector<int> cnt(k * CELL_NCLS, 0);
-    std::vector<unsigned char> cls(ncap);
-    for (size_t c = 0; c < k; ++c)
-        for (int64_t v = bound[c]; v < bound[c + 1]; ++v) {
-            cls[v] = (unsigned char)cell_class(capv[v]);
-            ++cnt[c * CELL_NCLS + cls[v]];
-        }
-    s.h_cells.assign(k, CellDesc{});
-    std::vector<int> next(k * CELL_NCLS);
-    int o = 0, mx = 0;
-    for (size_t c = 0; c < k; ++c) {
-        const int b = o;
-        for (int q = 0; q < CELL_NCLS; ++q) {
-            s.h_cells[c].cb[q] = o;
-            next[c * CELL_NCLS + q] = o;
-            o += cnt[c * CELL_NCLS + q];
-        }
-        s.h_cells[c].cb[CELL_NCLS] = o;
-        mx = std::max(mx, o - b);
-    }
-    std::vector<int> perm(ncap);
-    for (size_t c = 0; c < k; ++c)
-        for (int64_t v = bound[c]; v < bound[c + 1]; ++v) perm[v] = next[c * CELL_NCLS + cls[v]]++;
-    if (ncap) KS_CHECK(hipMemcpyAsync(s.perm.p, perm.data(), ncap * sizeof(int), hipMemcpyHostToDevice, st));
-    s.cell_max = mx;
-    for (int c = 0; c <= NGC; ++c) s.ncls[c] = 0;
-    for (int c = 0; c <= NGC; ++c) s.obeg[c] = s.wbeg[c] = 0;
-    for (int c = 0; c < NGC; ++c) s.oend[c] = 0;
-    s.nheavy = 0;
-    s.hub_base = (int)ncap;
-    s.nn = (int)ncap;
-    const int nn = (int)ncap;
-    KS_CHECK(s.cells.ensure(k));
-    KS_CHECK(hipMemcpyAsync(s.cells.p, s.h_cells.data(), k * sizeof(CellDesc), hipMemcpyHostToDevice, st));
-    KS_CHECK(s.cl_lists.ensure(2 * (size_t)std::max(nn, 1)));
-    KS_CHECK(s.cl_rln.ensure(std::max(nn, 1)));
-    KS_CHECK(s.cl_rlp.ensure(std::max(nn, 1)));
-    KS_CHECK(s.cl_out.ensure(k));
-    KS_CHECK(s.cl_bad.ensure(1));
-    s.h_cell_out.resize(k);
-    return KS_OK;
-}
-
-// ------------------------------------------------------------------ build ---
-static int build(EngineImpl& s, std::string& err) {
-    hipStream_t st = s.stream;
-    const int hi = s.hi();
-    const int64_t spare = s.incremental ? std::max<int64_t>(64, s.nslots / 16) : 0;
-    const int64_t ncap = s.nslots + spare;
-    int rc = ensure_nodes(s, ncap, err);
-    if (rc) return rc;
-    s.ncap = ncap;
-    s.mult = ncap + 1;
-    KS_CHECK(s.deg.ensure(std::max<int64_t>(ncap, 1)));
-    KS_CHECK(s.capv.ensure(std::max<int64_t>(ncap, 1)));
-    KS_CHECK(s.cls.ensure(std::max<int64_t>(ncap, 1)));
-    KS_CHECK(s.perm.ensure(std::max<int64_t>(ncap, 1)));
-    for (auto& b : s.cls_list) KS_CHECK(b.ensure(std::max<int64_t>(ncap, 1)));
-    KS_CHECK(s.nsel.ensure(NGC + 1));
-    KS_CHECK(s.part.ensure(2 * 4096));
-    KS_CHECK(hipMemsetAsync(s.deg.p, 0, ncap * sizeof(int), st));
-    // 1. degrees → segment capacities → classes
-    if (hi)
-        hipLaunchKernelGGL(k_degree, dim3(grid_for(hi)), dim3(BLK), 0, st, hi, (const unsigned char*)s.a_alive.p,
-                           (const int*)s.a_src.p, (const int*)s.a_dst.p, s.deg.p);
-    hipLaunchKernelGGL(k_capacity, dim3(grid_for(ncap)), dim3(BLK), 0, st, (int)ncap, (int)s.nstore,
-                       (const int*)s.deg.p, (const unsigned char*)s.n_alive.p, (const unsigned char*)s.n_type.p,
-                       s.incremental ? 1 : 0, s.n_hint.p,
-                       s.n_grow.p, s.capv.p, s.cls.p);
-    if (s.cell_layout) {
-        int rc = cell_order(s, ncap, err);   // perm, cell descriptors; no lane-group classes or hubs
-        if (rc) return rc;
-    } else {
-        {
-            hipcub::CountingInputIterator<int> it(0);
-            size_t tmp = 0, t2 = 0;
-            for (unsigned char c = 0; c <= NGC; ++c) {
-                KS_CHECK(hipcub::DeviceSelect::If(nullptr, t2, it, s.cls_list[c].p, s.nsel.p + c, (int)ncap,
-                                                  ClassIs{s.cls.p, c}, st));
-                tmp = std::max(tmp, t2);
-            }
-            KS_CHECK(s.sel_tmp.ensure(tmp));
-            for (unsigned char c = 0; c <= NGC; ++c) {
-                t2 = tmp;
-                KS_CHECK(hipcub::DeviceSelect::If(s.sel_tmp.p, t2, it, s.cls_list[c].p, s.nsel.p + c, (int)ncap,
-                                                  ClassIs{s.cls.p, c}, st));
-            }
-        }
-        KS_CHECK(hipMemcpyAsync(s.ncls, s.nsel.p, (NGC + 1) * sizeof(int), hipMemcpyDeviceToHost, st));
-        KS_CHECK(hipStreamSynchronize(st));
-        s.nheavy = s.ncls[NGC];
-        // 2. internal ids: classes in order, each padded to whole 64-node blocks, hubs last
-        {
-            int o = 0, wv = 0;
-            for (int c = 0; c < NGC; ++c) {
-                s.obeg[c] = o;
-                s.oend[c] = o + s.ncls[c];
-                s.wbeg[c] = wv;
-                const int pad = (s.ncls[c] + 63) / 64 * 64;
-                o += pad;
-                wv += pad / win_slots(c);
-            }
-            s.obeg[NGC] = o;
-            s.wbeg[NGC] = wv;
-            s.hub_base = o;
-            s.nn = o + s.nheavy;
-        }
-        for (int c = 0; c <= NGC; ++c)
-            if (s.ncls[c])
-                hipLaunchKernelGGL(k_make_perm, dim3(grid_for(s.ncls[c])), dim3(BLK), 0, st, s.ncls[c],
-                                   c < NGC ? s.obeg[c] : s.hub_base, (const int*)s.cls_list[c].p, s.perm.p);
-    }
-    const int nn = s.nn;
-    KS_CHECK(s.capi.ensure(nn + 1));
-    KS_CHECK(s.iperm.ensure(nn + 1));
-    KS_CHECK(s.first.ensure(nn + 1));
-    KS_CHECK(s.used.ensure(std::max(nn, 1)));
-    KS_CHECK(s.scur.ensure(std::max(nn, 1)));
-    KS_CHECK(hipMemsetAsync(s.scur.p, 0, std::max(nn, 1) * sizeof(int), st));
-    KS_CHECK(s.rs.ensure(nn + 1));
-    KS_CHECK(hipMemsetAsync(s.capi.p, 0, (nn + 1) * sizeof(int), st));
-    KS_CHECK(hipMemsetAsync(s.iperm.p, 0xff, (nn + 1) * sizeof(int), st));
-    hipLaunchKernelGGL(k_capi, dim3(grid_for(ncap)), dim3(BLK), 0, st, (int)ncap, (const int*)s.perm.p,
-                       (const int*)s.capv.p, s.capi.p, s.iperm.p);
-    {   // first = exclusive scan of the capacities (nn + 1 entries: first[nn] = Σ)
-        size_t t = 0;
-        KS_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, t, s.capi.p, s.first.p, nn + 1, st));
-        KS_CHECK(s.sort_tmp.ensure(std::max<size_t>(t, s.sort_tmp.n)));
-        t = s.sort_tmp.n;
-        KS_CHECK(hipcub::DeviceScan::ExclusiveSum(s.sort_tmp.p, t, s.capi.p, s.first.p, nn + 1, st));
-    }
-    int m2c = 0;
-    KS_CHECK(hipMemcpyAsync(&m2c, s.first.p + nn, sizeof(int), hipMemcpyDeviceToHost, st));
-    KS_CHECK(hipStreamSynchronize(st));
-    s.m2cap = m2c;
-    const int64_t m2cap = std::max<int64_t>(m2c, 1);
-    KS_CHECK(s.pos.ensure(m2cap));
-    KS_CHECK(s.ent.ensure(m2cap));
-    KS_CHECK(s.excess.ensure(std::max(nn, 1)));
-    KS_CHECK(s.nd.ensure(4 * (size_t)std::max(nn, 1)));
-    if (nn)
-        hipLaunchKernelGGL(k_node_bounds, dim3(grid_for(nn)), dim3(BLK), 0, st, nn, (const int*)s.first.p, s.nd.p);
-    if (m2c)
-        hipLaunchKernelGGL(k_inert_all, dim3(grid_for(m2c)), dim3(BLK), 0, st, (long long)m2c, nn,
-                           (const int*)s.first.p, s.pos.p, s.ent.p);
-    // 3. live arcs into their segments, ordered by tail (radix sort of 2·hi keys)
-    const int64_t m2 = 2 * (int64_t)hi;
-    if (s.acap) KS_CHECK(hipMemsetAsync(s.fwd.p, 0xff, s.acap * sizeof(int), st));
-    if (m2) {
-        KS_CHECK(s.keys_in.ensure(m2));
-        KS_CHECK(s.keys_out.ensure(m2));
-        KS_CHECK(s.vals_in.ensure(m2));
-        KS_CHECK(s.vals_out.ensure(m2));
-        KS_CHECK(s.pos_of.ensure(m2));
-        int bits = 1;
-        while ((1LL << bits) <= nn + 1) ++bits;
-        hipLaunchKernelGGL(k_pos_keys, dim3(grid_for(hi)), dim3(BLK), 0, st, hi, nn,
-                           (const unsigned char*)s.a_alive.p, (const int*)s.a_src.p, (const int*)s.a_dst.p,
-                           (const int*)s.perm.p, s.keys_in.p, s.vals_in.p);
-        size_t t = 0;
-        KS_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, t, s.keys_in.p, s.keys_out.p, s.vals_in.p,
-                                                    s.vals_out.p, (int)m2, 0, bits, st));
-        KS_CHECK(s.sort_tmp.ensure(std::max<size_t>(t, s.sort_tmp.n)));
-        t = s.sort_tmp.n;
-        KS_CHECK(hipcub::DeviceRadixSort::SortPairs(s.sort_tmp.p, t, s.keys_in.p, s.keys_out.p, s.vals_in.p,
-                                                    s.vals_out.p, (int)m2, 0, bits, st));
-        hipLaunchKernelGGL(k_first, dim3(grid_for(nn + 1)), dim3(BLK), 0, st, nn, (long long)m2,
-                           (const unsigned*)s.keys_out.p, s.rs.p);
-        hipLaunchKernelGGL(k_fill_csr, dim3(grid_for(m2)), dim3(BLK), 0, st, (long long)m2, nn,
-                           (const unsigned*)s.keys_out.p, (const int*)s.vals_out.p, (const int*)s.rs.p,
-                           (const int*)s.first.p, (const int*)s.perm.p, (const int*)s.a_src.p, (const int*)s.a_dst.p,
-                           (const long long*)s.a_low.p, (const long long*)s.a_cap.p, (const long long*)s.a_cost.p,
-                           s.mult, s.pos.p, s.ent.p, s.fwd.p, s.pos_of.p);
-        hipLaunchKernelGGL(k_fill_rev, dim3(grid_for(m2)), dim3(BLK), 0, st, (long long)m2, nn,
-                           (const unsigned*)s.keys_out.p, (const int*)s.vals_out.p, (const int*)s.pos_of.p, s.pos.p);
-        hipLaunchKernelGGL(k_used, dim3(grid_for(nn)), dim3(BLK), 0, st, nn, (const int*)s.rs.p, s.used.p);
-    } else {
-        KS_CHECK(hipMemsetAsync(s.used.p, 0, std::max(nn, 1) * sizeof(int), st));
-    }
-    // 4. hub chunk table and the chunked class's 64-arc chunks (from the segments)
-    {
-        std::vector<int> hf(s.nheavy + 1);
-        if (s.nheavy) {
-            KS_CHECK(hipMemcpyAsync(hf.data(), s.first.p + s.hub_base, (s.nheavy + 1) * sizeof(int),
-                                    hipMemcpyDeviceToHost, st));
-            KS_CHECK(hipStreamSynchronize(st));
-        }
-        std::vector<HItem> items;
-        std::vector<int> nch(s.nheavy);
-        for (int h = 0; h < s.nheavy; ++h) {
-            int c = 0;
-            for (int b = hf[h]; b < hf[h + 1]; b += CHUNK, ++c)
-                items.push_back(HItem{s.hub_base + h, h, b, std::min(b + CHUNK, hf[h + 1])});
-            nch[h] = c;
-        }
-        s.nhitems = (int)items.size();
-        KS_CHECK(s.hitems.ensure(items.size()));
-        KS_CHECK(s.hnchunks.ensure(s.nheavy));
-        KS_CHECK(s.inbox.ensure((size_t)s.nheavy * SHARDS));
-        KS_CHECK(s.flags.ensure(6 * (size_t)std::max(1, s.hub_base)));
-        KS_CHECK(s.fl.ensure(3 * ((size_t)std::max(1, s.nn) + 4096)));
-        KS_CHECK(s.hubflags.ensure(6 * (size_t)std::max(1, s.nheavy)));
-        KS_CHECK(hipMemsetAsync(s.flags.p, 0, 6 * (size_t)std::max(1, s.hub_base), st));
-        KS_CHECK(hipMemsetAsync(s.hubflags.p, 0, 6 * (size_t)std::max(1, s.nheavy) * sizeof(int), st));
-        if (s.nheavy) {
-            KS_CHECK(hipMemcpyAsync(s.hitems.p, items.data(), items.size() * sizeof(HItem), hipMemcpyHostToDevice, st));
-            KS_CHECK(hipMemcpyAsync(s.hnchunks.p, nch.data(), nch.size() * sizeof(int), hipMemcpyHostToDevice, st));
-            KS_CHECK(hipMemsetAsync(s.inbox.p, 0, (size_t)s.nheavy * SHARDS * sizeof(long long), st));
-        }
-        const int c0 = s.obeg[CCLS], cn = s.ncls[CCLS];
-        std::vector<int> cf(cn + 1);
-        if (cn) KS_CHECK(hipMemcpyAsync(cf.data(), s.first.p + c0, (cn + 1) * sizeof(int), hipMemcpyDeviceToHost, st));
-        KS_CHECK(hipStreamSynchronize(st));
-        std::vector<CItem> ci;
-        for (int k = 0; k < cn; ++k)
-            for (int b = cf[k]; b < cf[k + 1]; b += 64)
-                ci.push_back(CItem{c0 + k, b, std::min(b + 64, cf[k + 1]), b == cf[k] ? 1 : 0});
-        s.ncitems = (int)ci.size();
-        KS_CHECK(s.citems.ensure(std::max<size_t>(1, ci.size())));
-        if (!ci.empty())
-            KS_CHECK(hipMemcpyAsync(s.citems.p, ci.data(), ci.size() * sizeof(CItem), hipMemcpyHostToDevice, st));
-        const int nq = std::max(1, s.nheavy);
-        KS_CHECK(s.q_req.ensure(nq));
-        KS_CHECK(s.aug_req.ensure(nq));
-        KS_CHECK(hipMemsetAsync(s.aug_req.p, 0, nq * sizeof(long long), st));
-        KS_CHECK(s.q_taken.ensure(nq));
-        KS_CHECK(s.q_min.ensure(nq));
-        KS_CHECK(s.q_unsat.ensure(nq));
-        KS_CHECK(s.q_arrive.ensure(nq));
-        std::vector<long long> qm(nq, INF64);
-        KS_CHECK(hipMemcpyAsync(s.q_min.p, qm.data(), nq * sizeof(long long), hipMemcpyHostToDevice, st));
-        KS_CHECK(hipMemsetAsync(s.q_req.p, 0, nq * sizeof(long long), st));
-        KS_CHECK(hipMemsetAsync(s.q_taken.p, 0, nq * sizeof(long long), st));
-        KS_CHECK(hipMemsetAsync(s.q_unsat.p, 0, nq * sizeof(int), st));
-        KS_CHECK(hipMemsetAsync(s.q_arrive.p, 0, nq * sizeof(int), st));
-        KS_CHECK(hipStreamSynchronize(st));
-    }
-    s.csr_valid = true;
-    ++s.rebuilds;
-    return KS_OK;
-}
-
-// zero flow, supplies with the lower-bound transform, zero prices
-static int cold_reset(EngineImpl& s, std::string& err) {
-    hipStream_t st = s.stream;
-    const int hi = s.hi();
-    if (s.m2cap)
-        hipLaunchKernelGGL(k_reset_pos, dim3(grid_for(s.m2cap)), dim3(BLK), 0, st, (long long)s.m2cap,
-                           (const int*)s.ent.p, s.pos.p);
-    hipLaunchKernelGGL(k_reset_nodes, dim3(grid_for(s.nn)), dim3(BLK), 0, st, s.nn, (int)s.ncap,
-                       (const int*)s.iperm.p, (const unsigned char*)s.n_alive.p, (const long long*)s.n_supply.p,
-                       s.excess.p, s.nd.p, (s.nd.p + 2));
-    if (hi)
-        hipLaunchKernelGGL(k_reset_low, dim3(grid_for(hi)), dim3(BLK), 0, st, hi, (const unsigned char*)s.a_alive.p,
-                           (const int*)s.a_src.p, (const int*)s.a_dst.p, (const int*)s.perm.p,
-                           (const long long*)s.a_low.p, s.excess.p);
-    KS_CHECK(hipGetLastError());
     return KS_OK;
 }
 
@@ -4178,574 +2855,215 @@ static bool want_cells(const EngineImpl& s) {
     return true;
 }
 
-int Engine::set_nodes(const NodeEdit* edits, size_t ne, std::string& err) {
-    EngineImpl& s = *p_;
-    KS_CHECK(hipSetDevice(s.device));
-    return run_apply(s, edits, ne, nullptr, 0, err);
+// ================================================================== solve ===
+namespace {
+
+// One Bellman-Ford round of kind PR (0: global update; 1: price refinement; 2:
+// refinement with parents, the cycle-cancelling finish) in the solve's record layout.
+template <int PR>
+void launch_bf_round(bool cpv, int grid, hipStream_t st, const DG& g, int seq, int dense) {
+    if (cpv) k_bf_round<PR, true><<<dim3(grid), dim3(BLK), 0, st>>>(g, seq, dense);
+    else k_bf_round<PR, false><<<dim3(grid), dim3(BLK), 0, st>>>(g, seq, dense);
 }
 
-int Engine::task_pu(uint64_t* dev_out, size_t cap, size_t* count, int64_t n_tasks, std::string& err) {
-    EngineImpl& s = *p_;
-    if (!s.solved) {
-        err = "no successful solve";
-        return KS_E_INVALID;
-    }
-    KS_CHECK(hipSetDevice(s.device));
-    hipStream_t st = s.stream;
-    *count = (size_t)n_tasks;
-    if (!dev_out || cap < (size_t)n_tasks || n_tasks == 0) {
-        if (dev_out && cap < (size_t)n_tasks) {
-            err = "output buffer smaller than the task count";
-            return KS_E_INVALID;
-        }
-        return KS_OK;
-    }
-    const int64_t m2 = std::max<int64_t>(s.m2cap, 1), ncap = s.ncap;
-    const int nn = s.nn;
-    KS_CHECK(s.map_outv.ensure(m2));
-    KS_CHECK(s.map_inv.ensure(m2));
-    KS_CHECK(s.map_outs.ensure(m2));
-    KS_CHECK(s.map_ins.ensure(m2));
-    KS_CHECK(s.map_itype.ensure(nn + 1));
-    KS_CHECK(s.map_rank.ensure(ncap + 1));
-    KS_CHECK(s.map_is_task.ensure(ncap + 1));
-    KS_CHECK(hipMemsetAsync(s.map_itype.p, 0, nn + 1, st));
-    if (s.m2cap)
-        hipLaunchKernelGGL(k_unit_vals, dim3(grid_for(s.m2cap)), dim3(BLK), 0, st, (long long)s.m2cap,
-                           (const int*)s.ent.p, (const long long*)s.flows.p, s.map_outv.p, s.map_inv.p);
-    hipLaunchKernelGGL(k_node_meta, dim3(grid_for(ncap)), dim3(BLK), 0, st, (int)ncap, (const int*)s.perm.p,
-                       (const unsigned char*)s.n_type.p, (const unsigned char*)s.n_alive.p, s.map_itype.p,
-                       s.map_is_task.p);
-    size_t t1 = 0, t2 = 0;
-    if (s.m2cap) KS_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, t1, s.map_outv.p, s.map_outs.p, (int)s.m2cap, st));
-    KS_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, t2, s.map_is_task.p, s.map_rank.p, (int)ncap, st));
-    KS_CHECK(s.map_tmp.ensure(std::max(t1, t2)));
-    size_t tt = s.map_tmp.n;
-    if (s.m2cap) {
-        KS_CHECK(hipcub::DeviceScan::ExclusiveSum(s.map_tmp.p, tt, s.map_outv.p, s.map_outs.p, (int)s.m2cap, st));
-        tt = s.map_tmp.n;
-        KS_CHECK(hipcub::DeviceScan::ExclusiveSum(s.map_tmp.p, tt, s.map_inv.p, s.map_ins.p, (int)s.m2cap, st));
-    }
-    tt = s.map_tmp.n;
-    KS_CHECK(hipcub::DeviceScan::ExclusiveSum(s.map_tmp.p, tt, s.map_is_task.p, s.map_rank.p, (int)ncap, st));
-    hipLaunchKernelGGL(k_task_paths, dim3(grid_for(ncap)), dim3(BLK), 0, st, (int)ncap, nn, (const int*)s.perm.p,
-                       (const int*)s.first.p, (const Pos*)s.pos.p,
-                       (const long long*)s.map_outv.p, (const long long*)s.map_outs.p,
-                       (const long long*)s.map_inv.p, (const long long*)s.map_ins.p, (const int*)s.iperm.p,
-                       (const unsigned char*)s.map_itype.p, (const int*)s.map_rank.p,
-                       (const int*)s.map_is_task.p, (long long)cap, (unsigned long long*)dev_out);
-    KS_CHECK(hipGetLastError());
-    KS_CHECK(hipStreamSynchronize(st));
-    return KS_OK;
-}
+// One solve from the state in place, on the stack of Engine::solve. run() is the
+// order of events; the members are what its steps share, by kind: the plan (fixed
+// once plan() has run), the tally (what ends in ks_result) and the running state.
+struct SolveRun {
+    // the engine must take the solve over from the cell solver (Engine::solve runs again)
+    enum Retry { RETRY_NONE, RETRY_RANGE, RETRY_CELLS };
+    enum { CYCLE_NEXT = 0, PHASE_OVER = 1 };   // what a cycle tells its phase (< 0: an error)
 
-int Engine::download(void* host_dst, const void* dev_src, size_t bytes, std::string& err) {
-    EngineImpl& s = *p_;
-    KS_CHECK(hipSetDevice(s.device));
-    if (bytes) {
-        KS_CHECK(hipMemcpyAsync(host_dst, dev_src, bytes, hipMemcpyDeviceToHost, s.stream));
-        KS_CHECK(hipStreamSynchronize(s.stream));
-    }
-    return KS_OK;
-}
-
-int Engine::scratch(uint64_t** dev, size_t n, std::string& err) {
-    EngineImpl& s = *p_;
-    KS_CHECK(hipSetDevice(s.device));
-    KS_CHECK(s.map_scratch.ensure(std::max<size_t>(1, n)));
-    *dev = s.map_scratch.p;
-    return KS_OK;
-}
-
-int Engine::flows(std::vector<ks_flow>& out, std::string& err) {
-    EngineImpl& s = *p_;
-    if (!s.solved) {
-        err = "no successful solve";
-        return KS_E_INVALID;
-    }
-    KS_CHECK(hipSetDevice(s.device));
-    hipStream_t st = s.stream;
-    const int hi = s.hi();
-    out.clear();
-    if (!hi) return KS_OK;
-    KS_CHECK(s.flow_sel.ensure(hi));
-    KS_CHECK(s.flow_cnt.ensure(1));
-    hipcub::CountingInputIterator<int> it(0);
-    FlowPositive pred{s.a_alive.p, s.flows.p};
-    size_t t = 0;
-    KS_CHECK(hipcub::DeviceSelect::If(nullptr, t, it, s.flow_sel.p, s.flow_cnt.p, hi, pred, st));
-    KS_CHECK(s.map_tmp.ensure(std::max(t, s.map_tmp.n)));
-    t = s.map_tmp.n;
-    KS_CHECK(hipcub::DeviceSelect::If(s.map_tmp.p, t, it, s.flow_sel.p, s.flow_cnt.p, hi, pred, st));
-    int cnt = 0;
-    KS_CHECK(hipMemcpyAsync(&cnt, s.flow_cnt.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    KS_CHECK(hipStreamSynchronize(st));
-    if (!cnt) return KS_OK;
-    KS_CHECK(s.flow_recs.ensure(cnt));
-    hipLaunchKernelGGL(k_flow_records, dim3(grid_for(cnt)), dim3(BLK), 0, st, cnt, (const int*)s.flow_sel.p,
-                       (const int*)s.a_src.p, (const int*)s.a_dst.p, (const long long*)s.flows.p, s.flow_recs.p);
-    out.resize(cnt);
-    KS_CHECK(hipMemcpyAsync(out.data(), s.flow_recs.p, cnt * sizeof(ks_flow), hipMemcpyDeviceToHost, st));
-    KS_CHECK(hipStreamSynchronize(st));
-    return KS_OK;
-}
-
-// ------------------------------------------------- scheduler-side sweeps ---
-int Engine::set_bindings(const uint64_t* task, const uint64_t* pu, size_t k, std::string& err) {
-    EngineImpl& s = *p_;
-    KS_CHECK(hipSetDevice(s.device));
-    if (!k) return KS_OK;
-    std::vector<unsigned long long> ids(task, task + k), vals(pu, pu + k);
-    for (size_t i = 0; i < k; ++i)
-        if (ids[i] == 0 || (int64_t)ids[i] > s.nstore) {
-            err = "binding for a task id beyond the graph";
-            return KS_E_INVALID;
-        }
-    KS_CHECK(s.sched_u.ensure(2 * k));
-    hipStream_t st = s.stream;
-    KS_CHECK(hipMemcpyAsync(s.sched_u.p, ids.data(), k * 8, hipMemcpyHostToDevice, st));
-    KS_CHECK(hipMemcpyAsync(s.sched_u.p + k, vals.data(), k * 8, hipMemcpyHostToDevice, st));
-    // the same scatter as the running counts: n_bind[id − 1] = pu
-    KS_CHECK(sched_running_counts(s.schd(), s.sched_u.p, s.sched_u.p + k, (int)k, s.n_bind.p, st));
-    KS_CHECK(hipStreamSynchronize(st));
-    return KS_OK;
-}
-
-int Engine::sched_deltas(int commit, std::vector<ks_sched_delta>* out, size_t* count, int64_t n_tasks,
-                         std::string& err) {
-    EngineImpl& s = *p_;
-    if (!s.solved) {
-        err = "no successful solve";
-        return KS_E_INVALID;
-    }
-    KS_CHECK(hipSetDevice(s.device));
-    hipStream_t st = s.stream;
-    uint64_t* dense = nullptr;
-    size_t nt = 0;
-    int rc = scratch(&dense, std::max<int64_t>(n_tasks, 1), err);
-    if (rc == KS_OK) rc = task_pu(n_tasks ? dense : nullptr, n_tasks, &nt, n_tasks, err);   // also is_task / rank
-    if (rc) return rc;
-    const int64_t ncap = s.ncap;
-    if (!n_tasks) {   // no tasks: map arrays were not built; every binding is a preemption
-        KS_CHECK(s.map_is_task.ensure(ncap + 1));
-        KS_CHECK(s.map_rank.ensure(ncap + 1));
-        KS_CHECK(hipMemsetAsync(s.map_is_task.p, 0, (ncap + 1) * sizeof(int), st));
-        KS_CHECK(hipMemsetAsync(s.map_rank.p, 0, (ncap + 1) * sizeof(int), st));
-    }
-    KS_CHECK(s.sched_i.ensure(4 * (ncap + 1) + 4));
-    int* pre = s.sched_i.p;
-    int* other = pre + (ncap + 1);
-    int* pre_pos = other + (ncap + 1);
-    int* other_pos = pre_pos + (ncap + 1);
-    int* bad = other_pos + (ncap + 1);
-    KS_CHECK(hipMemsetAsync(bad, 0, 4 * sizeof(int), st));
-    const SchedDev d = s.schd();
-    KS_CHECK(sched_delta_kinds(d, s.map_is_task.p, s.map_rank.p, (const unsigned long long*)dense, pre, other, bad, st));
-    size_t t = 0;
-    KS_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, t, pre, pre_pos, (int)ncap + 1, st));
-    KS_CHECK(s.map_tmp.ensure(std::max(t, s.map_tmp.n)));
-    t = s.map_tmp.n;
-    KS_CHECK(hipcub::DeviceScan::ExclusiveSum(s.map_tmp.p, t, pre, pre_pos, (int)ncap + 1, st));
-    t = s.map_tmp.n;
-    KS_CHECK(hipcub::DeviceScan::ExclusiveSum(s.map_tmp.p, t, other, other_pos, (int)ncap + 1, st));
-    int h[3] = {0, 0, 0};
-    KS_CHECK(hipMemcpyAsync(&h[0], pre_pos + ncap, sizeof(int), hipMemcpyDeviceToHost, st));
-    KS_CHECK(hipMemcpyAsync(&h[1], other_pos + ncap, sizeof(int), hipMemcpyDeviceToHost, st));
-    KS_CHECK(hipMemcpyAsync(&h[2], bad, sizeof(int), hipMemcpyDeviceToHost, st));
-    KS_CHECK(hipStreamSynchronize(st));
-    if (h[2]) {
-        err = "mapping names a destination that is not a PU (graph_manager.go:259-262)";
-        return KS_E_VERIFY;
-    }
-    const int npre = h[0], noth = h[1];
-    *count = (size_t)(npre + noth);
-    if (!out) return KS_OK;
-    KS_CHECK(s.sched_d.ensure(std::max(1, npre + noth)));
-    KS_CHECK(sched_delta_emit(d, s.map_rank.p, (const unsigned long long*)dense, pre, pre_pos, other, other_pos, npre,
-                              s.sched_d.p, commit, st));
-    out->resize(npre + noth);
-    if (npre + noth)
-        KS_CHECK(hipMemcpyAsync(out->data(), s.sched_d.p, (npre + noth) * sizeof(ks_sched_delta), hipMemcpyDeviceToHost,
-                                st));
-    KS_CHECK(hipStreamSynchronize(st));
-    return KS_OK;
-}
-
-int Engine::unsched_costs(const uint64_t* ids, size_t k, int mode, int64_t ucost, int64_t ccost, size_t* changed,
-                          std::string& err) {
-    EngineImpl& s = *p_;
-    KS_CHECK(hipSetDevice(s.device));
-    hipStream_t st = s.stream;
-    const int64_t nb = (s.nstore + 4) & ~3LL;   // byte flags, word-aligned for the atomics
-    KS_CHECK(s.sched_b.ensure(nb));
-    KS_CHECK(s.sched_i.ensure(4));
-    KS_CHECK(hipMemsetAsync(s.sched_b.p, 0, nb, st));
-    KS_CHECK(hipMemsetAsync(s.sched_i.p, 0, sizeof(int), st));
-    const unsigned long long* dids = nullptr;
-    if (ids && k) {
-        for (size_t i = 0; i < k; ++i)
-            if (ids[i] == 0 || (int64_t)ids[i] > s.nstore) {
-                err = "unscheduled aggregator id beyond the graph";
-                return KS_E_INVALID;
-            }
-        KS_CHECK(s.sched_u.ensure(k));
-        KS_CHECK(hipMemcpyAsync(s.sched_u.p, ids, k * 8, hipMemcpyHostToDevice, st));
-        dids = s.sched_u.p;
-    }
-    KS_CHECK(sched_unsched_costs(s.schd(), ids ? dids : nullptr, (int)k, s.sched_b.p, mode, ucost, ccost, s.sched_i.p,
-                                 st));
-    int h = 0;
-    KS_CHECK(hipMemcpyAsync(&h, s.sched_i.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    KS_CHECK(hipStreamSynchronize(st));
-    if (changed) *changed = (size_t)h;
-    if (h) s.solved = false;
-    return KS_OK;
-}
-
-// The level-synchronous BFS of ComputeTopologyStatistics from the sink (slot sink_slot <
-// ncap) over the residual CSR's in-arcs; slots / run (per node slot) start zeroed.
-// Uses sched_i.
-static int topo_bfs(EngineImpl& s, const SchedDev& d, int64_t sink_slot, uint64_t mtpp,
-                    const unsigned long long* pu_slots, const unsigned long long* cnt, unsigned long long* slots,
-                    unsigned long long* run, std::string& err) {
-    hipStream_t st = s.stream;
-    const int64_t nn = s.nn;
-    KS_CHECK(s.sched_i.ensure(3 * (nn + 1) + 2));
-    int* lvl = s.sched_i.p;
-    int* fa = lvl + (nn + 1);
-    int* fb = fa + (nn + 1);
-    int* nnext = fb + (nn + 1);
-    KS_CHECK(hipMemsetAsync(lvl, 0xff, (nn + 1) * sizeof(int), st));
-    int sink_x = 0;
-    KS_CHECK(hipMemcpyAsync(&sink_x, s.perm.p + sink_slot, sizeof(int), hipMemcpyDeviceToHost, st));
-    KS_CHECK(hipStreamSynchronize(st));
-    const int zero = 0;
-    KS_CHECK(hipMemcpyAsync(lvl + sink_x, &zero, sizeof(int), hipMemcpyHostToDevice, st));
-    KS_CHECK(hipMemcpyAsync(fa, &sink_x, sizeof(int), hipMemcpyHostToDevice, st));
-    int nfront = 1;
-    for (int level = 0; nfront > 0 && level <= nn; ++level) {
-        KS_CHECK(hipMemsetAsync(nnext, 0, sizeof(int), st));
-        KS_CHECK(sched_topo_level(d, fa, nfront, level, lvl, fb, nnext, mtpp, pu_slots, cnt, slots, run, st));
-        KS_CHECK(hipMemcpyAsync(&nfront, nnext, sizeof(int), hipMemcpyDeviceToHost, st));
-        KS_CHECK(hipStreamSynchronize(st));
-        std::swap(fa, fb);
-    }
-    return KS_OK;
-}
-
-int Engine::topology_stats(uint64_t mtpp, const uint64_t* pu_ids, const uint64_t* pu_running, size_t k,
-                           int64_t sink_slot, uint64_t* slots_below, uint64_t* running_below, std::string& err) {
-    EngineImpl& s = *p_;
-    KS_CHECK(hipSetDevice(s.device));
-    hipStream_t st = s.stream;
-    if (!s.csr_valid) {   // the BFS walks the residual CSR's in-arcs
-        int rc = build(s, err);
-        if (rc) return rc;
-        s.has_prev = false;
-        s.solved = false;
-    }
-    const int64_t ncap = s.ncap;
-    if (sink_slot < 0 || sink_slot >= ncap || ncap == 0) {
-        std::memset(slots_below, 0, s.nslots * sizeof(uint64_t));
-        std::memset(running_below, 0, s.nslots * sizeof(uint64_t));
-        return KS_OK;
-    }
-    KS_CHECK(s.sched_u.ensure(3 * (ncap + 1) + 2 * k));
-    unsigned long long* cnt = s.sched_u.p;
-    unsigned long long* slots = cnt + (ncap + 1);
-    unsigned long long* run = slots + (ncap + 1);
-    unsigned long long* kid = run + (ncap + 1);
-    KS_CHECK(hipMemsetAsync(cnt, 0, 3 * (ncap + 1) * 8, st));
-    if (pu_ids && k) {
-        for (size_t i = 0; i < k; ++i)
-            if (pu_ids[i] == 0 || (int64_t)pu_ids[i] > ncap) {
-                err = "PU id beyond the graph";
-                return KS_E_INVALID;
-            }
-        KS_CHECK(hipMemcpyAsync(kid, pu_ids, k * 8, hipMemcpyHostToDevice, st));
-        KS_CHECK(hipMemcpyAsync(kid + k, pu_running, k * 8, hipMemcpyHostToDevice, st));
-    }
-    const SchedDev d = s.schd();
-    KS_CHECK(sched_running_counts(d, pu_ids ? kid : nullptr, kid + k, (int)k, cnt, st));
-    int rc = topo_bfs(s, d, sink_slot, mtpp, nullptr, cnt, slots, run, err);
-    if (rc) return rc;
-    const int64_t n = std::min<int64_t>(s.nslots, ncap);
-    if (n) {
-        KS_CHECK(hipMemcpyAsync(slots_below, slots, n * 8, hipMemcpyDeviceToHost, st));
-        KS_CHECK(hipMemcpyAsync(running_below, run, n * 8, hipMemcpyDeviceToHost, st));
-        KS_CHECK(hipStreamSynchronize(st));
-    }
-    return KS_OK;
-}
-
-static double ev_ms(hipEvent_t a, hipEvent_t b);
-
-// ks_commit_schedule: the deltas of the last solve, then — all of them being PLACEs — the
-// pin, aggregator and resource-capacity records generated in d_recs and applied by
-// store_apply with no node edit. Two host syncs beside the deltas' own and the BFS
-// levels': the record counts (CommitCtl, one copy) and the store's counters.
-// *dirty: the device state may have changed (a failure after that leaves it unknown).
-int Engine::commit_schedule(int flags, int64_t ccost, const uint64_t* ids, size_t k, int64_t sink_slot,
-                            int64_t n_tasks, size_t cap, std::vector<ks_sched_delta>* out, size_t* count,
-                            ks_commit_stats* stats, bool* dirty, std::string& err) {
-    EngineImpl& s = *p_;
-    *dirty = false;
-    if (!s.solved || !s.csr_valid) {
-        err = "no successful solve";
-        return KS_E_INVALID;
-    }
-    KS_CHECK(hipSetDevice(s.device));
-    hipStream_t st = s.stream;
-    const bool log = s.opts.log_cycles != 0;   // (ks_opts.log_cycles: where a commit's time goes)
-    const auto t0 = std::chrono::steady_clock::now();
-    int rc = sched_deltas(0, out, count, n_tasks, err);   // leaves the kinds and their scan in sched_i
-    if (rc) return rc;
-    const auto t1 = std::chrono::steady_clock::now();
-    if (log) KS_CHECK(hipEventRecord(s.kev[0], st));
-    if (cap < out->size()) {
-        err = "output buffer smaller than the delta count";
-        return KS_E_INVALID;
-    }
-    for (const ks_sched_delta& x : *out)
-        if (x.type != KS_DELTA_PLACE) {
-            err = "the solve preempts or migrates task " + std::to_string(x.task) +
-                  ": ks_commit_schedule pins placements only (no preemption mode)";
-            return KS_E_INVALID;
-        }
-    const int resource_caps = (flags & KS_COMMIT_RESOURCE_CAPS) ? 1 : 0;
-    const int64_t ncap = s.ncap, nst = s.nstore;
-    if (resource_caps && (sink_slot < 0 || sink_slot >= ncap)) {
-        err = "resource capacities need exactly one sink";
-        return KS_E_INVALID;
-    }
-    const int hi = s.hi();
-    const int64_t np = (int64_t)out->size();
-    const int64_t ni_max = np + s.m2cap / 64 + 1;
-    // scratch: int arrays of np + 1, ni_max + 1 and hi + 1 entries; per-node-slot counters and flags
-    KS_CHECK(s.cm_i.ensure(7 * (np + 1) + 2 * (ni_max + 1) + 2 * ((int64_t)hi + 1)));
-    KS_CHECK(s.cm_u.ensure(5 * (nst + 1) + k));
-    const int64_t nb = (nst + 4) & ~3LL;
-    KS_CHECK(s.cm_b.ensure(nb));
-    KS_CHECK(s.cm_ctl.ensure(1));
-    KS_CHECK(hipMemsetAsync(s.cm_i.p, 0, s.cm_i.n * sizeof(int), st));
-    KS_CHECK(hipMemsetAsync(s.cm_u.p, 0, 5 * (nst + 1) * 8, st));
-    KS_CHECK(hipMemsetAsync(s.cm_b.p, 0, nb, st));
-    KS_CHECK(hipMemsetAsync(s.cm_ctl.p, 0, sizeof(CommitCtl), st));
-    CommitDev c{};
-    c.np = (int)np;
-    c.ni_max = (int)ni_max;
-    c.pl_task = s.cm_i.p;
-    c.pl_pu = c.pl_task + (np + 1);
-    c.pl_has = c.pl_pu + (np + 1);
-    c.pl_noarc = c.pl_has + (np + 1);
-    c.add_off = c.pl_noarc + (np + 1);
-    c.nch = c.add_off + (np + 1);
-    c.ch_off = c.nch + (np + 1);
-    c.icnt = c.ch_off + (np + 1);
-    c.i_off = c.icnt + (ni_max + 1);
-    c.aflag = c.i_off + (ni_max + 1);
-    c.a_off = c.aflag + (hi + 1);
-    c.fl = s.cm_b.p;
-    c.agg_cnt = s.cm_u.p;
-    c.pu_slots = c.agg_cnt + (nst + 1);
-    c.pu_run = c.pu_slots + (nst + 1);
-    c.slots = c.pu_run + (nst + 1);
-    c.running = c.slots + (nst + 1);
-    c.ctl = s.cm_ctl.p;
-    const unsigned long long* dids = nullptr;
-    if (ids) {
-        for (size_t i = 0; i < k; ++i)
-            if (ids[i] == 0 || (int64_t)ids[i] > nst) {
-                err = "unscheduled aggregator id beyond the graph";
-                return KS_E_INVALID;
-            }
-        unsigned long long* p = c.running + (nst + 1);
-        if (k) KS_CHECK(hipMemcpyAsync(p, ids, k * 8, hipMemcpyHostToDevice, st));
-        dids = p;
-    }
-    auto scan = [&](const int* in, int* o, int64_t n) -> hipError_t {
-        size_t t = 0;
-        hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, t, in, o, (int)n, st);
-        if (e == hipSuccess) e = s.map_tmp.ensure(std::max(t, s.map_tmp.n));
-        t = s.map_tmp.n;
-        if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(s.map_tmp.p, t, in, o, (int)n, st);
-        return e;
-    };
-    SchedDev d = s.schd();
-    {   // the kinds of sched_deltas: [pre | other | pre_pos | other_pos] × (ncap + 1)
-        const int* other = s.sched_i.p + (ncap + 1);
-        const int* other_pos = other + 2 * (ncap + 1);
-        KS_CHECK(sched_commit_places(d, c, s.map_rank.p, (const unsigned long long*)s.map_scratch.p, other, other_pos,
-                                     dids, (int)k, st));
-    }
-    KS_CHECK(scan(c.nch, c.ch_off, np + 1));
-    KS_CHECK(sched_commit_count(d, c, st));
-    KS_CHECK(scan(c.icnt, c.i_off, ni_max + 1));
-    KS_CHECK(scan(c.pl_noarc, c.add_off, np + 1));
-    if (resource_caps) {
-        KS_CHECK(sched_commit_pu_counts(d, c, st));
-        rc = topo_bfs(s, d, sink_slot, 0, c.pu_slots, c.pu_run, c.slots, c.running, err);
-        if (rc) return rc;
-    }
-    KS_CHECK(sched_commit_arc_flags(d, c, resource_caps, st));
-    KS_CHECK(scan(c.aflag, c.a_off, (int64_t)hi + 1));
-    KS_CHECK(sched_commit_totals(d, c, st));
-    CommitCtl h{};
-    KS_CHECK(hipMemcpyAsync(&h, c.ctl, sizeof(CommitCtl), hipMemcpyDeviceToHost, st));
-    KS_CHECK(hipStreamSynchronize(st));
-    const auto t2 = std::chrono::steady_clock::now();
-    if (h.bad) {
-        err = "a capacity would fall below its arc's lower bound";
-        return KS_E_VERIFY;
-    }
-    const int64_t nrec = (int64_t)h.rec_pin + h.rec_add + h.rec_arc;
-    if (h.rec_pin < 0 || h.rec_add < 0 || h.rec_add > np || h.rec_arc < 0 || h.rec_arc > hi ||
-        h.rec_pin > s.m2cap || nrec > INT32_MAX) {
-        err = "inconsistent record counts";
-        return KS_E_DEVICE;
-    }
-    rc = ensure_arcs(s, (int64_t)hi + h.rec_add, err);   // the only new arcs: one running arc per placed task
-    if (rc == KS_OK) rc = ensure_hash(s, h.rec_add, err);
-    if (rc) return rc;
-    KS_CHECK(s.d_recs.ensure(std::max<size_t>(nrec, 1)));
-    KS_CHECK(s.rec_ent.ensure(std::max<size_t>(nrec, 1)));
-    KS_CHECK(s.d_edits.ensure(1));
-    d = s.schd();   // (the arc table may have moved)
-    *dirty = true;
-    KS_CHECK(sched_commit_emit(d, c, ccost, resource_caps, s.d_recs.p, st));
-    KS_CHECK(store_apply(s.sd(), s.d_recs.p, (int)nrec, s.rec_ent.p, s.d_edits.p, 0, st));
-    if (log) KS_CHECK(hipEventRecord(s.kev[1], st));
-    rc = read_sctl(s, err);
-    if (rc == KS_OK) rc = applied(s, err);
-    if (rc) return rc;
-    if (log) {
-        const auto t3 = std::chrono::steady_clock::now();
-        auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-        std::fprintf(stderr,
-                     "commit: %lld records, deltas %.3f ms, count passes %.3f ms, emit + apply %.3f ms, "
-                     "device span after the deltas %.3f ms\n",
-                     (long long)nrec, ms(t0, t1), ms(t1, t2), ms(t2, t3), ev_ms(s.kev[0], s.kev[1]));
-    }
-    s.incremental = true;
-    s.solved = false;
-    if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        stats->placed = np;
-        stats->running_converted = np - h.rec_add;
-        stats->running_added = h.rec_add;
-        stats->arcs_removed = h.rec_pin - stats->running_converted;
-        stats->unsched_updates = h.unsched;
-        stats->cap_updates = h.caps;
-        stats->records = nrec;
-    }
-    return KS_OK;
-}
-
-int Engine::arcs(std::vector<ks_arc>& out, std::string& err) {
-    EngineImpl& s = *p_;
-    KS_CHECK(hipSetDevice(s.device));
-    hipStream_t st = s.stream;
-    const int hi = s.hi();
-    out.clear();
-    if (!hi) return KS_OK;
-    KS_CHECK(s.flow_sel.ensure(hi));
-    KS_CHECK(s.flow_cnt.ensure(1));
-    hipcub::CountingInputIterator<int> it(0);
-    SlotAlive pred{s.a_alive.p};
-    size_t t = 0;
-    KS_CHECK(hipcub::DeviceSelect::If(nullptr, t, it, s.flow_sel.p, s.flow_cnt.p, hi, pred, st));
-    KS_CHECK(s.map_tmp.ensure(std::max(t, s.map_tmp.n)));
-    t = s.map_tmp.n;
-    KS_CHECK(hipcub::DeviceSelect::If(s.map_tmp.p, t, it, s.flow_sel.p, s.flow_cnt.p, hi, pred, st));
-    int cnt = 0;
-    KS_CHECK(hipMemcpyAsync(&cnt, s.flow_cnt.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    KS_CHECK(hipStreamSynchronize(st));
-    if (!cnt) return KS_OK;
-    ks_arc* d = nullptr;
-    KS_CHECK(hipMalloc(&d, cnt * sizeof(ks_arc)));
-    hipLaunchKernelGGL(k_arc_records, dim3(grid_for(cnt)), dim3(BLK), 0, st, cnt, (const int*)s.flow_sel.p,
-                       (const int*)s.a_src.p, (const int*)s.a_dst.p, (const long long*)s.a_low.p,
-                       (const long long*)s.a_cap.p, (const long long*)s.a_cost.p, (const unsigned char*)s.a_type.p, d);
-    out.resize(cnt);
-    hipError_t e = hipMemcpyAsync(out.data(), d, cnt * sizeof(ks_arc), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(d);
-    KS_CHECK(e);
-    return KS_OK;
-}
-
-hipStream_t Engine::stream() const { return p_->stream; }
-
-int Engine::cell_sums(const int64_t* off, size_t k, int64_t* dev_cost, int64_t* dev_flow, std::string& err) {
-    EngineImpl& s = *p_;
-    if (!s.solved) {
-        err = "no successful solve";
-        return KS_E_INVALID;
-    }
-    if (k > (size_t)MAX_CELLS) {
-        err = "more than 1024 graphs in one union";
-        return KS_E_INVALID;
-    }
-    KS_CHECK(hipSetDevice(s.device));
-    hipStream_t st = s.stream;
-    const int hi = s.hi();
-    KS_CHECK(s.sched_u.ensure(k + 1));
-    KS_CHECK(hipMemcpyAsync(s.sched_u.p, off, (k + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    KS_CHECK(hipMemsetAsync(dev_cost, 0, k * sizeof(int64_t), st));
-    KS_CHECK(hipMemsetAsync(dev_flow, 0, k * sizeof(int64_t), st));
-    if (hi && k)
-        hipLaunchKernelGGL(k_cell_sums, dim3(grid_for(hi, 1024)), dim3(BLK), 0, st, hi, (int)k,
-                           (const long long*)s.sched_u.p, (const unsigned char*)s.a_alive.p, (const int*)s.a_src.p,
-                           (const int*)s.a_dst.p, (const long long*)s.n_supply.p, (const long long*)s.a_cost.p,
-                           (const long long*)s.flows.p, (long long*)dev_cost, (long long*)dev_flow);
-    KS_CHECK(hipGetLastError());
-    KS_CHECK(hipStreamSynchronize(st));
-    return KS_OK;
-}
-
-static double ev_ms(hipEvent_t a, hipEvent_t b) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, a, b) != hipSuccess) return 0.0;
-    return ms;
-}
-
-int Engine::solve(ks_result& res, bool warm, std::string& err) {
-    EngineImpl& s = *p_;
-    KS_CHECK(hipSetDevice(s.device));
-    const auto t_host0 = std::chrono::steady_clock::now();
-    auto wall_s = [&]() {
-        return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_host0).count();
-    };
-    hipStream_t st = s.stream;
+    EngineImpl& s;
+    ks_result& res;
+    std::string& err;
+    const ks_opts& o;
+    const hipStream_t st;
+    const std::chrono::steady_clock::time_point t_host0 = std::chrono::steady_clock::now();
     // a per-cell fallback carries the cell solver's state (the cells that converged
     // keep their optima; the failing ones restart cold, k_fb_reset)
-    const bool fb = s.fb_active;
-    const bool use_warm = (warm && s.has_prev) || fb;
-    s.solved = false;
-    {   // the cell solver's node order, or the multi-kernel engine's (a change rebuilds the CSR)
-        const bool cells_now = want_cells(s);
-        if (cells_now != s.cell_layout) {
-            s.cell_layout = cells_now;
-            s.csr_valid = false;
-        }
+    const bool fb;
+    const bool use_warm;
+    Retry retry = RETRY_NONE;
+
+    // ---- the graph as prepare() leaves it
+    int hi = 0, nn = 0, ncells = 0;
+    int64_t m2 = 0;
+    long long mult = 1, maxc = 0;
+    bool cpv = false;   // the hot kernels read the 16-B compact positions
+    DG g{};
+
+    // ---- plan: derived once from ks_opts and the graph's size (plan(); eps_start: warm_start())
+    int alpha = 8, gi_base = 24, gi_tail = 4, pr_cap = 160, prc_cap = 4096, kb_margin = 6, kb_min = 8;
+    long long pr_div = 32;   // certify at ε = 1 once ε·pr_div < one (scaled) cost unit
+    int phase_exit = 256, phase_frac = 128, aug_slack = 4, walk_passes = 1, fwd_k = 64;
+    bool use_pr = false, use_prc = false, use_fwd = false, use_aug = false, cycle_log = false;
+    int cyc_lg = CYC_LOG;    // doubling steps of the finish's full searches (both solvers)
+    int nhit = 0;
+    int fgrid = 0, dgrid = 0, sgrid = 0, wgrid = 0, ngrid = 0, fsgrid = 0, vgrid = 0;
+    long long eps_start = 1;   // ε before the first phase's division by α
+
+    // ---- tally: what ends in ks_result
+    uint64_t sweeps = 0, gus = 0, sweep_launches = 0, bf_launches = 0, sweep_kernels = 0, early_exits = 0;
+    uint64_t fwd_updates = 0, fs_launches = 0;
+    double ms_bf_k = 0, ms_sw_k = 0, ms_fs_k = 0;   // event-timed spans: BF rounds / sweeps / forward rounds
+    double ms_sat = 0, ms_cycles = 0, ms_pr = 0, ms_cell = 0;
+    int phases = 0;
+    int prc_cycles = 0, prc_searches = 0;
+    long long prc_rejected = 0;   // nodes / leader walks the searches' union-of-cycles test rejected
+    unsigned long long cell_ctr[5] = {0, 0, 0, 0, 0};   // scans, visits, pushes, relabels, gu scans
+    unsigned long long cell_rounds = 0, cticks_max = 0, cticks_sum = 0;
+    long long tot_cost = 0, tot_flow = 0;
+    unsigned long long gu_prev = 0;   // cycle log: Bellman-Ford relaxations counted so far
+
+    // ---- running state
+    long long eps = 1;
+    int kb = 24;                        // Bellman-Ford rounds enqueued per cycle (adaptive)
+    int kf = 16;                        // forward rounds enqueued per cycle (adaptive)
+    int sseq = 0, bseq = 0;             // frontier buffer sequences
+    bool cp_dirty = false;              // the compact residuals hold changes Pos does not have yet
+    int status = KS_OK;
+    bool pr_failed = false;             // the last phase's refinement did not certify the flow
+    bool prc_tried = false;
+    long long solve_units = -1;         // excess units at the solve's first update (cold: the supply)
+    long long warm_thr = 0;
+
+    // the running phase (run_phase; its two kinds of cycle read and steer it)
+    struct Phase {
+        long long eps = 1;
+        int wsl = 1;              // the tail walks' slack
+        bool early = false;       // may end with a few excess nodes left
+        int* prc_early = nullptr;
+        uint64_t sweeps = 0;
+        int gi = 0;               // sweeps in the next cycle (fewer in a phase's tail, where walks augment)
+        int peak = 0;             // most excess nodes seen by an update of this phase
+        int list = 0;             // the next update lists its excess nodes for the bound (the last apply found ≤ BX_CAP)
+        int fwd = 0;              // the next cycle is a forward tail update (≤ fwd_k excess nodes left)
+        int fwd_block = 0;        // a forward cycle failed or moved nothing: the next one is a backward update
+        int fwd_budget = 64;      // rounds a forward search may take: twice the last global update's
+        bool first_upd = true;
+        int nupd = 1;             // forward updates per cycle (FWD_UPD once a search finished within its rounds)
+        int completed0 = 0;       // fs_completed at the phase's start of forward cycles
+        int cur = 0;              // the cycle's slot (control snapshot, events)
+        int bf_pend = -1;         // a cycle whose Bellman-Ford event span is not read yet
+        int rc = KS_OK;
+    } ph;
+
+    // the running finish (finish; search, enqueue_batch and batch_time share it)
+    struct Finish {
+        int2 *JMa, *JMb;          // jump words, double-buffered (8-B aligned)
+        int *J0, *onc, *R, *gbad;
+        int* indeg;               // members of its group pointing at a node
+        long long *gsum, *gcap;
+        bool lds_search;          // the whole search in one workgroup's LDS (k_cyc_lds)
+        int nsearch, cap, used;
+        int nb;                   // batches enqueued
+        unsigned long long srch_seen;
+    } fin{};
+
+    SolveRun(EngineImpl& s_, ks_result& res_, std::string& err_, bool warm)
+        : s(s_), res(res_), err(err_), o(s_.opts), st(s_.stream), fb(s_.fb_active),
+          use_warm((warm && s_.has_prev) || s_.fb_active) {}
+
+    double wall_s() const {
+        return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_host0).count();
     }
-    res.warm_started = use_warm ? 1 : 0;
-    res.rebuilt = s.csr_valid ? 0 : 1;
-    res.recoveries = 0;
-    res.cell_fallbacks = 0;
-    res.cycles_cancelled = 0;
-    res.fb_resets = 0;
-    res.cycles_rejected = 0;
-    KS_CHECK(hipEventRecord(s.ev[0], st));
-    KS_CHECK(hipMemsetAsync(s.ctr.p, 0, CTR_SHARDS * NCTR * sizeof(unsigned long long), st));
-    KS_CHECK(hipMemsetAsync(s.ctl.p, 0, sizeof(Ctl), st));
-    std::memset(s.h_ctl, 0, sizeof(Ctl));
+
+    // A cold engine solve reads top to bottom: prepare, plan, phase_loop (run_phase, the
+    // finish), certify (verify, recover), report. A cell solve takes cell_solve instead of
+    // phase_loop; when it sets `retry`, Engine::solve runs the engine over the same graph.
+    int run() {
+        int rc = prepare();
+        if (rc || nn == 0) return rc;
+        plan();
+        if ((rc = warm_start())) return rc;
+        rc = s.cell_layout ? cell_solve() : phase_loop();
+        if (rc || retry != RETRY_NONE) return rc;
+        if (cycle_log)
+            std::fprintf(stderr, "solve phases %d updates %llu (forward %llu) early phase ends %llu\n", phases,
+                         (unsigned long long)gus, (unsigned long long)fwd_updates, (unsigned long long)early_exits);
+        if (status == KS_E_INFEASIBLE && !s.cell_layout)
+            err = "infeasible: some supply cannot reach a demand node (code " + std::to_string(s.h_ctl->infeasible) +
+                  ", phase " + std::to_string(phases) + ", eps " + std::to_string(eps) + ", updates " +
+                  std::to_string(gus) + ", sweeps " + std::to_string(sweep_launches) + ")";
+        KS_CHECK(hipEventRecord(s.ev[5], st));
+        if (status == KS_OK && (rc = certify())) return rc;
+        return report();
+    }
 
     // ------------------------------------------------- build / reset ---
     // The CSR persists between solves; it is rebuilt from the arc table only when
     // an in-place delta did not fit (or after a load). A cold solve resets the
     // residual state; a warm one keeps it (carried across a rebuild by slot).
-    if (!s.csr_valid) {
+    int prepare() {
+        s.solved = false;
+        {   // the cell solver's node order, or the multi-kernel engine's (a change rebuilds the CSR)
+            const bool cells_now = want_cells(s);
+            if (cells_now != s.cell_layout) {
+                s.cell_layout = cells_now;
+                s.csr_valid = false;
+            }
+        }
+        res.warm_started = use_warm ? 1 : 0;
+        res.rebuilt = s.csr_valid ? 0 : 1;
+        res.recoveries = 0;
+        res.cell_fallbacks = 0;
+        res.cycles_cancelled = 0;
+        res.fb_resets = 0;
+        res.cycles_rejected = 0;
+        KS_CHECK(hipEventRecord(s.ev[0], st));
+        KS_CHECK(hipMemsetAsync(s.ctr.p, 0, CTR_SHARDS * NCTR * sizeof(unsigned long long), st));
+        KS_CHECK(hipMemsetAsync(s.ctl.p, 0, sizeof(Ctl), st));
+        std::memset(s.h_ctl, 0, sizeof(Ctl));
+        if (!s.csr_valid) {
+            if (int rc = rebuild()) return rc;
+        } else if (!use_warm) {
+            if (int rc = cold_reset(s, err)) return rc;
+        }
+        hi = s.hi();
+        nn = s.nn;
+        m2 = s.m2cap;
+        mult = s.mult;
+        ncells = (int)s.h_cells.size();
+        res.n_nodes = s.nslots;
+        res.n_arcs = s.h_sctl->live;
+        if (nn == 0) {
+            res.total_cost = 0;
+            res.flow_value = 0;   // no nodes: nothing flows
+            s.solved = true;
+            s.has_prev = true;
+            return KS_OK;
+        }
+        // max |cost| → the first phase's ε
+        if (hi)
+            hipLaunchKernelGGL(k_max_cost, dim3(grid_for(hi, 512)), dim3(BLK), 0, st, hi,
+                               (const unsigned char*)s.a_alive.p, (const long long*)s.a_cost.p, &s.ctl.p->gu_L);
+        // the engine's hot kernels read 16-B copies of the positions when every value
+        // fits; the range flag comes back with the control block below
+        const bool want_cp = !s.cell_layout && s.opts.compact_pos >= 0 && m2 > 0;
+        if (want_cp) {
+            KS_CHECK(s.cpos.ensure(m2));
+            KS_CHECK(s.crev.ensure(m2));
+            hipLaunchKernelGGL(k_pack_pos, dim3(grid_for(m2, 4096)), dim3(BLK), 0, st, (long long)m2,
+                               (const Pos*)s.pos.p, s.cpos.p, s.crev.p, &s.ctl.p->cp_bad);
+        }
+        KS_CHECK(read_ctl());
+        maxc = s.h_ctl->gu_L;
+        cpv = want_cp && !s.h_ctl->cp_bad;
+        cp_dirty = false;
+        res.compact = cpv ? 1 : 0;
+        KS_CHECK(hipMemsetAsync(&s.ctl.p->gu_L, 0, sizeof(long long), st));
+        if (maxc > 0 && (double)maxc * (double)mult * 8.0 * (double)mult > 4.0e18) {
+            err = "cost range too large for int64 scaled prices";
+            return KS_E_RANGE;
+        }
+        KS_CHECK(hipEventRecord(s.ev[1], st));
+        return KS_OK;
+    }
+
+    // The build, with a warm solve's flows and prices carried across it by slot (and
+    // the failing cells of a per-cell fallback restarted cold).
+    int rebuild() {
         const int64_t ncap_prev = s.ncap;
         const long long mult_prev = s.mult;
         const bool carry = use_warm && s.nn > 0;
@@ -4796,184 +3114,492 @@ int Engine::solve(ks_result& res, bool warm, std::string& err) {
                                (int)ncap_prev, mult_prev, s.mult, (const long long*)s.p_slot.p, (const int*)s.perm.p,
                                s.nd.p, (s.nd.p + 2));
         }
-    } else if (!use_warm) {
-        int rc = cold_reset(s, err);
-        if (rc) return rc;
-    }
-    const int hi = s.hi();
-    const int nn = s.nn;
-    const int64_t m2 = s.m2cap;
-    res.n_nodes = s.nslots;
-    res.n_arcs = s.h_sctl->live;
-    if (nn == 0) {
-        res.total_cost = 0;
-        res.flow_value = 0;   // no nodes: nothing flows
-        s.solved = true;
-        s.has_prev = true;
         return KS_OK;
     }
-    // max |cost| → the first phase's ε
-    if (hi)
-        hipLaunchKernelGGL(k_max_cost, dim3(grid_for(hi, 512)), dim3(BLK), 0, st, hi,
-                           (const unsigned char*)s.a_alive.p, (const long long*)s.a_cost.p, &s.ctl.p->gu_L);
-    // the engine's hot kernels read 16-B copies of the positions when every value
-    // fits; the range flag comes back with the control block below
-    const bool want_cp = !s.cell_layout && s.opts.compact_pos >= 0 && m2 > 0;
-    if (want_cp) {
-        KS_CHECK(s.cpos.ensure(m2));
-        KS_CHECK(s.crev.ensure(m2));
-        hipLaunchKernelGGL(k_pack_pos, dim3(grid_for(m2, 4096)), dim3(BLK), 0, st, (long long)m2,
-                           (const Pos*)s.pos.p, s.cpos.p, s.crev.p, &s.ctl.p->cp_bad);
-    }
-    KS_CHECK(hipMemcpyAsync(s.h_ctl, s.ctl.p, sizeof(Ctl), hipMemcpyDeviceToHost, st));
-    KS_CHECK(hipStreamSynchronize(st));
-    const long long maxc = s.h_ctl->gu_L;
-    const bool cpv = want_cp && !s.h_ctl->cp_bad;
-    bool cp_dirty = false;   // the compact residuals hold changes Pos does not have yet
-    res.compact = cpv ? 1 : 0;
-    KS_CHECK(hipMemsetAsync(&s.ctl.p->gu_L, 0, sizeof(long long), st));
-    const long long mult = s.mult;
-    if (maxc > 0 && (double)maxc * (double)mult * 8.0 * (double)mult > 4.0e18) {
-        err = "cost range too large for int64 scaled prices";
-        return KS_E_RANGE;
-    }
-    KS_CHECK(hipEventRecord(s.ev[1], st));
 
-    // ------------------------------------------------------------ phases ---
+    // -------------------------------------------------------------- plan ---
     // Tuning comes from ks_opts only (0 = default; include/ksmcmf.h): nothing in
     // the environment changes the algorithm.
-    const ks_opts& o = s.opts;
-    DG g = s.dg();
-    g.cp = cpv ? s.cpos.p : nullptr;
-    g.crev = cpv ? s.crev.p : nullptr;
-    g.expand = o.two_hop < 0 ? 0 : 1;      // two hops per round through tasks and PUs
-    g.bound = o.bf_bound < 0 ? 0 : 1;      // tail updates bounded at the excess nodes' distances
-    g.fs_wide = std::max(2048, nn / 4);   // (measured: config 4's searches ≤ nn/6 wide, config 3's hub-bound ones ~nn/4 to 3nn/4)
-    g.aug_k = o.tail_nodes > 0 ? std::min(AUG_KMAX, (int)o.tail_nodes) : 64;
-    const int fgrid = s.window_grid();     // dense passes over every window (saturate)
-    const int dgrid = s.dense_grid();      // dense Bellman-Ford round
-    const int sgrid = s.sparse_grid();     // sparse Bellman-Ford rounds
-    const int wgrid = s.sweep_grid();      // sweeps
-    const int ngrid = grid_for(nn, 2048);
-    const int fsgrid = s.nhitems * HSPLIT + FS_LIST_BLOCKS;   // forward tail rounds
-    // forward tail updates once ≤ fwd_k nodes hold excess (ks_opts.fwd_nodes; the
-    // search key packs an arc position into FS_PB bits)
-    const bool use_fwd = o.fwd_nodes >= 0 && s.m2cap < FS_NONE;
-    // (default by size: config 2's 12k-node searches widen sooner; interleaved A/B,
-    // config 2 28.0 / 26.4 → 25.5 / 25.0 ms at 32, config 4 slower at 32 than at 64)
-    const int fwd_k = o.fwd_nodes > 0 ? (int)o.fwd_nodes : (nn < 32768 ? 32 : 64);
-    int kf = 16;                        // forward rounds enqueued per cycle (adaptive)
-    uint64_t fwd_updates = 0, fs_launches = 0;
-    // α by size: with the cycle-cancelling finish a small engine graph is best with
-    // one coarse phase and the finish (12 config-2 graphs, median / max ms: α 8 14.6 /
-    // 17.9, 16 14.9 / 16.5, 32 11.6 / 15.4, 48 12.6 / 15.9, 1024 — a single phase at
-    // the final ε — 13.4 / 24.4); config 3 and the config-4 rounds are slower at 16
-    // and 32, and the cell solver's ladder stays at 8 (config 5 36 ms at 32) — DESIGN §3
-    // (the small-graph α and the D below were tuned for the finish: they follow use_prc,
-    // so a graph whose positions do not fit the packed keys keeps the plain schedule)
-    const bool use_pr = o.price_refine != 0;
-    const bool use_prc = use_pr && o.price_refine == 1 && !s.cell_layout && s.m2cap < PK_NONE;
-    const int alpha = o.alpha >= 2 ? o.alpha : (!s.cell_layout && nn < 32768 && use_prc) ? 32 : 8;
-    int gi_base = o.gu_interval > 0 ? o.gu_interval : 24;
-    gi_base = std::max(2, std::min(MAXB, gi_base)) & ~1;     // even: sweeps end on p0
-    const int pr_cap = o.pr_rounds > 0 ? o.pr_rounds : 160;  // price-refinement rounds before giving up
-    long long pr_div = 32;   // certify at ε = 1 once ε·pr_div < one (scaled) cost unit
-    const bool cycle_log = o.log_cycles != 0;
-    const int nhit = s.nhitems;
-    const bool use_aug = o.walk_slack >= 0;               // tail augmentation (walks)
-    const int aug_slack = o.walk_slack > 0 ? o.walk_slack : 4;   // walks take arcs of rc <= slack·ε
-    const int walk_passes = o.walk_passes > 0 ? std::min(8, (int)o.walk_passes) : 1;
-    // Bellman-Ford rounds enqueued per cycle: the last update's count + kb_margin,
-    // at least kb_min (a launch that finds the update converged still costs ≈ 5 µs
-    // with the gap before the next kernel; an update that needs more than was
-    // enqueued costs a whole extra cycle)
-    const int kb_margin = o.bf_margin > 0 ? o.bf_margin : 6, kb_min = 8;
-    bool pr_failed = false;   // the last phase's refinement did not certify the flow
-    // the cycle-cancelling finish replaces the final cost-scaling phase (ks_opts.price_refine
-    // 1, the default; 2: the final phase and plain refinement, as before round 5)
-    // refinement rounds before the final phase takes over (TESTS ONLY, fault_inject bit 5: one batch)
-    const int prc_cap = (o.fault_inject & 32) ? 32 : 4096;
-    bool prc_tried = false;
-    const int gi_tail = o.tail_sweeps > 0 ? std::max(2, std::min(MAXB, (int)o.tail_sweeps)) & ~1 : 4;
-    // A phase that another phase follows may end with a few excess nodes left:
-    // refine's start (saturate every negative reduced cost) accepts any
-    // pseudoflow, so the next, finer phase absorbs them with its own excess.
-    // Only the last phase (the one price refinement may certify, or ε = 1) must
-    // end with a feasible flow. A coarse phase ends once at most phase_exit
-    // nodes AND at most 1/phase_frac of its peak hold excess (the relative bound
-    // keeps phases that start small — incremental rounds — doing their share).
-    const int phase_exit = o.phase_exit < 0 ? 0 : (o.phase_exit > 0 ? o.phase_exit : 256);
-    const int phase_frac = o.phase_frac > 0 ? o.phase_frac : 128;
-    // ε schedule: the phase that price refinement certifies runs at 1/D of a cost
-    // unit (ks_opts.final_div), the others at α-multiples of it, the first in
-    // [max|cost|/α², max|cost|/α) scaled. D = 48 on large graphs. Measured on config 3
-    // (40 solves each): ending at 1/32 of a unit (the plain max|cost|/α^k sequence)
-    // left the flow short of optimal in 15 of 40 solves — a sixth phase, ≈ 28 ms —
-    // at 1/48 in none; 1/64 and 1/96 cost more per phase. D = 20 on small graphs and
-    // cells (under 32,768 nodes; every cell is): their flow is usually optimal a
-    // phase earlier (config 2 26–27 → 20–21 ms, config 5 53–54 → 41–43 ms).
-    // Round 5: with the cycle-cancelling finish the final phase no longer runs, and
-    // D only places the ladder; large graphs take D = 24 — one coarse phase fewer
-    // (config 3: 35.4–36.9 vs 36.6–38.6 ms in interleaved pairs).
-    long long eps = std::max<long long>(1, maxc * mult);
-    {
-        const long long D = o.final_div < 0 ? 0
-                            : o.final_div > 0 ? o.final_div
-                            : (s.cell_layout || nn < 32768) ? 20 : (use_prc ? 24 : 48);
-        if (D > 0 && use_pr && maxc > 0) {
-            long long e = std::max<long long>(1, (mult - 1) / D);
-            // the cell solver's ladder is powers of two (α = 8): its arc lengths
-            // floor(rc/ε) are then shifts (the final phase lands in (1/2D, 1/D] of a unit)
-            if (s.cell_layout && (alpha & (alpha - 1)) == 0)
-                while (e & (e - 1)) e &= e - 1;
-            const long long lo = std::max<long long>(1, eps / ((long long)alpha * alpha));
-            while (e < lo && e <= (1LL << 58) / alpha) e *= alpha;
-            eps = e * alpha;   // the loop divides before each phase
-            pr_div = D;
+    void plan() {
+        g = s.dg();
+        g.cp = cpv ? s.cpos.p : nullptr;
+        g.crev = cpv ? s.crev.p : nullptr;
+        g.expand = o.two_hop < 0 ? 0 : 1;      // two hops per round through tasks and PUs
+        g.bound = o.bf_bound < 0 ? 0 : 1;      // tail updates bounded at the excess nodes' distances
+        g.fs_wide = std::max(2048, nn / 4);   // (measured: config 4's searches ≤ nn/6 wide, config 3's hub-bound ones ~nn/4 to 3nn/4)
+        g.aug_k = o.tail_nodes > 0 ? std::min(AUG_KMAX, (int)o.tail_nodes) : 64;
+        fgrid = s.window_grid();     // dense passes over every window (saturate)
+        dgrid = s.dense_grid();      // dense Bellman-Ford round
+        sgrid = s.sparse_grid();     // sparse Bellman-Ford rounds
+        wgrid = s.sweep_grid();      // sweeps
+        ngrid = grid_for(nn, 2048);
+        fsgrid = s.nhitems * HSPLIT + FS_LIST_BLOCKS;   // forward tail rounds
+        vgrid = grid_for(hi, 2048);  // verification
+        // forward tail updates once ≤ fwd_k nodes hold excess (ks_opts.fwd_nodes; the
+        // search key packs an arc position into FS_PB bits)
+        use_fwd = o.fwd_nodes >= 0 && s.m2cap < FS_NONE;
+        // (default by size: config 2's 12k-node searches widen sooner; interleaved A/B,
+        // config 2 28.0 / 26.4 → 25.5 / 25.0 ms at 32, config 4 slower at 32 than at 64)
+        fwd_k = o.fwd_nodes > 0 ? (int)o.fwd_nodes : (nn < 32768 ? 32 : 64);
+        // α by size: with the cycle-cancelling finish a small engine graph is best with
+        // one coarse phase and the finish (12 config-2 graphs, median / max ms: α 8 14.6 /
+        // 17.9, 16 14.9 / 16.5, 32 11.6 / 15.4, 48 12.6 / 15.9, 1024 — a single phase at
+        // the final ε — 13.4 / 24.4); config 3 and the config-4 rounds are slower at 16
+        // and 32, and the cell solver's ladder stays at 8 (config 5 36 ms at 32) — DESIGN §3
+        // (the small-graph α and the D below were tuned for the finish: they follow use_prc,
+        // so a graph whose positions do not fit the packed keys keeps the plain schedule)
+        use_pr = o.price_refine != 0;
+        use_prc = use_pr && o.price_refine == 1 && !s.cell_layout && s.m2cap < PK_NONE;
+        alpha = o.alpha >= 2 ? o.alpha : (!s.cell_layout && nn < 32768 && use_prc) ? 32 : 8;
+        gi_base = o.gu_interval > 0 ? o.gu_interval : 24;
+        gi_base = std::max(2, std::min(MAXB, gi_base)) & ~1;     // even: sweeps end on p0
+        pr_cap = o.pr_rounds > 0 ? o.pr_rounds : 160;  // price-refinement rounds before giving up
+        cycle_log = o.log_cycles != 0;
+        nhit = s.nhitems;
+        use_aug = o.walk_slack >= 0;               // tail augmentation (walks)
+        aug_slack = o.walk_slack > 0 ? o.walk_slack : 4;   // walks take arcs of rc <= slack·ε
+        walk_passes = o.walk_passes > 0 ? std::min(8, (int)o.walk_passes) : 1;
+        // Bellman-Ford rounds enqueued per cycle: the last update's count + kb_margin,
+        // at least kb_min (a launch that finds the update converged still costs ≈ 5 µs
+        // with the gap before the next kernel; an update that needs more than was
+        // enqueued costs a whole extra cycle)
+        kb_margin = o.bf_margin > 0 ? o.bf_margin : 6;
+        kb_min = 8;
+        // the cycle-cancelling finish replaces the final cost-scaling phase (ks_opts.price_refine
+        // 1, the default; 2: the final phase and plain refinement, as before round 5)
+        // refinement rounds before the final phase takes over (TESTS ONLY, fault_inject bit 5: one batch)
+        prc_cap = (o.fault_inject & 32) ? 32 : 4096;
+        // (TESTS ONLY, fault_inject bit 7: every search 5 steps, a window shorter than
+        // the parent chains — their nodes get marked and run into cycles' groups)
+        cyc_lg = (o.fault_inject & 128) ? 5 : CYC_LOG;
+        gi_tail = o.tail_sweeps > 0 ? std::max(2, std::min(MAXB, (int)o.tail_sweeps)) & ~1 : 4;
+        // A phase that another phase follows may end with a few excess nodes left:
+        // refine's start (saturate every negative reduced cost) accepts any
+        // pseudoflow, so the next, finer phase absorbs them with its own excess.
+        // Only the last phase (the one price refinement may certify, or ε = 1) must
+        // end with a feasible flow. A coarse phase ends once at most phase_exit
+        // nodes AND at most 1/phase_frac of its peak hold excess (the relative bound
+        // keeps phases that start small — incremental rounds — doing their share).
+        phase_exit = o.phase_exit < 0 ? 0 : (o.phase_exit > 0 ? o.phase_exit : 256);
+        phase_frac = o.phase_frac > 0 ? o.phase_frac : 128;
+        // ε schedule: the phase that price refinement certifies runs at 1/D of a cost
+        // unit (ks_opts.final_div), the others at α-multiples of it, the first in
+        // [max|cost|/α², max|cost|/α) scaled. D = 48 on large graphs. Measured on config 3
+        // (40 solves each): ending at 1/32 of a unit (the plain max|cost|/α^k sequence)
+        // left the flow short of optimal in 15 of 40 solves — a sixth phase, ≈ 28 ms —
+        // at 1/48 in none; 1/64 and 1/96 cost more per phase. D = 20 on small graphs and
+        // cells (under 32,768 nodes; every cell is): their flow is usually optimal a
+        // phase earlier (config 2 26–27 → 20–21 ms, config 5 53–54 → 41–43 ms).
+        // Round 5: with the cycle-cancelling finish the final phase no longer runs, and
+        // D only places the ladder; large graphs take D = 24 — one coarse phase fewer
+        // (config 3: 35.4–36.9 vs 36.6–38.6 ms in interleaved pairs).
+        eps = std::max<long long>(1, maxc * mult);
+        {
+            const long long D = o.final_div < 0 ? 0
+                                : o.final_div > 0 ? o.final_div
+                                : (s.cell_layout || nn < 32768) ? 20 : (use_prc ? 24 : 48);
+            if (D > 0 && use_pr && maxc > 0) {
+                long long e = std::max<long long>(1, (mult - 1) / D);
+                // the cell solver's ladder is powers of two (α = 8): its arc lengths
+                // floor(rc/ε) are then shifts (the final phase lands in (1/2D, 1/D] of a unit)
+                if (s.cell_layout && (alpha & (alpha - 1)) == 0)
+                    while (e & (e - 1)) e &= e - 1;
+                const long long lo = std::max<long long>(1, eps / ((long long)alpha * alpha));
+                while (e < lo && e <= (1LL << 58) / alpha) e *= alpha;
+                eps = e * alpha;   // the loop divides before each phase
+                pr_div = D;
+            }
         }
+        eps_start = eps;
     }
-    uint64_t sweeps = 0, gus = 0, sweep_launches = 0, bf_launches = 0, sweep_kernels = 0, early_exits = 0;
-    double ms_bf_k = 0, ms_sw_k = 0, ms_fs_k = 0;   // event-timed spans: BF rounds / sweeps / forward rounds
-    int phases = 0;
-    int kb = 24;                        // Bellman-Ford rounds enqueued per cycle (adaptive)
-    int sseq = 0, bseq = 0;             // frontier buffer sequences
-    double ms_sat = 0, ms_cycles = 0, ms_pr = 0;
-    int status = KS_OK;
 
-    auto read_ctl = [&]() -> hipError_t {
+    // warm start: the previous flow and prices (in place), fresh nodes priced off
+    // their out-arcs, then a start at a small ε (≤ 8 cost units) saturating only
+    // the arcs that violate it
+    int warm_start() {
+        if (!use_warm || fb) return KS_OK;
+        if (o.warm_shift >= 0)
+            hipLaunchKernelGGL(k_price_shift, dim3(grid_for(s.ncap, 2048)), dim3(BLK), 0, st, (int)s.ncap,
+                               (const unsigned long long*)s.n_cshift.p, (const int*)s.perm.p, mult, s.nd.p);
+        hipLaunchKernelGGL(k_fresh_prices, dim3(grid_for(s.ncap, 2048)), dim3(BLK), 0, st, (int)s.ncap,
+                           (const unsigned char*)s.n_fresh.p, (const int*)s.perm.p, g);
+        if (m2) hipLaunchKernelGGL(k_max_viol, dim3(grid_for(m2, 2048)), dim3(BLK), 0, st, g, (long long)m2);
+        KS_CHECK(read_ctl());
+        const long long viol = s.h_ctl->gu_L;
+        constexpr long long kWarmUnits = 8;   // the first warm phase at ≤ 8 cost units (DESIGN §5, §9)
+        long long e0 = std::max<long long>(1, std::min<long long>({viol, kWarmUnits * mult, eps}));
+        if (s.cell_layout && (alpha & (alpha - 1)) == 0)   // a power of two ≥ the violation (cell ladder)
+            while (e0 & (e0 - 1)) e0 += e0 & -e0;
+        warm_thr = e0;
+        eps = e0 * alpha;   // the first phase runs at e0
+        eps_start = eps;
+        KS_CHECK(hipMemsetAsync(&s.ctl.p->gu_L, 0, sizeof(long long), st));
+        if (cycle_log) {   // diagnostics: the carried prices' span (in cost units) and the start
+            std::vector<long long> h((size_t)4 * nn);
+            KS_CHECK(hipMemcpyAsync(h.data(), s.nd.p, h.size() * sizeof(long long), hipMemcpyDeviceToHost, st));
+            KS_CHECK(hipStreamSynchronize(st));
+            long long lo = INF64, hi2 = -INF64;
+            for (int v = 0; v < nn; ++v) {
+                lo = std::min(lo, h[(size_t)4 * v]);
+                hi2 = std::max(hi2, h[(size_t)4 * v]);
+            }
+            std::fprintf(stderr, "warm start: largest violation %.3f units, first phase at %.3f units, price span %.1f units\n",
+                         (double)viol / mult, (double)e0 / mult, (double)(hi2 - lo) / mult);
+        }
+        return KS_OK;
+    }
+
+    // -------------------------------------------------------- primitives ---
+    hipError_t read_ctl() {
         hipError_t e = hipMemcpyAsync(s.h_ctl, s.ctl.p, sizeof(Ctl), hipMemcpyDeviceToHost, st);
         if (e != hipSuccess) return e;
         return hipStreamSynchronize(st);
-    };
+    }
     // ε (and, by flags, the control words a phase or the finish starts from) set by a
     // one-thread kernel: a host-to-device copy is a copy kernel behind a staging gap,
     // and each memset another launch
-    auto set_eps = [&](long long e, int flags = 0) -> hipError_t {
+    hipError_t set_eps(long long e, int flags = 0) {
         hipLaunchKernelGGL(k_set_eps, dim3(1), dim3(1), 0, st, g, e, flags);
         return hipGetLastError();
-    };
+    }
+    // One Bellman-Ford round on the next frontier buffer.
     // mode 0: global update; 1: price refinement; 2: refinement with parents (cycle cancelling)
-    auto bf_rounds = [&](int mode, int k, bool first_dense) {
-        for (int r = 0; r < k; ++r) {
-            const int dense = (first_dense && r == 0) ? 1 : 0;
-            const int grid = dense ? dgrid : sgrid;
-            if (mode == 2) {
-                if (cpv) k_bf_round<2, true><<<dim3(grid), dim3(BLK), 0, st>>>(g, bseq, dense);
-                else k_bf_round<2, false><<<dim3(grid), dim3(BLK), 0, st>>>(g, bseq, dense);
-            } else if (mode) {
-                if (cpv) k_bf_round<1, true><<<dim3(grid), dim3(BLK), 0, st>>>(g, bseq, dense);
-                else k_bf_round<1, false><<<dim3(grid), dim3(BLK), 0, st>>>(g, bseq, dense);
-            } else {
-                if (cpv) k_bf_round<0, true><<<dim3(grid), dim3(BLK), 0, st>>>(g, bseq, dense);
-                else k_bf_round<0, false><<<dim3(grid), dim3(BLK), 0, st>>>(g, bseq, dense);
+    void bf_round(int mode, bool dense) {
+        const int grid = dense ? dgrid : sgrid;
+        if (mode == 2) launch_bf_round<2>(cpv, grid, st, g, bseq, dense ? 1 : 0);
+        else if (mode) launch_bf_round<1>(cpv, grid, st, g, bseq, dense ? 1 : 0);
+        else launch_bf_round<0>(cpv, grid, st, g, bseq, dense ? 1 : 0);
+        ++bseq;
+        ++bf_launches;
+    }
+    void bf_rounds(int mode, int k, bool first_dense) {
+        for (int r = 0; r < k; ++r) bf_round(mode, first_dense && r == 0);
+    }
+    // the compact solve's residuals back into the 32-B records (Pos is the authoritative copy)
+    void sync_pos() {
+        if (!cp_dirty) return;
+        hipLaunchKernelGGL(k_unpack_pos, dim3(grid_for(m2, 4096)), dim3(BLK), 0, st, (long long)m2,
+                           (const CPos*)s.cpos.p, s.pos.p);
+        cp_dirty = false;
+    }
+    // (diagnostics, ks_opts.log_cycles) Bellman-Ford relaxations since the last call,
+    // from the sharded counters
+    int relaxations(unsigned long long* since) {
+        std::vector<unsigned long long> hctr((size_t)CTR_SHARDS * NCTR);
+        KS_CHECK(hipMemcpy(hctr.data(), s.ctr.p, hctr.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        unsigned long long gsc = 0;
+        for (int i = 0; i < CTR_SHARDS; ++i) gsc += hctr[(size_t)i * NCTR + C_GUSCAN];
+        *since = gsc - gu_prev;
+        gu_prev = gsc;
+        return KS_OK;
+    }
+
+    // ------------------------------------------------------------ phases ---
+    // The "last phase" of the ladder: the one price refinement may certify, or ε = 1.
+    bool is_last(long long e) const { return e / alpha < 1 || e <= 1 || (use_pr && e * pr_div < mult); }
+
+    // The ε ladder of the multi-kernel engine.
+    int phase_loop() {
+        do {
+            eps = std::max<long long>(1, eps / alpha);
+            ++phases;
+            // After a failed refinement the flow is feasible and ε-optimal at the old ε:
+            // saturating only the arcs that violate the new ε (rc < −ε) is a valid start
+            // (push-relabel at ε needs an ε-optimal pseudoflow, not a 0-optimal one) and
+            // disturbs far less than saturating every negative arc.
+            // warm_start 2: every phase of a warm solve saturates only the arcs that
+            // violate its ε (the previous optimum's arcs in [−1, 0) stay as they are)
+            // per-cell fallback: the cold ε ladder, every phase saturating only the arcs
+            // that violate its ε (the converged cells' optimal flows stay untouched)
+            long long sat_thr = phases == 1 && use_warm && !fb
+                                    ? warm_thr
+                                    : ((pr_failed || fb || (use_warm && o.warm_start >= 2)) ? eps : 0LL);
+            pr_failed = false;
+            const bool last_phase = is_last(eps);
+            // the phase before the final one drains completely when the cycle-cancelling
+            // finish replaces the final phase
+            const long long eps_next = std::max<long long>(1, eps / alpha);
+            const bool before_last = !last_phase && !prc_tried && is_last(eps_next);
+            const bool prc_now = use_prc && before_last;
+            // two phases before the last: the finish may follow this phase instead
+            // (run_phase prc_early) when the flow is already close to optimal
+            const long long eps_next2 = std::max<long long>(1, eps_next / alpha);
+            const bool before_last2 = !last_phase && !before_last && is_last(eps_next2);
+            // walk slack > 1 only while a finer phase or price refinement still follows
+            // (ε > 1): a phase at ε = 1 must end 1-optimal (fault_inject bit 0 breaks
+            // exactly this, for the certificate-recovery test)
+            const int walk_sl = (eps > 1 || (o.fault_inject & 1)) ? aug_slack : 1;
+            int prc_early = 0;
+            // (only from a phase at most two cost units coarse: earlier, the finish has
+            // too many cycles to cancel — config 4 with D = 24 at 2.6 units: 26 vs 20 ms)
+            const bool may_early = use_prc && !prc_tried && before_last2 && !use_warm && !fb && eps <= 2 * mult;
+            const int rc = run_phase(eps, sat_thr, !last_phase && !prc_now, walk_sl, may_early ? &prc_early : nullptr);
+            if (rc == KS_E_INFEASIBLE) {
+                status = rc;
+                break;
             }
-            ++bseq;
-            ++bf_launches;
+            if (rc) return rc;
+            if (prc_now || prc_early) {   // the feasible flow of the last coarse phase: cancel its negative cycles
+                prc_tried = true;
+                int used = 0;
+                const int pr = finish(&used, prc_early ? std::min(prc_cap, 1024) : prc_cap);
+                if (pr < 0) return pr;
+                if (pr == 1) {
+                    eps = 1;
+                    break;
+                }
+                pr_failed = true;   // the final phase follows, saturating only its violations
+                continue;
+            }
+            // certify optimality early: a flow that is 1-optimal (scaled) is optimal.
+            // Tried once ε is below 1/32 of a cost unit, where it usually succeeds.
+            if (use_pr && eps > 1 && eps * pr_div < mult) {
+                int used = 0;
+                const int pr = price_refine(1, &used, pr_cap);
+                if (pr < 0) return pr;
+                if (pr == 1) eps = 1;
+                else pr_failed = true;
+            }
+        } while (eps > 1);
+        return KS_OK;
+    }
+
+    // One ε-phase from the pseudoflow in place: saturate every residual arc whose
+    // reduced cost is below −sat_thr (thr 0: Goldberg's refine start; thr ε: only
+    // the arcs that violate ε-optimality), then update/sweep cycles until no node
+    // holds excess — a coarse phase (may_end_early) may stop with a few excess
+    // nodes left for the next, finer one. walk_sl: the tail walks' slack (1 when the
+    // phase must end ε-optimal at ε = 1). Returns KS_OK, KS_E_INFEASIBLE (status),
+    // or a device / convergence error.
+    // prc_early: when non-null, the phase may turn itself into the one the cycle-
+    // cancelling finish follows (*prc_early = 1, the phase then drains): at its first
+    // update, if at most 1/KS_PRC_UNITS_DIV of the solve's first-update units hold
+    // excess — the flow is already close to optimal (DESIGN §3: config 4's churn
+    // rounds, 0.07–0.11 of the supply, vs ≥ 1.9 for cold configs 2 and 3)
+    int run_phase(long long eps_ph, long long sat_thr, bool may_end_early, int walk_sl, int* prc_early = nullptr) {
+        KS_CHECK(hipEventRecord(s.ev[2], st));
+        KS_CHECK(set_eps(eps_ph, use_fwd ? SET_FWD : 0));   // a phase never continues another phase's forward search
+        KS_HOT(cpv, k_saturate, fgrid, BLK, st, g, sat_thr);
+        cp_dirty = cpv;
+        KS_CHECK(hipEventRecord(s.ev[3], st));
+        ph = Phase{};
+        ph.eps = eps_ph;
+        ph.wsl = walk_sl;
+        ph.early = may_end_early;
+        ph.prc_early = prc_early;
+        ph.gi = gi_base;
+        // Cycles run one at a time (enqueueing the next one before reading this
+        // one's control block was measured slower: the speculative launches cost
+        // more GPU time than the host's decision gap).
+        for (;;) {
+            const int r = ph.fwd ? fwd_cycle() : bwd_cycle();
+            if (r < 0) return r;
+            if (r == PHASE_OVER) break;
         }
-    };
+        flush_bf();
+        KS_CHECK(hipEventRecord(s.ev[4], st));
+        KS_CHECK(hipEventSynchronize(s.ev[4]));
+        ms_sat += ev_ms(s.ev[2], s.ev[3]);
+        ms_cycles += ev_ms(s.ev[3], s.ev[4]);
+        return ph.rc;
+    }
+
+    // Forward cycle: nupd × [init (or continue the pending search)][kf rounds][apply]
+    // [trace][end], then the cycle end; no sweeps (the trace routes the units). An
+    // update whose search has not converged when the next one starts is continued
+    // by it. fev brackets each update's search rounds (the forward kind's time).
+    hipError_t enqueue_fwd(int par, int nupd) {
+        hipError_t e = hipSuccess;
+        for (int u = 0; u < nupd; ++u) {
+            hipLaunchKernelGGL(k_fs_init, dim3(ngrid), dim3(BLK), 0, st, g, bseq);
+            if ((e = hipEventRecord(s.fev[par][2 * u], st)) != hipSuccess) return e;
+            for (int r = 0; r < kf; ++r) {
+                KS_HOT(cpv, k_fs_round, fsgrid, BLK, st, g, bseq);
+                ++bseq;
+                ++fs_launches;
+            }
+            if ((e = hipEventRecord(s.fev[par][2 * u + 1], st)) != hipSuccess) return e;
+            hipLaunchKernelGGL(k_fs_apply, dim3(ngrid), dim3(BLK), 0, st, g);
+            KS_HOT(cpv, k_fs_trace, FDEF_CAP, WAVE, st, g);
+            hipLaunchKernelGGL(k_fs_end, dim3(1), dim3(WAVE), 0, st, g);
+        }
+        hipLaunchKernelGGL(k_cycle_end, dim3(1), dim3(128), 0, st, g, s.d_cyc[par], 1);
+        return hipEventRecord(s.cdone[par], st);
+    }
+    int fwd_cycle() {
+        KS_CHECK(enqueue_fwd(ph.cur, ph.nupd));
+        KS_CHECK(hipEventSynchronize(s.cdone[ph.cur]));
+        const Ctl* hc = s.h_cyc[ph.cur];
+        double t_fs = 0;
+        for (int u = 0; u < ph.nupd; ++u) t_fs += ev_ms(s.fev[ph.cur][2 * u], s.fev[ph.cur][2 * u + 1]);
+        ms_fs_k += t_fs;
+        ph.cur ^= 1;
+        const bool completed = hc->fs_done || hc->fs_fail;
+        if (cycle_log)
+            std::fprintf(stderr, "fwd cycle phase %d eps %lld updates %d rounds %d fs_ms %.3f units %lld n_exc %d done %d fail %d D %lld deficits %d moved %d width %d\n",
+                         phases, ph.eps, ph.nupd, hc->fs_rounds, t_fs, hc->u_exc_rep, hc->n_exc_rep,
+                         hc->fs_done, hc->fs_fail, hc->fs_D < FS_DMAX ? hc->fs_D : -1LL, hc->n_fdef,
+                         hc->fs_moved_cyc, hc->fs_maxcnt);
+        if (completed && hc->n_exc_rep == 0) return PHASE_OVER;   // no excess left: the phase is done
+        const int done_now = hc->fs_completed - ph.completed0;
+        ph.completed0 = hc->fs_completed;
+        gus += done_now;
+        fwd_updates += done_now;
+        bool wide = hc->fs_fail == 2;
+        if (!completed && hc->fs_rounds >= ph.fwd_budget) {
+            // longer than two global updates: drop it like a wide one
+            KS_CHECK(hipMemsetAsync(&s.ctl.p->fs_pending, 0, sizeof(int), st));
+            KS_CHECK(hipMemsetAsync(s.ctl.p->fs_cnt, 0, sizeof(s.ctl.p->fs_cnt), st));
+            wide = true;
+        }
+        if (hc->fs_fail || wide) {
+            // list overflow, no deficit in range, or a search too wide or too long
+            // (a hub's arcs in reach): ONE global update, then forward again
+            ph.fwd = 0;
+            ph.fwd_block = 1;
+            ph.nupd = 1;
+            return CYCLE_NEXT;
+        }
+        if (!completed) {            // the search continues next cycle
+            kf = std::min(256, 2 * kf);
+            ph.nupd = 1;
+            return CYCLE_NEXT;
+        }
+        kf = std::max(8, std::min(256, hc->fs_rounds + 4));
+        ph.nupd = FWD_UPD;
+        if (hc->fs_moved_cyc == 0) {
+            ph.fwd = 0;
+            ph.fwd_block = 1;
+        }
+        if (wall_s() > kSolveWallLimitS) {
+            (void)hipStreamSynchronize(st);
+            err = "forward tail did not converge (" + std::to_string(wall_s()) + " s)";
+            return KS_E_DEVICE;
+        }
+        return CYCLE_NEXT;
+    }
+
+    // One cycle: [GU init (or continue the pending update)][kb BF rounds][max]
+    // [apply][tail walks][gi sweeps][end: control block → pinned host memory].
+    // cev[0..1] bracket the Bellman-Ford rounds (the sweeps: device clock).
+    hipError_t enqueue_bwd(int par) {   // one cycle into slot par
+        const int gi = ph.gi, wsl = ph.wsl;
+        hipLaunchKernelGGL(k_gu_init, dim3(ngrid), dim3(BLK), 0, st, g, bseq, ph.list);
+        hipError_t e = hipEventRecord(s.cev[par][0], st);
+        if (e != hipSuccess) return e;
+        for (int r = 0; r < kb; ++r) bf_round(0, false);   // sparse from the first round: k_gu_init flags the deficits
+        if ((e = hipEventRecord(s.cev[par][1], st)) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_gu_max, dim3(ngrid), dim3(BLK), 0, st, g);
+        hipLaunchKernelGGL(k_gu_apply, dim3(ngrid), dim3(BLK), 0, st, g, sseq);
+        if (use_aug) {   // tail: walkers, hub distribution, walkers from what it fed
+            KS_HOT(cpv, k_augment, g.aug_k, WAVE, st, g, sseq, 0, wsl);
+            if (nhit) KS_HOT(cpv, k_aug_hub, nhit, BLK, st, g, sseq, wsl);
+            KS_HOT(cpv, k_augment, AUG_K2, WAVE, st, g, sseq, 1, wsl);
+            // further passes retry the units left short at the listed nodes
+            for (int wp = 1; wp < walk_passes; ++wp)
+                KS_HOT(cpv, k_augment, g.aug_k, WAVE, st, g, sseq, 0, wsl);
+        }
+        // (the sweeps are timed by the device clock — the first sweep's start to
+        // k_cycle_end's — not by HIP events: an event between two kernels costs a
+        // ~5.7 µs gap of its own, two per cycle; profiles/r06_*)
+        for (int k = 0; k < gi; ++k) KS_HOT(cpv, k_sweep, wgrid, BLK, st, g, k, sseq + k);
+        hipLaunchKernelGGL(k_cycle_end, dim3(1), dim3(128), 0, st, g, s.d_cyc[par], 0);
+        sseq += gi;
+        return hipEventRecord(s.cdone[par], st);
+    }
+    void flush_bf() {
+        if (ph.bf_pend >= 0) ms_bf_k += ev_ms(s.cev[ph.bf_pend][0], s.cev[ph.bf_pend][1]);
+        ph.bf_pend = -1;
+    }
+    int bwd_cycle() {
+        const int cur = ph.cur, gi = ph.gi;
+        if (ph.bf_pend == cur) flush_bf();   // (the slot's events are about to be recorded again)
+        KS_CHECK(enqueue_bwd(cur));
+        flush_bf();   // the previous cycle's event time, read while this one runs
+        KS_CHECK(hipEventSynchronize(s.cdone[cur]));
+        const Ctl* hc = s.h_cyc[cur];
+        sweep_kernels += gi;
+        double t_bf = 0;
+        if (cycle_log) {
+            t_bf = ev_ms(s.cev[cur][0], s.cev[cur][1]);
+            ms_bf_k += t_bf;   // BF rounds only
+        } else {
+            ph.bf_pend = cur;  // read after the next cycle is enqueued (off the host's critical path)
+        }
+        const double t_sw = hc->t_end > hc->t_sw0 ? (double)(hc->t_end - hc->t_sw0) / 1e5 : 0.0;   // 100 MHz ticks
+        ms_sw_k += t_sw;   // sweeps only
+        if (hc->infeasible) {
+            ph.rc = KS_E_INFEASIBLE;
+            std::memcpy(s.h_ctl, hc, sizeof(Ctl));
+            return PHASE_OVER;
+        }
+        if (!hc->bf_done) {
+            // update still running: its sweeps were skipped and the next cycle continues it
+            kb = std::min(256, kb * 2);
+            ph.cur ^= 1;
+            return CYCLE_NEXT;
+        }
+        if (cycle_log) {
+            // (diagnostics: the update's relaxations, from the sharded counters)
+            unsigned long long relax = 0;
+            if (int rc = relaxations(&relax)) return rc;
+            std::fprintf(stderr, "cycle phase %d eps %lld bf %d relax %llu bf_ms %.3f sw_ms %.3f active %d units %lld n_exc %d walks %d/%d",
+                         phases, ph.eps, hc->bf_count - hc->bf_r0, relax, t_bf, t_sw, hc->sweep_act[gi - 1], hc->u_exc, hc->n_exc,
+                         hc->aug_reached, hc->aug_short);
+            for (int k = 0; k < std::min(4, hc->n_exc); ++k) {
+                const int x = hc->dbg_x[k];
+                int c = 0;
+                while (c < NGC && x >= s.obeg[c + 1]) ++c;
+                std::fprintf(stderr, " [x%d c%d e%d]", x, x >= s.hub_base ? 9 : c, hc->dbg_e[k]);
+            }
+            std::fprintf(stderr, "\n");
+        }
+        if (ph.first_upd) {
+            ph.first_upd = false;
+            if (solve_units < 0) solve_units = hc->u_exc;
+            if (ph.prc_early && ph.early && hc->u_exc * kPrcUnitsDiv <= solve_units) {
+                ph.early = false;
+                *ph.prc_early = 1;
+            }
+        }
+        kb = std::max(kb_min, std::min(256, hc->bf_count - hc->bf_r0 + kb_margin));
+        ph.fwd_budget = std::max(16, 2 * (hc->bf_count - hc->bf_r0));
+        ++gus;
+        sweeps += gi;
+        sweep_launches += gi;
+        ph.sweeps += gi;
+        int last = 0;
+        for (int k = 0; k < gi; ++k)
+            if (hc->sweep_act[k]) last = k + 1;
+        if (!hc->sweep_act[gi - 1]) {
+            sweeps -= gi - last;
+            return PHASE_OVER;   // no excess left: refine done
+        }
+        ph.peak = std::max(ph.peak, hc->n_exc);
+        if (ph.early && hc->n_exc <= phase_exit && (long long)hc->n_exc * phase_frac <= ph.peak) {
+            ++early_exits;
+            return PHASE_OVER;   // a coarse phase: the next one absorbs the few units left
+        }
+
+        ph.gi = (use_aug && hc->n_exc <= g.aug_k) ? gi_tail : gi_base;
+        ph.list = g.bound && hc->n_exc > 0 && hc->n_exc <= BX_CAP;
+        // forward tail updates only in coarse phases: in the last phase config 3's
+        // searches reach the cluster aggregator and widen
+        ph.fwd = use_fwd && ph.early && !ph.fwd_block && hc->n_exc > 0 && hc->n_exc <= fwd_k;
+        ph.fwd_block = 0;
+        if (ph.sweeps > (uint64_t)(64 * ((uint64_t)nn + 64)) || wall_s() > kSolveWallLimitS) {
+            (void)hipStreamSynchronize(st);
+            err = "push/relabel did not converge (sweeps " + std::to_string(ph.sweeps) + ", " +
+                  std::to_string(wall_s()) + " s)";
+            return KS_E_DEVICE;
+        }
+        ph.cur ^= 1;
+        return CYCLE_NEXT;
+    }
+
     // Price refinement at eps_try: 1 = success (prices updated), 0 = failed, <0 error.
-    auto price_refine = [&](long long eps_try, int* rounds_used, int cap, int from_p = 0) -> int {
-        KS_CHECK(hipEventRecord(s.ev[6], st));
+    int price_refine(long long eps_try, int* rounds_used, int cap, int from_p = 0) {
+        KS_CHECK(hipEventRecord(s.ev[5], st));
         KS_CHECK(set_eps(eps_try));
         hipLaunchKernelGGL(k_pr_init, dim3(ngrid), dim3(BLK), 0, st, g, bseq, from_p);
         int used = 0, ok = 0;
@@ -4991,86 +3617,44 @@ int Engine::solve(ks_result& res, bool warm, std::string& err) {
             }
         }
         if (ok) hipLaunchKernelGGL(k_pr_apply, dim3(ngrid), dim3(BLK), 0, st, g, 0);
-        KS_CHECK(hipEventRecord(s.ev[7], st));
-        KS_CHECK(hipEventSynchronize(s.ev[7]));
-        ms_pr += ev_ms(s.ev[6], s.ev[7]);
+        KS_CHECK(hipEventRecord(s.ev[6], st));
+        KS_CHECK(hipEventSynchronize(s.ev[6]));
+        ms_pr += ev_ms(s.ev[5], s.ev[6]);
         *rounds_used = used;
         return ok;
-    };
+    }
 
+    // ------------------------------------------------------------ finish ---
     // The cycle-cancelling finish: refinement rounds that record parents
     // (PR = 2), and after every batch that has not converged a search of the parent
     // graph that cancels the negative cycles it holds. 1 = certified (prices set),
     // 0 = gave up within cap rounds (the final cost-scaling phase follows), < 0 error.
-    int prc_cycles = 0, prc_searches = 0;
-    long long prc_rejected = 0;   // nodes / leader walks the searches' union-of-cycles test rejected
-    long long solve_units = -1;   // excess units at the solve's first update (cold: the supply)
-    unsigned long long gu_prev = 0;   // cycle log: Bellman-Ford relaxations counted so far
-    auto prc_refine = [&](int* rounds_used, int cap) -> int {
-        KS_CHECK(hipEventRecord(s.ev[6], st));
+    int finish(int* rounds_used, int cap) {
+        KS_CHECK(hipEventRecord(s.ev[5], st));
         KS_CHECK(s.cyc.ensure((size_t)9 * nn));
         KS_CHECK(s.cyc64.ensure((size_t)2 * nn));
-        int2* JMa = reinterpret_cast<int2*>(s.cyc.p);   // jump words, double-buffered (8-B aligned)
-        int2* JMb = JMa + nn;
-        int* J0 = reinterpret_cast<int*>(JMb + nn);
-        int* onc = J0 + nn;
-        int* R = onc + nn;
-        int* gbad = R + nn;
-        int* indeg = gbad + nn;   // members of its group pointing at a node
-        long long* gsum = s.cyc64.p;
-        long long* gcap = gsum + nn;
+        fin = Finish{};
+        fin.cap = cap;
+        fin.JMa = reinterpret_cast<int2*>(s.cyc.p);
+        fin.JMb = fin.JMa + nn;
+        fin.J0 = reinterpret_cast<int*>(fin.JMb + nn);
+        fin.onc = fin.J0 + nn;
+        fin.R = fin.onc + nn;
+        fin.gbad = fin.R + nn;
+        fin.indeg = fin.gbad + nn;
+        fin.gsum = s.cyc64.p;
+        fin.gcap = fin.gsum + nn;
         KS_CHECK(set_eps(1, SET_CYC));   // and cyc_done, cyc_rej zeroed
         hipLaunchKernelGGL(k_pr_init, dim3(ngrid), dim3(BLK), 0, st, g, bseq, 2);
-        const int* done = &s.ctl.p->bf_done;
-        // the parent graph: pointer doubling over CYC_WALK steps, cycles grouped by
-        // their least id, every good negative one cancelled in parallel (each kernel
-        // returns at once when the refinement has converged)
-        int nsearch = 0;
         // graphs whose parent graph fits one workgroup's LDS search in one launch
         // (k_cyc_lds) instead of 12–15
-        const bool lds_search = nn <= CYC_LDS_MAX && cyc_lds_bytes(nn) <= s.lds_limit;
-        if (lds_search) {
+        fin.lds_search = nn <= CYC_LDS_MAX && cyc_lds_bytes(nn) <= s.lds_limit;
+        if (fin.lds_search) {
             KS_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cyc_lds<true>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)cyc_lds_bytes(nn)));
             KS_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cyc_lds<false>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)cyc_lds_bytes(nn)));
         }
-        auto search = [&]() {
-            // three of four searches double only CYC_SHORT times (cycles of up to 128
-            // arcs: the ones the finish meets); every fourth covers 2^CYC_LOG
-            // (TESTS ONLY, fault_inject bit 7: every search 5 steps, a window shorter than
-            // the parent chains — their nodes get marked and run into cycles' groups)
-            const int lg = (o.fault_inject & 128) ? 5 : (nsearch++ % 4 == 3) ? CYC_LOG : CYC_SHORT;
-            const int apply_check = (o.fault_inject & 256) ? 0 : 1;
-            if (lds_search) {   // small graphs: the whole search in one workgroup, in LDS
-                const size_t sh = cyc_lds_bytes(nn);
-                if (cpv) k_cyc_lds<true><<<dim3(1), dim3(CYC_LDS_T), sh, st>>>(g, lg, apply_check, bseq, gsum, gcap, gbad);
-                else k_cyc_lds<false><<<dim3(1), dim3(CYC_LDS_T), sh, st>>>(g, lg, apply_check, bseq, gsum, gcap, gbad);
-                return;
-            }
-            KS_HOT(cpv, k_cyc_par, ngrid, BLK, st, g, J0, JMa, onc, R, gsum, gcap, gbad, indeg);
-            const int2* JMK = JMa;
-            for (int left = lg, k = 0; left > 0; ++k) {   // ×4 per launch, ×2 for an odd remainder
-                const int2* in = (k & 1) ? JMb : JMa;
-                int2* out = (k & 1) ? JMa : JMb;
-                const int f2 = left >= 2 ? 2 : 1;
-                left -= f2;
-                const int mark = left == 0 ? 1 : 0;
-                if (f2 == 2)
-                    hipLaunchKernelGGL(k_cyc_jump<4>, dim3(ngrid), dim3(BLK), 0, st, nn, done, in, out, mark,
-                                       (const int*)J0, onc);
-                else
-                    hipLaunchKernelGGL(k_cyc_jump<2>, dim3(ngrid), dim3(BLK), 0, st, nn, done, in, out, mark,
-                                       (const int*)J0, onc);
-                JMK = out;
-            }
-            KS_HOT(cpv, k_cyc_group, ngrid, BLK, st, g, (const int*)J0, JMK, (const int*)onc, (const int*)R, gsum, gcap,
-                   gbad, indeg);
-            hipLaunchKernelGGL(k_cyc_check, dim3(ngrid), dim3(BLK), 0, st, nn, done, (const int*)J0, JMK,
-                               (const int*)onc, (const int*)indeg, gbad, apply_check, &s.ctl.p->cyc_rej);
-            KS_HOT(cpv, k_cyc_push, ngrid, BLK, st, g, (const int*)J0, JMK, (const int*)onc, (const int*)R,
-                   (const long long*)gsum, (const long long*)gcap, (const int*)gbad, bseq);
-        };
         // Batches of CYC_PERIODS × (CYC_EVERY[_LDS] rounds + a search), pipelined two deep:
         // batch b+1 is enqueued before the host waits for batch b's control snapshot
         // (k_prc_snap, into pinned memory), so the GPU does not idle through the
@@ -5080,52 +3664,25 @@ int Engine::solve(ks_result& res, bool warm, std::string& err) {
         // searches (device clock: k_cyc_par / k_cyc_lds to the next round's start).
         // One event per batch, after its snapshot: batch b's span runs from batch
         // b−1's event (the first: fin_ev[3]) — two events back to back cost a gap each.
-        int used = 0, ok = 0, nb = 0;   // nb: batches enqueued
-        unsigned long long srch_seen = 0;
+        int ok = 0;
         KS_CHECK(hipEventRecord(s.fin_ev[3], st));
-        auto end_ev = [&](int b) { return s.fin_ev[b % 3]; };
-        auto start_ev = [&](int b) { return b == 0 ? s.fin_ev[3] : s.fin_ev[(b - 1) % 3]; };
-        auto enqueue_batch = [&](int slot) -> hipError_t {
-            const int b = nb++;
-            for (int per = 0; per < (b == 0 ? 1 : CYC_PERIODS) && used < cap; ++per) {
-                const int every = lds_search ? CYC_EVERY_LDS : CYC_EVERY;
-                const int k = std::min(b == 0 ? 2 * every : every, cap - used);
-                bf_rounds(2, k, b == 0);
-                used += k;
-                search();
-                ++prc_searches;
-            }
-            hipLaunchKernelGGL(k_prc_snap, dim3(1), dim3(128), 0, st, g, s.d_cyc[slot]);
-            return hipEventRecord(end_ev(b), st);
-        };
-        auto batch_time = [&](int b) {   // → ms_bf_k
-            const Ctl* hc = s.h_cyc[b & 1];
-            const double span = ev_ms(start_ev(b), end_ev(b));
-            const double srch = hc->srch_ticks > srch_seen ? (double)(hc->srch_ticks - srch_seen) / 1e5 : 0.0;
-            srch_seen = std::max(srch_seen, hc->srch_ticks);
-            ms_bf_k += std::max(0.0, span - srch);
-            return span;
-        };
         KS_CHECK(enqueue_batch(0));
         int done_b = 0;   // batches whose snapshot the host has read
         for (int batch = 0;; ++batch) {
             const int slot = batch & 1;
-            const bool more = used < cap;
+            const bool more = fin.used < fin.cap;
             if (more) KS_CHECK(enqueue_batch(slot ^ 1));
-            KS_CHECK(hipEventSynchronize(end_ev(batch)));
+            KS_CHECK(hipEventSynchronize(batch_end(batch)));
             ++done_b;
             const Ctl* hc = s.h_cyc[slot];
             const double span = batch_time(batch);
             cp_dirty = cpv;
             if (cycle_log) {   // one line per batch: rounds so far, cycles so far, relaxations, time
-                std::vector<unsigned long long> hctr((size_t)CTR_SHARDS * NCTR);
-                KS_CHECK(hipMemcpy(hctr.data(), s.ctr.p, hctr.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-                unsigned long long gsc = 0;
-                for (int i = 0; i < CTR_SHARDS; ++i) gsc += hctr[(size_t)i * NCTR + C_GUSCAN];
+                unsigned long long relax = 0;
+                if (int rc = relaxations(&relax)) return rc;
                 std::fprintf(stderr, "finish batch %d rounds %d worked %d cycles %d rejected %d relax %llu ms %.3f (searches %.3f)\n",
-                             batch, used, hc->bf_count, hc->cyc_done, hc->cyc_rej, gsc - gu_prev, span,
+                             batch, fin.used, hc->bf_count, hc->cyc_done, hc->cyc_rej, relax, span,
                              (double)hc->srch_ticks / 1e5);
-                gu_prev = gsc;
             }
             if (hc->bf_done) {
                 ok = 1;
@@ -5133,307 +3690,114 @@ int Engine::solve(ks_result& res, bool warm, std::string& err) {
             }
             if (!more) break;   // the round cap: this was the last batch
         }
-        if (nb > done_b) {   // the batch enqueued behind the converged one (its kernels exited at once)
-            KS_CHECK(hipEventSynchronize(end_ev(nb - 1)));
-            batch_time(nb - 1);
+        if (fin.nb > done_b) {   // the batch enqueued behind the converged one (its kernels exited at once)
+            KS_CHECK(hipEventSynchronize(batch_end(fin.nb - 1)));
+            batch_time(fin.nb - 1);
         }
         if (ok) hipLaunchKernelGGL(k_pr_apply, dim3(ngrid), dim3(BLK), 0, st, g, 1);
-        KS_CHECK(hipEventRecord(s.ev[7], st));
-        KS_CHECK(hipEventSynchronize(s.ev[7]));
-        ms_pr += ev_ms(s.ev[6], s.ev[7]);
+        KS_CHECK(hipEventRecord(s.ev[6], st));
+        KS_CHECK(hipEventSynchronize(s.ev[6]));
+        ms_pr += ev_ms(s.ev[5], s.ev[6]);
         KS_CHECK(read_ctl());
         prc_cycles += s.h_ctl->cyc_done;
         prc_rejected += s.h_ctl->cyc_rej;
-        *rounds_used = used;
+        *rounds_used = fin.used;
         if (cycle_log)
             std::fprintf(stderr, "cycle-cancelling refinement: %s after %d rounds, %d searches, %d cycles cancelled\n",
-                         ok ? "certified" : "gave up", used, prc_searches, s.h_ctl->cyc_done);
+                         ok ? "certified" : "gave up", fin.used, prc_searches, s.h_ctl->cyc_done);
         return ok;
-    };
-
-    // One ε-phase from the pseudoflow in place: saturate every residual arc whose
-    // reduced cost is below −sat_thr (thr 0: Goldberg's refine start; thr ε: only
-    // the arcs that violate ε-optimality), then update/sweep cycles until no node
-    // holds excess — a coarse phase (may_end_early) may stop with a few excess
-    // nodes left for the next, finer one. walk_sl: the tail walks' slack (1 when the
-    // phase must end ε-optimal at ε = 1). Returns KS_OK, KS_E_INFEASIBLE (status),
-    // or a device / convergence error.
-    // prc_early: when non-null, the phase may turn itself into the one the cycle-
-    // cancelling finish follows (*prc_early = 1, the phase then drains): at its first
-    // update, if at most 1/KS_PRC_UNITS_DIV of the solve's first-update units hold
-    // excess — the flow is already close to optimal (DESIGN §3: config 4's churn
-    // rounds, 0.07–0.11 of the supply, vs ≥ 1.9 for cold configs 2 and 3)
-    auto run_phase = [&](long long eps_ph, long long sat_thr, bool may_end_early, int walk_sl,
-                         int* prc_early = nullptr) -> int {
-        KS_CHECK(hipEventRecord(s.ev[2], st));
-        KS_CHECK(set_eps(eps_ph, use_fwd ? SET_FWD : 0));   // a phase never continues another phase's forward search
-        KS_HOT(cpv, k_saturate, fgrid, BLK, st, g, sat_thr);
-        cp_dirty = cpv;
-        KS_CHECK(hipEventRecord(s.ev[3], st));
-        uint64_t phase_sweeps = 0;
-        int gi = gi_base;     // sweeps in the next cycle (fewer in a phase's tail, where walks augment)
-        int phase_peak = 0;   // most excess nodes seen by an update of this phase
-        int list = 0;         // the next update lists its excess nodes for the bound (the last apply found ≤ BX_CAP)
-        int fwd = 0;          // the next cycle is a forward tail update (≤ fwd_k excess nodes left)
-        int fwd_block = 0;    // a forward cycle failed or moved nothing: the next one is a backward update
-        int fwd_budget = 64;  // rounds a forward search may take: twice the last global update's
-        const int wsl = walk_sl;
-        bool early = may_end_early;
-        bool first_upd = true;
-        int rc = KS_OK;
-        // Forward cycle: nupd × [init (or continue the pending search)][kf rounds][apply]
-        // [trace][end], then the cycle end; no sweeps (the trace routes the units). An
-        // update whose search has not converged when the next one starts is continued
-        // by it. fev brackets each update's search rounds (the forward kind's time).
-        auto enqueue_fwd = [&](int par, int nupd) -> hipError_t {
-            hipError_t e = hipSuccess;
-            for (int u = 0; u < nupd; ++u) {
-                hipLaunchKernelGGL(k_fs_init, dim3(ngrid), dim3(BLK), 0, st, g, bseq);
-                if ((e = hipEventRecord(s.fev[par][2 * u], st)) != hipSuccess) return e;
-                for (int r = 0; r < kf; ++r) {
-                    KS_HOT(cpv, k_fs_round, fsgrid, BLK, st, g, bseq);
-                    ++bseq;
-                    ++fs_launches;
-                }
-                if ((e = hipEventRecord(s.fev[par][2 * u + 1], st)) != hipSuccess) return e;
-                hipLaunchKernelGGL(k_fs_apply, dim3(ngrid), dim3(BLK), 0, st, g);
-                KS_HOT(cpv, k_fs_trace, FDEF_CAP, WAVE, st, g);
-                hipLaunchKernelGGL(k_fs_end, dim3(1), dim3(WAVE), 0, st, g);
-            }
-            hipLaunchKernelGGL(k_cycle_end, dim3(1), dim3(128), 0, st, g, s.d_cyc[par], 1);
-            return hipEventRecord(s.cdone[par], st);
-        };
-        int nupd = 1;         // forward updates per cycle (FWD_UPD once a search finished within its rounds)
-        int completed0 = 0;   // fs_completed at the phase's start of forward cycles
-        // One cycle: [GU init (or continue the pending update)][kb BF rounds][max]
-        // [apply][tail walks][gi sweeps][end: control block → pinned host memory].
-        // cev[0..1] bracket the Bellman-Ford rounds (the sweeps: device clock).
-        auto enqueue = [&](int par) -> hipError_t {   // one cycle into slot par
-            hipLaunchKernelGGL(k_gu_init, dim3(ngrid), dim3(BLK), 0, st, g, bseq, list);
-            hipError_t e = hipEventRecord(s.cev[par][0], st);
-            if (e != hipSuccess) return e;
-            for (int r = 0; r < kb; ++r) {   // sparse from the first round: k_gu_init flags the deficits
-                if (cpv) k_bf_round<0, true><<<dim3(sgrid), dim3(BLK), 0, st>>>(g, bseq, 0);
-                else k_bf_round<0, false><<<dim3(sgrid), dim3(BLK), 0, st>>>(g, bseq, 0);
-                ++bseq;
-                ++bf_launches;
-            }
-            if ((e = hipEventRecord(s.cev[par][1], st)) != hipSuccess) return e;
-            hipLaunchKernelGGL(k_gu_max, dim3(ngrid), dim3(BLK), 0, st, g);
-            hipLaunchKernelGGL(k_gu_apply, dim3(ngrid), dim3(BLK), 0, st, g, sseq);
-            if (use_aug) {   // tail: walkers, hub distribution, walkers from what it fed
-                KS_HOT(cpv, k_augment, g.aug_k, WAVE, st, g, sseq, 0, wsl);
-                if (nhit) KS_HOT(cpv, k_aug_hub, nhit, BLK, st, g, sseq, wsl);
-                KS_HOT(cpv, k_augment, AUG_K2, WAVE, st, g, sseq, 1, wsl);
-                // further passes retry the units left short at the listed nodes
-                for (int wp = 1; wp < walk_passes; ++wp)
-                    KS_HOT(cpv, k_augment, g.aug_k, WAVE, st, g, sseq, 0, wsl);
-            }
-            // (the sweeps are timed by the device clock — the first sweep's start to
-            // k_cycle_end's — not by HIP events: an event between two kernels costs a
-            // ~5.7 µs gap of its own, two per cycle; profiles/r06_*)
-            for (int k = 0; k < gi; ++k) KS_HOT(cpv, k_sweep, wgrid, BLK, st, g, k, sseq + k);
-            hipLaunchKernelGGL(k_cycle_end, dim3(1), dim3(128), 0, st, g, s.d_cyc[par], 0);
-            sseq += gi;
-            return hipEventRecord(s.cdone[par], st);
-        };
-        // Cycles run one at a time (enqueueing the next one before reading this
-        // one's control block was measured slower: the speculative launches cost
-        // more GPU time than the host's decision gap).
-        int cur = 0;
-        int bf_pend = -1;   // a cycle whose Bellman-Ford event span is not read yet
-        auto flush_bf = [&]() {
-            if (bf_pend >= 0) ms_bf_k += ev_ms(s.cev[bf_pend][0], s.cev[bf_pend][1]);
-            bf_pend = -1;
-        };
-        for (;;) {
-            if (fwd) {
-                KS_CHECK(enqueue_fwd(cur, nupd));
-                KS_CHECK(hipEventSynchronize(s.cdone[cur]));
-                const Ctl* hc = s.h_cyc[cur];
-                double t_fs = 0;
-                for (int u = 0; u < nupd; ++u) t_fs += ev_ms(s.fev[cur][2 * u], s.fev[cur][2 * u + 1]);
-                ms_fs_k += t_fs;
-                cur ^= 1;
-                const bool completed = hc->fs_done || hc->fs_fail;
-                if (cycle_log)
-                    std::fprintf(stderr, "fwd cycle phase %d eps %lld updates %d rounds %d fs_ms %.3f units %lld n_exc %d done %d fail %d D %lld deficits %d moved %d width %d\n",
-                                 phases, eps_ph, nupd, hc->fs_rounds, t_fs, hc->u_exc_rep, hc->n_exc_rep,
-                                 hc->fs_done, hc->fs_fail, hc->fs_D < FS_DMAX ? hc->fs_D : -1LL, hc->n_fdef,
-                                 hc->fs_moved_cyc, hc->fs_maxcnt);
-                if (completed && hc->n_exc_rep == 0) break;   // no excess left: the phase is done
-                const int done_now = hc->fs_completed - completed0;
-                completed0 = hc->fs_completed;
-                gus += done_now;
-                fwd_updates += done_now;
-                bool wide = hc->fs_fail == 2;
-                if (!completed && hc->fs_rounds >= fwd_budget) {
-                    // longer than two global updates: drop it like a wide one
-                    KS_CHECK(hipMemsetAsync(&s.ctl.p->fs_pending, 0, sizeof(int), st));
-                    KS_CHECK(hipMemsetAsync(s.ctl.p->fs_cnt, 0, sizeof(s.ctl.p->fs_cnt), st));
-                    wide = true;
-                }
-                if (hc->fs_fail || wide) {
-                    // list overflow, no deficit in range, or a search too wide or too long
-                    // (a hub's arcs in reach): ONE global update, then forward again
-                    fwd = 0;
-                    fwd_block = 1;
-                    nupd = 1;
-                    continue;
-                }
-                if (!completed) {            // the search continues next cycle
-                    kf = std::min(256, 2 * kf);
-                    nupd = 1;
-                    continue;
-                }
-                kf = std::max(8, std::min(256, hc->fs_rounds + 4));
-                nupd = FWD_UPD;
-                if (hc->fs_moved_cyc == 0) {
-                    fwd = 0;
-                    fwd_block = 1;
-                }
-                if (wall_s() > kSolveWallLimitS) {
-                    (void)hipStreamSynchronize(st);
-                    err = "forward tail did not converge (" + std::to_string(wall_s()) + " s)";
-                    return KS_E_DEVICE;
-                }
-                continue;
-            }
-            if (bf_pend == cur) flush_bf();   // (the slot's events are about to be recorded again)
-            KS_CHECK(enqueue(cur));
-            flush_bf();   // the previous cycle's event time, read while this one runs
-            KS_CHECK(hipEventSynchronize(s.cdone[cur]));
-            const Ctl* hc = s.h_cyc[cur];
-            sweep_kernels += gi;
-            double t_bf = 0;
-            if (cycle_log) {
-                t_bf = ev_ms(s.cev[cur][0], s.cev[cur][1]);
-                ms_bf_k += t_bf;   // BF rounds only
-            } else {
-                bf_pend = cur;     // read after the next cycle is enqueued (off the host's critical path)
-            }
-            const double t_sw = hc->t_end > hc->t_sw0 ? (double)(hc->t_end - hc->t_sw0) / 1e5 : 0.0;   // 100 MHz ticks
-            ms_sw_k += t_sw;   // sweeps only
-            if (hc->infeasible) {
-                rc = KS_E_INFEASIBLE;
-                std::memcpy(s.h_ctl, hc, sizeof(Ctl));
-                break;
-            }
-            if (!hc->bf_done) {
-                // update still running: its sweeps were skipped and the next cycle continues it
-                kb = std::min(256, kb * 2);
-                cur ^= 1;
-                continue;
-            }
-            if (cycle_log) {
-                // (diagnostics: the update's relaxations, from the sharded counters)
-                std::vector<unsigned long long> hctr((size_t)CTR_SHARDS * NCTR);
-                KS_CHECK(hipMemcpy(hctr.data(), s.ctr.p, hctr.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-                unsigned long long gsc = 0;
-                for (int i = 0; i < CTR_SHARDS; ++i) gsc += hctr[(size_t)i * NCTR + C_GUSCAN];
-                std::fprintf(stderr, "cycle phase %d eps %lld bf %d relax %llu bf_ms %.3f sw_ms %.3f active %d units %lld n_exc %d walks %d/%d",
-                             phases, eps_ph, hc->bf_count - hc->bf_r0, gsc - gu_prev, t_bf, t_sw, hc->sweep_act[gi - 1], hc->u_exc, hc->n_exc,
-                             hc->aug_reached, hc->aug_short);
-                gu_prev = gsc;
-                for (int k = 0; k < std::min(4, hc->n_exc); ++k) {
-                    const int x = hc->dbg_x[k];
-                    int c = 0;
-                    while (c < NGC && x >= s.obeg[c + 1]) ++c;
-                    std::fprintf(stderr, " [x%d c%d e%d]", x, x >= s.hub_base ? 9 : c, hc->dbg_e[k]);
-                }
-                std::fprintf(stderr, "\n");
-            }
-            if (first_upd) {
-                first_upd = false;
-                if (solve_units < 0) solve_units = hc->u_exc;
-                if (prc_early && early && hc->u_exc * kPrcUnitsDiv <= solve_units) {
-                    early = false;
-                    *prc_early = 1;
-                }
-            }
-            kb = std::max(kb_min, std::min(256, hc->bf_count - hc->bf_r0 + kb_margin));
-            fwd_budget = std::max(16, 2 * (hc->bf_count - hc->bf_r0));
-            ++gus;
-            sweeps += gi;
-            sweep_launches += gi;
-            phase_sweeps += gi;
-            int last = 0;
-            for (int k = 0; k < gi; ++k)
-                if (hc->sweep_act[k]) last = k + 1;
-            if (!hc->sweep_act[gi - 1]) {
-                sweeps -= gi - last;
-                break;   // no excess left: refine done
-            }
-            phase_peak = std::max(phase_peak, hc->n_exc);
-            if (early && hc->n_exc <= phase_exit && (long long)hc->n_exc * phase_frac <= phase_peak) {
-                ++early_exits;
-                break;   // a coarse phase: the next one absorbs the few units left
-            }
-
-            gi = (use_aug && hc->n_exc <= g.aug_k) ? gi_tail : gi_base;
-            list = g.bound && hc->n_exc > 0 && hc->n_exc <= BX_CAP;
-            // forward tail updates only in coarse phases: in the last phase config 3's
-            // searches reach the cluster aggregator and widen
-            fwd = use_fwd && early && !fwd_block && hc->n_exc > 0 && hc->n_exc <= fwd_k;
-            fwd_block = 0;
-            if (phase_sweeps > (uint64_t)(64 * ((uint64_t)nn + 64)) || wall_s() > kSolveWallLimitS) {
-                (void)hipStreamSynchronize(st);
-                err = "push/relabel did not converge (sweeps " + std::to_string(phase_sweeps) + ", " +
-                      std::to_string(wall_s()) + " s)";
-                return KS_E_DEVICE;
-            }
-            cur ^= 1;
+    }
+    // the parent graph: pointer doubling over CYC_WALK steps, cycles grouped by
+    // their least id, every good negative one cancelled in parallel (each kernel
+    // returns at once when the refinement has converged)
+    void search() {
+        const Finish& f = fin;
+        const int* done = &s.ctl.p->bf_done;
+        // three of four searches double only CYC_SHORT times (cycles of up to 128
+        // arcs: the ones the finish meets); every fourth covers 2^CYC_LOG
+        // (fault_inject bit 7: every search cyc_lg = 5 steps)
+        const bool full = (o.fault_inject & 128) || fin.nsearch++ % 4 == 3;
+        const int lg = full ? cyc_lg : CYC_SHORT;
+        const int apply_check = (o.fault_inject & 256) ? 0 : 1;
+        if (f.lds_search) {   // small graphs: the whole search in one workgroup, in LDS
+            KS_HOT_LDS(cpv, k_cyc_lds, 1, CYC_LDS_T, cyc_lds_bytes(nn), st, g, lg, apply_check, bseq, f.gsum, f.gcap,
+                       f.gbad);
+            return;
         }
-        flush_bf();
-        KS_CHECK(hipEventRecord(s.ev[5], st));
-        KS_CHECK(hipEventSynchronize(s.ev[5]));
-        ms_sat += ev_ms(s.ev[2], s.ev[3]);
-        ms_cycles += ev_ms(s.ev[3], s.ev[5]);
-        return rc;
-    };
-
-    // warm start: the previous flow and prices (in place), fresh nodes priced off
-    // their out-arcs, then a start at a small ε (≤ 8 cost units) saturating only
-    // the arcs that violate it
-    long long warm_thr = 0;
-    if (use_warm && !fb) {
-        if (o.warm_shift >= 0)
-            hipLaunchKernelGGL(k_price_shift, dim3(grid_for(s.ncap, 2048)), dim3(BLK), 0, st, (int)s.ncap,
-                               (const unsigned long long*)s.n_cshift.p, (const int*)s.perm.p, mult, s.nd.p);
-        hipLaunchKernelGGL(k_fresh_prices, dim3(grid_for(s.ncap, 2048)), dim3(BLK), 0, st, (int)s.ncap,
-                           (const unsigned char*)s.n_fresh.p, (const int*)s.perm.p, g);
-        if (m2) hipLaunchKernelGGL(k_max_viol, dim3(grid_for(m2, 2048)), dim3(BLK), 0, st, g, (long long)m2);
-        KS_CHECK(read_ctl());
-        const long long viol = s.h_ctl->gu_L;
-        constexpr long long kWarmUnits = 8;   // the first warm phase at ≤ 8 cost units (DESIGN §5, §9)
-        long long e0 = std::max<long long>(1, std::min<long long>({viol, kWarmUnits * mult, eps}));
-        if (s.cell_layout && (alpha & (alpha - 1)) == 0)   // a power of two ≥ the violation (cell ladder)
-            while (e0 & (e0 - 1)) e0 += e0 & -e0;
-        warm_thr = e0;
-        eps = e0 * alpha;   // the first phase runs at e0
-        KS_CHECK(hipMemsetAsync(&s.ctl.p->gu_L, 0, sizeof(long long), st));
-        if (cycle_log) {   // diagnostics: the carried prices' span (in cost units) and the start
-            std::vector<long long> h((size_t)4 * nn);
-            KS_CHECK(hipMemcpyAsync(h.data(), s.nd.p, h.size() * sizeof(long long), hipMemcpyDeviceToHost, st));
-            KS_CHECK(hipStreamSynchronize(st));
-            long long lo = INF64, hi2 = -INF64;
-            for (int v = 0; v < nn; ++v) {
-                lo = std::min(lo, h[(size_t)4 * v]);
-                hi2 = std::max(hi2, h[(size_t)4 * v]);
-            }
-            std::fprintf(stderr, "warm start: largest violation %.3f units, first phase at %.3f units, price span %.1f units\n",
-                         (double)viol / mult, (double)e0 / mult, (double)(hi2 - lo) / mult);
+        KS_HOT(cpv, k_cyc_par, ngrid, BLK, st, g, f.J0, f.JMa, f.onc, f.R, f.gsum, f.gcap, f.gbad, f.indeg);
+        const int2* JMK = f.JMa;
+        for (int left = lg, k = 0; left > 0; ++k) {   // ×4 per launch, ×2 for an odd remainder
+            const int2* in = (k & 1) ? f.JMb : f.JMa;
+            int2* out = (k & 1) ? f.JMa : f.JMb;
+            const int f2 = left >= 2 ? 2 : 1;
+            left -= f2;
+            const int mark = left == 0 ? 1 : 0;
+            if (f2 == 2)
+                hipLaunchKernelGGL(k_cyc_jump<4>, dim3(ngrid), dim3(BLK), 0, st, nn, done, in, out, mark,
+                                   (const int*)f.J0, f.onc);
+            else
+                hipLaunchKernelGGL(k_cyc_jump<2>, dim3(ngrid), dim3(BLK), 0, st, nn, done, in, out, mark,
+                                   (const int*)f.J0, f.onc);
+            JMK = out;
         }
+        KS_HOT(cpv, k_cyc_group, ngrid, BLK, st, g, (const int*)f.J0, JMK, (const int*)f.onc, (const int*)f.R, f.gsum,
+               f.gcap, f.gbad, f.indeg);
+        hipLaunchKernelGGL(k_cyc_check, dim3(ngrid), dim3(BLK), 0, st, nn, done, (const int*)f.J0, JMK,
+                           (const int*)f.onc, (const int*)f.indeg, f.gbad, apply_check, &s.ctl.p->cyc_rej);
+        KS_HOT(cpv, k_cyc_push, ngrid, BLK, st, g, (const int*)f.J0, JMK, (const int*)f.onc, (const int*)f.R,
+               (const long long*)f.gsum, (const long long*)f.gcap, (const int*)f.gbad, bseq);
+    }
+    hipEvent_t batch_end(int b) const { return s.fin_ev[b % 3]; }
+    hipEvent_t batch_start(int b) const { return b == 0 ? s.fin_ev[3] : s.fin_ev[(b - 1) % 3]; }
+    hipError_t enqueue_batch(int slot) {
+        const int b = fin.nb++;
+        for (int per = 0; per < (b == 0 ? 1 : CYC_PERIODS) && fin.used < fin.cap; ++per) {
+            const int every = fin.lds_search ? CYC_EVERY_LDS : CYC_EVERY;
+            const int k = std::min(b == 0 ? 2 * every : every, fin.cap - fin.used);
+            bf_rounds(2, k, b == 0);
+            fin.used += k;
+            search();
+            ++prc_searches;
+        }
+        hipLaunchKernelGGL(k_prc_snap, dim3(1), dim3(128), 0, st, g, s.d_cyc[slot]);
+        return hipEventRecord(batch_end(b), st);
+    }
+    double batch_time(int b) {   // → ms_bf_k
+        const Ctl* hc = s.h_cyc[b & 1];
+        const double span = ev_ms(batch_start(b), batch_end(b));
+        const double srch = hc->srch_ticks > fin.srch_seen ? (double)(hc->srch_ticks - fin.srch_seen) / 1e5 : 0.0;
+        fin.srch_seen = std::max(fin.srch_seen, hc->srch_ticks);
+        ms_bf_k += std::max(0.0, span - srch);
+        return span;
     }
 
-    // ---- the cell solver (ks_cell.h): every cell's whole solve in one workgroup,
-    // one launch for all cells; per-cell status and counters come back in CellOut
-    const int ncells = (int)s.h_cells.size();
-    const long long eps_cells = eps;   // ε before the first phase's division (as the loop below)
-    double ms_cell = 0;
-    unsigned long long cell_ctr[5] = {0, 0, 0, 0, 0};   // scans, visits, pushes, relabels, gu scans
-    unsigned long long cell_rounds = 0, cticks_max = 0, cticks_sum = 0;
-    auto run_cells = [&](int mode) -> int {
+    // ------------------------------------------------------- cell solver ---
+    // The cell solver (ks_cell.h): every cell's whole solve in one workgroup, one
+    // launch for all cells. `retry` is set when the engine must take over: a value the
+    // compact record cannot hold (RETRY_RANGE), or cells that gave up (RETRY_CELLS).
+    int cell_solve() {
+        KS_CHECK(s.cl_pos.ensure(std::max<int64_t>(m2, 1)));
+        KS_CHECK(hipEventRecord(s.ev[3], st));
+        const int cs = run_cells(0);
+        if (cs < 0) return cs;
+        if (cs == CS_RANGE) {
+            retry = RETRY_RANGE;
+            return KS_OK;
+        }
+        KS_CHECK(hipEventRecord(s.ev[4], st));
+        KS_CHECK(hipEventSynchronize(s.ev[4]));
+        ms_cycles += ev_ms(s.ev[3], s.ev[4]);
+        if (cs == CS_TIMEOUT || cs == CS_NOCONV) {
+            retry = RETRY_CELLS;
+            return KS_OK;
+        }
+        if (int rc = cell_status(cs, "solve")) return rc;
+        eps = 1;
+        return KS_OK;
+    }
+    // One launch (mode 0: the solve; 1: certificate recovery at ε = 1); per-cell status
+    // and counters come back in CellOut. Returns the worst CellStatus, or < 0.
+    int run_cells(int mode) {
         CellArgs a{};
         a.pos = s.pos.p;
         a.cp = s.cl_pos.p;
@@ -5449,7 +3813,7 @@ int Engine::solve(ks_result& res, bool warm, std::string& err) {
         a.rl_p = s.cl_rlp.p;
         a.out = s.cl_out.p;
         a.mult = mult;
-        a.eps_start = eps_cells;
+        a.eps_start = eps_start;
         a.sat_thr0 = warm_thr;
         a.warm = use_warm ? (o.warm_start >= 2 ? 2 : 1) : 0;
         a.alpha = alpha;
@@ -5457,7 +3821,7 @@ int Engine::solve(ks_result& res, bool warm, std::string& err) {
         a.use_pr = use_pr ? 1 : 0;
         a.pr_cap = pr_cap;
         a.use_prc = (use_pr && o.price_refine == 1 && !use_warm && mode == 0) ? 1 : 0;
-        a.prc_cap = (o.fault_inject & 32) ? 32 : 4096;
+        a.prc_cap = prc_cap;
         a.gi = gi_base;
         a.bound = o.bf_bound < 0 ? 0 : 1;
         a.phase_exit = phase_exit;
@@ -5469,7 +3833,7 @@ int Engine::solve(ks_result& res, bool warm, std::string& err) {
         // TESTS ONLY (fault_inject bit 4): the middle cell gives up after 40 operations
         a.fault_cell = (o.fault_inject & 16) && mode == 0 ? ncells / 2 : -1;
         a.fault_ops = 40;
-        a.cyc_lg = (o.fault_inject & 128) ? 5 : 10;   // (ks_cell.hip CYC_LOG)
+        a.cyc_lg = cyc_lg;
         KS_CHECK(hipEventRecord(s.kev[2], st));
         {   // a launch the device refuses (its LDS) → the multi-kernel engine instead; any
             // other launch error is reported (it used to disable the cell solver)
@@ -5506,44 +3870,46 @@ int Engine::solve(ks_result& res, bool warm, std::string& err) {
             cticks_sum += o.ticks;
         }
         phases += pmax;
-        if (cycle_log) {   // per-operation device time of the slowest cell (ks_opts.log_cycles)
-            size_t w = 0;
-            for (size_t i = 1; i < s.h_cell_out.size(); ++i)
-                if (s.h_cell_out[i].ticks > s.h_cell_out[w].ticks) w = i;
-            const CellOut& o = s.h_cell_out[w];
-            static const char* names[CELL_NOPS] = {"sat", "gu_init", "bf", "gu_fin", "sweep", "pr_init", "pr", "pr_fin",
-                                                   "cyc"};
-            std::fprintf(stderr, "cell %zu of %d: %.3f ms, phases %d updates %d sweeps %llu rounds %llu:", w, ncells,
-                         o.ticks / 1e5, o.phases, o.updates, o.sweeps, o.bf_rounds);
-            for (int i = 0; i < CELL_NOPS; ++i)
-                if (o.op_n[i])
-                    std::fprintf(stderr, " %s %u x %.2f us (items %.2f..%.2f)", names[i], o.op_n[i],
-                                 o.op_ticks[i] / 100.0 / o.op_n[i], o.first_ticks[i] / 100.0 / o.op_n[i],
-                                 o.item_ticks[i] / 100.0 / o.op_n[i]);
-            static const char* const steps[4] = {"sweep", "bf", "pr", "sat"};
-            for (int s = 0; s < 4; ++s) {
-                std::fprintf(stderr, "\n  %s items:", steps[s]);
-                for (int c = 0; c < 7; ++c)
-                    if (o.cls_n[8 * s + c])
-                        std::fprintf(stderr, " c%d %u x %.2f us", c, o.cls_n[8 * s + c],
-                                     o.cls_ticks[8 * s + c] / 100.0 / o.cls_n[8 * s + c]);
-            }
-            std::fprintf(stderr, "\n  finish: cycles %d searches %d parents %u marked %u leaders %u closed %u", o.cycles,
-                         o.searches, o.cyc_dbg[0], o.cyc_dbg[1], o.cyc_dbg[2], o.cyc_dbg[3]);
-            std::fprintf(stderr, "\n  ms by phase:");
-            for (int i = 0; i < 8; ++i)
-                if (o.phase_ticks[i]) std::fprintf(stderr, " %s%d %.2f", i == 7 ? "pr/" : "p", i + 1, o.phase_ticks[i] / 1e5);
-            static const char* const sz[6] = {"<=16", "<=64", "<=256", "<=1k", "<=4k", ">4k"};
-            for (int h = 0; h < 12; ++h) {
-                if (h % 6 == 0) std::fprintf(stderr, "\n  %s by frontier:", h ? "bf" : "sweep");
-                if (o.hist_n[h])
-                    std::fprintf(stderr, " %s %u x %.2f us", sz[h % 6], o.hist_n[h], o.hist_t[h] / 100.0 / o.hist_n[h]);
-            }
-            std::fprintf(stderr, "\n");
-        }
+        if (cycle_log) log_slowest_cell();
         return worst;
-    };
-    auto cell_status = [&](int cs, const char* what) -> int {
+    }
+    // per-operation device time of the slowest cell (ks_opts.log_cycles)
+    void log_slowest_cell() const {
+        size_t w = 0;
+        for (size_t i = 1; i < s.h_cell_out.size(); ++i)
+            if (s.h_cell_out[i].ticks > s.h_cell_out[w].ticks) w = i;
+        const CellOut& o = s.h_cell_out[w];
+        static const char* names[CELL_NOPS] = {"sat", "gu_init", "bf", "gu_fin", "sweep", "pr_init", "pr", "pr_fin",
+                                               "cyc"};
+        std::fprintf(stderr, "cell %zu of %d: %.3f ms, phases %d updates %d sweeps %llu rounds %llu:", w, ncells,
+                     o.ticks / 1e5, o.phases, o.updates, o.sweeps, o.bf_rounds);
+        for (int i = 0; i < CELL_NOPS; ++i)
+            if (o.op_n[i])
+                std::fprintf(stderr, " %s %u x %.2f us (items %.2f..%.2f)", names[i], o.op_n[i],
+                             o.op_ticks[i] / 100.0 / o.op_n[i], o.first_ticks[i] / 100.0 / o.op_n[i],
+                             o.item_ticks[i] / 100.0 / o.op_n[i]);
+        static const char* const steps[4] = {"sweep", "bf", "pr", "sat"};
+        for (int s = 0; s < 4; ++s) {
+            std::fprintf(stderr, "\n  %s items:", steps[s]);
+            for (int c = 0; c < 7; ++c)
+                if (o.cls_n[8 * s + c])
+                    std::fprintf(stderr, " c%d %u x %.2f us", c, o.cls_n[8 * s + c],
+                                 o.cls_ticks[8 * s + c] / 100.0 / o.cls_n[8 * s + c]);
+        }
+        std::fprintf(stderr, "\n  finish: cycles %d searches %d parents %u marked %u leaders %u closed %u", o.cycles,
+                     o.searches, o.cyc_dbg[0], o.cyc_dbg[1], o.cyc_dbg[2], o.cyc_dbg[3]);
+        std::fprintf(stderr, "\n  ms by phase:");
+        for (int i = 0; i < 8; ++i)
+            if (o.phase_ticks[i]) std::fprintf(stderr, " %s%d %.2f", i == 7 ? "pr/" : "p", i + 1, o.phase_ticks[i] / 1e5);
+        static const char* const sz[6] = {"<=16", "<=64", "<=256", "<=1k", "<=4k", ">4k"};
+        for (int h = 0; h < 12; ++h) {
+            if (h % 6 == 0) std::fprintf(stderr, "\n  %s by frontier:", h ? "bf" : "sweep");
+            if (o.hist_n[h])
+                std::fprintf(stderr, " %s %u x %.2f us", sz[h % 6], o.hist_n[h], o.hist_t[h] / 100.0 / o.hist_n[h]);
+        }
+        std::fprintf(stderr, "\n");
+    }
+    int cell_status(int cs, const char* what) {
         if (cs == CS_OK) return KS_OK;
         if (cs == CS_INFEASIBLE) {
             status = KS_E_INFEASIBLE;
@@ -5553,129 +3919,38 @@ int Engine::solve(ks_result& res, bool warm, std::string& err) {
         err = std::string("cell solver did not converge (") + (cs == CS_TIMEOUT ? "wall-clock limit" : "step cap") +
               ", " + what + ")";
         return KS_E_DEVICE;
-    };
-    if (s.cell_layout) {
-        KS_CHECK(s.cl_pos.ensure(std::max<int64_t>(m2, 1)));
-        KS_CHECK(hipEventRecord(s.ev[3], st));
-        const int cs = run_cells(0);
-        if (cs < 0) return cs;
-        if (cs == CS_RANGE) {   // a value the compact record cannot hold: the multi-kernel engine instead
-            s.cell_refused = true;
-            s.cell_layout = false;
-            s.csr_valid = false;
-            // the warm start's price shift is already in the carried prices: the retry
-            // must not apply it a second time
-            if (use_warm) KS_CHECK(hipMemsetAsync(s.n_cshift.p, 0, s.nstore * sizeof(unsigned long long), st));
-            return solve(res, warm, err);
-        }
-        KS_CHECK(hipEventRecord(s.ev[5], st));
-        KS_CHECK(hipEventSynchronize(s.ev[5]));
-        ms_cycles += ev_ms(s.ev[3], s.ev[5]);
-        if (cs == CS_TIMEOUT || cs == CS_NOCONV) {
-            // Per-cell fallback: only the cells that gave up are solved again, on the
-            // multi-kernel engine (engine order, the state carried across the rebuild:
-            // the converged cells keep their optimal flows and prices, the failing ones
-            // restart cold). One hard cell no longer discards the batch.
-            std::vector<int> bad;
-            for (size_t i = 0; i < s.h_cell_out.size(); ++i)
-                if (s.h_cell_out[i].status == CS_TIMEOUT || s.h_cell_out[i].status == CS_NOCONV) bad.push_back((int)i);
-            s.fb_cells = bad;
-            s.fb_active = true;
-            s.cell_layout = false;
-            s.csr_valid = false;
-            const int rc = solve(res, warm, err);
-            s.fb_active = false;
-            s.fb_cells.clear();
-            res.cell_fallbacks = bad.size();
-            res.solver = 1;
-            res.cells = ncells;
-            return rc;
-        }
-        if (int rc = cell_status(cs, "solve")) return rc;
-        eps = 1;
-    } else do {
-        eps = std::max<long long>(1, eps / alpha);
-        ++phases;
-        // After a failed refinement the flow is feasible and ε-optimal at the old ε:
-        // saturating only the arcs that violate the new ε (rc < −ε) is a valid start
-        // (push-relabel at ε needs an ε-optimal pseudoflow, not a 0-optimal one) and
-        // disturbs far less than saturating every negative arc.
-        // warm_start 2: every phase of a warm solve saturates only the arcs that
-        // violate its ε (the previous optimum's arcs in [−1, 0) stay as they are)
-        // per-cell fallback: the cold ε ladder, every phase saturating only the arcs
-        // that violate its ε (the converged cells' optimal flows stay untouched)
-        long long sat_thr = phases == 1 && use_warm && !fb
-                                ? warm_thr
-                                : ((pr_failed || fb || (use_warm && o.warm_start >= 2)) ? eps : 0LL);
-        pr_failed = false;
-        const bool last_phase = eps / alpha < 1 || eps <= 1 || (use_pr && eps * pr_div < mult);
-        // the phase before the final one drains completely when the cycle-cancelling
-        // finish replaces the final phase
-        const long long eps_next = std::max<long long>(1, eps / alpha);
-        const bool before_last = !last_phase && !prc_tried &&
-                                 (eps_next / alpha < 1 || eps_next <= 1 || (use_pr && eps_next * pr_div < mult));
-        const bool prc_now = use_prc && before_last;
-        // two phases before the last: the finish may follow this phase instead
-        // (run_phase prc_early) when the flow is already close to optimal
-        const long long eps_next2 = std::max<long long>(1, eps_next / alpha);
-        const bool before_last2 = !last_phase && !before_last &&
-                                  (eps_next2 / alpha < 1 || eps_next2 <= 1 || (use_pr && eps_next2 * pr_div < mult));
-        // walk slack > 1 only while a finer phase or price refinement still follows
-        // (ε > 1): a phase at ε = 1 must end 1-optimal (fault_inject bit 0 breaks
-        // exactly this, for the certificate-recovery test)
-        const int walk_sl = (eps > 1 || (o.fault_inject & 1)) ? aug_slack : 1;
-        int prc_early = 0;
-        // (only from a phase at most two cost units coarse: earlier, the finish has
-        // too many cycles to cancel — config 4 with D = 24 at 2.6 units: 26 vs 20 ms)
-        const bool may_early = use_prc && !prc_tried && before_last2 && !use_warm && !fb && eps <= 2 * mult;
-        const int rc = run_phase(eps, sat_thr, !last_phase && !prc_now, walk_sl, may_early ? &prc_early : nullptr);
-        if (rc == KS_E_INFEASIBLE) {
-            status = rc;
-            break;
-        }
-        if (rc) return rc;
-        if (prc_now || prc_early) {   // the feasible flow of the last coarse phase: cancel its negative cycles
-            prc_tried = true;
-            int used = 0;
-            const int pr = prc_refine(&used, prc_early ? std::min(prc_cap, 1024) : prc_cap);
-            if (pr < 0) return pr;
-            if (pr == 1) {
-                eps = 1;
-                break;
-            }
-            pr_failed = true;   // the final phase follows, saturating only its violations
-            continue;
-        }
-        // certify optimality early: a flow that is 1-optimal (scaled) is optimal.
-        // Tried once ε is below 1/32 of a cost unit, where it usually succeeds.
-        if (use_pr && eps > 1 && eps * pr_div < mult) {
-            int used = 0;
-            const int pr = price_refine(1, &used, pr_cap);
-            if (pr < 0) return pr;
-            if (pr == 1) eps = 1;
-            else pr_failed = true;
-        }
-    } while (eps > 1);
-
-    if (cycle_log)
-        std::fprintf(stderr, "solve phases %d updates %llu (forward %llu) early phase ends %llu\n", phases,
-                     (unsigned long long)gus, (unsigned long long)fwd_updates, (unsigned long long)early_exits);
-    if (status == KS_E_INFEASIBLE && !s.cell_layout)
-        err = "infeasible: some supply cannot reach a demand node (code " + std::to_string(s.h_ctl->infeasible) +
-              ", phase " + std::to_string(phases) + ", eps " + std::to_string(eps) + ", updates " +
-              std::to_string(gus) + ", sweeps " + std::to_string(sweep_launches) + ")";
+    }
 
     // ------------------------------------------------------------ verify ---
+    // The certificate of a solve that ended feasible: verification, the repair of a
+    // failed optimality certificate, and a warm start's canonical prices.
+    int certify() {
+        if (o.fault_inject & 2)   // TESTS ONLY: break the certificate, not the flow
+            hipLaunchKernelGGL(k_perturb_price, dim3(1), dim3(1), 0, st, g, 0, 1000 * mult);
+        int bad = 0;
+        int rc = verify(&bad);
+        if (rc) return rc;
+        if ((rc = recover(&bad))) return rc;
+        if (status == KS_OK && bad && o.verify) {
+            status = KS_E_VERIFY;
+            err = std::string("on-device verification failed (") + ((bad & 1) ? "capacity " : "") +
+                  ((bad & 2) ? "optimality " : "") + ((bad & 4) ? "conservation" : "") + ")";
+        }
+        // warm starts: replace the carried prices by the flow's canonical ones (the
+        // next round starts from prices without history). Kept only if the
+        // Bellman-Ford converges; the certificate holds either way.
+        if (status == KS_OK && !bad && o.warm_start > 0 && o.warm_canon >= 0 && !s.cell_layout) {
+            int used = 0;
+            const int pr = price_refine(1, &used, 4 * pr_cap, 1);
+            if (pr < 0) return pr;
+            if (cycle_log) std::fprintf(stderr, "canonical prices: %s after %d rounds\n", pr ? "set" : "not converged", used);
+        }
+        return KS_OK;
+    }
     // Conservation, capacity, 1-optimality of the final prices (scaled units), the
     // int64 cost and the flow value measured from the resident flow. → verify_bad bits
-    const int vgrid = grid_for(hi, 2048);
-    long long tot_cost = 0, tot_flow = 0;
-    auto verify = [&](int* bad) -> int {
-        if (cp_dirty) {   // the compact solve's residuals back into the 32-B records first
-            hipLaunchKernelGGL(k_unpack_pos, dim3(grid_for(m2, 4096)), dim3(BLK), 0, st, (long long)m2,
-                               (const CPos*)s.cpos.p, s.pos.p);
-            cp_dirty = false;
-        }
+    int verify(int* bad) {
+        sync_pos();   // the compact solve's residuals back into the 32-B records first
         if ((o.fault_inject & 64) && m2)   // TESTS ONLY: break conservation, not the excess words
             hipLaunchKernelGGL(k_break_conservation, dim3(1), dim3(64), 0, st, g, (long long)m2);
         KS_CHECK(hipMemsetAsync(&s.ctl.p->verify_bad, 0, sizeof(int), st));
@@ -5707,129 +3982,148 @@ int Engine::solve(ks_result& res, bool warm, std::string& err) {
         for (long long x : partf) tot_flow += x;
         *bad = s.h_ctl->verify_bad;
         return KS_OK;
-    };
-    KS_CHECK(hipEventRecord(s.ev[6], st));
-    if (status == KS_OK) {
-        if (o.fault_inject & 2)   // TESTS ONLY: break the certificate, not the flow
-            hipLaunchKernelGGL(k_perturb_price, dim3(1), dim3(1), 0, st, g, 0, 1000 * mult);
-        int bad = 0;
-        int rc = verify(&bad);
-        if (rc) return rc;
-        // A failed optimality certificate on a feasible flow is repaired, not fatal:
-        // price refinement at ε = 1 (the flow may be optimal, only its prices off),
-        // else one more ε = 1 phase from the current flow (saturating only the arcs
-        // that violate 1-optimality), then verification again. Capacity and
-        // conservation violations stay fatal (KS_E_VERIFY).
-        for (int attempt = 0; attempt < 2 && bad == 2; ++attempt) {
+    }
+    // A failed optimality certificate on a feasible flow is repaired, not fatal:
+    // price refinement at ε = 1 (the flow may be optimal, only its prices off),
+    // else one more ε = 1 phase from the current flow (saturating only the arcs
+    // that violate 1-optimality), then verification again. Capacity and
+    // conservation violations stay fatal (KS_E_VERIFY).
+    int recover(int* bad) {
+        for (int attempt = 0; attempt < 2 && *bad == 2; ++attempt) {
             ++res.recoveries;
             if (s.cell_layout) {   // the same repair inside each cell's workgroup
                 const int cs = run_cells(1);
                 if (cs < 0) return cs;
-                if (int rc2 = cell_status(cs, "certificate recovery")) return rc2;
-                if (status != KS_OK) break;
-                rc = verify(&bad);
-                if (rc) return rc;
-                continue;
-            }
-            int used = 0;
-            const int pr = price_refine(1, &used, 4 * pr_cap);
-            if (pr < 0) return pr;
-            if (pr == 0) {
-                ++phases;
-                rc = run_phase(1, 1, false, 1);
-                if (rc == KS_E_INFEASIBLE) {
-                    status = rc;
-                    err = "infeasible during certificate recovery";
-                    break;
+                if (int rc = cell_status(cs, "certificate recovery")) return rc;
+                if (status != KS_OK) return KS_OK;
+            } else {
+                int used = 0;
+                const int pr = price_refine(1, &used, 4 * pr_cap);
+                if (pr < 0) return pr;
+                if (pr == 0) {
+                    ++phases;
+                    const int rc = run_phase(1, 1, false, 1);
+                    if (rc == KS_E_INFEASIBLE) {
+                        status = rc;
+                        err = "infeasible during certificate recovery";
+                        return KS_OK;
+                    }
+                    if (rc) return rc;
                 }
-                if (rc) return rc;
             }
-            rc = verify(&bad);
-            if (rc) return rc;
+            if (int rc = verify(bad)) return rc;
         }
-        if (status == KS_OK && bad && o.verify) {
-            status = KS_E_VERIFY;
-            err = std::string("on-device verification failed (") + ((bad & 1) ? "capacity " : "") +
-                  ((bad & 2) ? "optimality " : "") + ((bad & 4) ? "conservation" : "") + ")";
-        }
-        // warm starts: replace the carried prices by the flow's canonical ones (the
-        // next round starts from prices without history). Kept only if the
-        // Bellman-Ford converges; the certificate holds either way.
-        if (status == KS_OK && !bad && o.warm_start > 0 && o.warm_canon >= 0 && !s.cell_layout) {
-            int used = 0;
-            const int pr = price_refine(1, &used, 4 * pr_cap, 1);
-            if (pr < 0) return pr;
-            if (cycle_log) std::fprintf(stderr, "canonical prices: %s after %d rounds\n", pr ? "set" : "not converged", used);
-        }
+        return KS_OK;
     }
-    if (cp_dirty) {   // (a solve that ended without verification: Pos stays the authoritative copy)
-        hipLaunchKernelGGL(k_unpack_pos, dim3(grid_for(m2, 4096)), dim3(BLK), 0, st, (long long)m2,
-                           (const CPos*)s.cpos.p, s.pos.p);
-        cp_dirty = false;
-    }
-    KS_CHECK(hipEventRecord(s.ev[7], st));
-    unsigned long long hc[CTR_SHARDS * NCTR];
-    KS_CHECK(hipMemcpyAsync(hc, s.ctr.p, sizeof(hc), hipMemcpyDeviceToHost, st));
-    KS_CHECK(hipStreamSynchronize(st));
-    unsigned long long tc[NCTR] = {0};
-    for (int i = 0; i < CTR_SHARDS; ++i)
-        for (int k = 0; k < NCTR; ++k) tc[k] += hc[i * NCTR + k];
-    if (s.cell_layout) {
-        tc[C_SCAN] += cell_ctr[0];
-        tc[C_VISIT] += cell_ctr[1];
-        tc[C_PUSH] += cell_ctr[2];
-        tc[C_RELABEL] += cell_ctr[3];
-        tc[C_GUSCAN] += cell_ctr[4];
-        tc[C_BFROUND] += cell_rounds;
-    }
-    if (cycle_log)
-        std::fprintf(stderr, "solve tail walks to a deficit %llu, hops %llu, recoveries %d\n", tc[C_AUGWALK],
-                     tc[C_AUGHOP], res.recoveries);
 
-    res.total_cost = tot_cost;
-    res.flow_value = tot_flow;
-    res.phases = phases;
-    res.sweeps = sweeps;
-    res.arc_scans = tc[C_SCAN];
-    res.node_visits = tc[C_VISIT];
-    res.pushes = tc[C_PUSH];
-    res.relabels = tc[C_RELABEL];
-    res.global_updates = gus;
-    res.gu_iterations = tc[C_BFROUND];
-    res.ms_phase[0] = ev_ms(s.ev[0], s.ev[1]);
-    res.ms_phase[1] = ms_sat;
-    res.ms_phase[2] = ms_cycles;
-    res.ms_phase[3] = ms_pr;
-    res.ms_phase[4] = ev_ms(s.ev[6], s.ev[7]);
-    res.ms_phase[5] = 1e3 * wall_s();
-    res.gu_arc_scans = tc[C_GUSCAN];
-    res.gu_leaf_scans = tc[C_GULEAF];
-    res.fs_arc_scans = tc[C_FSSCAN];
-    res.sweep_launches = sweep_kernels;
-    res.ms_sweep_kernels = ms_sw_k;
-    res.gu_launches = bf_launches;
-    res.ms_gu_kernels = ms_bf_k;
-    res.fs_launches = fs_launches;
-    res.ms_fs_kernels = ms_fs_k;
-    res.fwd_updates = fwd_updates;
-    res.solver = s.cell_layout ? 1 : 0;
-    res.cells = s.cell_layout ? ncells : 0;
-    res.ms_cell_kernel = ms_cell;
-    res.cell_ticks_max = cticks_max;
-    res.cell_ticks_sum = cticks_sum;
-    res.status = status;
-    res.cycles_cancelled = (uint64_t)prc_cycles;
-    res.cycles_rejected = (uint64_t)prc_rejected;
-    KS_CHECK(hipMemsetAsync(s.n_cshift.p, 0, s.nstore * sizeof(unsigned long long), st));
-    if (status == KS_OK) {
-        KS_CHECK(hipMemsetAsync(s.n_fresh.p, 0, s.nstore, st));
+    // ------------------------------------------------------------ report ---
+    int report() {
+        sync_pos();   // (a solve that ended without verification: Pos stays the authoritative copy)
+        KS_CHECK(hipEventRecord(s.ev[6], st));
+        unsigned long long hc[CTR_SHARDS * NCTR];
+        KS_CHECK(hipMemcpyAsync(hc, s.ctr.p, sizeof(hc), hipMemcpyDeviceToHost, st));
         KS_CHECK(hipStreamSynchronize(st));
-        s.solved = true;
-        s.has_prev = true;
-    } else {
-        s.has_prev = false;   // a failed solve leaves no usable warm state
+        unsigned long long tc[NCTR] = {0};
+        for (int i = 0; i < CTR_SHARDS; ++i)
+            for (int k = 0; k < NCTR; ++k) tc[k] += hc[i * NCTR + k];
+        if (s.cell_layout) {
+            tc[C_SCAN] += cell_ctr[0];
+            tc[C_VISIT] += cell_ctr[1];
+            tc[C_PUSH] += cell_ctr[2];
+            tc[C_RELABEL] += cell_ctr[3];
+            tc[C_GUSCAN] += cell_ctr[4];
+            tc[C_BFROUND] += cell_rounds;
+        }
+        if (cycle_log)
+            std::fprintf(stderr, "solve tail walks to a deficit %llu, hops %llu, recoveries %d\n", tc[C_AUGWALK],
+                         tc[C_AUGHOP], res.recoveries);
+
+        res.total_cost = tot_cost;
+        res.flow_value = tot_flow;
+        res.phases = phases;
+        res.sweeps = sweeps;
+        res.arc_scans = tc[C_SCAN];
+        res.node_visits = tc[C_VISIT];
+        res.pushes = tc[C_PUSH];
+        res.relabels = tc[C_RELABEL];
+        res.global_updates = gus;
+        res.gu_iterations = tc[C_BFROUND];
+        res.ms_phase[0] = ev_ms(s.ev[0], s.ev[1]);
+        res.ms_phase[1] = ms_sat;
+        res.ms_phase[2] = ms_cycles;
+        res.ms_phase[3] = ms_pr;
+        res.ms_phase[4] = ev_ms(s.ev[5], s.ev[6]);
+        res.ms_phase[5] = 1e3 * wall_s();
+        res.gu_arc_scans = tc[C_GUSCAN];
+        res.gu_leaf_scans = tc[C_GULEAF];
+        res.fs_arc_scans = tc[C_FSSCAN];
+        res.sweep_launches = sweep_kernels;
+        res.ms_sweep_kernels = ms_sw_k;
+        res.gu_launches = bf_launches;
+        res.ms_gu_kernels = ms_bf_k;
+        res.fs_launches = fs_launches;
+        res.ms_fs_kernels = ms_fs_k;
+        res.fwd_updates = fwd_updates;
+        res.solver = s.cell_layout ? 1 : 0;
+        res.cells = s.cell_layout ? ncells : 0;
+        res.ms_cell_kernel = ms_cell;
+        res.cell_ticks_max = cticks_max;
+        res.cell_ticks_sum = cticks_sum;
+        res.status = status;
+        res.cycles_cancelled = (uint64_t)prc_cycles;
+        res.cycles_rejected = (uint64_t)prc_rejected;
+        KS_CHECK(hipMemsetAsync(s.n_cshift.p, 0, s.nstore * sizeof(unsigned long long), st));
+        if (status == KS_OK) {
+            KS_CHECK(hipMemsetAsync(s.n_fresh.p, 0, s.nstore, st));
+            KS_CHECK(hipStreamSynchronize(st));
+            s.solved = true;
+            s.has_prev = true;
+        } else {
+            s.has_prev = false;   // a failed solve leaves no usable warm state
+        }
+        return status;
     }
-    return status;
+};
+
+}  // namespace
+
+// The driver: one SolveRun, and the cell solver's two hand-overs to the multi-kernel
+// engine, each a second run over the same graph in the engine's node order.
+int Engine::solve(ks_result& res, bool warm, std::string& err) {
+    EngineImpl& s = *p_;
+    KS_CHECK(hipSetDevice(s.device));
+    SolveRun run(s, res, err, warm);
+    const int rc = run.run();
+    if (run.retry == SolveRun::RETRY_RANGE) {   // a value the compact record cannot hold: the multi-kernel engine instead
+        s.cell_refused = true;
+        s.cell_layout = false;
+        s.csr_valid = false;
+        // the warm start's price shift is already in the carried prices: the retry
+        // must not apply it a second time
+        if (run.use_warm) KS_CHECK(hipMemsetAsync(s.n_cshift.p, 0, s.nstore * sizeof(unsigned long long), s.stream));
+        return solve(res, warm, err);
+    }
+    if (run.retry == SolveRun::RETRY_CELLS) {
+        // Per-cell fallback: only the cells that gave up are solved again, on the
+        // multi-kernel engine (engine order, the state carried across the rebuild:
+        // the converged cells keep their optimal flows and prices, the failing ones
+        // restart cold). One hard cell no longer discards the batch.
+        std::vector<int> bad;
+        for (size_t i = 0; i < s.h_cell_out.size(); ++i)
+            if (s.h_cell_out[i].status == CS_TIMEOUT || s.h_cell_out[i].status == CS_NOCONV) bad.push_back((int)i);
+        s.fb_cells = bad;
+        s.fb_active = true;
+        s.cell_layout = false;
+        s.csr_valid = false;
+        const int rc2 = solve(res, warm, err);
+        s.fb_active = false;
+        s.fb_cells.clear();
+        res.cell_fallbacks = bad.size();
+        res.solver = 1;
+        res.cells = run.ncells;
+        return rc2;
+    }
+    return rc;
 }
 
 }  // namespace ks

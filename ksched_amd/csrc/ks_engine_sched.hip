@@ -1,0 +1,368 @@
+// ks_engine_sched.hip — the engine's scheduler glue: bindings, scheduling deltas,
+// unscheduled costs, topology statistics and ks_commit_schedule. It launches the
+// kernels of ks_sched.hip and ks_store.hip through their launchers, none of the engine's.
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "ks_engine_impl.h"
+
+namespace ks {
+
+// ------------------------------------------------- scheduler-side sweeps ---
+int Engine::set_bindings(const uint64_t* task, const uint64_t* pu, size_t k, std::string& err) {
+    EngineImpl& s = *p_;
+    KS_CHECK(hipSetDevice(s.device));
+    if (!k) return KS_OK;
+    std::vector<unsigned long long> ids(task, task + k), vals(pu, pu + k);
+    for (size_t i = 0; i < k; ++i)
+        if (ids[i] == 0 || (int64_t)ids[i] > s.nstore) {
+            err = "binding for a task id beyond the graph";
+            return KS_E_INVALID;
+        }
+    KS_CHECK(s.sched_u.ensure(2 * k));
+    hipStream_t st = s.stream;
+    KS_CHECK(hipMemcpyAsync(s.sched_u.p, ids.data(), k * 8, hipMemcpyHostToDevice, st));
+    KS_CHECK(hipMemcpyAsync(s.sched_u.p + k, vals.data(), k * 8, hipMemcpyHostToDevice, st));
+    // the same scatter as the running counts: n_bind[id − 1] = pu
+    KS_CHECK(sched_running_counts(s.schd(), s.sched_u.p, s.sched_u.p + k, (int)k, s.n_bind.p, st));
+    KS_CHECK(hipStreamSynchronize(st));
+    return KS_OK;
+}
+
+int Engine::sched_deltas(int commit, std::vector<ks_sched_delta>* out, size_t* count, int64_t n_tasks,
+                         std::string& err) {
+    EngineImpl& s = *p_;
+    if (!s.solved) {
+        err = "no successful solve";
+        return KS_E_INVALID;
+    }
+    KS_CHECK(hipSetDevice(s.device));
+    hipStream_t st = s.stream;
+    uint64_t* dense = nullptr;
+    size_t nt = 0;
+    int rc = scratch(&dense, std::max<int64_t>(n_tasks, 1), err);
+    if (rc == KS_OK) rc = task_pu(n_tasks ? dense : nullptr, n_tasks, &nt, n_tasks, err);   // also is_task / rank
+    if (rc) return rc;
+    const int64_t ncap = s.ncap;
+    if (!n_tasks) {   // no tasks: map arrays were not built; every binding is a preemption
+        KS_CHECK(s.map_is_task.ensure(ncap + 1));
+        KS_CHECK(s.map_rank.ensure(ncap + 1));
+        KS_CHECK(hipMemsetAsync(s.map_is_task.p, 0, (ncap + 1) * sizeof(int), st));
+        KS_CHECK(hipMemsetAsync(s.map_rank.p, 0, (ncap + 1) * sizeof(int), st));
+    }
+    KS_CHECK(s.sched_i.ensure(4 * (ncap + 1) + 4));
+    int* pre = s.sched_i.p;
+    int* other = pre + (ncap + 1);
+    int* pre_pos = other + (ncap + 1);
+    int* other_pos = pre_pos + (ncap + 1);
+    int* bad = other_pos + (ncap + 1);
+    KS_CHECK(hipMemsetAsync(bad, 0, 4 * sizeof(int), st));
+    const SchedDev d = s.schd();
+    KS_CHECK(sched_delta_kinds(d, s.map_is_task.p, s.map_rank.p, (const unsigned long long*)dense, pre, other, bad, st));
+    size_t t = 0;
+    KS_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, t, pre, pre_pos, (int)ncap + 1, st));
+    KS_CHECK(s.map_tmp.ensure(std::max(t, s.map_tmp.n)));
+    t = s.map_tmp.n;
+    KS_CHECK(hipcub::DeviceScan::ExclusiveSum(s.map_tmp.p, t, pre, pre_pos, (int)ncap + 1, st));
+    t = s.map_tmp.n;
+    KS_CHECK(hipcub::DeviceScan::ExclusiveSum(s.map_tmp.p, t, other, other_pos, (int)ncap + 1, st));
+    int h[3] = {0, 0, 0};
+    KS_CHECK(hipMemcpyAsync(&h[0], pre_pos + ncap, sizeof(int), hipMemcpyDeviceToHost, st));
+    KS_CHECK(hipMemcpyAsync(&h[1], other_pos + ncap, sizeof(int), hipMemcpyDeviceToHost, st));
+    KS_CHECK(hipMemcpyAsync(&h[2], bad, sizeof(int), hipMemcpyDeviceToHost, st));
+    KS_CHECK(hipStreamSynchronize(st));
+    if (h[2]) {
+        err = "mapping names a destination that is not a PU (graph_manager.go:259-262)";
+        return KS_E_VERIFY;
+    }
+    const int npre = h[0], noth = h[1];
+    *count = (size_t)(npre + noth);
+    if (!out) return KS_OK;
+    KS_CHECK(s.sched_d.ensure(std::max(1, npre + noth)));
+    KS_CHECK(sched_delta_emit(d, s.map_rank.p, (const unsigned long long*)dense, pre, pre_pos, other, other_pos, npre,
+                              s.sched_d.p, commit, st));
+    out->resize(npre + noth);
+    if (npre + noth)
+        KS_CHECK(hipMemcpyAsync(out->data(), s.sched_d.p, (npre + noth) * sizeof(ks_sched_delta), hipMemcpyDeviceToHost,
+                                st));
+    KS_CHECK(hipStreamSynchronize(st));
+    return KS_OK;
+}
+
+int Engine::unsched_costs(const uint64_t* ids, size_t k, int mode, int64_t ucost, int64_t ccost, size_t* changed,
+                          std::string& err) {
+    EngineImpl& s = *p_;
+    KS_CHECK(hipSetDevice(s.device));
+    hipStream_t st = s.stream;
+    const int64_t nb = (s.nstore + 4) & ~3LL;   // byte flags, word-aligned for the atomics
+    KS_CHECK(s.sched_b.ensure(nb));
+    KS_CHECK(s.sched_i.ensure(4));
+    KS_CHECK(hipMemsetAsync(s.sched_b.p, 0, nb, st));
+    KS_CHECK(hipMemsetAsync(s.sched_i.p, 0, sizeof(int), st));
+    const unsigned long long* dids = nullptr;
+    if (ids && k) {
+        for (size_t i = 0; i < k; ++i)
+            if (ids[i] == 0 || (int64_t)ids[i] > s.nstore) {
+                err = "unscheduled aggregator id beyond the graph";
+                return KS_E_INVALID;
+            }
+        KS_CHECK(s.sched_u.ensure(k));
+        KS_CHECK(hipMemcpyAsync(s.sched_u.p, ids, k * 8, hipMemcpyHostToDevice, st));
+        dids = s.sched_u.p;
+    }
+    KS_CHECK(sched_unsched_costs(s.schd(), ids ? dids : nullptr, (int)k, s.sched_b.p, mode, ucost, ccost, s.sched_i.p,
+                                 st));
+    int h = 0;
+    KS_CHECK(hipMemcpyAsync(&h, s.sched_i.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    KS_CHECK(hipStreamSynchronize(st));
+    if (changed) *changed = (size_t)h;
+    if (h) s.solved = false;
+    return KS_OK;
+}
+
+// The level-synchronous BFS of ComputeTopologyStatistics from the sink (slot sink_slot <
+// ncap) over the residual CSR's in-arcs; slots / run (per node slot) start zeroed.
+// Uses sched_i.
+static int topo_bfs(EngineImpl& s, const SchedDev& d, int64_t sink_slot, uint64_t mtpp,
+                    const unsigned long long* pu_slots, const unsigned long long* cnt, unsigned long long* slots,
+                    unsigned long long* run, std::string& err) {
+    hipStream_t st = s.stream;
+    const int64_t nn = s.nn;
+    KS_CHECK(s.sched_i.ensure(3 * (nn + 1) + 2));
+    int* lvl = s.sched_i.p;
+    int* fa = lvl + (nn + 1);
+    int* fb = fa + (nn + 1);
+    int* nnext = fb + (nn + 1);
+    KS_CHECK(hipMemsetAsync(lvl, 0xff, (nn + 1) * sizeof(int), st));
+    int sink_x = 0;
+    KS_CHECK(hipMemcpyAsync(&sink_x, s.perm.p + sink_slot, sizeof(int), hipMemcpyDeviceToHost, st));
+    KS_CHECK(hipStreamSynchronize(st));
+    const int zero = 0;
+    KS_CHECK(hipMemcpyAsync(lvl + sink_x, &zero, sizeof(int), hipMemcpyHostToDevice, st));
+    KS_CHECK(hipMemcpyAsync(fa, &sink_x, sizeof(int), hipMemcpyHostToDevice, st));
+    int nfront = 1;
+    for (int level = 0; nfront > 0 && level <= nn; ++level) {
+        KS_CHECK(hipMemsetAsync(nnext, 0, sizeof(int), st));
+        KS_CHECK(sched_topo_level(d, fa, nfront, level, lvl, fb, nnext, mtpp, pu_slots, cnt, slots, run, st));
+        KS_CHECK(hipMemcpyAsync(&nfront, nnext, sizeof(int), hipMemcpyDeviceToHost, st));
+        KS_CHECK(hipStreamSynchronize(st));
+        std::swap(fa, fb);
+    }
+    return KS_OK;
+}
+
+int Engine::topology_stats(uint64_t mtpp, const uint64_t* pu_ids, const uint64_t* pu_running, size_t k,
+                           int64_t sink_slot, uint64_t* slots_below, uint64_t* running_below, std::string& err) {
+    EngineImpl& s = *p_;
+    KS_CHECK(hipSetDevice(s.device));
+    hipStream_t st = s.stream;
+    if (!s.csr_valid) {   // the BFS walks the residual CSR's in-arcs
+        int rc = build(s, err);
+        if (rc) return rc;
+        s.has_prev = false;
+        s.solved = false;
+    }
+    const int64_t ncap = s.ncap;
+    if (sink_slot < 0 || sink_slot >= ncap || ncap == 0) {
+        std::memset(slots_below, 0, s.nslots * sizeof(uint64_t));
+        std::memset(running_below, 0, s.nslots * sizeof(uint64_t));
+        return KS_OK;
+    }
+    KS_CHECK(s.sched_u.ensure(3 * (ncap + 1) + 2 * k));
+    unsigned long long* cnt = s.sched_u.p;
+    unsigned long long* slots = cnt + (ncap + 1);
+    unsigned long long* run = slots + (ncap + 1);
+    unsigned long long* kid = run + (ncap + 1);
+    KS_CHECK(hipMemsetAsync(cnt, 0, 3 * (ncap + 1) * 8, st));
+    if (pu_ids && k) {
+        for (size_t i = 0; i < k; ++i)
+            if (pu_ids[i] == 0 || (int64_t)pu_ids[i] > ncap) {
+                err = "PU id beyond the graph";
+                return KS_E_INVALID;
+            }
+        KS_CHECK(hipMemcpyAsync(kid, pu_ids, k * 8, hipMemcpyHostToDevice, st));
+        KS_CHECK(hipMemcpyAsync(kid + k, pu_running, k * 8, hipMemcpyHostToDevice, st));
+    }
+    const SchedDev d = s.schd();
+    KS_CHECK(sched_running_counts(d, pu_ids ? kid : nullptr, kid + k, (int)k, cnt, st));
+    int rc = topo_bfs(s, d, sink_slot, mtpp, nullptr, cnt, slots, run, err);
+    if (rc) return rc;
+    const int64_t n = std::min<int64_t>(s.nslots, ncap);
+    if (n) {
+        KS_CHECK(hipMemcpyAsync(slots_below, slots, n * 8, hipMemcpyDeviceToHost, st));
+        KS_CHECK(hipMemcpyAsync(running_below, run, n * 8, hipMemcpyDeviceToHost, st));
+        KS_CHECK(hipStreamSynchronize(st));
+    }
+    return KS_OK;
+}
+
+
+// ks_commit_schedule: the deltas of the last solve, then — all of them being PLACEs — the
+// pin, aggregator and resource-capacity records generated in d_recs and applied by
+// store_apply with no node edit. Two host syncs beside the deltas' own and the BFS
+// levels': the record counts (CommitCtl, one copy) and the store's counters.
+// *dirty: the device state may have changed (a failure after that leaves it unknown).
+int Engine::commit_schedule(int flags, int64_t ccost, const uint64_t* ids, size_t k, int64_t sink_slot,
+                            int64_t n_tasks, size_t cap, std::vector<ks_sched_delta>* out, size_t* count,
+                            ks_commit_stats* stats, bool* dirty, std::string& err) {
+    EngineImpl& s = *p_;
+    *dirty = false;
+    if (!s.solved || !s.csr_valid) {
+        err = "no successful solve";
+        return KS_E_INVALID;
+    }
+    KS_CHECK(hipSetDevice(s.device));
+    hipStream_t st = s.stream;
+    const bool log = s.opts.log_cycles != 0;   // (ks_opts.log_cycles: where a commit's time goes)
+    const auto t0 = std::chrono::steady_clock::now();
+    int rc = sched_deltas(0, out, count, n_tasks, err);   // leaves the kinds and their scan in sched_i
+    if (rc) return rc;
+    const auto t1 = std::chrono::steady_clock::now();
+    if (log) KS_CHECK(hipEventRecord(s.kev[0], st));
+    if (cap < out->size()) {
+        err = "output buffer smaller than the delta count";
+        return KS_E_INVALID;
+    }
+    for (const ks_sched_delta& x : *out)
+        if (x.type != KS_DELTA_PLACE) {
+            err = "the solve preempts or migrates task " + std::to_string(x.task) +
+                  ": ks_commit_schedule pins placements only (no preemption mode)";
+            return KS_E_INVALID;
+        }
+    const int resource_caps = (flags & KS_COMMIT_RESOURCE_CAPS) ? 1 : 0;
+    const int64_t ncap = s.ncap, nst = s.nstore;
+    if (resource_caps && (sink_slot < 0 || sink_slot >= ncap)) {
+        err = "resource capacities need exactly one sink";
+        return KS_E_INVALID;
+    }
+    const int hi = s.hi();
+    const int64_t np = (int64_t)out->size();
+    const int64_t ni_max = np + s.m2cap / 64 + 1;
+    // scratch: int arrays of np + 1, ni_max + 1 and hi + 1 entries; per-node-slot counters and flags
+    KS_CHECK(s.cm_i.ensure(7 * (np + 1) + 2 * (ni_max + 1) + 2 * ((int64_t)hi + 1)));
+    KS_CHECK(s.cm_u.ensure(5 * (nst + 1) + k));
+    const int64_t nb = (nst + 4) & ~3LL;
+    KS_CHECK(s.cm_b.ensure(nb));
+    KS_CHECK(s.cm_ctl.ensure(1));
+    KS_CHECK(hipMemsetAsync(s.cm_i.p, 0, s.cm_i.n * sizeof(int), st));
+    KS_CHECK(hipMemsetAsync(s.cm_u.p, 0, 5 * (nst + 1) * 8, st));
+    KS_CHECK(hipMemsetAsync(s.cm_b.p, 0, nb, st));
+    KS_CHECK(hipMemsetAsync(s.cm_ctl.p, 0, sizeof(CommitCtl), st));
+    CommitDev c{};
+    c.np = (int)np;
+    c.ni_max = (int)ni_max;
+    c.pl_task = s.cm_i.p;
+    c.pl_pu = c.pl_task + (np + 1);
+    c.pl_has = c.pl_pu + (np + 1);
+    c.pl_noarc = c.pl_has + (np + 1);
+    c.add_off = c.pl_noarc + (np + 1);
+    c.nch = c.add_off + (np + 1);
+    c.ch_off = c.nch + (np + 1);
+    c.icnt = c.ch_off + (np + 1);
+    c.i_off = c.icnt + (ni_max + 1);
+    c.aflag = c.i_off + (ni_max + 1);
+    c.a_off = c.aflag + (hi + 1);
+    c.fl = s.cm_b.p;
+    c.agg_cnt = s.cm_u.p;
+    c.pu_slots = c.agg_cnt + (nst + 1);
+    c.pu_run = c.pu_slots + (nst + 1);
+    c.slots = c.pu_run + (nst + 1);
+    c.running = c.slots + (nst + 1);
+    c.ctl = s.cm_ctl.p;
+    const unsigned long long* dids = nullptr;
+    if (ids) {
+        for (size_t i = 0; i < k; ++i)
+            if (ids[i] == 0 || (int64_t)ids[i] > nst) {
+                err = "unscheduled aggregator id beyond the graph";
+                return KS_E_INVALID;
+            }
+        unsigned long long* p = c.running + (nst + 1);
+        if (k) KS_CHECK(hipMemcpyAsync(p, ids, k * 8, hipMemcpyHostToDevice, st));
+        dids = p;
+    }
+    auto scan = [&](const int* in, int* o, int64_t n) -> hipError_t {
+        size_t t = 0;
+        hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, t, in, o, (int)n, st);
+        if (e == hipSuccess) e = s.map_tmp.ensure(std::max(t, s.map_tmp.n));
+        t = s.map_tmp.n;
+        if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(s.map_tmp.p, t, in, o, (int)n, st);
+        return e;
+    };
+    SchedDev d = s.schd();
+    {   // the kinds of sched_deltas: [pre | other | pre_pos | other_pos] × (ncap + 1)
+        const int* other = s.sched_i.p + (ncap + 1);
+        const int* other_pos = other + 2 * (ncap + 1);
+        KS_CHECK(sched_commit_places(d, c, s.map_rank.p, (const unsigned long long*)s.map_scratch.p, other, other_pos,
+                                     dids, (int)k, st));
+    }
+    KS_CHECK(scan(c.nch, c.ch_off, np + 1));
+    KS_CHECK(sched_commit_count(d, c, st));
+    KS_CHECK(scan(c.icnt, c.i_off, ni_max + 1));
+    KS_CHECK(scan(c.pl_noarc, c.add_off, np + 1));
+    if (resource_caps) {
+        KS_CHECK(sched_commit_pu_counts(d, c, st));
+        rc = topo_bfs(s, d, sink_slot, 0, c.pu_slots, c.pu_run, c.slots, c.running, err);
+        if (rc) return rc;
+    }
+    KS_CHECK(sched_commit_arc_flags(d, c, resource_caps, st));
+    KS_CHECK(scan(c.aflag, c.a_off, (int64_t)hi + 1));
+    KS_CHECK(sched_commit_totals(d, c, st));
+    CommitCtl h{};
+    KS_CHECK(hipMemcpyAsync(&h, c.ctl, sizeof(CommitCtl), hipMemcpyDeviceToHost, st));
+    KS_CHECK(hipStreamSynchronize(st));
+    const auto t2 = std::chrono::steady_clock::now();
+    if (h.bad) {
+        err = "a capacity would fall below its arc's lower bound";
+        return KS_E_VERIFY;
+    }
+    const int64_t nrec = (int64_t)h.rec_pin + h.rec_add + h.rec_arc;
+    if (h.rec_pin < 0 || h.rec_add < 0 || h.rec_add > np || h.rec_arc < 0 || h.rec_arc > hi ||
+        h.rec_pin > s.m2cap || nrec > INT32_MAX) {
+        err = "inconsistent record counts";
+        return KS_E_DEVICE;
+    }
+    rc = ensure_arcs(s, (int64_t)hi + h.rec_add, err);   // the only new arcs: one running arc per placed task
+    if (rc == KS_OK) rc = ensure_hash(s, h.rec_add, err);
+    if (rc) return rc;
+    KS_CHECK(s.d_recs.ensure(std::max<size_t>(nrec, 1)));
+    KS_CHECK(s.rec_ent.ensure(std::max<size_t>(nrec, 1)));
+    KS_CHECK(s.d_edits.ensure(1));
+    d = s.schd();   // (the arc table may have moved)
+    *dirty = true;
+    KS_CHECK(sched_commit_emit(d, c, ccost, resource_caps, s.d_recs.p, st));
+    KS_CHECK(store_apply(s.sd(), s.d_recs.p, (int)nrec, s.rec_ent.p, s.d_edits.p, 0, st));
+    if (log) KS_CHECK(hipEventRecord(s.kev[1], st));
+    rc = read_sctl(s, err);
+    if (rc == KS_OK) rc = applied(s, err);
+    if (rc) return rc;
+    if (log) {
+        const auto t3 = std::chrono::steady_clock::now();
+        auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+        std::fprintf(stderr,
+                     "commit: %lld records, deltas %.3f ms, count passes %.3f ms, emit + apply %.3f ms, "
+                     "device span after the deltas %.3f ms\n",
+                     (long long)nrec, ms(t0, t1), ms(t1, t2), ms(t2, t3), ev_ms(s.kev[0], s.kev[1]));
+    }
+    s.incremental = true;
+    s.solved = false;
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        stats->placed = np;
+        stats->running_converted = np - h.rec_add;
+        stats->running_added = h.rec_add;
+        stats->arcs_removed = h.rec_pin - stats->running_converted;
+        stats->unsched_updates = h.unsched;
+        stats->cap_updates = h.caps;
+        stats->records = nrec;
+    }
+    return KS_OK;
+}
+
+
+}  // namespace ks

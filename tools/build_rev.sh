@@ -12,7 +12,7 @@ done
 git -C "$ROOT" show "$REV:include/ksmcmf.h" > "$T/include/ksmcmf.h"
 cd "$T/ksched_amd/csrc"
 SRCS=""
-for f in ks_engine.hip ks_cell.hip ks_store.hip ks_sched.hip ks_batch.hip ks_host.cpp; do
+for f in ks_engine.hip ks_engine_build.hip ks_engine_io.hip ks_engine_sched.hip ks_cell.hip ks_store.hip ks_sched.hip ks_batch.hip ks_host.cpp; do
     [ -f "$f" ] && SRCS="$SRCS $f"
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -Wno-unused-function -I"$T/include" \
