@@ -171,8 +171,13 @@ __device__ int claim_pos(const StoreDev& d, int x, int tag) {
     if (ps < cap && atomicCAS(&d.ent[b + ps], -1, tag) == -1) return b + ps;
     constexpr int SCAN = 64;
     const int chunks = (cap + SCAN - 1) / SCAN;
+    if (chunks == 0) return -1;   // an empty segment (a node without arcs in the tight CSR of a load)
+    // the cursor gives the first chunk only; the lane then walks the following ones itself
+    // (a cursor drawn per chunk is shared with the other lanes claiming in x, which can hand
+    // one lane the same full chunk every time while another chunk has room)
+    const int c0 = (int)((unsigned)atomicAdd(&d.scur[x], 1) % (unsigned)chunks);
     for (int k = 0; k < chunks && k < 64; ++k) {
-        const int c = (int)((unsigned)atomicAdd(&d.scur[x], 1) % (unsigned)chunks);
+        const int c = (c0 + k) % chunks;
         const int lo = b + c * SCAN, hi = min(e, lo + SCAN);
         for (int p = lo; p < hi; ++p)
             if (__hip_atomic_load(&d.ent[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == -1 &&

@@ -249,4 +249,116 @@ def random_hub_graphs(seed: int, count: int, n_lo: int = 300, n_hi: int = 6000, 
         supply[ends[:k] - 1] += units
         supply[ends[k:] - 1] -= units
         ntype = np.zeros(n, np.int32)
-        yield trial, gen.Graph(ntype, supply, src, dst, low, cap.astype(np.int64), cost.astype(np.int64))
+        g = gen.Graph(ntype, supply, src, dst, low, cap.astype(np.int64), cost.astype(np.int64))
+        g.hubs = [int(h) for h in hubs]   # (hubs[0] carries the feasibility arcs, when there are any)
+        yield trial, g
+
+
+# (seed, first stream applied after a first solve) of the adversarial random-stream cases
+# (test_gpu_stress); test_store_ref_cpu checks on the oracle that they stay feasible
+ADVERSARIAL_SEEDS = [(24, True), (31, True), (28, False)]
+
+
+def random_stream(rng, nodes, arcs, nrec, hubs=(), adversarial=False):
+    """A random ks_delta stream over the store state (nodes {id: [excess, type]},
+    arcs {(s, d): (low, cap, cost)}), applied to that state as it is made: node
+    removals (zero-supply nodes; their arcs go with them) and re-additions of the
+    freed ids with new arcs, arc upserts, in-place edits, deletions (UPDATE 0/0),
+    an arc deleted and re-created inside one stream (the store keeps the LAST
+    record for a key), and a few units moved between two sources (SET_EXCESS
+    pairs). The generator's expensive feasibility arcs are left alone, so most
+    rounds stay feasible.
+
+    adversarial: the stream also removes, a quarter of the way in, three pairs of
+    adjacent zero-supply nodes (an arc with both endpoints removed) and, half way
+    in, one hub of the generator (hubs[1:], never the feasibility hub hubs[0] nor an
+    end of a feasibility arc; once those are gone, the eligible node of the highest
+    degree): a node of hundreds of arcs removed among nodes of a few. Without the
+    flag the stream is what it always was for a given rng."""
+    from ksched_amd import native
+    recs = []
+    free_ids = []
+    alive = sorted(nodes)
+    keep = {x for (s, d), (_, _, c) in arcs.items() if c >= 50_000 for x in (s, d)}   # feasibility arcs' ends
+    keep |= set(hubs[:1]) if adversarial else set()
+    todo = [(nrec // 2, "hub"), (nrec // 4, "pairs")] if adversarial else []
+
+    def emit(**x):
+        r = np.zeros(1, native.DELTA_DT)
+        for k, v in x.items():
+            r[0][k] = v
+        apply_deltas_to_arcs(nodes, arcs, r)
+        recs.append(r[0])
+
+    def removable(i):
+        return i in nodes and nodes[i][0] == 0 and i not in keep
+
+    def remove(i):
+        emit(kind=native.KS_REMOVE_NODE, id=i)
+        free_ids.append(i)
+
+    keys = list(arcs)
+    while len(recs) < nrec:
+        if todo and len(recs) >= todo[-1][0]:
+            if todo.pop()[1] == "pairs":
+                for _ in range(3):
+                    adj = [k for k in arcs if removable(k[0]) and removable(k[1]) and not set(k) & set(hubs)]
+                    if adj:
+                        for i in adj[int(rng.integers(0, len(adj)))]:
+                            remove(i)
+            else:
+                deg = {}
+                for k in arcs:
+                    for i in k:
+                        deg[i] = deg.get(i, 0) + 1
+                # (a hub removed in an earlier round may be back under its id with three arcs)
+                cand = [h for h in hubs[1:] if removable(h) and deg.get(h, 0) >= 64]
+                if not cand:
+                    cand = sorted((i for i in deg if removable(i)), key=lambda i: (-deg[i], i))[:1]
+                if cand:
+                    remove(cand[0])
+            alive = sorted(nodes)
+            continue
+        op = rng.random()
+        if op < 0.05:
+            i = int(rng.choice(alive))
+            if nodes.get(i, [1])[0] == 0 and i not in keep:
+                emit(kind=native.KS_REMOVE_NODE, id=i)
+                free_ids.append(i)
+                alive = sorted(nodes)
+        elif op < 0.10 and free_ids:
+            i = free_ids.pop(0)   # FIFO id reuse (graph.go:169-182)
+            emit(kind=native.KS_ADD_NODE, id=i, excess=0, type=0)
+            alive = sorted(nodes)
+            for j in rng.choice(alive, 3, replace=False).tolist():
+                if j != i:
+                    s, d = (i, j) if rng.random() < 0.5 else (j, i)
+                    emit(kind=native.KS_ADD_ARC, src=s, dst=d, low=0, cap=int(rng.integers(1, 30)),
+                         cost=int(rng.integers(0, 1000)))
+        elif op < 0.40:
+            s, d = (int(x) for x in rng.choice(alive, 2, replace=False))
+            emit(kind=native.KS_ADD_ARC, src=s, dst=d, low=0, cap=int(rng.integers(0, 30)),
+                 cost=int(rng.integers(0, 1000)))
+        elif op < 0.90 and keys:
+            s, d = keys[int(rng.integers(0, len(keys)))]
+            if (s, d) not in arcs or arcs[(s, d)][2] >= 50_000:   # (the generator's feasibility arcs stay)
+                continue
+            low, cap, cost = arcs[(s, d)]
+            r = rng.random()
+            if r < 0.3:     # delete (UPDATE to 0/0), sometimes re-created later in this stream
+                emit(kind=native.KS_UPDATE_ARC, src=s, dst=d, low=0, cap=0, cost=cost, old_cost=cost)
+                if rng.random() < 0.3:
+                    emit(kind=native.KS_ADD_ARC, src=s, dst=d, low=0, cap=int(rng.integers(1, 30)),
+                         cost=int(rng.integers(0, 1000)))
+            else:           # new capacity and cost in place (the flow is clamped)
+                emit(kind=native.KS_UPDATE_ARC, src=s, dst=d, low=low, cap=max(low, int(rng.integers(0, 60))),
+                     cost=int(rng.integers(0, 1000)), old_cost=cost)
+        elif op < 0.92:    # a few units moved from one source to another
+            src = [i for i in alive if nodes[i][0] > 3]
+            if len(src) < 2:
+                continue
+            a, b = (int(x) for x in rng.choice(src, 2, replace=False))
+            k = int(rng.integers(1, 4))
+            emit(kind=native.KS_SET_EXCESS, id=a, excess=nodes[a][0] + k)
+            emit(kind=native.KS_SET_EXCESS, id=b, excess=nodes[b][0] - k)
+    return np.array(recs, native.DELTA_DT)

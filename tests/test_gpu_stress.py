@@ -9,10 +9,11 @@ with KS_E_INFEASIBLE."""
 import numpy as np
 import pytest
 
-from graphs import random_hub_graphs
+from graphs import ADVERSARIAL_SEEDS, graph_from_store, random_hub_graphs, random_stream
 from ksched_amd import native
 from oracle import ko
-from test_gpu_parity import solve_and_check
+from store_ref import StoreRef, check_counters, same_store
+from test_gpu_parity import flows_by_arc, solve_and_check
 
 pytestmark = pytest.mark.gpu
 
@@ -53,105 +54,62 @@ def test_resolve_is_repeatable(ctx_engine):
             assert r.raw["recoveries"] == 0
 
 
-def _random_stream(rng, nodes, arcs, nrec):
-    """A random ks_delta stream over the store state (nodes {id: [excess, type]},
-    arcs {(s, d): (low, cap, cost)}), applied to that state as it is made: node
-    removals (zero-supply nodes; their arcs go with them) and re-additions of the
-    freed ids with new arcs, arc upserts, in-place edits, deletions (UPDATE 0/0),
-    an arc deleted and re-created inside one stream (the store keeps the LAST
-    record for a key), and a few units moved between two sources (SET_EXCESS
-    pairs). The generator's expensive feasibility arcs are left alone, so most
-    rounds stay feasible."""
-    from graphs import apply_deltas_to_arcs
-    recs = []
-    free_ids = []
-    alive = sorted(nodes)
-    keep = {x for (s, d), (_, _, c) in arcs.items() if c >= 50_000 for x in (s, d)}   # feasibility arcs' ends
-
-    def emit(**x):
-        r = np.zeros(1, native.DELTA_DT)
-        for k, v in x.items():
-            r[0][k] = v
-        apply_deltas_to_arcs(nodes, arcs, r)
-        recs.append(r[0])
-
-    keys = list(arcs)
-    while len(recs) < nrec:
-        op = rng.random()
-        if op < 0.05:
-            i = int(rng.choice(alive))
-            if nodes.get(i, [1])[0] == 0 and i not in keep:
-                emit(kind=native.KS_REMOVE_NODE, id=i)
-                free_ids.append(i)
-                alive = sorted(nodes)
-        elif op < 0.10 and free_ids:
-            i = free_ids.pop(0)   # FIFO id reuse (graph.go:169-182)
-            emit(kind=native.KS_ADD_NODE, id=i, excess=0, type=0)
-            alive = sorted(nodes)
-            for j in rng.choice(alive, 3, replace=False).tolist():
-                if j != i:
-                    s, d = (i, j) if rng.random() < 0.5 else (j, i)
-                    emit(kind=native.KS_ADD_ARC, src=s, dst=d, low=0, cap=int(rng.integers(1, 30)),
-                         cost=int(rng.integers(0, 1000)))
-        elif op < 0.40:
-            s, d = (int(x) for x in rng.choice(alive, 2, replace=False))
-            emit(kind=native.KS_ADD_ARC, src=s, dst=d, low=0, cap=int(rng.integers(0, 30)),
-                 cost=int(rng.integers(0, 1000)))
-        elif op < 0.90 and keys:
-            s, d = keys[int(rng.integers(0, len(keys)))]
-            if (s, d) not in arcs or arcs[(s, d)][2] >= 50_000:   # (the generator's feasibility arcs stay)
-                continue
-            low, cap, cost = arcs[(s, d)]
-            r = rng.random()
-            if r < 0.3:     # delete (UPDATE to 0/0), sometimes re-created later in this stream
-                emit(kind=native.KS_UPDATE_ARC, src=s, dst=d, low=0, cap=0, cost=cost, old_cost=cost)
-                if rng.random() < 0.3:
-                    emit(kind=native.KS_ADD_ARC, src=s, dst=d, low=0, cap=int(rng.integers(1, 30)),
-                         cost=int(rng.integers(0, 1000)))
-            else:           # new capacity and cost in place (the flow is clamped)
-                emit(kind=native.KS_UPDATE_ARC, src=s, dst=d, low=low, cap=max(low, int(rng.integers(0, 60))),
-                     cost=int(rng.integers(0, 1000)), old_cost=cost)
-        elif op < 0.92:    # a few units moved from one source to another
-            src = [i for i in alive if nodes[i][0] > 3]
-            if len(src) < 2:
-                continue
-            a, b = (int(x) for x in rng.choice(src, 2, replace=False))
-            k = int(rng.integers(1, 4))
-            emit(kind=native.KS_SET_EXCESS, id=a, excess=nodes[a][0] + k)
-            emit(kind=native.KS_SET_EXCESS, id=b, excess=nodes[b][0] - k)
-    return np.array(recs, native.DELTA_DT)
-
-
-@pytest.mark.parametrize("seed,nrec", [(5, 2000), (6, 2000), (7, 20000)])
-def test_random_delta_streams_match_full_graph(any_ctx, seed, nrec):
-    """Random delta streams (four rounds of 2,000 or of 20,000 records) on a hub
-    graph: after ks_apply_deltas the device solve equals the oracle on the full
-    graph the test-side restatement of the store builds
-    (graphs.apply_deltas_to_arcs), or both are infeasible."""
-    from graphs import graph_from_store
-    ctx = any_ctx
+def _run_streams(ctx, seed, nrec, adversarial=False, solve_first=True):
+    """Four rounds of random_stream on a feasible hub graph. After every
+    ks_apply_deltas the store read back (ks_get_graph) equals the reference state and
+    the path-independent counters equal its expectation (store_ref); the solve equals
+    the oracle on the restated graph, its downloaded flows pass the oracle's verifier
+    at that cost, or both are infeasible. → rounds solved."""
     rng = np.random.default_rng(seed)
     g = next(g for _, g in random_hub_graphs(seed, 20, n_lo=1500, n_hi=4000) if ko.ssp(g)[0] == 0)
-    nodes = {i + 1: [int(g.supply[i]), int(g.ntype[i])] for i in range(g.n)}
-    arcs = {(int(s), int(d)): (int(lo), int(c), int(k))
-            for s, d, lo, c, k in zip(g.src, g.dst, g.low, g.cap, g.cost)}
+    ref = StoreRef.from_graph(g)
+    nodes, arcs = ref.nodes, ref.arcs   # the generator applies each record to them as it emits it
     ctx.load_graph(g)
-    ctx.solve()
+    if solve_first:
+        ctx.solve()
     solved = 0
     for rnd in range(4):
-        ctx.apply_deltas(_random_stream(rng, nodes, arcs, nrec))
+        before = set(arcs)
+        stream = random_stream(rng, nodes, arcs, nrec, g.hubs, adversarial)
+        ctx.apply_deltas(stream)
+        want = ref.account(before, stream)
+        same_store(ctx, ref)
+        check_counters(ctx.store_stats(), want, exact=False)
         h = graph_from_store(nodes, arcs)
         st, cost, fv, _, _ = ko.ssp(h)
         if st == 0:
             r = ctx.solve()
             assert (r.cost, r.flow) == (cost, fv), f"round {rnd}"
             assert r.raw["recoveries"] == 0
+            vst, vcost, _ = ko.verify(h, flows_by_arc(ctx, h))
+            assert vst == 0 and vcost == cost, f"round {rnd}: the oracle's verifier rejected the downloaded flows"
             solved += 1
         else:
             with pytest.raises(native.KsError) as ei:
                 ctx.solve()
             assert ei.value.code == native.KS_E_INFEASIBLE, f"round {rnd}"
-    assert solved >= 2
+    return solved
+
+
+@pytest.mark.parametrize("seed,nrec", [(5, 2000), (6, 2000), (7, 20000)])
+def test_random_delta_streams_match_full_graph(any_ctx, seed, nrec):
+    """Random delta streams (four rounds of 2,000 or of 20,000 records) on a hub
+    graph: after ks_apply_deltas the store equals the test-side restatement
+    (graphs.apply_deltas_to_arcs, store_ref) arc by arc and counter by counter, and
+    the device solve equals the oracle on the full graph that restatement builds,
+    or both are infeasible."""
+    assert _run_streams(any_ctx, seed, nrec) >= 2
+
+
+@pytest.mark.parametrize("seed,solve_first", ADVERSARIAL_SEEDS)
+def test_adversarial_delta_streams_match_full_graph(any_ctx, seed, solve_first):
+    """The same with streams of 2,000 records that also remove a hub of the generator
+    (hundreds of arcs, among removed nodes of a few) and pairs of adjacent nodes
+    (graphs.random_stream, adversarial); one case applies its first stream before the
+    first solve, where the removals go through the store's scan of every arc slot
+    instead of the removed nodes' CSR segments. The seeds were checked on the CPU
+    against the oracle to keep at least two of the four rounds feasible."""
+    assert _run_streams(any_ctx, seed, 2000, adversarial=True, solve_first=solve_first) >= 2
 
 
 @pytest.mark.parametrize("bad", ["missing_endpoint", "self_loop", "remove_missing", "add_present"])
@@ -159,16 +117,16 @@ def test_large_stream_error_rolls_back(ctx_engine, bad):
     """A 20,000-record stream with one bad record near its end: the call fails,
     nothing of the stream is applied (host or device: all or nothing, ks_host.cpp),
     and the valid stream alone then solves as the oracle says."""
-    from graphs import graph_from_store
     rng = np.random.default_rng(11)
     g = next(g for _, g in random_hub_graphs(11, 20, n_lo=3000, n_hi=5000) if ko.ssp(g)[0] == 0)
     nodes = {i + 1: [int(g.supply[i]), int(g.ntype[i])] for i in range(g.n)}
     arcs = {(int(s), int(d)): (int(lo), int(c), int(k))
             for s, d, lo, c, k in zip(g.src, g.dst, g.low, g.cap, g.cost)}
+    ref = StoreRef.from_graph(g)
     ctx_engine.load_graph(g)
     ctx_engine.solve()
     before = (dict((k, list(v)) for k, v in nodes.items()), dict(arcs))
-    good = _random_stream(rng, nodes, arcs, 20000)
+    good = random_stream(rng, nodes, arcs, 20000)
     alive = sorted(nodes)
     row = np.zeros(1, native.DELTA_DT)
     if bad == "missing_endpoint":   # (an id past every node ever present)
@@ -183,6 +141,7 @@ def test_large_stream_error_rolls_back(ctx_engine, bad):
     with pytest.raises(native.KsError) as ei:
         ctx_engine.apply_deltas(stream)
     assert ei.value.code in (native.KS_E_INVALID, native.KS_E_RANGE)
+    same_store(ctx_engine, ref)   # the store read back: untouched, node table and arcs
     # nothing applied: the original graph still solves as before
     nodes, arcs = before
     h = graph_from_store(nodes, arcs)
