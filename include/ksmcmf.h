@@ -131,8 +131,14 @@ typedef struct ks_opts {
     int32_t  tail_sweeps;      /* sweeps per cycle once ≤ 64 nodes hold excess [4]      */
     int32_t  bf_margin;        /* Bellman-Ford rounds enqueued per cycle beyond the last
                                   update's count [6]                                    */
-    int32_t  two_hop;          /* Bellman-Ford relaxes a task's / PU's in-arcs in the round
-                                  its distance dropped [1]; < 0 off                     */
+    int32_t  two_hop;          /* hops one Bellman-Ford launch covers. 1: a task's / PU's
+                                  in-arcs are relaxed in the round its distance dropped
+                                  (two hops). 2: the continuation — a 16-, 32- or 64-lane
+                                  class node (a machine) lowered by that second hop is
+                                  relaxed, and the tasks it lowers expanded, by the same
+                                  workgroup before it retires (four hops; a workgroup-
+                                  local LDS queue, overflow falls back to the frontier
+                                  flag). < 0: one hop. [2]                              */
     int32_t  log_cycles;       /* 1: one diagnostic line per update cycle on stderr [0] */
     int32_t  fault_inject;     /* TESTS ONLY [0]: bit 0 — the last phase's walks use the
                                   coarse slack at ε = 1 (may end non-1-optimal); bit 1 —
@@ -160,7 +166,10 @@ typedef struct ks_opts {
                                   them — cycles_rejected). Bit 8 (engine): that test
                                   only counts, rejecting nothing (with bit 7 a chain
                                   is pushed along: the verifier must then fail the
-                                  solve with KS_E_VERIFY, never return a wrong cost). */
+                                  solve with KS_E_VERIFY, never return a wrong cost).
+                                  Bit 9 (engine, two_hop 2): the continuation queue
+                                  holds 2 entries, so almost every enqueue takes the
+                                  overflow path (the frontier flag).                    */
     int32_t  walk_passes;      /* tail walker passes from the update's excess nodes per
                                   cycle [1]; later passes retry units left short        */
     int32_t  tail_nodes;       /* a phase's tail — walks over each update, few sweeps —

@@ -1092,10 +1092,52 @@ __device__ __forceinline__ bool offer(const DG& g, const Front& nf, int u, long 
     return true;
 }
 
+// Continuation queue (ks_opts.two_hop 2): a lane that lowered a node
+// of a lane-group class (16, 32 or 64 lanes: not a leaf, not chunked, not a hub)
+// hands it to its own workgroup, which relaxes it behind the main pass of the
+// same launch (bf_drain) instead of flagging it for the next one. An entry
+// holds what that pass needs without a dependent load; all of it sits in
+// registers where the node is lowered (the segment shares the record's line
+// with the price). Entries live in LDS and never outlive the launch.
+constexpr int TWO_HOP_DEFAULT = 2;   // ks_opts.two_hop 0 (1: two hops, 2: the continuation — measured faster on configs 2, 3 and 4)
+constexpr int BF_DEPTH = 1;    // queue levels: 1 = four hops per launch, 2 = six (a drained node's lowerings queue once more; measured, no gain)
+constexpr int BFQ_GROUP = 32;  // lanes that relax one queued node (a 64-lane class node in two steps)
+// entries per level (32 B each): what the workgroup's groups relax in ONE step. A
+// longer queue is drained step after step by the one workgroup that filled it while
+// the rest of the grid has retired (config 3, 256 entries: a working launch 16 → 31 µs,
+// the solve 3.6 ms slower); what does not fit takes the flags, which spread it over
+// the next launch's whole grid.
+constexpr int BFQ_CAP = BLK / BFQ_GROUP;
+struct QEnt {
+    long long pu, d;    // the node's price; the distance it was lowered to (decoded in every mode)
+    int b0, b1, u, pad;
+};
+struct BfQ {
+    QEnt* q;     // LDS
+    int* n;      // LDS: entries claimed (may run past cap: the drain takes min(n, cap))
+    int cap;     // 0: no queue (lowered nodes are flagged)
+    int lo, hi;  // queued node ids: [obeg[2], obeg[CCLS])
+};
+// true: u is queued (the workgroup owns propagating it); false: the caller flags it
+__device__ __forceinline__ bool bf_enqueue(const BfQ& Q, int u, unsigned long long seg, long long d, long long pu) {
+    if (u < Q.lo || u >= Q.hi) return false;   // (cap 0: lo = hi = 0)
+    const unsigned i = (unsigned)atomicAdd(Q.n, 1);
+    if (i >= (unsigned)Q.cap) return false;    // full: today's flag path
+    QEnt e;
+    e.pu = pu;
+    e.d = d;
+    e.b0 = (int)(unsigned)(seg & 0xffffffffULL);
+    e.b1 = (int)(unsigned)(seg >> 32);
+    e.u = u;
+    e.pad = 0;
+    Q.q[i] = e;
+    return true;
+}
+
 // Relax the in-arcs of a low-degree node u (≤ 8 arcs: tasks, PUs) right after
 // its distance dropped to du: a second hop inside the same round.
 template <int PR, bool CP>
-__device__ __forceinline__ void expand_leaf(const DG& g, const Front& nf, int u, long long du, long long pu,
+__device__ __forceinline__ void expand_leaf(const DG& g, const Front& nf, const BfQ& Q, int u, long long du, long long pu,
                                             int b0, int b1, long long eps, long long B, long long* hub_min, int& out,
                                             long long& lscan) {
     lscan += b1 - b0;   // the second hop's in-arc positions examined (ks_result.gu_leaf_scans)
@@ -1119,9 +1161,11 @@ __device__ __forceinline__ void expand_leaf(const DG& g, const Front& nf, int u,
         const Pos q = PL<CP>::ld_nr(g, b);
         if (q.ucap - q.rcap > 0) {
             const int u2 = q.head;
-            long long cand = du + arc_len<PR>(g.p0[ni(u2)], q.cost, pu, eps);
+            const long long pu2 = g.p0[ni(u2)];
+            long long cand = du + arc_len<PR>(pu2, q.cost, pu, eps);
             if (PR == 2) cand = pk(cand, b);
-            if (offer<PR>(g, nf, u2, cand, u2 < g.hub_base ? g.dist[ni(u2)] : INF64, B, hub_min, out)) {
+            if (offer<PR>(g, nf, u2, cand, u2 < g.hub_base ? g.dist[ni(u2)] : INF64, B, hub_min, out) &&
+                !bf_enqueue(Q, u2, Q.cap ? (unsigned long long)g.p0[ni(u2) + ND_SEG] : 0ULL, dkey<PR>(cand), pu2)) {
                 nf.flag[u2] = 1;
                 out = 1;
             }
@@ -1140,9 +1184,11 @@ __device__ __forceinline__ void expand_leaf(const DG& g, const Front& nf, int u,
             }
         const long long pu2 = g.p0[ni(u2)];
         const long long du2 = u2 < g.hub_base ? g.dist[ni(u2)] : INF64;
+        // (continuation: the segment comes with the record, for the queue entry)
+        const unsigned long long sg2 = Q.cap ? (unsigned long long)g.p0[ni(u2) + ND_SEG] : 0ULL;
         long long cand = du + arc_len<PR>(pu2, c2, pu, eps);
         if (PR == 2) cand = pk(cand, b0 + k);
-        if (offer<PR>(g, nf, u2, cand, du2, B, hub_min, out)) {
+        if (offer<PR>(g, nf, u2, cand, du2, B, hub_min, out) && !bf_enqueue(Q, u2, sg2, dkey<PR>(cand), pu2)) {
             nf.flag[u2] = 1;
             out = 1;
         }
@@ -1151,10 +1197,11 @@ __device__ __forceinline__ void expand_leaf(const DG& g, const Front& nf, int u,
 
 // Relax in-arc (u→v) = reverse of CSR arc a = (v→u); residual ucap − rcap,
 // cost −cost(a). Loads are issued before the residual test (short chain).
+// (relax_pos: the position record q of arc a already loaded)
 template <int PR, bool CP>
-__device__ __forceinline__ void relax_in(const DG& g, const Front& nf, int v, int a, long long dv, long long pv,
-                                         long long eps, long long B, long long* hub_min, int& out, long long& lscan) {
-    const Pos q = PL<CP>::ld_nr(g, a);
+__device__ __forceinline__ void relax_pos(const DG& g, const Front& nf, const BfQ& Q, const Pos& q, int a, long long dv,
+                                          long long pv, long long eps, long long B, long long* hub_min, int& out,
+                                          long long& lscan) {
     const long long rin = q.ucap - q.rcap;
     // an arc that cannot relax reads node 0's (hot) record instead of its head's
     // random line: the loads stay unconditional (no branch join to wait at) and
@@ -1164,21 +1211,53 @@ __device__ __forceinline__ void relax_in(const DG& g, const Front& nf, int v, in
     const long long pu = g.p0[ni(u)];
     const long long du = u < g.hub_base ? g.dist[ni(u)] : INF64;
     const bool leaf = g.expand && u < g.obeg[2];
-    int b0 = 0, b1 = 0;
-    if (leaf) seg_of(g.p0, u, b0, b1);   // same record line as pu, du
+    // a leaf's segment for its expansion, a queued class's for its queue entry
+    unsigned long long sg = 0;
+    if (leaf || (u >= Q.lo && u < Q.hi)) sg = (unsigned long long)g.p0[ni(u) + ND_SEG];   // same record line as pu, du
     if (rin <= 0) return;
     const long long cand = dv + arc_len<PR>(pu, ca, pv, eps);   // (dv decoded: a distance in every mode)
-    if (!offer<PR>(g, nf, u, PR == 2 ? pk(cand, a) : cand, du, B, hub_min, out)) return;
+    const long long key = PR == 2 ? pk(cand, a) : cand;
+    if (!offer<PR>(g, nf, u, key, du, B, hub_min, out)) return;
     if (leaf) {
-        expand_leaf<PR, CP>(g, nf, u, cand, pu, b0, b1, eps, B, hub_min, out, lscan);   // tasks, PUs: two hops per round
-    } else {
+        const int b0 = (int)(unsigned)(sg & 0xffffffffULL), b1 = (int)(unsigned)(sg >> 32);
+        expand_leaf<PR, CP>(g, nf, Q, u, cand, pu, b0, b1, eps, B, hub_min, out, lscan);   // tasks, PUs: two hops per round
+    } else if (!bf_enqueue(Q, u, sg, dkey<PR>(key), pu)) {
         nf.flag[u] = 1;
         out = 1;
     }
 }
 
+template <int PR, bool CP>
+__device__ __forceinline__ void relax_in(const DG& g, const Front& nf, const BfQ& Q, int v, int a, long long dv, long long pv,
+                                         long long eps, long long B, long long* hub_min, int& out, long long& lscan) {
+    relax_pos<PR, CP>(g, nf, Q, PL<CP>::ld_nr(g, a), a, dv, pv, eps, B, hub_min, out, lscan);
+}
+
+// The continuation's second pass: the workgroup's 32-lane groups take the queued
+// nodes in turn (a 64-lane class node in two steps) and relax their in-arcs from
+// the queued distance. The node's current distance is loaded with the positions:
+// an entry whose node was lowered further since is skipped — that lowerer owns
+// the propagation, through its own entry or its flag. Nodes lowered here go to
+// Qn (the next level; cap 0: the frontier flags of the next launch).
+template <int PR, bool CP>
+__device__ __forceinline__ void bf_drain(const DG& g, const Front& nf, const QEnt* q, int n, const BfQ& Qn, long long eps,
+                                         long long B, long long* hub_min, int& out, long long& scans, long long& lscan) {
+    constexpr int QG = BFQ_GROUP;
+    const int lig = threadIdx.x & (QG - 1);
+    for (int i = threadIdx.x / QG; i < n; i += BLK / QG) {
+        const QEnt e = q[i];
+        const long long cur = atom_load(&g.dist[ni(e.u)]);
+        for (int a = e.b0 + lig; a < e.b1; a += QG) {
+            Pos p = PL<CP>::ld_nr(g, a);
+            if (dkey<PR>(cur) != e.d) p.rcap = p.ucap;   // stale entry: no residual (a select, the loads stay issued together)
+            relax_pos<PR, CP>(g, nf, Qn, p, a, e.d, e.pu, eps, B, hub_min, out, lscan);
+            scans++;
+        }
+    }
+}
+
 template <int G, int PR, bool CP>
-__device__ __forceinline__ void bf_group_pre(const DG& g, const Front& nf, int v, long long dv, long long pv, int b0,
+__device__ __forceinline__ void bf_group_pre(const DG& g, const Front& nf, const BfQ& Q, int v, long long dv, long long pv, int b0,
                                              int en, long long eps, long long B, long long* hub_min, int& out, long long& scans, long long& lscan) {
     const int lig = lane_id() & (G - 1);
     const bool act = v >= 0 && (PR || dv < INF64);
@@ -1187,7 +1266,7 @@ __device__ __forceinline__ void bf_group_pre(const DG& g, const Front& nf, int v
     for (int it = 0; it < iters; ++it) {
         const int a = b0 + it * G + lig;
         if (a < en) {
-            relax_in<PR, CP>(g, nf, v, a, dkey<PR>(dv), pv, eps, B, hub_min, out, lscan);
+            relax_in<PR, CP>(g, nf, Q, v, a, dkey<PR>(dv), pv, eps, B, hub_min, out, lscan);
             scans++;
         }
     }
@@ -1195,7 +1274,7 @@ __device__ __forceinline__ void bf_group_pre(const DG& g, const Front& nf, int v
 
 // Sparse Bellman-Ford pass over window w of class C (mask from window_mask).
 template <int C, int PR, bool CP>
-__device__ __forceinline__ void bf_win(const DG& g, const Front& N, int w, unsigned long long mask, const WinFlag& f,
+__device__ __forceinline__ void bf_win(const DG& g, const Front& N, const BfQ& Q, int w, unsigned long long mask, const WinFlag& f,
                                        long long eps, long long B, long long* hub_min, int& out, long long& scans, long long& lscan) {
     constexpr int G = class_lanes(C);
     constexpr int PER = 64 / G;
@@ -1210,26 +1289,26 @@ __device__ __forceinline__ void bf_win(const DG& g, const Front& N, int w, unsig
         int b0 = 0, en = 0;
         window_node(f, v, base, d, pv, b0, en);
         if (v < 0) d = INF64;
-        bf_group_pre<G, PR, CP>(g, N, v, d, pv, b0, en, eps, B, hub_min, out, scans, lscan);
+        bf_group_pre<G, PR, CP>(g, N, Q, v, d, pv, b0, en, eps, B, hub_min, out, scans, lscan);
         for (int j = 0; j < PER; ++j) mask &= mask - 1;
     }
 }
 
 // One 64-arc chunk of a chunked-class node (its flag already tested).
 template <int PR, bool CP>
-__device__ __forceinline__ void bf_chunk(const DG& g, const Front& N, const CItem& ci, long long eps,
+__device__ __forceinline__ void bf_chunk(const DG& g, const Front& N, const BfQ& Q, const CItem& ci, long long eps,
                                          long long B, long long* hub_min, int& out, long long& scans, long long& lscan) {
     const long long dv = atom_load(&g.dist[ni(ci.node)]);
     if (!PR && dv >= INF64) return;
     const int a = ci.begin + lane_id();
     if (a < ci.end) {
-        relax_in<PR, CP>(g, N, ci.node, a, dkey<PR>(dv), g.p0[ni(ci.node)], eps, B, hub_min, out, lscan);
+        relax_in<PR, CP>(g, N, Q, ci.node, a, dkey<PR>(dv), g.p0[ni(ci.node)], eps, B, hub_min, out, lscan);
         scans++;
     }
 }
 
 template <int G, int PR, bool CP>
-__device__ __forceinline__ void bf_group(const DG& g, const Front& nf, int v, long long eps, long long B, long long* hub_min,
+__device__ __forceinline__ void bf_group(const DG& g, const Front& nf, const BfQ& Q, int v, long long eps, long long B, long long* hub_min,
                                          int& out, long long& scans, long long& lscan) {
     const int lig = lane_id() & (G - 1);
     long long dv = INF64;
@@ -1245,7 +1324,7 @@ __device__ __forceinline__ void bf_group(const DG& g, const Front& nf, int v, lo
     for (int it = 0; it < iters; ++it) {
         const int a = b0 + it * G + lig;
         if (a < en) {
-            relax_in<PR, CP>(g, nf, v, a, dkey<PR>(dv), pv, eps, B, hub_min, out, lscan);
+            relax_in<PR, CP>(g, nf, Q, v, a, dkey<PR>(dv), pv, eps, B, hub_min, out, lscan);
             scans++;
         }
     }
@@ -1259,12 +1338,19 @@ __global__ __launch_bounds__(BLK) void k_bf_round(DG g, int seq, int dense_arg) 
     const unsigned long long t_entry = PR == 2 ? __builtin_amdgcn_s_memrealtime() : 0;
     const int dense = dense_arg >= 0 ? dense_arg : (seq == g.ctl->bf_seq0 ? 1 : 0);
     __shared__ long long hub_min[HUB_LDS];
+    __shared__ QEnt bfq[BF_DEPTH][BFQ_CAP];   // the continuation queue (g.expand ≥ 2), one level per extra hop pair
+    __shared__ int bfq_n[BF_DEPTH];
     if (blockIdx.x == 0) {
         for (int h = threadIdx.x; h < g.nheavy; h += BLK) g.bf[(seq + 2) % 3].hub[h] = 0;
         if (threadIdx.x == 0) g.ctl->bfa[(seq + 2) % 3] = 0;
     }
     const Front F = g.bf[seq % 3], N = g.bf[(seq + 1) % 3];
     if (threadIdx.x < HUB_LDS) hub_min[threadIdx.x] = INF64;
+    if (threadIdx.x < BF_DEPTH) bfq_n[threadIdx.x] = 0;
+    // g.expand 2: BFQ_CAP entries; 3 (TESTS ONLY, fault_inject bit 9): 2, so almost every enqueue overflows
+    const int qcap = g.expand < 2 ? 0 : (g.expand == 2 ? BFQ_CAP : 2);
+    const int qlo = qcap ? g.obeg[2] : 0, qhi = qcap ? g.obeg[CCLS] : 0;
+    const BfQ Q{bfq[0], &bfq_n[0], qcap, qlo, qhi};
     __syncthreads();   // (waits for outstanding loads: the control words are read after it)
     // The update is still running (!done) and this round's frontier is non-empty
     // (dense || any): read in each branch after its first loads and tested only
@@ -1298,7 +1384,7 @@ __global__ __launch_bounds__(BLK) void k_bf_round(DG g, int seq, int dense_arg) 
                 for (int k = 0; k < BF_PER_T; ++k) {
                     const int a = it.begin + sub * (CHUNK / HSPLIT) + threadIdx.x * BF_PER_T + k;
                     if (a < it.end) {
-                        relax_in<PR, CP>(g, N, it.node, a, dkey<PR>(dv), pv, eps, B, hub_min, out, lscan);
+                        relax_in<PR, CP>(g, N, Q, it.node, a, dkey<PR>(dv), pv, eps, B, hub_min, out, lscan);
                         scans++;
                     }
                 }
@@ -1311,11 +1397,11 @@ __global__ __launch_bounds__(BLK) void k_bf_round(DG g, int seq, int dense_arg) 
             // the update already converged
         } else if (w < g.wbeg[CCLS]) {
             const Scan sc{F.flag, 1};
-#define KS_BF_CALL(C) bf_group<G_, PR, CP>(g, N, v, eps, B, hub_min, out, scans, lscan)
+#define KS_BF_CALL(C) bf_group<G_, PR, CP>(g, N, Q, v, eps, B, hub_min, out, scans, lscan)
             KS_BY_CLASS(w, sc, KS_BF_CALL)
 #undef KS_BF_CALL
         } else if (w - g.wbeg[CCLS] < g.ncitems) {
-            bf_chunk<PR, CP>(g, N, g.citems[w - g.wbeg[CCLS]], eps, B, hub_min, out, scans, lscan);
+            bf_chunk<PR, CP>(g, N, Q, g.citems[w - g.wbeg[CCLS]], eps, B, hub_min, out, scans, lscan);
         }
     } else {
         const int tw = ((int)gridDim.x - nhb) * WPB;
@@ -1347,19 +1433,31 @@ __global__ __launch_bounds__(BLK) void k_bf_round(DG g, int seq, int dense_arg) 
             if (!mk[j]) continue;
             const int w = w0 + j * tw;
             if (w >= g.wbeg[CCLS]) {
-                bf_chunk<PR, CP>(g, N, g.citems[w - g.wbeg[CCLS]], eps, B, hub_min, out, scans, lscan);
+                bf_chunk<PR, CP>(g, N, Q, g.citems[w - g.wbeg[CCLS]], eps, B, hub_min, out, scans, lscan);
                 continue;
             }
             switch (class_of_window(g, w)) {
-                case 0: bf_win<0, PR, CP>(g, N, w, mk[j], wf[j], eps, B, hub_min, out, scans, lscan); break;
-                case 1: bf_win<1, PR, CP>(g, N, w, mk[j], wf[j], eps, B, hub_min, out, scans, lscan); break;
-                case 2: bf_win<2, PR, CP>(g, N, w, mk[j], wf[j], eps, B, hub_min, out, scans, lscan); break;
-                case 3: bf_win<3, PR, CP>(g, N, w, mk[j], wf[j], eps, B, hub_min, out, scans, lscan); break;
-                default: bf_win<4, PR, CP>(g, N, w, mk[j], wf[j], eps, B, hub_min, out, scans, lscan); break;
+                case 0: bf_win<0, PR, CP>(g, N, Q, w, mk[j], wf[j], eps, B, hub_min, out, scans, lscan); break;
+                case 1: bf_win<1, PR, CP>(g, N, Q, w, mk[j], wf[j], eps, B, hub_min, out, scans, lscan); break;
+                case 2: bf_win<2, PR, CP>(g, N, Q, w, mk[j], wf[j], eps, B, hub_min, out, scans, lscan); break;
+                case 3: bf_win<3, PR, CP>(g, N, Q, w, mk[j], wf[j], eps, B, hub_min, out, scans, lscan); break;
+                default: bf_win<4, PR, CP>(g, N, Q, w, mk[j], wf[j], eps, B, hub_min, out, scans, lscan); break;
             }
         }
     }
     __syncthreads();
+    // the continuation: nodes this workgroup lowered are relaxed before it retires
+    // (an empty queue costs this one LDS read; the count is uniform over the block)
+    if (bfq_n[0]) {
+#pragma unroll
+        for (int l = 0; l < BF_DEPTH; ++l) {
+            const int qn = min(bfq_n[l], qcap);
+            const BfQ Qn{bfq[l + 1 < BF_DEPTH ? l + 1 : 0], &bfq_n[l + 1 < BF_DEPTH ? l + 1 : 0],
+                         l + 1 < BF_DEPTH ? qcap : 0, l + 1 < BF_DEPTH ? qlo : 0, l + 1 < BF_DEPTH ? qhi : 0};
+            bf_drain<PR, CP>(g, N, bfq[l], qn, Qn, eps, B, hub_min, out, scans, lscan);
+            __syncthreads();   // the next level's entries and the hub minima
+        }
+    }
     if (threadIdx.x < HUB_LDS && (int)threadIdx.x < g.nheavy) {
         const long long val = hub_min[threadIdx.x];
         if (val < INF64) {
@@ -3124,7 +3222,13 @@ struct SolveRun {
         g = s.dg();
         g.cp = cpv ? s.cpos.p : nullptr;
         g.crev = cpv ? s.crev.p : nullptr;
-        g.expand = o.two_hop < 0 ? 0 : 1;      // two hops per round through tasks and PUs
+        // hops per Bellman-Ford launch (ks_opts.two_hop): 0 one, 1 two (through tasks and
+        // PUs), 2 four (the workgroup's continuation queue; 3: TESTS ONLY, fault_inject
+        // bit 9, a 2-entry queue). Default: DESIGN §3.
+        {
+            const int hops = o.two_hop < 0 ? 0 : (o.two_hop == 0 ? TWO_HOP_DEFAULT : std::min(2, (int)o.two_hop));
+            g.expand = (hops == 2 && (o.fault_inject & 512)) ? 3 : hops;
+        }
         g.bound = o.bf_bound < 0 ? 0 : 1;      // tail updates bounded at the excess nodes' distances
         g.fs_wide = std::max(2048, nn / 4);   // (measured: config 4's searches ≤ nn/6 wide, config 3's hub-bound ones ~nn/4 to 3nn/4)
         g.aug_k = o.tail_nodes > 0 ? std::min(AUG_KMAX, (int)o.tail_nodes) : 64;
