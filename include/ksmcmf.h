@@ -29,6 +29,11 @@
  *   ks_commit_schedule       TaskScheduled → pinTaskToNode and capacityFromResNodeToParent
  *                            (flowmanager/graph_manager.go:454-460, 675-720, 662-667) and the
  *                            change records they would log, generated and applied on device
+ *   ks_commit_preemptive     the same step with Preemption == true: TaskScheduled →
+ *                            updateArcsForScheduledTask (graph_manager.go:855-888) with
+ *                            updateRunningTaskToUnscheduledAggArc (:1164-1181), TaskEvicted
+ *                            (:412-433), TaskMigrated (:407-410) and capacityFromResNodeToParent
+ *                            returning NumSlotsBelow (:662-667)
  *   ks_last_error            the panics of solver.go:97-108, 148-153, 175-178, 223-225
  *                            become status codes + a message
  *
@@ -492,6 +497,58 @@ int ks_commit_schedule(ks_ctx* ctx, int32_t flags, int64_t continuation_cost,
                        const uint64_t* unsched_ids, size_t k,
                        ks_sched_delta* out, size_t cap, size_t* count,
                        ks_commit_stats* stats /* may be NULL */);
+
+typedef struct ks_preempt_stats {        /* 96 B */
+    int64_t placed, preempted, migrated;      /* deltas by kind                               */
+    int64_t running_added;                    /* new task→PU running arcs                     */
+    int64_t running_converted;                /* existing task→PU arcs turned into running    */
+    int64_t running_removed;                  /* running arcs deleted (PREEMPT, MIGRATE)      */
+    int64_t unsched_cost_updates;             /* task→aggregator arcs set to preemption_cost  */
+    int64_t cap_updates;                      /* resource arcs whose capacity changed         */
+    int64_t records;                          /* delta records generated and applied          */
+    int64_t reserved[3];
+} ks_preempt_stats;
+
+/* The graph edit that follows applySchedulingDeltas with Preemption == true, on device:
+ * the other branch of ks_commit_schedule, for a scheduler whose running tasks may move.
+ * The context stores no mode: pinned or preemptive is the caller's choice per call. The
+ * records (about two per placed task) are generated in device memory and applied as ONE
+ * stream with the semantics of ks_apply_deltas (no (src, dst) twice, so superseded is 0).
+ *   - The deltas are those of ks_scheduling_deltas, written to out in that call's order
+ *     (PREEMPTs first). out == NULL: *count only, nothing changes; cap < count:
+ *     KS_E_INVALID, nothing changes.
+ *   - PLACE t → p (updateArcsForScheduledTask, graph_manager.go:855-888): no arc of t is
+ *     deleted. The arc t → p becomes (UPDATE_ARC) or is added as (ADD_ARC) the running
+ *     arc — type 1, low 0, cap 1, cost continuation_cost; t is bound to p. Every arc of t
+ *     into an unscheduled aggregator (unsched_ids, k of them; NULL: every type-0 node with
+ *     an arc into the sink, as ks_update_unsched_costs) gets cost preemption_cost, bounds
+ *     and type kept (updateRunningTaskToUnscheduledAggArc, :1164-1181); a record only if
+ *     the cost differs (ChangeArcCost, graph_change_manager.go:171-182).
+ *   - PREEMPT t from p (TaskEvicted, :412-433): the running arc t → p is deleted
+ *     (DeleteArc's "x src dst 0 0"), t is unbound, nothing else of t changes: its arc
+ *     costs are the host's business before the next solve (:432).
+ *   - MIGRATE t to q (TaskMigrated, :407-410): PREEMPT from the device-kept binding of t,
+ *     then PLACE t → q.
+ *   - A PREEMPT or MIGRATE whose arc from t into the PU it leaves is missing or is not
+ *     type 1: KS_E_VERIFY, nothing changes (the reference panics, :416-419).
+ *   - No aggregator → sink capacity changes (the −1 of pinTaskToNode belongs to the
+ *     other mode: a running task may return to its aggregator).
+ *   - KS_COMMIT_RESOURCE_CAPS: the BFS and sums of ks_topology_stats, a PU's slots being
+ *     the capacity of its arc into the sink; every arc that is a resource arc under
+ *     ks_commit_schedule's rule is set to slots_below[v] — running tasks are not
+ *     subtracted (capacityFromResNodeToParent returns NumSlotsBelow, :662-667). Only
+ *     changed arcs get a record; 0 removes the arc; a capacity below the arc's lower
+ *     bound: KS_E_VERIFY, nothing changes.
+ * Any other flag: KS_E_INVALID; either cost beyond ±2^40: KS_E_RANGE; an aggregator id
+ * that is no live node: KS_E_INVALID. Requires a successful solve and invalidates it on
+ * success, as ks_commit_schedule; a device failure after the records were emitted leaves
+ * the store unusable until the next ks_load_graph. stats may be NULL;
+ * records == running_added + running_converted + running_removed + unsched_cost_updates
+ * + cap_updates. */
+int ks_commit_preemptive(ks_ctx* ctx, int32_t flags, int64_t continuation_cost, int64_t preemption_cost,
+                         const uint64_t* unsched_ids, size_t k,
+                         ks_sched_delta* out, size_t cap, size_t* count,
+                         ks_preempt_stats* stats /* may be NULL */);
 
 /* ---- config 5: independent graphs sharded over GPUs (SURVEY §7 step 6, §8 row e) --
  * No reference counterpart (ksched solves one graph per round,

@@ -25,6 +25,18 @@ placement/solver.go:118-123), in mutation order:
    graph_manager.go:487-492 with Preemption=false) and of U_j→sink, one
    ``x`` record per changed arc.
 
+With ``Cell(preemption=True)`` step 1 is the reference's other branch
+(``gm.Preemption == true``): the kinds come from the cell's own state — a waiting
+task in the mapping is PLACEd, a running task absent from it is PREEMPTed, one
+mapped to another PU MIGRATEs — and the records are those of ``TaskEvicted``
+(graph_manager.go:412-433: the running arc is deleted, nothing else),
+``updateArcsForScheduledTask`` (:855-888: a running arc with low 0 is added, every
+preference arc stays) and ``updateRunningTaskToUnscheduledAggArc`` (:1164-1181: the
+→U_j arc takes ``preemption_cost``), PREEMPTs first, then PLACE and MIGRATE by
+task id. U_j→sink then counts every live task of the job (a running task may
+return) and the resource arcs carry the slots with nothing subtracted
+(``capacityFromResNodeToParent`` returns ``NumSlotsBelow``).
+
 The sink's demand is left to the solver (``ks_opts.auto_sink``), exactly the
 drift of graph_manager.go:640, 808. Random draws come from the same splitmix64
 counter stream as the generator (seed = 4 + round in SURVEY §8d).
@@ -50,8 +62,10 @@ class Cell:
 
     WAIT, RUN, DEAD = 0, 1, 2
 
-    def __init__(self, T: int, M: int, R: int, J: int, seed: int):
+    def __init__(self, T: int, M: int, R: int, J: int, seed: int, preemption: bool = False,
+                 preemption_cost: int = 0):
         self.T0, self.M, self.R, self.J = T, M, R, J
+        self.preemption, self.preemption_cost = bool(preemption), int(preemption_cost)
         self.SINK, self.X, self.RACK0 = 1, 2, 3
         self.MACH0 = self.RACK0 + R
         self.PU0 = self.MACH0 + M
@@ -65,7 +79,7 @@ class Cell:
         self.state = np.full(cap, self.DEAD, np.int8)                # index = task slot (id − TASK0)
         self.state[:T] = self.WAIT
         self.job = np.zeros(cap, np.int64)
-        self.adst = np.zeros((cap, 5), np.int64)                     # preference arcs of a waiting task
+        self.adst = np.zeros((cap, 5), np.int64)                     # preference arcs (preemption: kept while running)
         self.acost = np.zeros((cap, 5), np.int64)
         self.pu = np.zeros(cap, np.int64)                            # PU node id of a running task
         self.job[:T] = g.dst[0:5 * T:5] - self.U0
@@ -97,10 +111,11 @@ class Cell:
 
     def waiting_per_job(self) -> np.ndarray:
         s = self.state[:self.n_slots]
-        return np.bincount(self.job[:self.n_slots][s == self.WAIT], minlength=self.J).astype(np.int64)
+        counted = s != self.DEAD if self.preemption else s == self.WAIT   # a running task may return
+        return np.bincount(self.job[:self.n_slots][counted], minlength=self.J).astype(np.int64)
 
     def resource_caps(self):
-        run = self.running_on
+        run = np.zeros_like(self.running_on) if self.preemption else self.running_on
         rack_free = np.bincount(self.rack_of, weights=self.slots - run, minlength=self.R).astype(np.int64)
         return rack_free, self.slots - run, self.slots - run           # X→rack, rack→machine, machine→PU
 
@@ -122,21 +137,23 @@ class Cell:
         supply[self.SINK - 1] = -int(alive.sum())
         w = st == self.WAIT
         r = st == self.RUN
-        tw = tid[w]
+        pref = w | r if self.preemption else w           # tasks that carry their preference arcs
+        tw = tid[pref]
         k = np.arange(M, dtype=np.int64)
         jj = np.arange(J, dtype=np.int64)
         rack_free, rm, mp = self.resource_caps()
         src = np.concatenate([np.repeat(tw, 5), tid[r], np.full(R, self.X, np.int64), self.RACK0 + self.rack_of,
                               self.MACH0 + k, self.PU0 + k, self.U0 + jj])
-        dst = np.concatenate([self.adst[:ns][w].reshape(-1), self.pu[:ns][r], self.RACK0 + np.arange(R),
+        dst = np.concatenate([self.adst[:ns][pref].reshape(-1), self.pu[:ns][r], self.RACK0 + np.arange(R),
                               self.MACH0 + k, self.PU0 + k, np.full(M, self.SINK, np.int64),
                               np.full(J, self.SINK, np.int64)])
         nr = int(r.sum())
-        low = np.concatenate([np.zeros(5 * tw.shape[0], np.int64), np.ones(nr, np.int64),
+        low = np.concatenate([np.zeros(5 * tw.shape[0], np.int64),
+                              np.full(nr, 0 if self.preemption else 1, np.int64),
                               np.zeros(R + 3 * M + J, np.int64)])
         cap = np.concatenate([np.ones(5 * tw.shape[0] + nr, np.int64), rack_free, rm, mp, self.slots,
                               self.waiting_per_job()])
-        cost = np.concatenate([self.acost[:ns][w].reshape(-1), np.zeros(nr + R + 3 * M + J, np.int64)])
+        cost = np.concatenate([self.acost[:ns][pref].reshape(-1), np.zeros(nr + R + 3 * M + J, np.int64)])
         atype = np.zeros(src.shape[0], np.int32)
         atype[5 * tw.shape[0]:5 * tw.shape[0] + nr] = RUNNING
         return gen.Graph(ntype, supply, src, dst, low, cap, cost, atype)
@@ -145,11 +162,49 @@ class Cell:
         return self.TASK0 + np.nonzero(self.state[:self.n_slots] == which)[0].astype(np.int64)
 
     # ---------------------------------------------------------------- rounds
+    def _reschedule(self, t: np.ndarray, p: np.ndarray, out: list):
+        """Step 1 with preemption: PREEMPTs, then PLACE and MIGRATE by task id."""
+        M, pc = self.M, self.preemption_cost
+        order = np.argsort(t, kind="stable")
+        t, p = t[order], p[order]
+        sl = t - self.TASK0
+        keep = (sl >= 0) & (sl < self.n_slots)
+        t, p, sl = t[keep], p[keep], sl[keep]
+        keep = self.state[sl] != self.DEAD
+        t, p, sl = t[keep], p[keep], sl[keep]
+        if np.any((p < self.PU0) | (p >= self.PU0 + M)):
+            raise ValueError("mapping names a non-PU node")
+        mapped = np.zeros(self.n_slots, bool)
+        mapped[sl] = True
+        for si in np.nonzero((self.state[:self.n_slots] == self.RUN) & ~mapped)[0].tolist():
+            ti, old = self.TASK0 + si, int(self.pu[si])
+            out.append((KS_UPDATE_ARC, RUNNING, 0, ti, old, 0, 0, 0, 0, 0))      # TaskEvicted: DeleteArc
+            self.running_on[old - self.PU0] -= 1
+            self.state[si] = self.WAIT
+            self.pu[si] = 0
+        for ti, pi, si in zip(t.tolist(), p.tolist(), sl.tolist()):
+            if self.state[si] == self.RUN:
+                old = int(self.pu[si])
+                if old == pi:
+                    continue
+                out.append((KS_UPDATE_ARC, RUNNING, 0, ti, old, 0, 0, 0, 0, 0))  # MIGRATE leaves its PU
+                self.running_on[old - self.PU0] -= 1
+            out.append((KS_ADD_ARC, RUNNING, 0, ti, pi, 0, 1, 0, 0, 0))
+            c = int(self.acost[si, 0])
+            if c != pc:                                                          # ChangeArcCost: changes only
+                out.append((KS_UPDATE_ARC, 0, 0, ti, int(self.adst[si, 0]), 0, 1, pc, c, 0))
+                self.acost[si, 0] = pc
+            self.state[si] = self.RUN
+            self.pu[si] = pi
+            self.running_on[pi - self.PU0] += 1
+
     def step(self, mapping, done: int, arrive: int, age_cost: int = 10,
              seed: int | None = None) -> np.ndarray:
         """Advance one scheduling round given the last solve's task→PU mapping (a
         dict, or the (task ids, PU ids) arrays of ks_get_task_mapping);
-        returns the delta records (``DELTA_DT``) in mutation order."""
+        returns the delta records (``DELTA_DT``) in mutation order. With preemption
+        a mapping, even an empty one, is a solve's whole answer (running tasks absent
+        from it are preempted); ``None`` is a round without a scheduling step."""
         self.round += 1
         seed = 4 + self.round if seed is None else seed
         out = []
@@ -166,9 +221,13 @@ class Cell:
         elif isinstance(mapping, dict) and mapping:
             t = np.fromiter(mapping.keys(), np.int64, len(mapping))
             p = np.fromiter(mapping.values(), np.int64, len(mapping))
+        elif self.preemption and mapping is not None:
+            t = p = np.zeros(0, np.int64)
         else:
             t = None
-        if t is not None:
+        if t is not None and self.preemption:
+            self._reschedule(t, p, out)
+        elif t is not None:
             order = np.argsort(t, kind="stable")
             t, p = t[order], p[order]
             sl = t - self.TASK0

@@ -17,6 +17,7 @@
 namespace ks {
 
 struct EngineImpl;
+struct CommitCtl;   // ks_sched.h
 
 class Engine {
 public:
@@ -90,9 +91,17 @@ public:
     int commit_schedule(int flags, int64_t ccost, const uint64_t* ids, size_t k, int64_t sink_slot, int64_t n_tasks,
                         size_t cap, std::vector<ks_sched_delta>* out, size_t* count, ks_commit_stats* stats,
                         bool* dirty, std::string& err);
+    // ks_commit_preemptive: the same contract; pcost: the preemption cost.
+    int commit_preemptive(int flags, int64_t ccost, int64_t pcost, const uint64_t* ids, size_t k, int64_t sink_slot,
+                          int64_t n_tasks, size_t cap, std::vector<ks_sched_delta>* out, size_t* count,
+                          ks_preempt_stats* stats, bool* dirty, std::string& err);
     int device() const;
 
 private:
+    // the body of both commits (ks_engine_sched.hip); *h: the device counters of the call
+    int commit(bool preempt, int flags, int64_t ccost, int64_t pcost, const uint64_t* ids, size_t k, int64_t sink_slot,
+               int64_t n_tasks, size_t cap, std::vector<ks_sched_delta>* out, size_t* count, CommitCtl* h,
+               bool* dirty, std::string& err);
     EngineImpl* p_;
 };
 

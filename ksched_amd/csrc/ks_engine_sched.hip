@@ -1,5 +1,5 @@
 // ks_engine_sched.hip — the engine's scheduler glue: bindings, scheduling deltas,
-// unscheduled costs, topology statistics and ks_commit_schedule. It launches the
+// unscheduled costs, topology statistics, ks_commit_schedule and ks_commit_preemptive. It launches the
 // kernels of ks_sched.hip and ks_store.hip through their launchers, none of the engine's.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -13,6 +13,12 @@
 #include "ks_engine_impl.h"
 
 namespace ks {
+
+namespace {
+struct NonZero {
+    __host__ __device__ int operator()(int x) const { return x != 0; }
+};
+}  // namespace
 
 // ------------------------------------------------- scheduler-side sweeps ---
 int Engine::set_bindings(const uint64_t* task, const uint64_t* pu, size_t k, std::string& err) {
@@ -70,8 +76,12 @@ int Engine::sched_deltas(int commit, std::vector<ks_sched_delta>* out, size_t* c
     KS_CHECK(s.map_tmp.ensure(std::max(t, s.map_tmp.n)));
     t = s.map_tmp.n;
     KS_CHECK(hipcub::DeviceScan::ExclusiveSum(s.map_tmp.p, t, pre, pre_pos, (int)ncap + 1, st));
+    // (other holds the kind, 1 PLACE or 2 MIGRATE: each counts as one delta)
+    hipcub::TransformInputIterator<int, NonZero, const int*> is_other(other, NonZero());
+    KS_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, t, is_other, other_pos, (int)ncap + 1, st));
+    KS_CHECK(s.map_tmp.ensure(std::max(t, s.map_tmp.n)));
     t = s.map_tmp.n;
-    KS_CHECK(hipcub::DeviceScan::ExclusiveSum(s.map_tmp.p, t, other, other_pos, (int)ncap + 1, st));
+    KS_CHECK(hipcub::DeviceScan::ExclusiveSum(s.map_tmp.p, t, is_other, other_pos, (int)ncap + 1, st));
     int h[3] = {0, 0, 0};
     KS_CHECK(hipMemcpyAsync(&h[0], pre_pos + ncap, sizeof(int), hipMemcpyDeviceToHost, st));
     KS_CHECK(hipMemcpyAsync(&h[1], other_pos + ncap, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -203,14 +213,16 @@ int Engine::topology_stats(uint64_t mtpp, const uint64_t* pu_ids, const uint64_t
 }
 
 
-// ks_commit_schedule: the deltas of the last solve, then — all of them being PLACEs — the
-// pin, aggregator and resource-capacity records generated in d_recs and applied by
-// store_apply with no node edit. Two host syncs beside the deltas' own and the BFS
-// levels': the record counts (CommitCtl, one copy) and the store's counters.
-// *dirty: the device state may have changed (a failure after that leaves it unknown).
-int Engine::commit_schedule(int flags, int64_t ccost, const uint64_t* ids, size_t k, int64_t sink_slot,
-                            int64_t n_tasks, size_t cap, std::vector<ks_sched_delta>* out, size_t* count,
-                            ks_commit_stats* stats, bool* dirty, std::string& err) {
+// ks_commit_schedule and ks_commit_preemptive: the deltas of the last solve, then the
+// records of their graph edit generated in d_recs and applied by store_apply with no node
+// edit. Pinned mode (preempt == false; all deltas must be PLACEs): the pin, aggregator and
+// resource-capacity records. Preemptive mode: the running-arc, delete, preemption-cost
+// (pcost) and resource-capacity records of every delta. Two host syncs beside the deltas'
+// own and the BFS levels': the record counts (CommitCtl → *h, one copy) and the store's
+// counters. *dirty: the device state may have changed (a failure after that leaves it unknown).
+int Engine::commit(bool preempt, int flags, int64_t ccost, int64_t pcost, const uint64_t* ids, size_t k,
+                   int64_t sink_slot, int64_t n_tasks, size_t cap, std::vector<ks_sched_delta>* out, size_t* count,
+                   CommitCtl* hc, bool* dirty, std::string& err) {
     EngineImpl& s = *p_;
     *dirty = false;
     if (!s.solved || !s.csr_valid) {
@@ -229,8 +241,11 @@ int Engine::commit_schedule(int flags, int64_t ccost, const uint64_t* ids, size_
         err = "output buffer smaller than the delta count";
         return KS_E_INVALID;
     }
+    int npre = 0;   // (the PREEMPTs come first)
     for (const ks_sched_delta& x : *out)
-        if (x.type != KS_DELTA_PLACE) {
+        if (x.type == KS_DELTA_PREEMPT && preempt) {
+            ++npre;
+        } else if (x.type != KS_DELTA_PLACE && !preempt) {
             err = "the solve preempts or migrates task " + std::to_string(x.task) +
                   ": ks_commit_schedule pins placements only (no preemption mode)";
             return KS_E_INVALID;
@@ -245,7 +260,7 @@ int Engine::commit_schedule(int flags, int64_t ccost, const uint64_t* ids, size_
     const int64_t np = (int64_t)out->size();
     const int64_t ni_max = np + s.m2cap / 64 + 1;
     // scratch: int arrays of np + 1, ni_max + 1 and hi + 1 entries; per-node-slot counters and flags
-    KS_CHECK(s.cm_i.ensure(7 * (np + 1) + 2 * (ni_max + 1) + 2 * ((int64_t)hi + 1)));
+    KS_CHECK(s.cm_i.ensure(10 * (np + 1) + 2 * (ni_max + 1) + 2 * ((int64_t)hi + 1)));
     KS_CHECK(s.cm_u.ensure(5 * (nst + 1) + k));
     const int64_t nb = (nst + 4) & ~3LL;
     KS_CHECK(s.cm_b.ensure(nb));
@@ -264,7 +279,10 @@ int Engine::commit_schedule(int flags, int64_t ccost, const uint64_t* ids, size_
     c.add_off = c.pl_noarc + (np + 1);
     c.nch = c.add_off + (np + 1);
     c.ch_off = c.nch + (np + 1);
-    c.icnt = c.ch_off + (np + 1);
+    c.pl_kind = c.ch_off + (np + 1);
+    c.pl_old = c.pl_kind + (np + 1);
+    c.pl_found = c.pl_old + (np + 1);
+    c.icnt = c.pl_found + (np + 1);
     c.i_off = c.icnt + (ni_max + 1);
     c.aflag = c.i_off + (ni_max + 1);
     c.a_off = c.aflag + (hi + 1);
@@ -296,27 +314,38 @@ int Engine::commit_schedule(int flags, int64_t ccost, const uint64_t* ids, size_
     };
     SchedDev d = s.schd();
     {   // the kinds of sched_deltas: [pre | other | pre_pos | other_pos] × (ncap + 1)
-        const int* other = s.sched_i.p + (ncap + 1);
-        const int* other_pos = other + 2 * (ncap + 1);
-        KS_CHECK(sched_commit_places(d, c, s.map_rank.p, (const unsigned long long*)s.map_scratch.p, other, other_pos,
-                                     dids, (int)k, st));
+        const int* pre = s.sched_i.p;
+        const int* other = pre + (ncap + 1);
+        const int* pre_pos = other + (ncap + 1);
+        const int* other_pos = pre_pos + (ncap + 1);
+        const unsigned long long* newpu = (const unsigned long long*)s.map_scratch.p;
+        if (preempt)
+            KS_CHECK(sched_preempt_items(d, c, s.map_rank.p, newpu, pre, pre_pos, other, other_pos, npre, dids, (int)k,
+                                         st));
+        else
+            KS_CHECK(sched_commit_places(d, c, s.map_rank.p, newpu, other, other_pos, dids, (int)k, st));
     }
     KS_CHECK(scan(c.nch, c.ch_off, np + 1));
-    KS_CHECK(sched_commit_count(d, c, st));
+    KS_CHECK(preempt ? sched_preempt_count(d, c, pcost, st) : sched_commit_count(d, c, st));
     KS_CHECK(scan(c.icnt, c.i_off, ni_max + 1));
     KS_CHECK(scan(c.pl_noarc, c.add_off, np + 1));
     if (resource_caps) {
-        KS_CHECK(sched_commit_pu_counts(d, c, st));
+        // (preemptive: no running count is subtracted, pu_run stays zero)
+        KS_CHECK(preempt ? sched_preempt_pu_slots(d, c, st) : sched_commit_pu_counts(d, c, st));
         rc = topo_bfs(s, d, sink_slot, 0, c.pu_slots, c.pu_run, c.slots, c.running, err);
         if (rc) return rc;
     }
-    KS_CHECK(sched_commit_arc_flags(d, c, resource_caps, st));
+    KS_CHECK(sched_commit_arc_flags(d, c, resource_caps, preempt ? 1 : 0, st));
     KS_CHECK(scan(c.aflag, c.a_off, (int64_t)hi + 1));
     KS_CHECK(sched_commit_totals(d, c, st));
-    CommitCtl h{};
+    CommitCtl& h = *hc;
     KS_CHECK(hipMemcpyAsync(&h, c.ctl, sizeof(CommitCtl), hipMemcpyDeviceToHost, st));
     KS_CHECK(hipStreamSynchronize(st));
     const auto t2 = std::chrono::steady_clock::now();
+    if (h.bad & 2) {
+        err = "a preempted or migrated task has no running arc into the PU it leaves (graph_manager.go:416-419)";
+        return KS_E_VERIFY;
+    }
     if (h.bad) {
         err = "a capacity would fall below its arc's lower bound";
         return KS_E_VERIFY;
@@ -335,7 +364,8 @@ int Engine::commit_schedule(int flags, int64_t ccost, const uint64_t* ids, size_
     KS_CHECK(s.d_edits.ensure(1));
     d = s.schd();   // (the arc table may have moved)
     *dirty = true;
-    KS_CHECK(sched_commit_emit(d, c, ccost, resource_caps, s.d_recs.p, st));
+    KS_CHECK(preempt ? sched_preempt_emit(d, c, ccost, pcost, resource_caps, s.d_recs.p, st)
+                     : sched_commit_emit(d, c, ccost, resource_caps, s.d_recs.p, st));
     KS_CHECK(store_apply(s.sd(), s.d_recs.p, (int)nrec, s.rec_ent.p, s.d_edits.p, 0, st));
     if (log) KS_CHECK(hipEventRecord(s.kev[1], st));
     rc = read_sctl(s, err);
@@ -351,7 +381,16 @@ int Engine::commit_schedule(int flags, int64_t ccost, const uint64_t* ids, size_
     }
     s.incremental = true;
     s.solved = false;
-    if (stats) {
+    return KS_OK;
+}
+
+int Engine::commit_schedule(int flags, int64_t ccost, const uint64_t* ids, size_t k, int64_t sink_slot,
+                            int64_t n_tasks, size_t cap, std::vector<ks_sched_delta>* out, size_t* count,
+                            ks_commit_stats* stats, bool* dirty, std::string& err) {
+    CommitCtl h{};
+    const int rc = commit(false, flags, ccost, 0, ids, k, sink_slot, n_tasks, cap, out, count, &h, dirty, err);
+    if (rc == KS_OK && stats) {
+        const int64_t np = (int64_t)out->size();
         std::memset(stats, 0, sizeof(*stats));
         stats->placed = np;
         stats->running_converted = np - h.rec_add;
@@ -359,9 +398,28 @@ int Engine::commit_schedule(int flags, int64_t ccost, const uint64_t* ids, size_
         stats->arcs_removed = h.rec_pin - stats->running_converted;
         stats->unsched_updates = h.unsched;
         stats->cap_updates = h.caps;
-        stats->records = nrec;
+        stats->records = (int64_t)h.rec_pin + h.rec_add + h.rec_arc;
     }
-    return KS_OK;
+    return rc;
+}
+
+int Engine::commit_preemptive(int flags, int64_t ccost, int64_t pcost, const uint64_t* ids, size_t k,
+                              int64_t sink_slot, int64_t n_tasks, size_t cap, std::vector<ks_sched_delta>* out,
+                              size_t* count, ks_preempt_stats* stats, bool* dirty, std::string& err) {
+    CommitCtl h{};
+    const int rc = commit(true, flags, ccost, pcost, ids, k, sink_slot, n_tasks, cap, out, count, &h, dirty, err);
+    if (rc == KS_OK && stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        for (const ks_sched_delta& x : *out)
+            ++(x.type == KS_DELTA_PLACE ? stats->placed : x.type == KS_DELTA_PREEMPT ? stats->preempted : stats->migrated);
+        stats->running_added = h.rec_add;
+        stats->running_converted = h.converted;
+        stats->running_removed = h.removed;
+        stats->unsched_cost_updates = h.rec_pin - h.converted - h.removed;
+        stats->cap_updates = h.caps;
+        stats->records = (int64_t)h.rec_pin + h.rec_add + h.rec_arc;
+    }
+    return rc;
 }
 
 

@@ -652,14 +652,18 @@ int ks_topology_stats(ks_ctx* c, uint64_t max_tasks_per_pu, const uint64_t* pu_i
     return rc;
 }
 
-int ks_commit_schedule(ks_ctx* c, int32_t flags, int64_t continuation_cost, const uint64_t* ids, size_t k,
-                       ks_sched_delta* out, size_t cap, size_t* count, ks_commit_stats* stats) {
+// Both commits: the checks, the count-only call and the bookkeeping around
+// run(sink slot, &deltas, &dirty), the engine call of the mode with its own stats type.
+extern "C++" {
+template <class Run>
+static int commit_call(ks_ctx* c, int32_t flags, int64_t continuation_cost, int64_t preemption_cost,
+                       const uint64_t* ids, size_t k, ks_sched_delta* out, size_t* count, Run run) {
     if (!c || !count) return KS_E_INVALID;
     if (int g = store_guard(c)) return g;
     if (!c->have_solution) return c->fail(KS_E_INVALID, "no successful solve on this context");
     if (flags & ~KS_COMMIT_RESOURCE_CAPS) return c->fail(KS_E_INVALID, "unknown commit flag");
     const int64_t lim = int64_t(1) << 40;
-    if (continuation_cost > lim || continuation_cost < -lim)
+    if (continuation_cost > lim || continuation_cost < -lim || preemption_cost > lim || preemption_cost < -lim)
         return c->fail(KS_E_RANGE, "cost outside the supported range");
     for (size_t i = 0; ids && i < k; ++i)
         if (!node_alive(c, ids[i])) return c->fail(KS_E_INVALID, "unscheduled aggregator " + std::to_string(ids[i]) +
@@ -673,8 +677,7 @@ int ks_commit_schedule(ks_ctx* c, int32_t flags, int64_t continuation_cost, cons
     const int64_t sink = c->n_sinks == 1 ? (int64_t)c->sink_id - 1 : -1;
     std::vector<ks_sched_delta> v;
     bool dirty = false;
-    const int rc = c->eng.commit_schedule(flags, continuation_cost, ids, ids ? k : 0, sink, c->n_tasks, cap, &v, count,
-                                          stats, &dirty, c->err);
+    const int rc = run(sink, &v, &dirty);
     if (rc) {
         if (dirty) c->store_bad = true;   // the stream may be half applied: reload first
         return rc;
@@ -685,6 +688,27 @@ int ks_commit_schedule(ks_ctx* c, int32_t flags, int64_t continuation_cost, cons
     c->map_fresh = false;
     c->flows_fresh = false;
     return KS_OK;
+}
+}  // extern "C++"
+
+int ks_commit_schedule(ks_ctx* c, int32_t flags, int64_t continuation_cost, const uint64_t* ids, size_t k,
+                       ks_sched_delta* out, size_t cap, size_t* count, ks_commit_stats* stats) {
+    return commit_call(c, flags, continuation_cost, 0, ids, k, out, count,
+                       [&](int64_t sink, std::vector<ks_sched_delta>* v, bool* dirty) {
+                           return c->eng.commit_schedule(flags, continuation_cost, ids, ids ? k : 0, sink, c->n_tasks,
+                                                         cap, v, count, stats, dirty, c->err);
+                       });
+}
+
+int ks_commit_preemptive(ks_ctx* c, int32_t flags, int64_t continuation_cost, int64_t preemption_cost,
+                         const uint64_t* ids, size_t k, ks_sched_delta* out, size_t cap, size_t* count,
+                         ks_preempt_stats* stats) {
+    return commit_call(c, flags, continuation_cost, preemption_cost, ids, k, out, count,
+                       [&](int64_t sink, std::vector<ks_sched_delta>* v, bool* dirty) {
+                           return c->eng.commit_preemptive(flags, continuation_cost, preemption_cost, ids,
+                                                           ids ? k : 0, sink, c->n_tasks, cap, v, count, stats, dirty,
+                                                           c->err);
+                       });
 }
 
 int ks_get_graph(ks_ctx* c, ks_node* nodes, size_t ncap, size_t* n, ks_arc* arcs, size_t acap, size_t* m) {

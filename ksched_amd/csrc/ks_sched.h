@@ -64,8 +64,10 @@ struct CommitCtl {
     int rec_arc;      // aggregator and resource-arc capacity records
     int unsched;      // of those, aggregator → sink arcs
     int caps;         // of those, resource arcs
-    int bad;          // a capacity would fall below its arc's lower bound
-    int _pad[2];
+    int bad;          // 1: a capacity would fall below its arc's lower bound; 2 (ks_commit_preemptive): a
+                      // PREEMPT or MIGRATE without its running arc
+    int converted;    // ks_commit_preemptive: of rec_pin, arcs turned into running arcs
+    int removed;      //   and running arcs deleted (the rest of rec_pin are cost records)
 };
 
 // Scratch of one commit (device pointers; np placed tasks, ni_max chunk items at most).
@@ -75,6 +77,9 @@ struct CommitDev {
     int* pl_task;                  // [np] task node slot, in delta order
     int* pl_pu;                    // [np] PU node slot
     int* pl_has;                   // [np + 1] 1: the arc task → PU exists (it is converted)
+    int* pl_kind;                  // [np + 1] ks_commit_preemptive: KS_DELTA_* of the item (pl_pu −1 for a PREEMPT)
+    int* pl_old;                   // [np + 1]   PU node slot the task leaves (PREEMPT, MIGRATE), else −1
+    int* pl_found;                 // [np + 1]   1: the running arc into pl_old exists
     int* pl_noarc;                 // [np + 1] 1 − pl_has, and its exclusive scan add_off
     int* add_off;                  // [np + 1]
     int* nch;                      // [np + 1] 64-position chunks of the task's segment; ch_off its scan
@@ -103,12 +108,28 @@ hipError_t sched_commit_count(const SchedDev& d, const CommitDev& c, hipStream_t
 // PU slots and running counts for the resource capacities (before the level BFS).
 hipError_t sched_commit_pu_counts(const SchedDev& d, const CommitDev& c, hipStream_t st);
 // Arc slots that emit a capacity record (aflag), resource_caps != 0: also the resource arcs.
-hipError_t sched_commit_arc_flags(const SchedDev& d, const CommitDev& c, int resource_caps, hipStream_t st);
+// preempt != 0 (ks_commit_preemptive): no aggregator record, a resource arc gets slots_below.
+hipError_t sched_commit_arc_flags(const SchedDev& d, const CommitDev& c, int resource_caps, int preempt,
+                                  hipStream_t st);
 // Record totals into c.ctl (after the scans icnt → i_off, pl_noarc → add_off, aflag → a_off).
 hipError_t sched_commit_totals(const SchedDev& d, const CommitDev& c, hipStream_t st);
 // Emit pass: the records into recs (pins, then new running arcs, then capacities) and the
 // bindings of the placed tasks.
 hipError_t sched_commit_emit(const SchedDev& d, const CommitDev& c, long long ccost, int resource_caps, ks_delta* recs,
                              hipStream_t st);
+
+// ---- ks_commit_preemptive: TaskScheduled with Preemption == true (graph_manager.go:855-888,
+// :1164-1181), TaskEvicted (:412-433) and TaskMigrated (:407-410) on the same scratch. An
+// item is a task with a delta of any kind, in delta order (np of them: the npre PREEMPTs
+// first); rec_pin counts the records on existing arcs (conversions, deletes, cost changes).
+hipError_t sched_preempt_items(const SchedDev& d, const CommitDev& c, const int* rank, const unsigned long long* newpu,
+                               const int* pre, const int* pre_pos, const int* other, const int* other_pos, int npre,
+                               const unsigned long long* ids, int k, hipStream_t st);
+hipError_t sched_preempt_count(const SchedDev& d, const CommitDev& c, long long pcost, hipStream_t st);
+// PU slots only: this mode subtracts no running tasks.
+hipError_t sched_preempt_pu_slots(const SchedDev& d, const CommitDev& c, hipStream_t st);
+// Emit pass: item records, then new running arcs, then capacities; the bindings of every item.
+hipError_t sched_preempt_emit(const SchedDev& d, const CommitDev& c, long long ccost, long long pcost,
+                              int resource_caps, ks_delta* recs, hipStream_t st);
 
 }  // namespace ks

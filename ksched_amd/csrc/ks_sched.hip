@@ -20,6 +20,10 @@
 //                       capacityFromResNodeToParent (:662-667): the records a host
 //                       would export for them, generated in device memory for
 //                       store_apply (ks_store.hip)
+//   commit, preemptive  the same step with Preemption == true: updateArcsForScheduledTask
+//                       (:855-888), updateRunningTaskToUnscheduledAggArc (:1164-1181),
+//                       TaskEvicted (:412-433), TaskMigrated (:407-410) and
+//                       capacityFromResNodeToParent returning NumSlotsBelow
 #include "ks_sched.h"
 
 namespace ks {
@@ -308,13 +312,15 @@ __global__ void k_commit_pu_places(CommitDev c) {
 // The capacity arc slot s gets from this commit: 1 an aggregator → sink arc (minus
 // the tasks pinned out of it), 2 a resource arc (slots − running below its head), 0
 // none or unchanged.
-__device__ __forceinline__ int commit_arc_cap(const SchedDev& d, const CommitDev& c, int resource_caps, int s,
-                                              long long* cap) {
+// With preempt (ks_commit_preemptive, capacityFromResNodeToParent returning NumSlotsBelow)
+// kind 1 never fires and a resource arc gets slots below its head: running tasks may move.
+__device__ __forceinline__ int commit_arc_cap(const SchedDev& d, const CommitDev& c, int resource_caps, int preempt,
+                                              int s, long long* cap) {
     if (!d.a_alive[s]) return 0;
     const int u = d.a_src[s], v = d.a_dst[s];
     const unsigned char tu = d.n_type[u], tv = d.n_type[v];
     if (tv == KS_NODE_SINK) {
-        if (!(c.fl[u] & 1) || c.agg_cnt[u] == 0) return 0;
+        if (preempt || !(c.fl[u] & 1) || c.agg_cnt[u] == 0) return 0;
         *cap = d.a_cap[s] - (long long)c.agg_cnt[u];
         return 1;
     }
@@ -322,17 +328,17 @@ __device__ __forceinline__ int commit_arc_cap(const SchedDev& d, const CommitDev
     const bool res = tv == KS_NODE_PU || tv == KS_NODE_MACHINE || tv == KS_NODE_INTERMEDIATE ||
                      (tv == KS_NODE_OTHER && c.slots[v] > 0);
     if (!res) return 0;
-    *cap = (long long)c.slots[v] - (long long)c.running[v];
+    *cap = (long long)c.slots[v] - (preempt ? 0 : (long long)c.running[v]);
     return *cap != d.a_cap[s] ? 2 : 0;
 }
 
-__global__ void k_commit_arc_flags(SchedDev d, CommitDev c, int resource_caps) {
+__global__ void k_commit_arc_flags(SchedDev d, CommitDev c, int resource_caps, int preempt) {
     for (long long s0 = blockIdx.x * (long long)SB; s0 <= d.hi; s0 += (long long)gridDim.x * SB) {
         const long long s = s0 + threadIdx.x;
         int kind = 0;
         if (s < d.hi) {
             long long cap = 0;
-            kind = commit_arc_cap(d, c, resource_caps, (int)s, &cap);
+            kind = commit_arc_cap(d, c, resource_caps, preempt, (int)s, &cap);
             if (kind && cap < d.a_low[s]) atomicOr(&c.ctl->bad, 1);
         }
         if (s <= d.hi) c.aflag[s] = kind != 0;
@@ -396,16 +402,134 @@ __global__ void k_commit_emit_adds(SchedDev d, CommitDev c, long long ccost, ks_
     }
 }
 
-__global__ void k_commit_emit_arcs(SchedDev d, CommitDev c, int resource_caps, ks_delta* __restrict__ recs) {
+__global__ void k_commit_emit_arcs(SchedDev d, CommitDev c, int resource_caps, int preempt,
+                                   ks_delta* __restrict__ recs) {
     const int base = c.ctl->rec_pin + c.ctl->rec_add;
     for (long long s = blockIdx.x * (long long)SB + threadIdx.x; s < d.hi; s += (long long)gridDim.x * SB) {
         if (!c.aflag[s]) continue;
         long long cap = 0;
-        if (!commit_arc_cap(d, c, resource_caps, (int)s, &cap)) continue;
+        if (!commit_arc_cap(d, c, resource_caps, preempt, (int)s, &cap)) continue;
         // capacity 0 removes the arc (the store's low == cap == 0 rule; cap ≥ low was checked)
         const long long co = d.a_cost[s];
         recs[base + c.a_off[s]] = arc_record(KS_UPDATE_ARC, d.a_type[s], d.a_src[s], d.a_dst[s], cap ? d.a_low[s] : 0,
                                              cap, co, co);
+    }
+}
+
+// -------------------------------------------------------- commit, preemptive ---
+// updateArcsForScheduledTask with Preemption == true (graph_manager.go:855-888): a
+// placed task keeps every arc; the one into its PU becomes (or is added as) the running
+// arc with low 0, and its arcs into unscheduled aggregators take the preemption cost
+// (updateRunningTaskToUnscheduledAggArc, :1164-1181). TaskEvicted (:412-433) deletes
+// the running arc and nothing else; TaskMigrated (:407-410) is both. The items are the
+// tasks with a delta of any kind, in delta order, on the chunk items of the pinned mode.
+__global__ void k_preempt_items(SchedDev d, CommitDev c, const int* __restrict__ rank,
+                                const unsigned long long* __restrict__ newpu, const int* __restrict__ pre,
+                                const int* __restrict__ pre_pos, const int* __restrict__ other,
+                                const int* __restrict__ other_pos, int npre) {
+    for (long long v = blockIdx.x * (long long)SB + threadIdx.x; v < d.ncap; v += (long long)gridDim.x * SB) {
+        int i, kind;
+        if (pre[v]) {
+            i = pre_pos[v];
+            kind = KS_DELTA_PREEMPT;
+        } else if (other[v]) {
+            i = npre + other_pos[v];
+            kind = other[v] == 1 ? KS_DELTA_PLACE : KS_DELTA_MIGRATE;
+        } else {
+            continue;
+        }
+        if (i < 0 || i >= c.np) continue;
+        c.pl_task[i] = (int)v;
+        c.pl_kind[i] = kind;
+        c.pl_pu[i] = kind == KS_DELTA_PREEMPT ? -1 : (int)newpu[rank[v]] - 1;
+        c.pl_old[i] = kind == KS_DELTA_PLACE ? -1 : (int)d.n_bind[v] - 1;
+        const int x = d.perm[v];
+        int len = 0;
+        if (x >= 0) len = min(d.used[x], d.first[x + 1] - d.first[x]);
+        c.nch[i] = (max(len, 0) + 63) >> 6;
+    }
+}
+
+// The record arc slot s of item i gets: 1 the arc into the new PU (it becomes the
+// running arc), 2 the running arc into the PU the task leaves (deleted), 3 an arc into
+// an unscheduled aggregator whose cost changes (ChangeArcCost emits nothing otherwise,
+// graph_change_manager.go:171-182), 0 none. An arc into the old PU that is no running
+// arc counts as missing (the reference panics, graph_manager.go:416-419).
+__device__ __forceinline__ int preempt_arc_kind(const SchedDev& d, const CommitDev& c, int i, int s, long long pcost) {
+    const int dst = d.a_dst[s];
+    if (dst == c.pl_pu[i]) return 1;
+    if (dst == c.pl_old[i]) return d.a_type[s] == 1 ? 2 : 0;
+    if ((c.fl[dst] & 1) && c.pl_kind[i] != KS_DELTA_PREEMPT && d.a_cost[s] != pcost) return 3;
+    return 0;
+}
+
+__global__ void k_preempt_count(SchedDev d, CommitDev c, long long pcost) {
+    const int lane = threadIdx.x & 63;
+    const int wave = (blockIdx.x * SB + threadIdx.x) >> 6;
+    const int nwaves = (gridDim.x * SB) >> 6;
+    const int ni = min(c.ch_off[c.np], c.ni_max);
+    for (int w = wave; w < ni; w += nwaves) {
+        int i;
+        const int p = commit_item(d, c, w, lane, &i);
+        const int e = p >= 0 ? d.ent[p] : -1;
+        const int kind = e >= 0 && !(e & 1) ? preempt_arc_kind(d, c, i, e >> 1, pcost) : 0;
+        if (kind == 1) c.pl_has[i] = 1;
+        if (kind == 2) c.pl_found[i] = 1;
+        const unsigned long long m = __ballot(kind != 0);
+        if (lane == 0) c.icnt[w] = __popcll(m);
+        wave_count(&c.ctl->converted, kind == 1);
+        wave_count(&c.ctl->removed, kind == 2);
+    }
+}
+
+__global__ void k_preempt_noarc(CommitDev c) {
+    for (long long i = blockIdx.x * (long long)SB + threadIdx.x; i <= c.np; i += (long long)gridDim.x * SB) {
+        int na = 0;
+        if (i < c.np) {
+            const int kind = c.pl_kind[i];
+            na = kind != KS_DELTA_PREEMPT && !c.pl_has[i];
+            if (kind != KS_DELTA_PLACE && !c.pl_found[i]) atomicOr(&c.ctl->bad, 2);
+        }
+        c.pl_noarc[i] = na;
+    }
+}
+
+__global__ void k_preempt_pu_slots(SchedDev d, CommitDev c) {
+    for (long long s = blockIdx.x * (long long)SB + threadIdx.x; s < d.hi; s += (long long)gridDim.x * SB)
+        if (d.a_alive[s] && d.n_type[d.a_dst[s]] == KS_NODE_SINK && d.n_type[d.a_src[s]] == KS_NODE_PU)
+            c.pu_slots[d.a_src[s]] = (unsigned long long)d.a_cap[s];
+}
+
+__global__ void k_preempt_emit_items(SchedDev d, CommitDev c, long long ccost, long long pcost,
+                                     ks_delta* __restrict__ recs) {
+    const int lane = threadIdx.x & 63;
+    const int wave = (blockIdx.x * SB + threadIdx.x) >> 6;
+    const int nwaves = (gridDim.x * SB) >> 6;
+    const int ni = min(c.ch_off[c.np], c.ni_max);
+    for (int w = wave; w < ni; w += nwaves) {
+        int i;
+        const int p = commit_item(d, c, w, lane, &i);
+        const int e = p >= 0 ? d.ent[p] : -1;
+        const int kind = e >= 0 && !(e & 1) ? preempt_arc_kind(d, c, i, e >> 1, pcost) : 0;
+        const unsigned long long m = __ballot(kind != 0);
+        if (!kind) continue;
+        const int s = e >> 1, t = c.pl_task[i], dst = d.a_dst[s];
+        const int r = c.i_off[w] + __popcll(m & ((1ULL << lane) - 1));
+        const long long co = d.a_cost[s];
+        recs[r] = kind == 1   ? arc_record(KS_UPDATE_ARC, 1, t, dst, 0, 1, ccost, co)
+                  : kind == 2 ? arc_record(KS_UPDATE_ARC, d.a_type[s], t, dst, 0, 0, co, co)
+                              : arc_record(KS_UPDATE_ARC, d.a_type[s], t, dst, d.a_low[s], d.a_cap[s], pcost, co);
+    }
+}
+
+// A placed or migrated task without an arc into its PU gets the running arc; every item its
+// binding (0 for a PREEMPT: pl_pu is −1).
+__global__ void k_preempt_emit_adds(SchedDev d, CommitDev c, long long ccost, ks_delta* __restrict__ recs) {
+    const int base = c.ctl->rec_pin;
+    for (long long i = blockIdx.x * (long long)SB + threadIdx.x; i < c.np; i += (long long)gridDim.x * SB) {
+        const int t = c.pl_task[i], pu = c.pl_pu[i];
+        d.n_bind[t] = (unsigned long long)(pu + 1);
+        if (c.pl_noarc[i]) recs[base + c.add_off[i]] = arc_record(KS_ADD_ARC, 1, t, pu, 0, 1, ccost, 0);
     }
 }
 
@@ -474,8 +598,9 @@ hipError_t sched_commit_pu_counts(const SchedDev& d, const CommitDev& c, hipStre
     return hipGetLastError();
 }
 
-hipError_t sched_commit_arc_flags(const SchedDev& d, const CommitDev& c, int resource_caps, hipStream_t st) {
-    hipLaunchKernelGGL(k_commit_arc_flags, dim3(grid(d.hi + 1)), dim3(SB), 0, st, d, c, resource_caps);
+hipError_t sched_commit_arc_flags(const SchedDev& d, const CommitDev& c, int resource_caps, int preempt,
+                                  hipStream_t st) {
+    hipLaunchKernelGGL(k_commit_arc_flags, dim3(grid(d.hi + 1)), dim3(SB), 0, st, d, c, resource_caps, preempt);
     return hipGetLastError();
 }
 
@@ -490,7 +615,44 @@ hipError_t sched_commit_emit(const SchedDev& d, const CommitDev& c, long long cc
         hipLaunchKernelGGL(k_commit_emit_pins, dim3(grid(64LL * c.ni_max)), dim3(SB), 0, st, d, c, ccost, recs);
         hipLaunchKernelGGL(k_commit_emit_adds, dim3(grid(c.np)), dim3(SB), 0, st, d, c, ccost, recs);
     }
-    if (d.hi) hipLaunchKernelGGL(k_commit_emit_arcs, dim3(grid(d.hi)), dim3(SB), 0, st, d, c, resource_caps, recs);
+    if (d.hi) hipLaunchKernelGGL(k_commit_emit_arcs, dim3(grid(d.hi)), dim3(SB), 0, st, d, c, resource_caps, 0, recs);
+    return hipGetLastError();
+}
+
+hipError_t sched_preempt_items(const SchedDev& d, const CommitDev& c, const int* rank, const unsigned long long* newpu,
+                               const int* pre, const int* pre_pos, const int* other, const int* other_pos, int npre,
+                               const unsigned long long* ids, int k, hipStream_t st) {
+    if (ids) {
+        if (k) hipLaunchKernelGGL(k_mark_ids, dim3(grid(k)), dim3(SB), 0, st, k, ids, c.fl);
+    } else if (d.hi) {
+        hipLaunchKernelGGL(k_mark_unsched_auto, dim3(grid(d.hi)), dim3(SB), 0, st, d.hi, d.a_alive, d.a_src, d.a_dst,
+                           d.n_type, c.fl);
+    }
+    if (c.np)
+        hipLaunchKernelGGL(k_preempt_items, dim3(grid(d.ncap)), dim3(SB), 0, st, d, c, rank, newpu, pre, pre_pos, other,
+                           other_pos, npre);
+    return hipGetLastError();
+}
+
+hipError_t sched_preempt_count(const SchedDev& d, const CommitDev& c, long long pcost, hipStream_t st) {
+    if (c.np) hipLaunchKernelGGL(k_preempt_count, dim3(grid(64LL * c.ni_max)), dim3(SB), 0, st, d, c, pcost);
+    hipLaunchKernelGGL(k_preempt_noarc, dim3(grid(c.np + 1)), dim3(SB), 0, st, c);
+    return hipGetLastError();
+}
+
+hipError_t sched_preempt_pu_slots(const SchedDev& d, const CommitDev& c, hipStream_t st) {
+    if (d.hi) hipLaunchKernelGGL(k_preempt_pu_slots, dim3(grid(d.hi)), dim3(SB), 0, st, d, c);
+    return hipGetLastError();
+}
+
+hipError_t sched_preempt_emit(const SchedDev& d, const CommitDev& c, long long ccost, long long pcost,
+                              int resource_caps, ks_delta* recs, hipStream_t st) {
+    if (c.np) {
+        hipLaunchKernelGGL(k_preempt_emit_items, dim3(grid(64LL * c.ni_max)), dim3(SB), 0, st, d, c, ccost, pcost, recs);
+        hipLaunchKernelGGL(k_preempt_emit_adds, dim3(grid(c.np)), dim3(SB), 0, st, d, c, ccost, recs);
+    }
+    if (d.hi && resource_caps)
+        hipLaunchKernelGGL(k_commit_emit_arcs, dim3(grid(d.hi)), dim3(SB), 0, st, d, c, resource_caps, 1, recs);
     return hipGetLastError();
 }
 

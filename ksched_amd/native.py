@@ -21,6 +21,7 @@ EXPORTED_SYMBOLS = (
     "ks_apply_deltas", "ks_solve", "ks_get_flows", "ks_get_task_mapping", "ks_get_task_pu_device", "ks_solve_many",
     "ks_coalesce_deltas", "ks_get_store_stats", "ks_set_bindings", "ks_scheduling_deltas",
     "ks_update_unsched_costs", "ks_topology_stats", "ks_get_graph", "ks_commit_schedule",
+    "ks_commit_preemptive",
     "ks_batch_create", "ks_batch_create_rank", "ks_batch_unique_id", "ks_batch_destroy", "ks_batch_last_error",
     "ks_batch_load", "ks_batch_solve", "ks_batch_gather",
     "ks_batch_slots", "ks_batch_owner", "ks_batch_block_len", "ks_batch_unpack",
@@ -94,6 +95,17 @@ class KsCommitStats(C.Structure):
     _fields_ = [("placed", C.c_int64), ("arcs_removed", C.c_int64), ("running_added", C.c_int64),
                 ("running_converted", C.c_int64), ("unsched_updates", C.c_int64), ("cap_updates", C.c_int64),
                 ("records", C.c_int64), ("reserved", C.c_int64 * 5)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class KsPreemptStats(C.Structure):
+    """ks_preempt_stats: what one ks_commit_preemptive generated on device."""
+    _fields_ = [("placed", C.c_int64), ("preempted", C.c_int64), ("migrated", C.c_int64),
+                ("running_added", C.c_int64), ("running_converted", C.c_int64), ("running_removed", C.c_int64),
+                ("unsched_cost_updates", C.c_int64), ("cap_updates", C.c_int64), ("records", C.c_int64),
+                ("reserved", C.c_int64 * 3)]
 
     def as_dict(self) -> dict:
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
@@ -192,6 +204,8 @@ def _bind(path: str):
     L.ks_topology_stats.argtypes = [V, C.c_uint64, V, V, C.c_size_t, V, V, C.c_size_t, P(C.c_size_t)]
     L.ks_commit_schedule.argtypes = [V, C.c_int32, C.c_int64, V, C.c_size_t, V, C.c_size_t, P(C.c_size_t),
                                      P(KsCommitStats)]
+    L.ks_commit_preemptive.argtypes = [V, C.c_int32, C.c_int64, C.c_int64, V, C.c_size_t, V, C.c_size_t,
+                                       P(C.c_size_t), P(KsPreemptStats)]
     return L
 
 
@@ -363,6 +377,26 @@ class Context:
         st = KsCommitStats()
         self._check(self._L.ks_commit_schedule(self._h, flags, continuation, pid, k, out.ctypes.data, cnt.value,
                                                C.byref(cnt), C.byref(st)))
+        return out[:cnt.value], st.as_dict()
+
+    def commit_preemptive(self, continuation: int = 0, preemption: int = 0, resource_caps: bool = True,
+                          unsched_ids=None):
+        """ks_commit_preemptive: commit every PLACE, PREEMPT and MIGRATE of the last solve
+        on device (running arcs with low 0, the preemption cost on the arcs into the
+        unscheduled aggregators and, with resource_caps, the resource arcs' capacities).
+        → (deltas SCHED_DELTA_DT, stats dict). Invalidates the solution: fetch the
+        mapping first."""
+        ids = None if unsched_ids is None else np.ascontiguousarray(unsched_ids, np.uint64)
+        pid = None if ids is None else ids.ctypes.data
+        k = 0 if ids is None else ids.shape[0]
+        flags = KS_COMMIT_RESOURCE_CAPS if resource_caps else 0
+        cnt = C.c_size_t()
+        self._check(self._L.ks_commit_preemptive(self._h, flags, continuation, preemption, pid, k, None, 0,
+                                                 C.byref(cnt), None))
+        out = np.zeros(max(cnt.value, 1), SCHED_DELTA_DT)
+        st = KsPreemptStats()
+        self._check(self._L.ks_commit_preemptive(self._h, flags, continuation, preemption, pid, k, out.ctypes.data,
+                                                 cnt.value, C.byref(cnt), C.byref(st)))
         return out[:cnt.value], st.as_dict()
 
     def task_pu_device(self, dev_ptr: int, cap: int) -> int:
