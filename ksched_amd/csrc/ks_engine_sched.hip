@@ -18,6 +18,30 @@ namespace {
 struct NonZero {
     __host__ __device__ int operator()(int x) const { return x != 0; }
 };
+
+// out[i] = in[0] + … + in[i − 1] for i < n, on st; hipcub's scratch is map_tmp.
+template <typename In>
+hipError_t exclusive_sum(EngineImpl& s, In in, int* out, int64_t n, hipStream_t st) {
+    size_t t = 0;
+    hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, t, in, out, (int)n, st);
+    if (e == hipSuccess) e = s.map_tmp.ensure(std::max(t, s.map_tmp.n));
+    t = s.map_tmp.n;
+    if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(s.map_tmp.p, t, in, out, (int)n, st);
+    return e;
+}
+
+// Bump-pointer carve of one buffer: a pass over base == nullptr sizes it (n), the same
+// statements over the allocation hand out the arrays.
+template <typename T>
+struct Carve {
+    T* base;
+    int64_t n = 0;
+    T* take(int64_t len) {
+        T* p = base ? base + n : nullptr;
+        n += len;
+        return p;
+    }
+};
 }  // namespace
 
 // ------------------------------------------------- scheduler-side sweeps ---
@@ -71,17 +95,10 @@ int Engine::sched_deltas(int commit, std::vector<ks_sched_delta>* out, size_t* c
     KS_CHECK(hipMemsetAsync(bad, 0, 4 * sizeof(int), st));
     const SchedDev d = s.schd();
     KS_CHECK(sched_delta_kinds(d, s.map_is_task.p, s.map_rank.p, (const unsigned long long*)dense, pre, other, bad, st));
-    size_t t = 0;
-    KS_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, t, pre, pre_pos, (int)ncap + 1, st));
-    KS_CHECK(s.map_tmp.ensure(std::max(t, s.map_tmp.n)));
-    t = s.map_tmp.n;
-    KS_CHECK(hipcub::DeviceScan::ExclusiveSum(s.map_tmp.p, t, pre, pre_pos, (int)ncap + 1, st));
+    KS_CHECK(exclusive_sum(s, (const int*)pre, pre_pos, ncap + 1, st));
     // (other holds the kind, 1 PLACE or 2 MIGRATE: each counts as one delta)
     hipcub::TransformInputIterator<int, NonZero, const int*> is_other(other, NonZero());
-    KS_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, t, is_other, other_pos, (int)ncap + 1, st));
-    KS_CHECK(s.map_tmp.ensure(std::max(t, s.map_tmp.n)));
-    t = s.map_tmp.n;
-    KS_CHECK(hipcub::DeviceScan::ExclusiveSum(s.map_tmp.p, t, is_other, other_pos, (int)ncap + 1, st));
+    KS_CHECK(exclusive_sum(s, is_other, other_pos, ncap + 1, st));
     int h[3] = {0, 0, 0};
     KS_CHECK(hipMemcpyAsync(&h[0], pre_pos + ncap, sizeof(int), hipMemcpyDeviceToHost, st));
     KS_CHECK(hipMemcpyAsync(&h[1], other_pos + ncap, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -242,76 +259,63 @@ int Engine::commit(bool preempt, int flags, int64_t ccost, int64_t pcost, const 
         return KS_E_INVALID;
     }
     int npre = 0;   // (the PREEMPTs come first)
-    for (const ks_sched_delta& x : *out)
-        if (x.type == KS_DELTA_PREEMPT && preempt) {
-            ++npre;
-        } else if (x.type != KS_DELTA_PLACE && !preempt) {
+    for (const ks_sched_delta& x : *out) {
+        if (x.type != KS_DELTA_PLACE && !preempt) {
             err = "the solve preempts or migrates task " + std::to_string(x.task) +
                   ": ks_commit_schedule pins placements only (no preemption mode)";
             return KS_E_INVALID;
         }
-    const int resource_caps = (flags & KS_COMMIT_RESOURCE_CAPS) ? 1 : 0;
+        npre += x.type == KS_DELTA_PREEMPT;
+    }
     const int64_t ncap = s.ncap, nst = s.nstore;
-    if (resource_caps && (sink_slot < 0 || sink_slot >= ncap)) {
+    const int hi = s.hi();
+    const int64_t np = (int64_t)out->size();
+    CommitDev c{};
+    c.preempt = preempt ? 1 : 0;
+    c.resource_caps = (flags & KS_COMMIT_RESOURCE_CAPS) ? 1 : 0;
+    c.ccost = ccost;
+    c.pcost = pcost;
+    c.np = (int)np;
+    c.ni_max = (int)(np + s.m2cap / 64 + 1);
+    if (c.resource_caps && (sink_slot < 0 || sink_slot >= ncap)) {
         err = "resource capacities need exactly one sink";
         return KS_E_INVALID;
     }
-    const int hi = s.hi();
-    const int64_t np = (int64_t)out->size();
-    const int64_t ni_max = np + s.m2cap / 64 + 1;
-    // scratch: int arrays of np + 1, ni_max + 1 and hi + 1 entries; per-node-slot counters and flags
-    KS_CHECK(s.cm_i.ensure(10 * (np + 1) + 2 * (ni_max + 1) + 2 * ((int64_t)hi + 1)));
-    KS_CHECK(s.cm_u.ensure(5 * (nst + 1) + k));
+    // scratch: int arrays per item, chunk item and arc slot in cm_i; counters per node slot
+    // and the aggregator ids in cm_u; flags per node slot in cm_b
+    unsigned long long* idbuf = nullptr;
+    auto carve = [&](Carve<int> ci, Carve<unsigned long long> cu) {
+        for (int** a : {&c.pl_task, &c.pl_kind, &c.pl_pu, &c.pl_old, &c.pl_has, &c.pl_found, &c.pl_noarc, &c.add_off,
+                        &c.nch, &c.ch_off})
+            *a = ci.take(np + 1);
+        for (int** a : {&c.icnt, &c.i_off}) *a = ci.take(c.ni_max + 1);
+        for (int** a : {&c.aflag, &c.a_off}) *a = ci.take((int64_t)hi + 1);
+        for (unsigned long long** a : {&c.agg_cnt, &c.pu_slots, &c.pu_run, &c.slots, &c.running}) *a = cu.take(nst + 1);
+        idbuf = cu.take(k);
+        return std::make_pair(ci.n, cu.n);
+    };
+    const auto [n_i, n_u] = carve({nullptr}, {nullptr});
     const int64_t nb = (nst + 4) & ~3LL;
+    KS_CHECK(s.cm_i.ensure(n_i));
+    KS_CHECK(s.cm_u.ensure(n_u));
     KS_CHECK(s.cm_b.ensure(nb));
     KS_CHECK(s.cm_ctl.ensure(1));
-    KS_CHECK(hipMemsetAsync(s.cm_i.p, 0, s.cm_i.n * sizeof(int), st));
-    KS_CHECK(hipMemsetAsync(s.cm_u.p, 0, 5 * (nst + 1) * 8, st));
+    carve({s.cm_i.p}, {s.cm_u.p});
+    c.fl = s.cm_b.p;
+    c.ctl = s.cm_ctl.p;
+    KS_CHECK(hipMemsetAsync(s.cm_i.p, 0, n_i * sizeof(int), st));
+    KS_CHECK(hipMemsetAsync(s.cm_u.p, 0, n_u * 8, st));
     KS_CHECK(hipMemsetAsync(s.cm_b.p, 0, nb, st));
     KS_CHECK(hipMemsetAsync(s.cm_ctl.p, 0, sizeof(CommitCtl), st));
-    CommitDev c{};
-    c.np = (int)np;
-    c.ni_max = (int)ni_max;
-    c.pl_task = s.cm_i.p;
-    c.pl_pu = c.pl_task + (np + 1);
-    c.pl_has = c.pl_pu + (np + 1);
-    c.pl_noarc = c.pl_has + (np + 1);
-    c.add_off = c.pl_noarc + (np + 1);
-    c.nch = c.add_off + (np + 1);
-    c.ch_off = c.nch + (np + 1);
-    c.pl_kind = c.ch_off + (np + 1);
-    c.pl_old = c.pl_kind + (np + 1);
-    c.pl_found = c.pl_old + (np + 1);
-    c.icnt = c.pl_found + (np + 1);
-    c.i_off = c.icnt + (ni_max + 1);
-    c.aflag = c.i_off + (ni_max + 1);
-    c.a_off = c.aflag + (hi + 1);
-    c.fl = s.cm_b.p;
-    c.agg_cnt = s.cm_u.p;
-    c.pu_slots = c.agg_cnt + (nst + 1);
-    c.pu_run = c.pu_slots + (nst + 1);
-    c.slots = c.pu_run + (nst + 1);
-    c.running = c.slots + (nst + 1);
-    c.ctl = s.cm_ctl.p;
-    const unsigned long long* dids = nullptr;
     if (ids) {
         for (size_t i = 0; i < k; ++i)
             if (ids[i] == 0 || (int64_t)ids[i] > nst) {
                 err = "unscheduled aggregator id beyond the graph";
                 return KS_E_INVALID;
             }
-        unsigned long long* p = c.running + (nst + 1);
-        if (k) KS_CHECK(hipMemcpyAsync(p, ids, k * 8, hipMemcpyHostToDevice, st));
-        dids = p;
+        if (k) KS_CHECK(hipMemcpyAsync(idbuf, ids, k * 8, hipMemcpyHostToDevice, st));
     }
-    auto scan = [&](const int* in, int* o, int64_t n) -> hipError_t {
-        size_t t = 0;
-        hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, t, in, o, (int)n, st);
-        if (e == hipSuccess) e = s.map_tmp.ensure(std::max(t, s.map_tmp.n));
-        t = s.map_tmp.n;
-        if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(s.map_tmp.p, t, in, o, (int)n, st);
-        return e;
-    };
+    const unsigned long long* dids = ids ? idbuf : nullptr;
     SchedDev d = s.schd();
     {   // the kinds of sched_deltas: [pre | other | pre_pos | other_pos] × (ncap + 1)
         const int* pre = s.sched_i.p;
@@ -319,24 +323,19 @@ int Engine::commit(bool preempt, int flags, int64_t ccost, int64_t pcost, const 
         const int* pre_pos = other + (ncap + 1);
         const int* other_pos = pre_pos + (ncap + 1);
         const unsigned long long* newpu = (const unsigned long long*)s.map_scratch.p;
-        if (preempt)
-            KS_CHECK(sched_preempt_items(d, c, s.map_rank.p, newpu, pre, pre_pos, other, other_pos, npre, dids, (int)k,
-                                         st));
-        else
-            KS_CHECK(sched_commit_places(d, c, s.map_rank.p, newpu, other, other_pos, dids, (int)k, st));
+        KS_CHECK(sched_commit_items(d, c, s.map_rank.p, newpu, pre, pre_pos, other, other_pos, npre, dids, (int)k, st));
     }
-    KS_CHECK(scan(c.nch, c.ch_off, np + 1));
-    KS_CHECK(preempt ? sched_preempt_count(d, c, pcost, st) : sched_commit_count(d, c, st));
-    KS_CHECK(scan(c.icnt, c.i_off, ni_max + 1));
-    KS_CHECK(scan(c.pl_noarc, c.add_off, np + 1));
-    if (resource_caps) {
-        // (preemptive: no running count is subtracted, pu_run stays zero)
-        KS_CHECK(preempt ? sched_preempt_pu_slots(d, c, st) : sched_commit_pu_counts(d, c, st));
+    KS_CHECK(exclusive_sum(s, (const int*)c.nch, c.ch_off, np + 1, st));
+    KS_CHECK(sched_commit_count(d, c, st));
+    KS_CHECK(exclusive_sum(s, (const int*)c.icnt, c.i_off, c.ni_max + 1, st));
+    KS_CHECK(exclusive_sum(s, (const int*)c.pl_noarc, c.add_off, np + 1, st));
+    if (c.resource_caps) {
+        KS_CHECK(sched_commit_pu(d, c, st));
         rc = topo_bfs(s, d, sink_slot, 0, c.pu_slots, c.pu_run, c.slots, c.running, err);
         if (rc) return rc;
     }
-    KS_CHECK(sched_commit_arc_flags(d, c, resource_caps, preempt ? 1 : 0, st));
-    KS_CHECK(scan(c.aflag, c.a_off, (int64_t)hi + 1));
+    KS_CHECK(sched_commit_arc_flags(d, c, st));
+    KS_CHECK(exclusive_sum(s, (const int*)c.aflag, c.a_off, (int64_t)hi + 1, st));
     KS_CHECK(sched_commit_totals(d, c, st));
     CommitCtl& h = *hc;
     KS_CHECK(hipMemcpyAsync(&h, c.ctl, sizeof(CommitCtl), hipMemcpyDeviceToHost, st));
@@ -364,8 +363,7 @@ int Engine::commit(bool preempt, int flags, int64_t ccost, int64_t pcost, const 
     KS_CHECK(s.d_edits.ensure(1));
     d = s.schd();   // (the arc table may have moved)
     *dirty = true;
-    KS_CHECK(preempt ? sched_preempt_emit(d, c, ccost, pcost, resource_caps, s.d_recs.p, st)
-                     : sched_commit_emit(d, c, ccost, resource_caps, s.d_recs.p, st));
+    KS_CHECK(sched_commit_emit(d, c, s.d_recs.p, st));
     KS_CHECK(store_apply(s.sd(), s.d_recs.p, (int)nrec, s.rec_ent.p, s.d_edits.p, 0, st));
     if (log) KS_CHECK(hipEventRecord(s.kev[1], st));
     rc = read_sctl(s, err);

@@ -54,33 +54,42 @@ hipError_t sched_unsched_costs(const SchedDev& d, const unsigned long long* ids,
                                long long ucost, long long ccost, int* changed, hipStream_t st);
 
 
-// ---- ks_commit_schedule: the pin of every placed task (pinTaskToNode,
-// graph_manager.go:675-720), the unscheduled aggregators' capacities (:1291-1305) and
-// the resource arcs' (:662-667) as ks_delta records generated in device memory.
+// ---- ks_commit_schedule and ks_commit_preemptive: the graph edit of the last solve's
+// scheduling deltas as ks_delta records generated in device memory. Pinned mode:
+// pinTaskToNode (graph_manager.go:675-720), the unscheduled aggregators' capacities
+// (:1291-1305) and the resource arcs' (:662-667). Preemptive mode: TaskScheduled with
+// Preemption == true (:855-888, :1164-1181), TaskEvicted (:412-433), TaskMigrated
+// (:407-410) and the resource arcs' slots below. An item is a task with a delta, in delta
+// order (the PREEMPTs first); in the pinned mode every item is a PLACE.
 // Device counters of one commit; the host reads them in one copy.
 struct CommitCtl {
-    int rec_pin;      // records of the placed tasks' existing out-arcs (deletes + conversions)
+    int rec_pin;      // records on existing arcs of the items (conversions, deletes, cost changes)
     int rec_add;      // new running arcs
     int rec_arc;      // aggregator and resource-arc capacity records
     int unsched;      // of those, aggregator → sink arcs
     int caps;         // of those, resource arcs
-    int bad;          // 1: a capacity would fall below its arc's lower bound; 2 (ks_commit_preemptive): a
-                      // PREEMPT or MIGRATE without its running arc
-    int converted;    // ks_commit_preemptive: of rec_pin, arcs turned into running arcs
-    int removed;      //   and running arcs deleted (the rest of rec_pin are cost records)
+    int bad;          // 1: a capacity would fall below its arc's lower bound; 2: a PREEMPT or MIGRATE
+                      // without its running arc
+    int converted;    // preemptive: of rec_pin, arcs turned into running arcs
+    int removed;      //   and running arcs deleted (the rest of rec_pin are cost records); pinned they stay 0:
+                      //   np − rec_add are converted, the rest of rec_pin deleted
 };
 
-// Scratch of one commit (device pointers; np placed tasks, ni_max chunk items at most).
+// Mode and scratch of one commit (device pointers; np items, ni_max chunk items at most).
 struct CommitDev {
-    int np;                        // PLACE deltas
+    int preempt;                   // 0 pinned (ks_commit_schedule), 1 preemptive (ks_commit_preemptive)
+    int resource_caps;             // KS_COMMIT_RESOURCE_CAPS: also the resource arcs' capacities
+    long long ccost;               // cost of a running arc (continuation)
+    long long pcost;               // preemptive: cost of an item's arcs into unscheduled aggregators
+    int np;                        // items
     int ni_max;                    // upper bound of the chunk items (np + residual positions / 64)
-    int* pl_task;                  // [np] task node slot, in delta order
-    int* pl_pu;                    // [np] PU node slot
-    int* pl_has;                   // [np + 1] 1: the arc task → PU exists (it is converted)
-    int* pl_kind;                  // [np + 1] ks_commit_preemptive: KS_DELTA_* of the item (pl_pu −1 for a PREEMPT)
-    int* pl_old;                   // [np + 1]   PU node slot the task leaves (PREEMPT, MIGRATE), else −1
-    int* pl_found;                 // [np + 1]   1: the running arc into pl_old exists
-    int* pl_noarc;                 // [np + 1] 1 − pl_has, and its exclusive scan add_off
+    int* pl_task;                  // [np + 1] task node slot, in delta order
+    int* pl_kind;                  // [np + 1] KS_DELTA_* of the item
+    int* pl_pu;                    // [np + 1] PU node slot the task enters, −1 for a PREEMPT
+    int* pl_old;                   // [np + 1] PU node slot the task leaves, −1 for a PLACE
+    int* pl_has;                   // [np + 1] 1: the arc task → pl_pu exists (it is converted)
+    int* pl_found;                 // [np + 1] 1: an arc of the task is deleted (preemptive: the running arc into pl_old)
+    int* pl_noarc;                 // [np + 1] 1: the running arc into pl_pu is added; add_off its scan
     int* add_off;                  // [np + 1]
     int* nch;                      // [np + 1] 64-position chunks of the task's segment; ch_off its scan
     int* ch_off;                   // [np + 1]
@@ -88,48 +97,33 @@ struct CommitDev {
     int* i_off;                    // [ni_max + 1]
     int* aflag;                    // [hi + 1] arc slot emits a capacity record; a_off its scan
     int* a_off;                    // [hi + 1]
-    unsigned char* fl;             // per node slot: 1 unscheduled aggregator, 2 placed by this call
-    unsigned long long* agg_cnt;   // per node slot: pinned tasks that had an arc into the aggregator
+    unsigned char* fl;             // per node slot: 1 unscheduled aggregator, 2 (pinned) placed by this call
+    unsigned long long* agg_cnt;   // per node slot (pinned): items that had an arc into the aggregator
     unsigned long long* pu_slots;  // per node slot: capacity of the PU → sink arc
-    unsigned long long* pu_run;    // per node slot: running arcs into the PU after the commit
+    unsigned long long* pu_run;    // per node slot (pinned): running arcs into the PU after the commit
     unsigned long long* slots;     // per node slot: slots_below (resource caps)
     unsigned long long* running;   // per node slot: running_below
     CommitCtl* ctl;
 };
 
-// The places of the delta kinds (sched_delta_kinds) in delta order, their chunk counts,
-// and the aggregator flags (ids: k node ids, or nullptr for every type-0 node with an
-// arc into the sink).
-hipError_t sched_commit_places(const SchedDev& d, const CommitDev& c, const int* rank, const unsigned long long* newpu,
-                               const int* other, const int* other_pos, const unsigned long long* ids, int k,
-                               hipStream_t st);
+// The items of the delta kinds (sched_delta_kinds) in delta order, their chunk counts, and
+// the aggregator flags (ids: k node ids, or nullptr for every type-0 node with an arc into
+// the sink).
+hipError_t sched_commit_items(const SchedDev& d, const CommitDev& c, const int* rank, const unsigned long long* newpu,
+                              const int* pre, const int* pre_pos, const int* other, const int* other_pos, int npre,
+                              const unsigned long long* ids, int k, hipStream_t st);
 // Count pass over the chunk items (after the scan nch → ch_off).
 hipError_t sched_commit_count(const SchedDev& d, const CommitDev& c, hipStream_t st);
-// PU slots and running counts for the resource capacities (before the level BFS).
-hipError_t sched_commit_pu_counts(const SchedDev& d, const CommitDev& c, hipStream_t st);
-// Arc slots that emit a capacity record (aflag), resource_caps != 0: also the resource arcs.
-// preempt != 0 (ks_commit_preemptive): no aggregator record, a resource arc gets slots_below.
-hipError_t sched_commit_arc_flags(const SchedDev& d, const CommitDev& c, int resource_caps, int preempt,
-                                  hipStream_t st);
+// PU slots, pinned also the running counts, for the resource capacities (before the level BFS).
+hipError_t sched_commit_pu(const SchedDev& d, const CommitDev& c, hipStream_t st);
+// Arc slots that emit a capacity record (aflag). Pinned: the aggregator → sink arcs and, with
+// resource_caps, a resource arc gets slots − running below its head. Preemptive: no aggregator
+// record, a resource arc gets slots_below.
+hipError_t sched_commit_arc_flags(const SchedDev& d, const CommitDev& c, hipStream_t st);
 // Record totals into c.ctl (after the scans icnt → i_off, pl_noarc → add_off, aflag → a_off).
 hipError_t sched_commit_totals(const SchedDev& d, const CommitDev& c, hipStream_t st);
-// Emit pass: the records into recs (pins, then new running arcs, then capacities) and the
-// bindings of the placed tasks.
-hipError_t sched_commit_emit(const SchedDev& d, const CommitDev& c, long long ccost, int resource_caps, ks_delta* recs,
-                             hipStream_t st);
-
-// ---- ks_commit_preemptive: TaskScheduled with Preemption == true (graph_manager.go:855-888,
-// :1164-1181), TaskEvicted (:412-433) and TaskMigrated (:407-410) on the same scratch. An
-// item is a task with a delta of any kind, in delta order (np of them: the npre PREEMPTs
-// first); rec_pin counts the records on existing arcs (conversions, deletes, cost changes).
-hipError_t sched_preempt_items(const SchedDev& d, const CommitDev& c, const int* rank, const unsigned long long* newpu,
-                               const int* pre, const int* pre_pos, const int* other, const int* other_pos, int npre,
-                               const unsigned long long* ids, int k, hipStream_t st);
-hipError_t sched_preempt_count(const SchedDev& d, const CommitDev& c, long long pcost, hipStream_t st);
-// PU slots only: this mode subtracts no running tasks.
-hipError_t sched_preempt_pu_slots(const SchedDev& d, const CommitDev& c, hipStream_t st);
-// Emit pass: item records, then new running arcs, then capacities; the bindings of every item.
-hipError_t sched_preempt_emit(const SchedDev& d, const CommitDev& c, long long ccost, long long pcost,
-                              int resource_caps, ks_delta* recs, hipStream_t st);
+// Emit pass: the records into recs (item records, then new running arcs, then capacities) and
+// the bindings of every item.
+hipError_t sched_commit_emit(const SchedDev& d, const CommitDev& c, ks_delta* recs, hipStream_t st);
 
 }  // namespace ks

@@ -15,14 +15,14 @@
 //                       every task's arc into its unscheduled aggregator re-costed
 //                       in place (residual pair included), running tasks' running
 //                       arcs set to the continuation cost
-//   commit schedule     TaskScheduled → pinTaskToNode (graph_manager.go:454-460, 675-720),
-//                       updateUnscheduledAggNode(−1) (:706) and
-//                       capacityFromResNodeToParent (:662-667): the records a host
-//                       would export for them, generated in device memory for
-//                       store_apply (ks_store.hip)
-//   commit, preemptive  the same step with Preemption == true: updateArcsForScheduledTask
-//                       (:855-888), updateRunningTaskToUnscheduledAggArc (:1164-1181),
-//                       TaskEvicted (:412-433), TaskMigrated (:407-410) and
+//   commit              the records a host would export for the solve's deltas, generated
+//                       in device memory for store_apply (ks_store.hip) by one kernel
+//                       family with a mode. Pinned: TaskScheduled → pinTaskToNode
+//                       (graph_manager.go:454-460, 675-720), updateUnscheduledAggNode(−1)
+//                       (:706) and capacityFromResNodeToParent (:662-667). Preemptive
+//                       (Preemption == true): updateArcsForScheduledTask (:855-888),
+//                       updateRunningTaskToUnscheduledAggArc (:1164-1181), TaskEvicted
+//                       (:412-433), TaskMigrated (:407-410) and
 //                       capacityFromResNodeToParent returning NumSlotsBelow
 #include "ks_sched.h"
 
@@ -194,16 +194,23 @@ __global__ void k_unsched_costs(SchedDev d, int hi, const unsigned char* __restr
     }
 }
 
-// ------------------------------------------------------------ commit schedule ---
-// pinTaskToNode (graph_manager.go:675-720) for every PLACE of the last solve, with
-// updateUnscheduledAggNode(−1) (:706, :1291-1305) and capacityFromResNodeToParent
-// (:662-667), as ks_delta records written in device memory for store_apply. Three
-// record families, disjoint in (src, dst): a placed task's out-arcs (the tail is a
-// task), aggregator → sink arcs (the head is the sink), resource arcs (neither).
+// --------------------------------------------------------------------- commit ---
+// The graph edit of the last solve's deltas as ks_delta records written in device memory
+// for store_apply. The items are the tasks with a delta, in delta order.
+// Pinned (c.preempt == 0, every item a PLACE): pinTaskToNode (graph_manager.go:675-720)
+// with updateUnscheduledAggNode(−1) (:706, :1291-1305) and capacityFromResNodeToParent
+// (:662-667).
+// Preemptive: updateArcsForScheduledTask with Preemption == true (:855-888): a placed
+// task keeps every arc; the one into its PU becomes (or is added as) the running arc with
+// low 0, and its arcs into unscheduled aggregators take the preemption cost
+// (updateRunningTaskToUnscheduledAggArc, :1164-1181). TaskEvicted (:412-433) deletes the
+// running arc and nothing else; TaskMigrated (:407-410) is both.
+// Three record families, disjoint in (src, dst): an item's out-arcs (the tail is a task),
+// aggregator → sink arcs (the head is the sink), resource arcs (neither).
 //
-// A placed task's out-arcs are found in its residual segment, one wave per
-// 64-position chunk of it (the chunk items of k_bf_round, built here on device:
-// nch → ch_off by a scan, the item's place by bisection): no lane walks a segment.
+// An item's out-arcs are found in its residual segment, one wave per 64-position chunk
+// of it (the chunk items of k_bf_round, built here on device: nch → ch_off by a scan,
+// the item's place by bisection): no lane walks a segment.
 
 // One atomicAdd per distinct idx among the pred lanes of a wave (hundreds of tasks
 // placed on one PU hit one word: same-word atomics serialise at ~10 ns each).
@@ -225,24 +232,35 @@ __device__ __forceinline__ void wave_count(int* ctr, bool pred) {
     if (m && (int)__lane_id() == __ffsll((long long)m) - 1) atomicAdd(ctr, __popcll(m));
 }
 
-__global__ void k_commit_places(SchedDev d, CommitDev c, const int* __restrict__ rank,
-                                const unsigned long long* __restrict__ newpu, const int* __restrict__ other,
-                                const int* __restrict__ other_pos) {
+__global__ void k_commit_items(SchedDev d, CommitDev c, const int* __restrict__ rank,
+                               const unsigned long long* __restrict__ newpu, const int* __restrict__ pre,
+                               const int* __restrict__ pre_pos, const int* __restrict__ other,
+                               const int* __restrict__ other_pos, int npre) {
     for (long long v = blockIdx.x * (long long)SB + threadIdx.x; v < d.ncap; v += (long long)gridDim.x * SB) {
-        if (other[v] != 1) continue;
-        const int i = other_pos[v];
+        int i, kind;
+        if (pre[v]) {
+            i = pre_pos[v];
+            kind = KS_DELTA_PREEMPT;
+        } else if (other[v]) {
+            i = npre + other_pos[v];
+            kind = other[v] == 1 ? KS_DELTA_PLACE : KS_DELTA_MIGRATE;
+        } else {
+            continue;
+        }
         if (i < 0 || i >= c.np) continue;
         c.pl_task[i] = (int)v;
-        c.pl_pu[i] = (int)newpu[rank[v]] - 1;
+        c.pl_kind[i] = kind;
+        c.pl_pu[i] = kind == KS_DELTA_PREEMPT ? -1 : (int)newpu[rank[v]] - 1;
+        c.pl_old[i] = kind == KS_DELTA_PLACE ? -1 : (int)d.n_bind[v] - 1;
         const int x = d.perm[v];
         int len = 0;
         if (x >= 0) len = min(d.used[x], d.first[x + 1] - d.first[x]);
         c.nch[i] = (max(len, 0) + 63) >> 6;
-        c.fl[v] |= 2;
+        if (!c.preempt) c.fl[v] |= 2;
     }
 }
 
-// Chunk item w → its place i (ch_off[i] ≤ w < ch_off[i + 1]) and the position this lane reads.
+// Chunk item w → its item i (ch_off[i] ≤ w < ch_off[i + 1]) and the position this lane reads.
 __device__ __forceinline__ int commit_item(const SchedDev& d, const CommitDev& c, int w, int lane, int* place) {
     int lo = 0, hi = c.np - 1;
     while (lo < hi) {
@@ -258,35 +276,74 @@ __device__ __forceinline__ int commit_item(const SchedDev& d, const CommitDev& c
     return p < b + len ? p : -1;
 }
 
+// The record the live out-arc in slot s of item i gets. 1: the arc into the PU the task
+// enters, it becomes the running arc. 2: a delete (DeleteArc's "x src dst 0 0",
+// graph_change_manager.go:184-193); pinned every other arc, preemptive the running arc
+// into the PU the task leaves (an arc into it that is no running arc counts as missing:
+// the reference panics, graph_manager.go:416-419). 3, preemptive: an arc into an
+// unscheduled aggregator whose cost changes (ChangeArcCost emits nothing otherwise,
+// graph_change_manager.go:171-182). 0: none.
+__device__ __forceinline__ int commit_arc_class(const SchedDev& d, const CommitDev& c, int i, int s) {
+    const int dst = d.a_dst[s];
+    if (dst == c.pl_pu[i]) return 1;
+    if (!c.preempt) return 2;
+    if (dst == c.pl_old[i]) return d.a_type[s] == 1 ? 2 : 0;
+    if ((c.fl[dst] & 1) && c.pl_kind[i] != KS_DELTA_PREEMPT && d.a_cost[s] != c.pcost) return 3;
+    return 0;
+}
+
+// Chunk item w of both passes: this lane's arc slot *s (−1 if it reads no live out-arc), its
+// item *i and the arc's class.
+__device__ __forceinline__ int commit_lane_arc(const SchedDev& d, const CommitDev& c, int w, int lane, int* i, int* s) {
+    const int p = commit_item(d, c, w, lane, i);
+    const int e = p >= 0 ? d.ent[p] : -1;
+    *s = e >= 0 && !(e & 1) ? e >> 1 : -1;   // forward positions: the task's out-arcs
+    return *s >= 0 ? commit_arc_class(d, c, *i, *s) : 0;
+}
+
 __global__ void k_commit_count(SchedDev d, CommitDev c) {
     const int lane = threadIdx.x & 63;
     const int wave = (blockIdx.x * SB + threadIdx.x) >> 6;
     const int nwaves = (gridDim.x * SB) >> 6;
     const int ni = min(c.ch_off[c.np], c.ni_max);
+    // Class counts over this wave's chunk items, one atomic each at the end. Preemptive only:
+    // pinned, every wave deletes, and its 16k atomics on one word cost 0.13 ms at 100k
+    // tasks; that mode's stats follow from rec_pin and rec_add.
+    int converted = 0, removed = 0;
     for (int w = wave; w < ni; w += nwaves) {
-        int i;
-        const int p = commit_item(d, c, w, lane, &i);
-        const int e = p >= 0 ? d.ent[p] : -1;
-        const bool live = e >= 0 && !(e & 1);   // forward positions: the task's out-arcs
-        if (live) {
-            const int dst = d.a_dst[e >> 1];
-            if (dst == c.pl_pu[i]) c.pl_has[i] = 1;
-            // (one task per wave and one arc per (src, dst): the lanes' aggregators are distinct words)
-            if (c.fl[dst] & 1) atomicAdd(&c.agg_cnt[dst], 1ULL);
-        }
-        const unsigned long long m = __ballot(live);
+        int i, s;
+        const int cls = commit_lane_arc(d, c, w, lane, &i, &s);
+        if (cls == 1) c.pl_has[i] = 1;
+        if (cls == 2) c.pl_found[i] = 1;
+        // pinned: the aggregators lose the task (one task per wave and one arc per (src, dst):
+        // the lanes' aggregators are distinct words)
+        if (!c.preempt && s >= 0 && (c.fl[d.a_dst[s]] & 1)) atomicAdd(&c.agg_cnt[d.a_dst[s]], 1ULL);
+        const unsigned long long m = __ballot(cls != 0);
         if (lane == 0) c.icnt[w] = __popcll(m);
+        converted += __popcll(__ballot(cls == 1));
+        removed += __popcll(__ballot(cls == 2));
+    }
+    if (c.preempt && lane == 0 && converted) atomicAdd(&c.ctl->converted, converted);
+    if (c.preempt && lane == 0 && removed) atomicAdd(&c.ctl->removed, removed);
+}
+
+// An item that enters a PU without an arc into it gets the running arc added; one that
+// leaves a PU must have found its running arc.
+__global__ void k_commit_noarc(CommitDev c) {
+    for (long long i = blockIdx.x * (long long)SB + threadIdx.x; i <= c.np; i += (long long)gridDim.x * SB) {
+        int na = 0;
+        if (i < c.np) {
+            const int kind = c.pl_kind[i];
+            na = kind != KS_DELTA_PREEMPT && !c.pl_has[i];
+            if (kind != KS_DELTA_PLACE && !c.pl_found[i]) atomicOr(&c.ctl->bad, 2);
+        }
+        c.pl_noarc[i] = na;
     }
 }
 
-__global__ void k_commit_noarc(CommitDev c) {
-    for (long long i = blockIdx.x * (long long)SB + threadIdx.x; i <= c.np; i += (long long)gridDim.x * SB)
-        c.pl_noarc[i] = i < c.np ? 1 - c.pl_has[i] : 0;
-}
-
-// A PU's slots are the capacity of its arc into the sink; its running count the
-// running arcs (type 1) into it that stay — a placed task's own arcs go or are
-// converted — plus the tasks this call places on it.
+// A PU's slots are the capacity of its arc into the sink. Pinned, its running count is the
+// running arcs (type 1) into it that stay — a placed task's own arcs go or are converted —
+// plus the tasks this call places on it; the preemptive mode subtracts no running tasks.
 __global__ void k_commit_pu_arcs(SchedDev d, CommitDev c) {
     for (long long s0 = blockIdx.x * (long long)SB; s0 < d.hi; s0 += (long long)gridDim.x * SB) {   // (uniform per workgroup)
         const long long s = s0 + threadIdx.x;
@@ -296,7 +353,7 @@ __global__ void k_commit_pu_arcs(SchedDev d, CommitDev c) {
             const int src = d.a_src[s];
             dst = d.a_dst[s];
             if (d.n_type[dst] == KS_NODE_SINK && d.n_type[src] == KS_NODE_PU) c.pu_slots[src] = (unsigned long long)d.a_cap[s];
-            run = d.a_type[s] == 1 && !(c.fl[src] & 2);
+            run = !c.preempt && d.a_type[s] == 1 && !(c.fl[src] & 2);
         }
         wave_add_distinct(c.pu_run, dst, run);
     }
@@ -312,33 +369,32 @@ __global__ void k_commit_pu_places(CommitDev c) {
 // The capacity arc slot s gets from this commit: 1 an aggregator → sink arc (minus
 // the tasks pinned out of it), 2 a resource arc (slots − running below its head), 0
 // none or unchanged.
-// With preempt (ks_commit_preemptive, capacityFromResNodeToParent returning NumSlotsBelow)
-// kind 1 never fires and a resource arc gets slots below its head: running tasks may move.
-__device__ __forceinline__ int commit_arc_cap(const SchedDev& d, const CommitDev& c, int resource_caps, int preempt,
-                                              int s, long long* cap) {
+// Preemptive (capacityFromResNodeToParent returning NumSlotsBelow) kind 1 never fires and
+// a resource arc gets slots below its head: running tasks may move.
+__device__ __forceinline__ int commit_arc_cap(const SchedDev& d, const CommitDev& c, int s, long long* cap) {
     if (!d.a_alive[s]) return 0;
     const int u = d.a_src[s], v = d.a_dst[s];
     const unsigned char tu = d.n_type[u], tv = d.n_type[v];
     if (tv == KS_NODE_SINK) {
-        if (preempt || !(c.fl[u] & 1) || c.agg_cnt[u] == 0) return 0;
+        if (c.preempt || !(c.fl[u] & 1) || c.agg_cnt[u] == 0) return 0;
         *cap = d.a_cap[s] - (long long)c.agg_cnt[u];
         return 1;
     }
-    if (!resource_caps || tu == KS_NODE_TASK) return 0;
+    if (!c.resource_caps || tu == KS_NODE_TASK) return 0;
     const bool res = tv == KS_NODE_PU || tv == KS_NODE_MACHINE || tv == KS_NODE_INTERMEDIATE ||
                      (tv == KS_NODE_OTHER && c.slots[v] > 0);
     if (!res) return 0;
-    *cap = (long long)c.slots[v] - (preempt ? 0 : (long long)c.running[v]);
+    *cap = (long long)c.slots[v] - (c.preempt ? 0 : (long long)c.running[v]);
     return *cap != d.a_cap[s] ? 2 : 0;
 }
 
-__global__ void k_commit_arc_flags(SchedDev d, CommitDev c, int resource_caps, int preempt) {
+__global__ void k_commit_arc_flags(SchedDev d, CommitDev c) {
     for (long long s0 = blockIdx.x * (long long)SB; s0 <= d.hi; s0 += (long long)gridDim.x * SB) {
         const long long s = s0 + threadIdx.x;
         int kind = 0;
         if (s < d.hi) {
             long long cap = 0;
-            kind = commit_arc_cap(d, c, resource_caps, preempt, (int)s, &cap);
+            kind = commit_arc_cap(d, c, (int)s, &cap);
             if (kind && cap < d.a_low[s]) atomicOr(&c.ctl->bad, 1);
         }
         if (s <= d.hi) c.aflag[s] = kind != 0;
@@ -369,167 +425,48 @@ __device__ __forceinline__ ks_delta arc_record(int kind, int type, int src, int 
     return r;
 }
 
-// Per out-arc of a placed task: the arc into its PU becomes the running arc (type 1,
-// low 1, cap 1, the continuation cost), every other one is deleted (DeleteArc's
-// "x src dst 0 0", graph_change_manager.go:184-193).
-__global__ void k_commit_emit_pins(SchedDev d, CommitDev c, long long ccost, ks_delta* __restrict__ recs) {
+// Per out-arc of an item, by class: the running arc (type 1, cap 1, the continuation
+// cost; low 1 pins the task, low 0 lets it move), a delete, or the preemption cost.
+__global__ void k_commit_emit_items(SchedDev d, CommitDev c, ks_delta* __restrict__ recs) {
     const int lane = threadIdx.x & 63;
     const int wave = (blockIdx.x * SB + threadIdx.x) >> 6;
     const int nwaves = (gridDim.x * SB) >> 6;
     const int ni = min(c.ch_off[c.np], c.ni_max);
     for (int w = wave; w < ni; w += nwaves) {
-        int i;
-        const int p = commit_item(d, c, w, lane, &i);
-        const int e = p >= 0 ? d.ent[p] : -1;
-        const bool live = e >= 0 && !(e & 1);
-        const unsigned long long m = __ballot(live);
-        if (!live) continue;
-        const int s = e >> 1, t = c.pl_task[i], dst = d.a_dst[s];
+        int i, s;
+        const int cls = commit_lane_arc(d, c, w, lane, &i, &s);
+        const unsigned long long m = __ballot(cls != 0);
+        if (!cls) continue;
+        const int t = c.pl_task[i], dst = d.a_dst[s];
         const int r = c.i_off[w] + __popcll(m & ((1ULL << lane) - 1));
         const long long co = d.a_cost[s];
-        recs[r] = dst == c.pl_pu[i] ? arc_record(KS_UPDATE_ARC, 1, t, dst, 1, 1, ccost, co)
-                                    : arc_record(KS_UPDATE_ARC, d.a_type[s], t, dst, 0, 0, co, co);
+        recs[r] = cls == 1   ? arc_record(KS_UPDATE_ARC, 1, t, dst, c.preempt ? 0 : 1, 1, c.ccost, co)
+                  : cls == 2 ? arc_record(KS_UPDATE_ARC, d.a_type[s], t, dst, 0, 0, co, co)
+                             : arc_record(KS_UPDATE_ARC, d.a_type[s], t, dst, d.a_low[s], d.a_cap[s], c.pcost, co);
     }
 }
 
-// A placed task without an arc into its PU gets the running arc; every placed task its binding.
-__global__ void k_commit_emit_adds(SchedDev d, CommitDev c, long long ccost, ks_delta* __restrict__ recs) {
-    const int base = c.ctl->rec_pin;
-    for (long long i = blockIdx.x * (long long)SB + threadIdx.x; i < c.np; i += (long long)gridDim.x * SB) {
-        const int t = c.pl_task[i], pu = c.pl_pu[i];
-        d.n_bind[t] = (unsigned long long)pu + 1;
-        if (!c.pl_has[i]) recs[base + c.add_off[i]] = arc_record(KS_ADD_ARC, 1, t, pu, 1, 1, ccost, 0);
-    }
-}
-
-__global__ void k_commit_emit_arcs(SchedDev d, CommitDev c, int resource_caps, int preempt,
-                                   ks_delta* __restrict__ recs) {
-    const int base = c.ctl->rec_pin + c.ctl->rec_add;
-    for (long long s = blockIdx.x * (long long)SB + threadIdx.x; s < d.hi; s += (long long)gridDim.x * SB) {
-        if (!c.aflag[s]) continue;
-        long long cap = 0;
-        if (!commit_arc_cap(d, c, resource_caps, preempt, (int)s, &cap)) continue;
-        // capacity 0 removes the arc (the store's low == cap == 0 rule; cap ≥ low was checked)
-        const long long co = d.a_cost[s];
-        recs[base + c.a_off[s]] = arc_record(KS_UPDATE_ARC, d.a_type[s], d.a_src[s], d.a_dst[s], cap ? d.a_low[s] : 0,
-                                             cap, co, co);
-    }
-}
-
-// -------------------------------------------------------- commit, preemptive ---
-// updateArcsForScheduledTask with Preemption == true (graph_manager.go:855-888): a
-// placed task keeps every arc; the one into its PU becomes (or is added as) the running
-// arc with low 0, and its arcs into unscheduled aggregators take the preemption cost
-// (updateRunningTaskToUnscheduledAggArc, :1164-1181). TaskEvicted (:412-433) deletes
-// the running arc and nothing else; TaskMigrated (:407-410) is both. The items are the
-// tasks with a delta of any kind, in delta order, on the chunk items of the pinned mode.
-__global__ void k_preempt_items(SchedDev d, CommitDev c, const int* __restrict__ rank,
-                                const unsigned long long* __restrict__ newpu, const int* __restrict__ pre,
-                                const int* __restrict__ pre_pos, const int* __restrict__ other,
-                                const int* __restrict__ other_pos, int npre) {
-    for (long long v = blockIdx.x * (long long)SB + threadIdx.x; v < d.ncap; v += (long long)gridDim.x * SB) {
-        int i, kind;
-        if (pre[v]) {
-            i = pre_pos[v];
-            kind = KS_DELTA_PREEMPT;
-        } else if (other[v]) {
-            i = npre + other_pos[v];
-            kind = other[v] == 1 ? KS_DELTA_PLACE : KS_DELTA_MIGRATE;
-        } else {
-            continue;
-        }
-        if (i < 0 || i >= c.np) continue;
-        c.pl_task[i] = (int)v;
-        c.pl_kind[i] = kind;
-        c.pl_pu[i] = kind == KS_DELTA_PREEMPT ? -1 : (int)newpu[rank[v]] - 1;
-        c.pl_old[i] = kind == KS_DELTA_PLACE ? -1 : (int)d.n_bind[v] - 1;
-        const int x = d.perm[v];
-        int len = 0;
-        if (x >= 0) len = min(d.used[x], d.first[x + 1] - d.first[x]);
-        c.nch[i] = (max(len, 0) + 63) >> 6;
-    }
-}
-
-// The record arc slot s of item i gets: 1 the arc into the new PU (it becomes the
-// running arc), 2 the running arc into the PU the task leaves (deleted), 3 an arc into
-// an unscheduled aggregator whose cost changes (ChangeArcCost emits nothing otherwise,
-// graph_change_manager.go:171-182), 0 none. An arc into the old PU that is no running
-// arc counts as missing (the reference panics, graph_manager.go:416-419).
-__device__ __forceinline__ int preempt_arc_kind(const SchedDev& d, const CommitDev& c, int i, int s, long long pcost) {
-    const int dst = d.a_dst[s];
-    if (dst == c.pl_pu[i]) return 1;
-    if (dst == c.pl_old[i]) return d.a_type[s] == 1 ? 2 : 0;
-    if ((c.fl[dst] & 1) && c.pl_kind[i] != KS_DELTA_PREEMPT && d.a_cost[s] != pcost) return 3;
-    return 0;
-}
-
-__global__ void k_preempt_count(SchedDev d, CommitDev c, long long pcost) {
-    const int lane = threadIdx.x & 63;
-    const int wave = (blockIdx.x * SB + threadIdx.x) >> 6;
-    const int nwaves = (gridDim.x * SB) >> 6;
-    const int ni = min(c.ch_off[c.np], c.ni_max);
-    for (int w = wave; w < ni; w += nwaves) {
-        int i;
-        const int p = commit_item(d, c, w, lane, &i);
-        const int e = p >= 0 ? d.ent[p] : -1;
-        const int kind = e >= 0 && !(e & 1) ? preempt_arc_kind(d, c, i, e >> 1, pcost) : 0;
-        if (kind == 1) c.pl_has[i] = 1;
-        if (kind == 2) c.pl_found[i] = 1;
-        const unsigned long long m = __ballot(kind != 0);
-        if (lane == 0) c.icnt[w] = __popcll(m);
-        wave_count(&c.ctl->converted, kind == 1);
-        wave_count(&c.ctl->removed, kind == 2);
-    }
-}
-
-__global__ void k_preempt_noarc(CommitDev c) {
-    for (long long i = blockIdx.x * (long long)SB + threadIdx.x; i <= c.np; i += (long long)gridDim.x * SB) {
-        int na = 0;
-        if (i < c.np) {
-            const int kind = c.pl_kind[i];
-            na = kind != KS_DELTA_PREEMPT && !c.pl_has[i];
-            if (kind != KS_DELTA_PLACE && !c.pl_found[i]) atomicOr(&c.ctl->bad, 2);
-        }
-        c.pl_noarc[i] = na;
-    }
-}
-
-__global__ void k_preempt_pu_slots(SchedDev d, CommitDev c) {
-    for (long long s = blockIdx.x * (long long)SB + threadIdx.x; s < d.hi; s += (long long)gridDim.x * SB)
-        if (d.a_alive[s] && d.n_type[d.a_dst[s]] == KS_NODE_SINK && d.n_type[d.a_src[s]] == KS_NODE_PU)
-            c.pu_slots[d.a_src[s]] = (unsigned long long)d.a_cap[s];
-}
-
-__global__ void k_preempt_emit_items(SchedDev d, CommitDev c, long long ccost, long long pcost,
-                                     ks_delta* __restrict__ recs) {
-    const int lane = threadIdx.x & 63;
-    const int wave = (blockIdx.x * SB + threadIdx.x) >> 6;
-    const int nwaves = (gridDim.x * SB) >> 6;
-    const int ni = min(c.ch_off[c.np], c.ni_max);
-    for (int w = wave; w < ni; w += nwaves) {
-        int i;
-        const int p = commit_item(d, c, w, lane, &i);
-        const int e = p >= 0 ? d.ent[p] : -1;
-        const int kind = e >= 0 && !(e & 1) ? preempt_arc_kind(d, c, i, e >> 1, pcost) : 0;
-        const unsigned long long m = __ballot(kind != 0);
-        if (!kind) continue;
-        const int s = e >> 1, t = c.pl_task[i], dst = d.a_dst[s];
-        const int r = c.i_off[w] + __popcll(m & ((1ULL << lane) - 1));
-        const long long co = d.a_cost[s];
-        recs[r] = kind == 1   ? arc_record(KS_UPDATE_ARC, 1, t, dst, 0, 1, ccost, co)
-                  : kind == 2 ? arc_record(KS_UPDATE_ARC, d.a_type[s], t, dst, 0, 0, co, co)
-                              : arc_record(KS_UPDATE_ARC, d.a_type[s], t, dst, d.a_low[s], d.a_cap[s], pcost, co);
-    }
-}
-
-// A placed or migrated task without an arc into its PU gets the running arc; every item its
+// An item that enters a PU without an arc into it gets the running arc; every item its
 // binding (0 for a PREEMPT: pl_pu is −1).
-__global__ void k_preempt_emit_adds(SchedDev d, CommitDev c, long long ccost, ks_delta* __restrict__ recs) {
+__global__ void k_commit_emit_adds(SchedDev d, CommitDev c, ks_delta* __restrict__ recs) {
     const int base = c.ctl->rec_pin;
     for (long long i = blockIdx.x * (long long)SB + threadIdx.x; i < c.np; i += (long long)gridDim.x * SB) {
         const int t = c.pl_task[i], pu = c.pl_pu[i];
         d.n_bind[t] = (unsigned long long)(pu + 1);
-        if (c.pl_noarc[i]) recs[base + c.add_off[i]] = arc_record(KS_ADD_ARC, 1, t, pu, 0, 1, ccost, 0);
+        if (c.pl_noarc[i]) recs[base + c.add_off[i]] = arc_record(KS_ADD_ARC, 1, t, pu, c.preempt ? 0 : 1, 1, c.ccost, 0);
+    }
+}
+
+__global__ void k_commit_emit_arcs(SchedDev d, CommitDev c, ks_delta* __restrict__ recs) {
+    const int base = c.ctl->rec_pin + c.ctl->rec_add;
+    for (long long s = blockIdx.x * (long long)SB + threadIdx.x; s < d.hi; s += (long long)gridDim.x * SB) {
+        if (!c.aflag[s]) continue;
+        long long cap = 0;
+        if (!commit_arc_cap(d, c, (int)s, &cap)) continue;
+        // capacity 0 removes the arc (the store's low == cap == 0 rule; cap ≥ low was checked)
+        const long long co = d.a_cost[s];
+        recs[base + c.a_off[s]] = arc_record(KS_UPDATE_ARC, d.a_type[s], d.a_src[s], d.a_dst[s], cap ? d.a_low[s] : 0,
+                                             cap, co, co);
     }
 }
 
@@ -572,17 +509,25 @@ hipError_t sched_topo_level(const SchedDev& d, const int* front, int nfront, int
     return hipGetLastError();
 }
 
-hipError_t sched_commit_places(const SchedDev& d, const CommitDev& c, const int* rank, const unsigned long long* newpu,
-                               const int* other, const int* other_pos, const unsigned long long* ids, int k,
-                               hipStream_t st) {
-    // the aggregators as ks_update_unsched_costs finds them, then the places (fl bit 2)
+// fl bit 1 on the unscheduled aggregators: the k node ids, or (ids == nullptr) every type-0
+// node with an arc into the sink.
+static void mark_aggregators(const SchedDev& d, const unsigned long long* ids, int k, unsigned char* fl,
+                             hipStream_t st) {
     if (ids) {
-        if (k) hipLaunchKernelGGL(k_mark_ids, dim3(grid(k)), dim3(SB), 0, st, k, ids, c.fl);
+        if (k) hipLaunchKernelGGL(k_mark_ids, dim3(grid(k)), dim3(SB), 0, st, k, ids, fl);
     } else if (d.hi) {
         hipLaunchKernelGGL(k_mark_unsched_auto, dim3(grid(d.hi)), dim3(SB), 0, st, d.hi, d.a_alive, d.a_src, d.a_dst,
-                           d.n_type, c.fl);
+                           d.n_type, fl);
     }
-    if (c.np) hipLaunchKernelGGL(k_commit_places, dim3(grid(d.ncap)), dim3(SB), 0, st, d, c, rank, newpu, other, other_pos);
+}
+
+hipError_t sched_commit_items(const SchedDev& d, const CommitDev& c, const int* rank, const unsigned long long* newpu,
+                              const int* pre, const int* pre_pos, const int* other, const int* other_pos, int npre,
+                              const unsigned long long* ids, int k, hipStream_t st) {
+    mark_aggregators(d, ids, k, c.fl, st);
+    if (c.np)
+        hipLaunchKernelGGL(k_commit_items, dim3(grid(d.ncap)), dim3(SB), 0, st, d, c, rank, newpu, pre, pre_pos, other,
+                           other_pos, npre);
     return hipGetLastError();
 }
 
@@ -592,15 +537,14 @@ hipError_t sched_commit_count(const SchedDev& d, const CommitDev& c, hipStream_t
     return hipGetLastError();
 }
 
-hipError_t sched_commit_pu_counts(const SchedDev& d, const CommitDev& c, hipStream_t st) {
+hipError_t sched_commit_pu(const SchedDev& d, const CommitDev& c, hipStream_t st) {
     if (d.hi) hipLaunchKernelGGL(k_commit_pu_arcs, dim3(grid(d.hi)), dim3(SB), 0, st, d, c);
-    if (c.np) hipLaunchKernelGGL(k_commit_pu_places, dim3(grid(c.np)), dim3(SB), 0, st, c);
+    if (c.np && !c.preempt) hipLaunchKernelGGL(k_commit_pu_places, dim3(grid(c.np)), dim3(SB), 0, st, c);
     return hipGetLastError();
 }
 
-hipError_t sched_commit_arc_flags(const SchedDev& d, const CommitDev& c, int resource_caps, int preempt,
-                                  hipStream_t st) {
-    hipLaunchKernelGGL(k_commit_arc_flags, dim3(grid(d.hi + 1)), dim3(SB), 0, st, d, c, resource_caps, preempt);
+hipError_t sched_commit_arc_flags(const SchedDev& d, const CommitDev& c, hipStream_t st) {
+    hipLaunchKernelGGL(k_commit_arc_flags, dim3(grid(d.hi + 1)), dim3(SB), 0, st, d, c);
     return hipGetLastError();
 }
 
@@ -609,61 +553,20 @@ hipError_t sched_commit_totals(const SchedDev& d, const CommitDev& c, hipStream_
     return hipGetLastError();
 }
 
-hipError_t sched_commit_emit(const SchedDev& d, const CommitDev& c, long long ccost, int resource_caps, ks_delta* recs,
-                             hipStream_t st) {
+hipError_t sched_commit_emit(const SchedDev& d, const CommitDev& c, ks_delta* recs, hipStream_t st) {
     if (c.np) {
-        hipLaunchKernelGGL(k_commit_emit_pins, dim3(grid(64LL * c.ni_max)), dim3(SB), 0, st, d, c, ccost, recs);
-        hipLaunchKernelGGL(k_commit_emit_adds, dim3(grid(c.np)), dim3(SB), 0, st, d, c, ccost, recs);
+        hipLaunchKernelGGL(k_commit_emit_items, dim3(grid(64LL * c.ni_max)), dim3(SB), 0, st, d, c, recs);
+        hipLaunchKernelGGL(k_commit_emit_adds, dim3(grid(c.np)), dim3(SB), 0, st, d, c, recs);
     }
-    if (d.hi) hipLaunchKernelGGL(k_commit_emit_arcs, dim3(grid(d.hi)), dim3(SB), 0, st, d, c, resource_caps, 0, recs);
-    return hipGetLastError();
-}
-
-hipError_t sched_preempt_items(const SchedDev& d, const CommitDev& c, const int* rank, const unsigned long long* newpu,
-                               const int* pre, const int* pre_pos, const int* other, const int* other_pos, int npre,
-                               const unsigned long long* ids, int k, hipStream_t st) {
-    if (ids) {
-        if (k) hipLaunchKernelGGL(k_mark_ids, dim3(grid(k)), dim3(SB), 0, st, k, ids, c.fl);
-    } else if (d.hi) {
-        hipLaunchKernelGGL(k_mark_unsched_auto, dim3(grid(d.hi)), dim3(SB), 0, st, d.hi, d.a_alive, d.a_src, d.a_dst,
-                           d.n_type, c.fl);
-    }
-    if (c.np)
-        hipLaunchKernelGGL(k_preempt_items, dim3(grid(d.ncap)), dim3(SB), 0, st, d, c, rank, newpu, pre, pre_pos, other,
-                           other_pos, npre);
-    return hipGetLastError();
-}
-
-hipError_t sched_preempt_count(const SchedDev& d, const CommitDev& c, long long pcost, hipStream_t st) {
-    if (c.np) hipLaunchKernelGGL(k_preempt_count, dim3(grid(64LL * c.ni_max)), dim3(SB), 0, st, d, c, pcost);
-    hipLaunchKernelGGL(k_preempt_noarc, dim3(grid(c.np + 1)), dim3(SB), 0, st, c);
-    return hipGetLastError();
-}
-
-hipError_t sched_preempt_pu_slots(const SchedDev& d, const CommitDev& c, hipStream_t st) {
-    if (d.hi) hipLaunchKernelGGL(k_preempt_pu_slots, dim3(grid(d.hi)), dim3(SB), 0, st, d, c);
-    return hipGetLastError();
-}
-
-hipError_t sched_preempt_emit(const SchedDev& d, const CommitDev& c, long long ccost, long long pcost,
-                              int resource_caps, ks_delta* recs, hipStream_t st) {
-    if (c.np) {
-        hipLaunchKernelGGL(k_preempt_emit_items, dim3(grid(64LL * c.ni_max)), dim3(SB), 0, st, d, c, ccost, pcost, recs);
-        hipLaunchKernelGGL(k_preempt_emit_adds, dim3(grid(c.np)), dim3(SB), 0, st, d, c, ccost, recs);
-    }
-    if (d.hi && resource_caps)
-        hipLaunchKernelGGL(k_commit_emit_arcs, dim3(grid(d.hi)), dim3(SB), 0, st, d, c, resource_caps, 1, recs);
+    // (preemptive without resource capacities: no arc slot is flagged)
+    if (d.hi && (!c.preempt || c.resource_caps))
+        hipLaunchKernelGGL(k_commit_emit_arcs, dim3(grid(d.hi)), dim3(SB), 0, st, d, c, recs);
     return hipGetLastError();
 }
 
 hipError_t sched_unsched_costs(const SchedDev& d, const unsigned long long* ids, int k, unsigned char* fl, int mode,
                                long long ucost, long long ccost, int* changed, hipStream_t st) {
-    if (ids) {
-        if (k) hipLaunchKernelGGL(k_mark_ids, dim3(grid(k)), dim3(SB), 0, st, k, ids, fl);
-    } else if (d.hi) {
-        hipLaunchKernelGGL(k_mark_unsched_auto, dim3(grid(d.hi)), dim3(SB), 0, st, d.hi, d.a_alive, d.a_src, d.a_dst,
-                           d.n_type, fl);
-    }
+    mark_aggregators(d, ids, k, fl, st);
     if (d.hi) {
         hipLaunchKernelGGL(k_mark_tasks, dim3(grid(d.hi)), dim3(SB), 0, st, d, d.hi, fl);
         hipLaunchKernelGGL(k_unsched_costs, dim3(grid(d.hi)), dim3(SB), 0, st, d, d.hi, (const unsigned char*)fl, mode,

@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from commit_ref import arc_table
+from commit_ref import arc_table, commit_reference
 from graphs import graph_from_lists, same_graph
 from ksched_amd import churn, native
 from oracle import ko, sched_ref
@@ -147,6 +147,60 @@ def test_long_segments(cell_nodes):
         # of equal cost with a free PU remain, so an optimum may migrate a task again)
         assert triples(ctx.scheduling_deltas(commit=False)) == sched_ref.scheduling_deltas(
             bindings, ctx.task_mapping(), [T0, T0 + 1, T0 + 2])
+
+
+@BOTH
+def test_both_modes_through_one_context(cell_nodes):
+    """The two commits share one kernel family and one scratch: a pinned commit after a
+    preemptive one with a PREEMPT and two MIGRATEs (item kinds, PUs left, running arcs
+    found) must see none of that call's items, and a preemptive commit after the pinned
+    one none of its."""
+    g = long_segment_graph()
+    U, M0, P0, T0 = 2, 3, 133, 263
+    with native.Context(0, cell_nodes=cell_nodes) as ctx:
+        # the preemptive test_long_segments sequence
+        ctx.load_graph(g)
+        ctx.solve()
+        mp = ctx.task_mapping()
+        assert len(mp) == 3
+        deltas, st, bindings = check_commit(ctx, g, {}, 2, 500)
+        assert triples(deltas) == [(PLACE, t, p) for t, p in sorted(mp.items())]
+        assert (st["running_added"], st["running_converted"], st["unsched_cost_updates"]) == (3, 0, 0)
+        recs = []
+        for t, p in sorted(mp.items()):
+            recs.append((3, 1, t, p, 0, 1, 1000))
+            if t < T0 + 2:
+                recs.append((3, 0, t, M0 + (p - P0), 0, 1, 1000))
+        recs.append((3, 0, T0 + 2, U, 0, 1, 0))
+        ctx.apply_deltas(arc_records(recs))
+        r = ctx.solve()
+        st0, cost, flow, _ = ko.cost_scaling(dev_graph(ctx, g))
+        assert st0 == 0 and (r.cost, r.flow) == (cost, flow)
+        deltas, st, bindings = check_commit(ctx, g, bindings, 2, 500)
+        assert [(k, t) for k, t, _ in triples(deltas)] == [(PREEMPT, T0 + 2), (MIGRATE, T0), (MIGRATE, T0 + 1)]
+        assert (st["running_removed"], st["running_added"]) == (3, 2)
+        # the pinned test_long_segments on the same context
+        ctx.load_graph(g)
+        ctx.solve()
+        mp = ctx.task_mapping()
+        assert len(mp) == 3
+        deltas, st = ctx.commit_schedule(continuation=2)
+        assert (st["placed"], st["arcs_removed"], st["running_added"]) == (3, 3 * 131, 3)
+        t = dev_table(ctx)
+        for task, pu in mp.items():
+            assert [(k, v) for k, v in t.items() if k[0] == task] == [((task, pu), (1, 1, 2, 1))]
+        assert (2, 1) not in t                      # U → sink reached 0
+        assert live(t) == commit_reference(g, mp, 2, True)
+        r = ctx.solve()
+        assert (r.cost, r.flow) == (6, 3)
+        # and the preemptive mode after the pinned one: three PLACEs, nothing to leave
+        ctx.load_graph(g)
+        ctx.solve()
+        mp = ctx.task_mapping()
+        deltas, st, _ = check_commit(ctx, g, {}, 2, 500)
+        assert triples(deltas) == [(PLACE, t, p) for t, p in sorted(mp.items())]
+        assert (st["placed"], st["preempted"], st["migrated"]) == (3, 0, 0)
+        assert (st["running_added"], st["running_removed"]) == (3, 0)
 
 
 def test_a_migrate_is_one_scheduling_delta():
