@@ -333,7 +333,17 @@ ks_ctx*     ks_create(int device, const ks_opts* opts);
 void        ks_destroy(ks_ctx* ctx);
 const char* ks_last_error(ks_ctx* ctx);
 
-/* Replace the whole graph (first Solve: solver.go:63-83). */
+/* Replace the whole graph (first Solve: solver.go:63-83).
+ *
+ * Value ranges (checked here and, record by record, in ks_apply_deltas; a value
+ * outside them is KS_E_RANGE and leaves the context, host and device, as it was):
+ *   cost      |cost| <= 2^40, either sign; negative-cost cycles are legal input
+ *   capacity  low <= cap <= 2^53
+ *   node ids  1 .. 2^30 - 1
+ *   excess    any int64; it is not range-checked, but a supply that the capacities
+ *             cannot carry makes the solve KS_E_INFEASIBLE, and the sum of the
+ *             supplies (the flow value) must fit int64
+ * Two more limits depend on the whole graph and are checked by ks_solve (below). */
 int ks_load_graph(ks_ctx* ctx, const ks_node* nodes, size_t n,
                   const ks_arc* arcs, size_t m);
 
@@ -351,7 +361,23 @@ int ks_apply_deltas(ks_ctx* ctx, const ks_delta* deltas, size_t k);
  * raised in ks_apply_deltas are not reported. */
 int ks_coalesce_deltas(const ks_delta* in, size_t k, ks_delta* out, size_t cap, size_t* count);
 
-/* Solve min-cost flow on the current graph. result may be NULL. */
+/* Solve min-cost flow on the current graph. result may be NULL.
+ *
+ * Solve-time ranges (KS_E_RANGE from ks_solve; the graph stays loaded, and deltas
+ * that bring it into range make the next solve succeed):
+ *   scaled prices  costs are multiplied by mult = N + 1, N the node-slot count (the
+ *                  highest node id in use, ks_result.n_nodes, plus max(64, N/16) spare
+ *                  slots once deltas have been applied), and prices stay within
+ *                  int64 only while  max|cost| * mult^2 * 8 <= 4e18:
+ *                  max|cost| ~ 5e17 / (highest id)^2. Sparse ids count in full: ids up
+ *                  to 4,000 allow max|cost| = 31,234,380,857, ids up to 10^6 about 5e5.
+ *   total cost     total_cost is exact whenever the sum over all arcs of |flow * cost|
+ *                  is below 2^63. Otherwise ks_solve returns KS_E_RANGE and
+ *                  ks_last_error names the sum; it never returns KS_OK with a wrapped
+ *                  number. (The same bound covers every partial sum, so the per-graph
+ *                  costs of ks_batch_gather are exact whenever the union's solve is.)
+ * Inside those limits which solver ran (the cell solver, the engine on 16- or 32-byte
+ * positions: ks_result.solver, .compact) depends on the values, the answer does not. */
 int ks_solve(ks_ctx* ctx, ks_result* result);
 
 /* Solve k independent contexts concurrently (config 5: cluster cells /

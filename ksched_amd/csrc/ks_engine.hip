@@ -2640,6 +2640,9 @@ __global__ void k_drain_all(DG g) {
     if (h < g.nheavy) drain_inbox(g, h);
 }
 
+constexpr int VERIFY_GRID = 2048;        // most blocks of k_verify_arcs: part holds 2 × 2 × VERIFY_GRID sums (build)
+constexpr int VERIFY_COST_RANGE = 8;     // verify_bad: a product flow·cost, or a thread's Σ |flow·cost|, left 64 bits
+
 // Per live arc slot: flow (lower bound included) into flows[s], capacity
 // feasibility, the cost sum, and the flow value measured from the resident
 // flow: net inflow into the demand nodes (supply < 0).
@@ -2668,7 +2671,11 @@ __global__ void k_verify_arcs(DG g, int hi, const unsigned char* __restrict__ al
         }
     };
     long long csum = 0, fsum = 0;
-    int bad = 0;
+    // Σ |flow·cost| beside the signed sum: below 2^63 no partial sum of the products, in
+    // any order, leaves int64, so the total is exact; at or above it the solve reports
+    // KS_E_RANGE (include/ksmcmf.h) instead of a wrapped number
+    unsigned long long asum = 0;
+    int bad = 0, ovf = 0;
     for (long long i = blockIdx.x * (long long)BLK + threadIdx.x; i < hi; i += (long long)gridDim.x * BLK) {
         if (!alive[i]) {
             flows[i] = 0;
@@ -2691,19 +2698,29 @@ __global__ void k_verify_arcs(DG g, int hi, const unsigned char* __restrict__ al
             add_bal(qr.head, src[i], -fl);   // (the reverse position's head is the arc's tail)
             add_bal(qf.head, dst[i], fl);
         }
-        csum += fl * cost[i];
+        long long prod;
+        ovf |= __builtin_mul_overflow(fl, cost[i], &prod);
+        const unsigned long long mag = prod < 0 ? 0ULL - (unsigned long long)prod : (unsigned long long)prod;
+        ovf |= __builtin_add_overflow(asum, mag, &asum);
+        csum = (long long)((unsigned long long)csum + (unsigned long long)prod);
         if (supply[dst[i]] < 0) fsum += fl;
         if (supply[src[i]] < 0) fsum -= fl;
     }
     csum = block_sum(csum, sh);
     fsum = block_sum(fsum, sh);
+    // the magnitudes in 32-bit halves (a block's sum of either half stays below 2^40)
+    const long long ahi = block_sum((long long)(asum >> 32), sh);
+    const long long alo = block_sum((long long)(asum & 0xffffffffULL), sh);
     __syncthreads();
     if (threadIdx.x < HUB_LDS && hbal[threadIdx.x]) atom_add(&bal[hslot[threadIdx.x]], hbal[threadIdx.x]);
     if (threadIdx.x == 0) {
         part[blockIdx.x] = csum;
         partf[blockIdx.x] = fsum;
+        part[gridDim.x + blockIdx.x] = ahi;
+        partf[gridDim.x + blockIdx.x] = alo;
     }
     if (__any(bad) && lane_id() == 0) atomicOr(&g.ctl->verify_bad, 1);
+    if (__any(ovf) && lane_id() == 0) atomicOr(&g.ctl->verify_bad, VERIFY_COST_RANGE);
 }
 
 // Every live node's net inflow plus its supply is zero (the sink's supply is the
@@ -3012,6 +3029,9 @@ struct SolveRun {
     unsigned long long cell_ctr[5] = {0, 0, 0, 0, 0};   // scans, visits, pushes, relabels, gu scans
     unsigned long long cell_rounds = 0, cticks_max = 0, cticks_sum = 0;
     long long tot_cost = 0, tot_flow = 0;
+    bool launch_refused = false;   // RETRY_RANGE because the device refused the cell launch, not for a value
+    bool cost_range = false, cost_wide = false;   // verify(): Σ |flow·cost| ≥ 2^63 / beyond what the kernel could add
+    double cost_mag = 0;
     unsigned long long gu_prev = 0;   // cycle log: Bellman-Ford relaxations counted so far
 
     // ---- running state
@@ -3238,7 +3258,7 @@ struct SolveRun {
         wgrid = s.sweep_grid();      // sweeps
         ngrid = grid_for(nn, 2048);
         fsgrid = s.nhitems * HSPLIT + FS_LIST_BLOCKS;   // forward tail rounds
-        vgrid = grid_for(hi, 2048);  // verification
+        vgrid = grid_for(hi, VERIFY_GRID);  // verification
         // forward tail updates once ≤ fwd_k nodes hold excess (ks_opts.fwd_nodes; the
         // search key packs an arc position into FS_PB bits)
         use_fwd = o.fwd_nodes >= 0 && s.m2cap < FS_NONE;
@@ -3945,7 +3965,10 @@ struct SolveRun {
             const hipError_t le = cell_launch(a, s.cl_bad.p, s.lds_limit, st, &refused);
             if (le != hipSuccess) {
                 (void)hipGetLastError();
-                if (refused) return (int)CS_RANGE;
+                if (refused) {
+                    launch_refused = true;
+                    return (int)CS_RANGE;
+                }
                 err = std::string("cell solver launch: ") + hipGetErrorString(le);
                 return KS_E_DEVICE;
             }
@@ -4035,6 +4058,16 @@ struct SolveRun {
         int rc = verify(&bad);
         if (rc) return rc;
         if ((rc = recover(&bad))) return rc;
+        if (status == KS_OK && cost_range) {   // (whatever ks_opts.verify says: the number would be wrong)
+            char what[96];
+            if (cost_wide)
+                std::snprintf(what, sizeof(what), "a single arc's flow * cost, or one thread's share, is beyond 2^64");
+            else
+                std::snprintf(what, sizeof(what), "the sum of |flow * cost| is %.6g", cost_mag);
+            status = KS_E_RANGE;
+            err = std::string("total cost outside int64: ") + what + ", the limit is 2^63 (9.22337e+18)";
+            tot_cost = 0;
+        }
         if (status == KS_OK && bad && o.verify) {
             status = KS_E_VERIFY;
             err = std::string("on-device verification failed (") + ((bad & 1) ? "capacity " : "") +
@@ -4074,17 +4107,28 @@ struct SolveRun {
                                (const long long*)s.vbal.p);
         if (m2) hipLaunchKernelGGL(k_verify_opt, dim3(grid_for(m2, 2048)), dim3(BLK), 0, st, g, (long long)m2);
         hipLaunchKernelGGL(k_verify_nodes, dim3(ngrid), dim3(BLK), 0, st, g);
-        std::vector<long long> parts(hi ? vgrid : 0), partf(hi ? vgrid : 0);
+        // per block: the signed cost sums, then the high halves of Σ |flow·cost|, in part; the
+        // flow values, then the low halves, in part + 4096
+        std::vector<long long> parts(hi ? 2 * vgrid : 0), partf(hi ? 2 * vgrid : 0);
         if (hi) {
-            KS_CHECK(hipMemcpyAsync(parts.data(), s.part.p, vgrid * sizeof(long long), hipMemcpyDeviceToHost, st));
-            KS_CHECK(hipMemcpyAsync(partf.data(), s.part.p + 4096, vgrid * sizeof(long long), hipMemcpyDeviceToHost,
+            KS_CHECK(hipMemcpyAsync(parts.data(), s.part.p, parts.size() * sizeof(long long), hipMemcpyDeviceToHost,
                                     st));
+            KS_CHECK(hipMemcpyAsync(partf.data(), s.part.p + 4096, partf.size() * sizeof(long long),
+                                    hipMemcpyDeviceToHost, st));
         }
         KS_CHECK(read_ctl());
         tot_cost = tot_flow = 0;
-        for (long long x : parts) tot_cost += x;
-        for (long long x : partf) tot_flow += x;
-        *bad = s.h_ctl->verify_bad;
+        unsigned __int128 mag = 0;
+        for (int b = 0; hi && b < vgrid; ++b) {
+            tot_cost = (long long)((unsigned long long)tot_cost + (unsigned long long)parts[b]);
+            tot_flow += partf[b];
+            mag += ((unsigned __int128)(unsigned long long)parts[vgrid + b] << 32) +
+                   (unsigned long long)partf[vgrid + b];
+        }
+        *bad = s.h_ctl->verify_bad & ~VERIFY_COST_RANGE;
+        cost_wide = (s.h_ctl->verify_bad & VERIFY_COST_RANGE) != 0;
+        cost_range = cost_wide || mag >= ((unsigned __int128)1 << 63);
+        cost_mag = (double)mag;
         return KS_OK;
     }
     // A failed optimality certificate on a feasible flow is repaired, not fatal:
@@ -4200,6 +4244,7 @@ int Engine::solve(ks_result& res, bool warm, std::string& err) {
     const int rc = run.run();
     if (run.retry == SolveRun::RETRY_RANGE) {   // a value the compact record cannot hold: the multi-kernel engine instead
         s.cell_refused = true;
+        s.cell_refused_values = !run.launch_refused;   // (an arc delta may bring the values back into range)
         s.cell_layout = false;
         s.csr_valid = false;
         // the warm start's price shift is already in the carried prices: the retry

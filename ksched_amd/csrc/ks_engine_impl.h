@@ -336,7 +336,8 @@ struct EngineImpl {
     DBuf<CellOut> cl_out;
     DBuf<CellPos> cl_pos;               // compact positions (k_cell_pack / k_cell_unpack)
     DBuf<int> cl_bad;
-    bool cell_refused = false;          // the graph's values do not fit the compact record: engine until reload
+    bool cell_refused = false;          // the cell solver handed this graph to the engine: engine until a reload,
+    bool cell_refused_values = false;   //   or, when a value did not fit the compact record, until arcs change
     size_t lds_limit = 0;               // the device's opt-in LDS per workgroup (sizes the cells)
     bool fb_active = false;             // a per-cell fallback solve is running (engine order, failing cells cold)
     std::vector<int> fb_cells;          // the cells it re-solves

@@ -266,6 +266,9 @@ static int run_apply(EngineImpl& s, const NodeEdit* edits, size_t ne, const ks_d
     rc = applied(s, err);
     if (rc) return rc;
     if (k || ne) s.solved = false;
+    // costs or capacities changed: values that sent the cell solver's graph to the engine may
+    // fit its record again (the next solve tries, and falls back once more if they do not)
+    if (narc && s.cell_refused_values) s.cell_refused = s.cell_refused_values = false;
     return KS_OK;
 }
 
@@ -307,7 +310,7 @@ int Engine::load(int64_t nslots, const int64_t* supply, const uint8_t* type, con
     s.rebuilds = 0;
     s.solved = false;
     s.has_prev = false;
-    s.cell_refused = false;
+    s.cell_refused = s.cell_refused_values = false;
     rc = ensure_arcs(s, (int64_t)m, err);
     if (rc) return rc;
     if (s.hcap) {   // clear the index (keeps its size)

@@ -362,3 +362,129 @@ def random_stream(rng, nodes, arcs, nrec, hubs=(), adversarial=False):
             emit(kind=native.KS_SET_EXCESS, id=a, excess=nodes[a][0] + k)
             emit(kind=native.KS_SET_EXCESS, id=b, excess=nodes[b][0] - k)
     return np.array(recs, native.DELTA_DT)
+
+
+# ------------------------------------------------------------------ ranges ---
+# The limits the library declares or guards (tests/test_exact_ref_cpu.py reads the
+# same values out of the headers, so a change there cannot pass unnoticed):
+CELL_MAX_CAP = (1 << 24) - 1      # ks_cell.h: capacity the cell solver's record holds
+CELL_MAX_COST = (1 << 31) - 2     # ks_cell.h: |cost · mult| the cell solver's record holds
+CPOS_MAX = 0x7FFFFFFE             # ks_pos.h: |cost · mult| or capacity a 16-byte position holds
+ABI_MAX_COST = 1 << 40            # ks_host.cpp check_arc: |cost|
+ABI_MAX_CAP = 1 << 53             # ks_host.cpp check_arc: capacity
+LEN_CAP = 1 << 40                 # ks_engine_impl.h: arc lengths rc / ε are clamped here
+FS_DMAX = 1 << 36                 # ks_engine_impl.h: the forward search's distance limit
+SOLVE_RANGE = 4.0e18              # ks_engine.hip SolveRun::prepare: maxc · mult · 8 · mult above this is refused
+
+
+def solve_range_maxc(mult: int) -> int:
+    """The largest max |cost| that SolveRun::prepare accepts for a cost multiplier
+    mult, by the same double arithmetic: maxc · mult · 8 · mult ≤ 4e18."""
+    ok = lambda c: float(c) * float(mult) * 8.0 * float(mult) <= SOLVE_RANGE
+    c = int(SOLVE_RANGE) // (8 * mult * mult)
+    while not ok(c):
+        c -= 1
+    while ok(c + 1):
+        c += 1
+    return c
+
+
+def scaled(g, cost_mul: int = 1, cap_mul: int = 1):
+    """g with every cost multiplied by cost_mul, and every capacity, lower bound
+    and supply by cap_mul. The exact optimum scales by cost_mul · cap_mul, the
+    flow value by cap_mul."""
+    mul = lambda a, k: np.asarray([int(x) * k for x in a.tolist()], np.int64)
+    return gen.Graph(g.ntype, mul(g.supply, cap_mul), g.src, g.dst, mul(g.low, cap_mul), mul(g.cap, cap_mul),
+                     mul(g.cost, cost_mul), g.atype)
+
+
+def signed_candidates(seed: int, count: int, max_n: int = 60, cost_hi: int = 100):
+    """random_graphs with costs in [−cost_hi, cost_hi): negative arcs and negative
+    cycles occur. Every second graph has its lower bounds removed."""
+    for trial, g in random_graphs(seed, count, max_n, -cost_hi, cost_hi):
+        if trial % 2:
+            g = gen.Graph(g.ntype, g.supply, g.src, g.dst, np.zeros_like(g.low), g.cap, g.cost)
+        yield trial, g
+
+
+_FAMILIES: dict = {}
+FAMILY_FEASIBLE, FAMILY_INFEASIBLE = 24, 6
+
+
+def select_family(candidates, feasible: int = FAMILY_FEASIBLE, infeasible: int = FAMILY_INFEASIBLE):
+    """The first `feasible` feasible and the first `infeasible` infeasible candidates,
+    as the exact reference alone judges them, in candidate order:
+    [(trial, graph, (feasible, cost, flows))]. About half of random_graphs' output is
+    infeasible (its lower bounds), so a test over the raw stream could pass while
+    exercising mostly the infeasible path."""
+    import exact_ref
+    out, nf, ni = [], 0, 0
+    for trial, g in candidates:
+        ref = exact_ref.mcf(g)
+        if ref[0] and nf < feasible:
+            nf += 1
+            out.append((trial, g, ref))
+        elif not ref[0] and ni < infeasible:
+            ni += 1
+            out.append((trial, g, ref))
+        if nf == feasible and ni == infeasible:
+            return out
+    raise AssertionError(f"only {nf} feasible and {ni} infeasible candidates")
+
+
+def signed_graphs(seed: int = 4242, max_n: int = 60, cost_hi: int = 100):
+    """The signed family of the GPU range tests: 24 feasible and 6 infeasible members
+    of signed_candidates(seed), each with its exact optimum (computed once)."""
+    key = ("signed", seed, max_n, cost_hi)
+    if key not in _FAMILIES:
+        _FAMILIES[key] = select_family(signed_candidates(seed, 400, max_n, cost_hi))
+    return _FAMILIES[key]
+
+
+def negative_cycle():
+    """A 3-cycle of cost −5 and capacity 2, no supplies: the optimum sends 2 units
+    round it (cost −10, flow value 0)."""
+    return graph_from_lists([(1, 0, 0), (2, 0, 0), (3, 0, 0)],
+                            [(1, 2, 0, 2, 3), (2, 3, 0, 2, -10), (3, 1, 0, 2, 2)])
+
+
+def star(arms: int = 200, cap: int = CELL_MAX_CAP):
+    """A centre with `arms` out-arcs of capacity cap and equal cost, so all of them
+    are admissible at once, and the supply to fill every one: the admissible
+    capacities of one node sum to arms · cap (200 · (2^24 − 1) > 2^31). Each arm
+    reaches the sink by an arc of cost 1: the optimum is arms · cap."""
+    centre, sink = 1, arms + 2
+    nodes = [(centre, arms * cap, 0), (sink, -arms * cap, 0)] + [(2 + i, 0, 0) for i in range(arms)]
+    arcs = [(centre, 2 + i, 0, cap, 0) for i in range(arms)] + [(2 + i, sink, 0, cap, 1) for i in range(arms)]
+    return graph_from_lists(nodes, arcs)
+
+
+SPARSE_TOP = 4000
+
+
+def sparse_id_network(maxc: int = 16):
+    """12 nodes whose highest id is 4,000: the cost multiplier (the node-slot count
+    + 1) is large while the graph is tiny. Costs are k · maxc / 16, the largest
+    exactly maxc on arcs the optimum must use (each source's only way to the far
+    sink)."""
+    ids = list(range(1, 12)) + [SPARSE_TOP]
+    sup = {1: 4, 2: 3, 3: 5, 10: -6, SPARSE_TOP: -6}
+    nodes = [(i, sup.get(i, 0), 0) for i in ids]
+    c = lambda k: maxc * k // 16
+    arcs = [(1, 4, 0, 3, c(2)), (1, 5, 0, 2, c(5)), (2, 4, 0, 2, c(1)), (2, 6, 0, 3, c(7)), (3, 5, 0, 4, c(3)),
+            (3, 6, 0, 2, c(2)), (3, 7, 0, 2, c(9)), (4, 8, 0, 4, c(4)), (5, 8, 0, 3, c(1)), (5, 9, 0, 3, c(6)),
+            (6, 9, 0, 4, c(2)), (7, 9, 0, 2, c(0)), (8, 10, 0, 5, c(3)), (9, 10, 0, 3, c(8)), (8, 11, 0, 3, c(2)),
+            (9, 11, 0, 5, c(1)), (11, SPARSE_TOP, 0, 6, maxc), (10, 11, 0, 2, c(12)), (6, 5, 0, 2, c(1)),
+            (9, 8, 0, 1, c(4)), (4, 1, 0, 1, c(3))]
+    return graph_from_lists(nodes, arcs)
+
+
+def long_chain(links: int = 7, link_cost: int = 1 << 37, cap: int = 3, supply: int = 5):
+    """A chain of `links` arcs of cost link_cost beside one direct arc of cost
+    ABI_MAX_COST. With links + 1 nodes the multiplier is links + 2, so in the ε = 1
+    phase every arc's length link_cost · mult / ε is beyond LEN_CAP and FS_DMAX.
+    The chain is cheaper (7 · 2^37 < 2^40) and takes `cap` units, the direct arc the rest."""
+    n = links + 1
+    nodes = [(1, supply, 0), (n, -supply, 0)] + [(i, 0, 0) for i in range(2, n)]
+    arcs = [(i, i + 1, 0, cap, link_cost) for i in range(1, n)] + [(1, n, 0, supply, ABI_MAX_COST)]
+    return graph_from_lists(nodes, arcs)
