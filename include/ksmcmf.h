@@ -79,7 +79,16 @@ extern "C" {
                                   cell_fallbacks and cycles_cancelled (two reserved words)
                                   and compact (the former _pad3); 5: ks_result.fb_resets
                                   (the last reserved word), ks_result.cycles_rejected and
-                                  gu_leaf_scans; ks_result grew to 352 B (2 reserved words).
+                                  gu_leaf_scans; ks_result grew to 352 B (2 reserved words);
+                                  Batch rounds (still 5: entry points were only added and
+                                  no struct changed size or moved a field, so a caller
+                                  built against ABI 5 keeps working) — ks_batch_reserve,
+                                  ks_batch_apply_deltas,
+                                  ks_batch_get_graph, ks_batch_set_bindings, both
+                                  ks_batch_commit_* calls, the layout helpers
+                                  ks_batch_node_offsets / ks_batch_translate_deltas, and
+                                  ks_result.cells_run (half of a reserved word: the struct
+                                  keeps its size).
                                   ks_opts (96 B) CHANGED SIZE in ABI 2 and ks_result in
                                   ABI 2, 3 and 5: a caller must check
                                   ks_abi_version() == KSMCMF_ABI_VERSION before ks_create. */
@@ -307,7 +316,13 @@ typedef struct ks_result {
                                   or PU whose distance just dropped, in the same round
                                   (two hops per round): those second-hop in-arc positions
                                   examined (gu_arc_scans counts the first hop only)      */
-    uint64_t reserved3[2];
+    int32_t  cells_run;        /* Batch rounds. Cells the cell solver launched in this solve: with
+                                  ks_opts.warm_start >= 1 a cell of a ks_batch union that no
+                                  record touched since its last solve is skipped (its flow,
+                                  prices and rows stay as they were); cells stays the
+                                  partition size                                         */
+    int32_t  reserved4;
+    uint64_t reserved3[1];
 } ks_result;
 
 /* Counters of the device-resident graph store (ks_get_store_stats). */
@@ -618,6 +633,68 @@ int         ks_batch_owner(size_t g, int world, int* rank, size_t* slot);
 size_t      ks_batch_block_len(size_t ngraphs, int world, size_t max_tasks);
 int         ks_batch_unpack(const int64_t* gathered, size_t ngraphs, int world, size_t max_tasks, uint64_t* pu,
                             int64_t* cost, int64_t* flow);
+
+/* ---- batch rounds: deltas, a re-solve of the changed cells, commits ------
+ * A batch goes through scheduling rounds as a single context does: the union stays
+ * resident, every graph keeps its own id range in it, and a warm re-solve
+ * (ks_opts.warm_start >= 1) launches only the cells some record touched since their
+ * last solve (ks_result.cells_run; DESIGN §3.5 "which cells run").
+ *
+ * Layout (host-only, no device: ks_batch_load and ks_batch_apply_deltas use exactly
+ * these). Graph i of a device's union owns the node ids (off[i], off[i+1]], where
+ * off[i+1] = off[i] + maxid[i] + spare: ks_batch_node_offsets writes the k + 1 offsets.
+ * ks_batch_translate_deltas moves a stream from graph-local ids into the range
+ * (lo, hi]: lo is added to id, src and dst of every record (each kind's unused id
+ * fields stay as they are; a record of an unknown kind is copied unchanged, for
+ * ks_apply_deltas to refuse). A used id that is 0 or greater than hi − lo: KS_E_RANGE
+ * and nothing is written. out == in works. */
+int ks_batch_node_offsets(const uint64_t* maxid, size_t k, size_t spare, int64_t* off /* k + 1 */);
+int ks_batch_translate_deltas(int64_t lo, int64_t hi, const ks_delta* in, size_t k, ks_delta* out);
+
+/* Node ids every graph may grow by after the load (new tasks beyond its highest id).
+ * Takes effect at the next ks_batch_load; 0 (the default) packs the graphs tightly, as
+ * before the batch had rounds. With spare_ids > 0 the load also builds the residual CSR with the
+ * slack of an incrementally edited graph, so the first delta stream lands in place. */
+int ks_batch_reserve(ks_batch* b, size_t spare_ids);
+
+/* Every rank passes all ngraphs streams (graph-local ids; deltas[g] == NULL or
+ * k[g] == 0: graph g untouched). Each local device translates the streams of the
+ * graphs it owns and applies them, in graph order, as ONE stream with the semantics of
+ * ks_apply_deltas (all or nothing per device). An id outside its graph's range — a new
+ * node beyond the reserved ids, an arc into another cell — is KS_E_RANGE: the error
+ * names the graph and the id, and that device is unchanged. With ks_opts.auto_sink a
+ * graph with exactly one sink then gets that sink's supply set to −Σ of its other
+ * nodes' supplies (a SET_EXCESS record at the end of the stream). No collective: a
+ * rank returns its own failure. */
+int ks_batch_apply_deltas(ks_batch* b, size_t ngraphs, const ks_delta* const* deltas, const size_t* k);
+
+/* Graph g as it stands, in graph-local ids (ks_get_graph of its part of the union).
+ * KS_E_INVALID on a rank that does not own g. Call with caps of 0 to size. */
+int ks_batch_get_graph(ks_batch* b, size_t g, ks_node* nodes, size_t ncap, size_t* n, ks_arc* arcs, size_t acap,
+                       size_t* m);
+
+/* ks_set_bindings for graph g, in graph-local ids (KS_E_INVALID when g is not local). */
+int ks_batch_set_bindings(ks_batch* b, size_t g, const uint64_t* task, const uint64_t* pu, size_t k);
+
+typedef struct ks_batch_delta {
+    int32_t  type;             /* KS_DELTA_*                                             */
+    int32_t  graph;            /* the graph the task belongs to                          */
+    uint64_t task;             /* graph-local ids, as in ks_sched_delta                  */
+    uint64_t pu;
+} ks_batch_delta;
+
+/* ks_commit_schedule / ks_commit_preemptive on every local device's union. The
+ * unscheduled aggregators are every type-0 node with an arc into a sink (the NULL rule
+ * of the single-graph calls). The deltas cover the calling process's graphs, grouped by
+ * graph in ascending order and within a graph in the order of ks_scheduling_deltas.
+ * out == NULL: *count only, nothing changes; cap < count: KS_E_INVALID, nothing changes.
+ * KS_COMMIT_RESOURCE_CAPS seeds the topology BFS with every live sink (one per graph).
+ * The records the commit generates mark their cells for the next solve, on the device.
+ * stats (may be NULL) are summed over the local devices. No collective. */
+int ks_batch_commit_schedule(ks_batch* b, int32_t flags, int64_t continuation_cost,
+                             ks_batch_delta* out, size_t cap, size_t* count, ks_commit_stats* stats);
+int ks_batch_commit_preemptive(ks_batch* b, int32_t flags, int64_t continuation_cost, int64_t preemption_cost,
+                               ks_batch_delta* out, size_t cap, size_t* count, ks_preempt_stats* stats);
 
 #ifdef __cplusplus
 }

@@ -136,6 +136,33 @@ __global__ void k_localize(int rows, int rowlen, const long long* __restrict__ o
         if (row[i] > 0) row[i] -= off[r];
 }
 
+// ---- a graph's delta stream inside its id range (host code: ks_batch_translate_deltas
+// and the error message of ks_batch_apply_deltas) ----
+inline bool kb_arc_kind(int32_t kind) { return kind == KS_ADD_ARC || kind == KS_UPDATE_ARC; }
+inline bool kb_node_kind(int32_t kind) { return kind == KS_ADD_NODE || kind == KS_REMOVE_NODE || kind == KS_SET_EXCESS; }
+// the id of record x that lies outside 1..span, 0 when none does (*any: whether one does)
+inline uint64_t kb_bad_id(const ks_delta& x, uint64_t span, bool* any) {
+    auto out = [&](uint64_t id) { return id == 0 || id > span; };
+    *any = true;
+    if (kb_arc_kind(x.kind)) {
+        if (out(x.src)) return x.src;
+        if (out(x.dst)) return x.dst;
+    } else if (kb_node_kind(x.kind) && out(x.id)) {
+        return x.id;
+    }
+    *any = false;
+    return 0;
+}
+// the first record with an id outside 1..span (k: none)
+inline size_t kb_first_bad(const ks_delta* in, size_t k, uint64_t span) {
+    for (size_t i = 0; i < k; ++i) {
+        bool any = false;
+        kb_bad_id(in[i], span, &any);
+        if (any) return i;
+    }
+    return k;
+}
+
 }  // namespace
 
 struct ks_batch {
@@ -160,6 +187,7 @@ struct ks_batch {
     std::string err;
     long long* root_buf = nullptr;      // rank 0: world × slots × rowlen
     size_t root_cap = 0;
+    size_t spare = 0;                   // ks_batch_reserve: ids each graph may grow by (read by the next load)
     int fault_pack = 0;                 // TESTS ONLY (ks_opts.fault_inject bit 2): global rank + 1 whose packing fails
     int fault_root = 0;                 // TESTS ONLY (ks_opts.fault_inject bit 3): rank 0's receive buffer allocation fails
 
@@ -205,6 +233,129 @@ ks_batch* make_batch(const Rccl* api, int world, const ks_opts* opts, const std:
     return b;
 }
 
+// The local device that owns graph g and g's index among its graphs (nullptr: another rank's).
+ks_batch::Local* owner_of(ks_batch* b, size_t g, size_t* idx) {
+    if (g >= b->ngraphs) return nullptr;
+    int r = 0;
+    size_t slot = 0;
+    ks_batch_owner(g, b->world, &r, &slot);
+    for (auto& l : b->loc)
+        if (l.grank == r && slot < l.graphs.size()) {
+            *idx = slot;
+            return &l;
+        }
+    return nullptr;
+}
+
+// The gather's task offsets from the host node table: row i of a graph stays "its i-th
+// live task in id order" after tasks arrive and complete.
+void recompute_toff(ks_batch::Local& l) {
+    const std::vector<NodeRec>& nodes = l.ctx->nodes;
+    l.toff.assign(1, 0);
+    for (size_t i = 0; i + 1 < l.off.size(); ++i) {
+        int64_t tasks = 0;
+        const uint64_t hi = std::min<uint64_t>((uint64_t)l.off[i + 1], nodes.size() ? nodes.size() - 1 : 0);
+        for (uint64_t id = (uint64_t)l.off[i] + 1; id <= hi; ++id)
+            tasks += nodes[id].alive && nodes[id].type == KS_NODE_TASK;
+        l.toff.push_back(l.toff.back() + tasks);
+    }
+}
+
+// Per-graph auto_sink (graph_manager.go:640, 808, per cell): graph i of l as it will
+// stand after its stream u[at..) (union ids) — when it then has exactly one sink whose
+// supply is not −Σ of its other nodes' supplies, the SET_EXCESS record that makes it so
+// is appended to u. A graph with no sink or several is left alone.
+void append_auto_sink(const ks_batch::Local& l, size_t i, std::vector<ks_delta>& u, size_t at) {
+    const std::vector<NodeRec>& nodes = l.ctx->nodes;
+    const uint64_t lo = (uint64_t)l.off[i], hi = (uint64_t)l.off[i + 1];
+    // the node records of the stream over the table (ids past the table are dead)
+    std::vector<NodeRec> now(hi - lo + 1);
+    for (uint64_t id = lo + 1; id <= hi; ++id)
+        if (id < nodes.size()) now[id - lo] = nodes[id];
+    for (size_t j = at; j < u.size(); ++j) {
+        const ks_delta& x = u[j];
+        if (!kb_node_kind(x.kind) || x.id <= lo || x.id > hi) continue;
+        NodeRec& r = now[x.id - lo];
+        if (x.kind == KS_ADD_NODE) r = NodeRec{x.excess, x.type, true, true};
+        else if (x.kind == KS_REMOVE_NODE) r = NodeRec{};
+        else if (r.alive) r.excess = x.excess;
+    }
+    int64_t sinks = 0, others = 0;
+    uint64_t sink = 0;
+    for (uint64_t id = lo + 1; id <= hi; ++id) {
+        const NodeRec& r = now[id - lo];
+        if (!r.alive) continue;
+        if (r.type == KS_NODE_SINK) {
+            ++sinks;
+            sink = id;
+        } else {
+            others += r.excess;
+        }
+    }
+    if (sinks != 1 || now[sink - lo].excess == -others) return;
+    ks_delta d;
+    std::memset(&d, 0, sizeof(d));
+    d.kind = KS_SET_EXCESS;
+    d.id = sink;
+    d.excess = -others;
+    u.push_back(d);
+}
+
+// A commit's deltas of one device (union ids, the order of ks_scheduling_deltas) as
+// ks_batch_delta records in graph-local ids.
+void localize_deltas(const ks_batch::Local& l, const std::vector<ks_sched_delta>& v, std::vector<ks_batch_delta>& out) {
+    for (const ks_sched_delta& x : v) {
+        // graph i owns the ids (off[i], off[i+1]]
+        size_t i = (size_t)(std::lower_bound(l.off.begin(), l.off.end(), (int64_t)x.task) - l.off.begin());
+        i = i ? i - 1 : 0;
+        if (i + 1 >= l.off.size()) i = l.off.size() >= 2 ? l.off.size() - 2 : 0;
+        const uint64_t base = (uint64_t)l.off[i];
+        out.push_back(ks_batch_delta{x.type, l.graphs.empty() ? 0 : l.graphs[i], x.task - base, x.pu ? x.pu - base : 0});
+    }
+}
+
+// Both batch commits: count over the local devices first (a cap that is too small
+// changes nothing), then commit device by device, and the deltas grouped by graph.
+template <class Stats, class Call>
+int batch_commit(ks_batch* b, ks_batch_delta* out, size_t cap, size_t* count, Stats* stats, Call call) {
+    if (!b || !count) return KS_E_INVALID;
+    std::vector<size_t> n(b->loc.size(), 0);
+    size_t total = 0;
+    for (size_t li = 0; li < b->loc.size(); ++li) {
+        const int rc = call(b->loc[li].ctx, nullptr, 0, &n[li], nullptr);
+        if (rc) return b->fail(rc, ks_last_error(b->loc[li].ctx));
+        total += n[li];
+    }
+    *count = total;
+    if (!out) return KS_OK;
+    if (cap < total) return b->fail(KS_E_INVALID, "output buffer smaller than the delta count");
+    Stats sum;
+    std::memset(&sum, 0, sizeof(sum));
+    static_assert(sizeof(Stats) % sizeof(int64_t) == 0, "commit stats are int64 counters");
+    std::vector<ks_batch_delta> all;
+    for (size_t li = 0; li < b->loc.size(); ++li) {
+        auto& l = b->loc[li];
+        std::vector<ks_sched_delta> v(std::max<size_t>(n[li], 1));
+        Stats st;
+        std::memset(&st, 0, sizeof(st));
+        size_t got = 0;
+        const int rc = call(l.ctx, v.data(), n[li], &got, &st);
+        if (rc) return b->fail(rc, ks_last_error(l.ctx));
+        v.resize(got);
+        localize_deltas(l, v, all);
+        for (size_t w = 0; w < sizeof(Stats) / sizeof(int64_t); ++w)
+            reinterpret_cast<int64_t*>(&sum)[w] += reinterpret_cast<const int64_t*>(&st)[w];
+        recompute_toff(l);
+    }
+    // grouped by graph, ascending; within a graph the order of ks_scheduling_deltas
+    std::stable_sort(all.begin(), all.end(),
+                     [](const ks_batch_delta& x, const ks_batch_delta& y) { return x.graph < y.graph; });
+    if (!all.empty()) std::memcpy(out, all.data(), all.size() * sizeof(ks_batch_delta));
+    *count = all.size();
+    if (stats) *stats = sum;
+    return KS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -236,6 +387,29 @@ int ks_batch_unpack(const int64_t* gathered, size_t ngraphs, int world, size_t m
         if (cost) cost[g] = row[0];
         if (flow) flow[g] = row[1];
         if (pu) std::memcpy(pu + g * max_tasks, row + 2, max_tasks * sizeof(uint64_t));
+    }
+    return KS_OK;
+}
+
+int ks_batch_node_offsets(const uint64_t* maxid, size_t k, size_t spare, int64_t* off) {
+    if (!off || (k && !maxid)) return KS_E_INVALID;
+    off[0] = 0;
+    for (size_t i = 0; i < k; ++i) off[i + 1] = off[i] + (int64_t)maxid[i] + (int64_t)spare;
+    return KS_OK;
+}
+
+int ks_batch_translate_deltas(int64_t lo, int64_t hi, const ks_delta* in, size_t k, ks_delta* out) {
+    if (lo < 0 || hi < lo || (k && (!in || !out))) return KS_E_INVALID;
+    if (kb_first_bad(in, k, (uint64_t)(hi - lo)) < k) return KS_E_RANGE;   // before anything is written
+    for (size_t i = 0; i < k; ++i) {
+        ks_delta x = in[i];   // (a copy first: out may be in)
+        if (kb_arc_kind(x.kind)) {
+            x.src += (uint64_t)lo;
+            x.dst += (uint64_t)lo;
+        } else if (kb_node_kind(x.kind)) {
+            x.id += (uint64_t)lo;
+        }
+        out[i] = x;
     }
     return KS_OK;
 }
@@ -318,16 +492,26 @@ int ks_batch_load(ks_batch* b, size_t ngraphs, const ks_node* const* nodes, cons
         // the disjoint union of this device's graphs: node ids offset per graph
         std::vector<ks_node> un;
         std::vector<ks_arc> ua;
-        l.off.assign(1, 0);
-        l.toff.assign(1, 0);
+        // every graph's id range in the union: its highest id plus the reserved ids
+        std::vector<uint64_t> maxids;
         for (int g : l.graphs) {
-            uint64_t maxid = 0;
+            uint64_t mx = 0;
+            for (size_t i = 0; i < n[g]; ++i) mx = std::max<uint64_t>(mx, nodes[g][i].id);
+            maxids.push_back(mx);
+        }
+        l.off.assign(l.graphs.size() + 1, 0);
+        if (int rc = ks_batch_node_offsets(maxids.data(), maxids.size(), b->spare, l.off.data()))
+            return b->fail(rc, "the union's node ids exceed the supported range");
+        l.toff.assign(1, 0);
+        for (size_t gi = 0; gi < l.graphs.size(); ++gi) {
+            const int g = l.graphs[gi];
+            const uint64_t maxid = maxids[gi];
+            const uint64_t base = (uint64_t)l.off[gi];
             int64_t tasks = 0;
             for (size_t i = 0; i < n[g]; ++i) {
                 ks_node x = nodes[g][i];
-                maxid = std::max<uint64_t>(maxid, x.id);
                 tasks += x.type == KS_NODE_TASK;
-                x.id += (uint64_t)l.off.back();
+                x.id += base;
                 un.push_back(x);
             }
             for (size_t i = 0; i < m[g]; ++i) {
@@ -337,15 +521,28 @@ int ks_batch_load(ks_batch* b, size_t ngraphs, const ks_node* const* nodes, cons
                 if (a.src == 0 || a.dst == 0 || a.src > maxid || a.dst > maxid)
                     return b->fail(KS_E_INVALID, "graph " + std::to_string(g) + ": arc " + std::to_string(a.src) +
                                                      "->" + std::to_string(a.dst) + " outside its node id range");
-                a.src += (uint64_t)l.off.back();
-                a.dst += (uint64_t)l.off.back();
+                a.src += base;
+                a.dst += base;
                 ua.push_back(a);
             }
-            l.off.push_back(l.off.back() + (int64_t)maxid);
             l.toff.push_back(l.toff.back() + tasks);
         }
         const int rc = ks_load_graph(l.ctx, un.data(), un.size(), ua.data(), ua.size());
         if (rc) return b->fail(rc, ks_last_error(l.ctx));
+        l.ctx->every_sink = true;   // one sink per graph: a commit's capacity refresh starts from all of them
+        if (b->spare) {
+            // the reserved ids are node slots from now on (dead until a stream adds them), and
+            // the first build already has an edited graph's slack: round 1 lands in place
+            ks_ctx* c = l.ctx;
+            if (c->nodes.size() < (size_t)l.off.back() + 1) {
+                c->nodes.resize((size_t)l.off.back() + 1);
+                c->ids.resize((size_t)l.off.back() + 1);
+            }
+            if (int rc2 = c->eng.expect_deltas(l.off.back(), c->err)) {
+                c->store_bad = true;
+                return b->fail(rc2, c->err);
+            }
+        }
         // the union's cells: the cell solver runs each in its own workgroup (ks_cell.h)
         l.ctx->eng.set_cells(l.off.data(), l.graphs.size());
     }
@@ -566,6 +763,129 @@ int ks_batch_gather(ks_batch* b, size_t max_tasks, uint64_t* pu, int64_t* cost, 
     const int rc = ks_batch_unpack((const int64_t*)host.data(), b->ngraphs, b->world, max_tasks, pu, cost, flow);
     if (rc != KS_OK) return b->fail(rc, "a rank failed to pack its rows (status " + std::to_string(rc) + ")");
     return KS_OK;
+}
+
+// ---- batch rounds: deltas, the graph as it stands, bindings, commits ----
+
+int ks_batch_reserve(ks_batch* b, size_t spare_ids) {
+    if (!b) return KS_E_INVALID;
+    if (spare_ids >= (size_t(1) << 30)) return b->fail(KS_E_RANGE, "reserved ids beyond the node id range");
+    b->spare = spare_ids;
+    return KS_OK;
+}
+
+int ks_batch_apply_deltas(ks_batch* b, size_t ngraphs, const ks_delta* const* deltas, const size_t* k) {
+    if (!b) return KS_E_INVALID;
+    if (ngraphs != b->ngraphs) return b->fail(KS_E_INVALID, "the stream count differs from the loaded graphs");
+    if (ngraphs && (!deltas || !k)) return b->fail(KS_E_INVALID, "null stream arrays");
+    // 1. every local device's union stream: its graphs' streams translated into their id
+    //    ranges and concatenated in graph order (a record that leaves its graph's range
+    //    stops the call here, before any device changed)
+    std::vector<std::vector<ks_delta>> us(b->loc.size());
+    for (size_t li = 0; li < b->loc.size(); ++li) {
+        auto& l = b->loc[li];
+        std::vector<ks_delta>& u = us[li];
+        for (size_t i = 0; i < l.graphs.size(); ++i) {
+            const size_t g = (size_t)l.graphs[i];
+            if (!deltas[g] || !k[g]) continue;
+            if (k[g] > (size_t)INT32_MAX - u.size()) return b->fail(KS_E_RANGE, "delta stream too long");
+            const size_t at = u.size();
+            u.resize(at + k[g]);
+            const int rc = ks_batch_translate_deltas(l.off[i], l.off[i + 1], deltas[g], k[g], u.data() + at);
+            if (rc == KS_E_RANGE) {
+                const uint64_t span = (uint64_t)(l.off[i + 1] - l.off[i]);
+                const size_t j = kb_first_bad(deltas[g], k[g], span);
+                bool any = false;
+                const uint64_t id = j < k[g] ? kb_bad_id(deltas[g][j], span, &any) : 0;
+                return b->fail(rc, "graph " + std::to_string(g) + ": record " + std::to_string(j) + " names node id " +
+                                       std::to_string(id) + ", outside the graph's ids 1.." + std::to_string(span) +
+                                       " (its highest id at the load plus the reserved ids)");
+            }
+            if (rc) return b->fail(rc, "graph " + std::to_string(g) + ": bad delta stream");
+            if (l.ctx->opts.auto_sink) append_auto_sink(l, i, u, at);
+        }
+    }
+    // 2. one ks_apply_deltas per device (all or nothing there; no collective: a rank
+    //    returns its own failure)
+    for (size_t li = 0; li < b->loc.size(); ++li) {
+        auto& l = b->loc[li];
+        if (us[li].empty()) continue;
+        const int rc = ks_apply_deltas(l.ctx, us[li].data(), us[li].size());
+        if (rc) return b->fail(rc, "rank " + std::to_string(l.grank) + ": " + ks_last_error(l.ctx));
+        recompute_toff(l);
+    }
+    return KS_OK;
+}
+
+int ks_batch_get_graph(ks_batch* b, size_t g, ks_node* nodes, size_t ncap, size_t* n, ks_arc* arcs, size_t acap,
+                       size_t* m) {
+    if (!b || !n || !m) return KS_E_INVALID;
+    size_t i = 0;
+    ks_batch::Local* l = owner_of(b, g, &i);
+    if (!l) return b->fail(KS_E_INVALID, "graph " + std::to_string(g) + " is not on this rank");
+    ks_ctx* c = l->ctx;
+    const uint64_t lo = (uint64_t)l->off[i], hi = (uint64_t)l->off[i + 1];
+    size_t cnt = 0;
+    for (uint64_t id = lo + 1; id <= hi && id < c->nodes.size(); ++id) {
+        const NodeRec& r = c->nodes[id];
+        if (!r.alive) continue;
+        if (nodes && cnt < ncap) nodes[cnt] = ks_node{id - lo, r.excess, r.type, 0};
+        ++cnt;
+    }
+    *n = cnt;
+    // the union's live arcs (arc-slot order), this graph's kept
+    if (c->store_bad) return b->fail(KS_E_INVALID, "the device graph store is inconsistent: reload the batch");
+    std::vector<ks_arc> v;
+    const int rc = c->eng.arcs(v, c->err);
+    if (rc) return b->fail(rc, c->err);
+    const size_t all = v.size();
+    cnt = 0;
+    for (size_t j = 0; j < all; ++j) {
+        ks_arc a = v[j];
+        if (a.src <= lo || a.src > hi) continue;
+        a.src -= lo;
+        a.dst -= lo;
+        if (arcs && cnt < acap) arcs[cnt] = a;
+        ++cnt;
+    }
+    *m = cnt;
+    return KS_OK;
+}
+
+int ks_batch_set_bindings(ks_batch* b, size_t g, const uint64_t* task, const uint64_t* pu, size_t k) {
+    if (!b) return KS_E_INVALID;
+    if (k && (!task || !pu)) return b->fail(KS_E_INVALID, "null binding array");
+    size_t i = 0;
+    ks_batch::Local* l = owner_of(b, g, &i);
+    if (!l) return b->fail(KS_E_INVALID, "graph " + std::to_string(g) + " is not on this rank");
+    const uint64_t lo = (uint64_t)l->off[i], span = (uint64_t)(l->off[i + 1] - l->off[i]);
+    std::vector<uint64_t> t(k), p(k);
+    for (size_t j = 0; j < k; ++j) {
+        if (task[j] == 0 || task[j] > span || pu[j] > span)
+            return b->fail(KS_E_RANGE, "graph " + std::to_string(g) + ": binding outside the graph's ids");
+        t[j] = task[j] + lo;
+        p[j] = pu[j] ? pu[j] + lo : 0;
+    }
+    const int rc = ks_set_bindings(l->ctx, t.data(), p.data(), k);
+    if (rc) return b->fail(rc, ks_last_error(l->ctx));
+    return KS_OK;
+}
+
+int ks_batch_commit_schedule(ks_batch* b, int32_t flags, int64_t continuation_cost, ks_batch_delta* out, size_t cap,
+                             size_t* count, ks_commit_stats* stats) {
+    return batch_commit(b, out, cap, count, stats,
+                        [&](ks_ctx* c, ks_sched_delta* o, size_t ocap, size_t* n, ks_commit_stats* st) {
+                            return ks_commit_schedule(c, flags, continuation_cost, nullptr, 0, o, ocap, n, st);
+                        });
+}
+
+int ks_batch_commit_preemptive(ks_batch* b, int32_t flags, int64_t continuation_cost, int64_t preemption_cost,
+                               ks_batch_delta* out, size_t cap, size_t* count, ks_preempt_stats* stats) {
+    return batch_commit(b, out, cap, count, stats,
+                        [&](ks_ctx* c, ks_sched_delta* o, size_t ocap, size_t* n, ks_preempt_stats* st) {
+                            return ks_commit_preemptive(c, flags, continuation_cost, preemption_cost, nullptr, 0, o,
+                                                        ocap, n, st);
+                        });
 }
 
 }  // extern "C"

@@ -103,6 +103,8 @@ struct CellArgs {
     long long* excess;
     const CellDesc* cells;
     int ncells;
+    const int* list;         // the cells this launch solves, one workgroup each (nlist of them, ascending);
+    int nlist;               //   nullptr: every cell, workgroup i solves cell i (nlist = ncells)
     int nn;                  // internal node ids
     int* lists;              // 2 × nn: two frontier buffers (a node's class slice at its class range)
     int* rl_node;            // nn: relabels pending until the end of a sweep

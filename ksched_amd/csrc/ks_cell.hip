@@ -1461,16 +1461,19 @@ __device__ __forceinline__ void cyc_search(const CellArgs& A, const K& k, int sr
 }
 
 __global__ __launch_bounds__(CT) void k_cell(CellArgs A) {
-    const CellDesc cd = A.cells[blockIdx.x];
+    // the workgroup's cell: from the launch's list when only some cells run (one uniform
+    // load ahead of the descriptor's, in the prologue only: nothing below reads the list)
+    const int cell = A.list ? A.list[blockIdx.x] : (int)blockIdx.x;
+    const CellDesc cd = A.cells[cell];
     const int N = cd.cb[CELL_NCLS] - cd.cb[0];
     const int pb = A.first[cd.cb[0]];
-    if (threadIdx.x < 8) s_.cbs[threadIdx.x] = A.cells[blockIdx.x].cb[threadIdx.x];
+    if (threadIdx.x < 8) s_.cbs[threadIdx.x] = A.cells[cell].cb[threadIdx.x];
     if (threadIdx.x < NCTR) ctr_[threadIdx.x] = 0;
     if (*A.bad) {   // a position the compact record cannot hold: nothing is touched
         if (threadIdx.x == 0) {
             CellOut o{};
             o.status = CS_RANGE;
-            A.out[blockIdx.x] = o;
+            A.out[cell] = o;
         }
         return;
     }
@@ -1647,7 +1650,7 @@ __global__ __launch_bounds__(CT) void k_cell(CellArgs A) {
             o.hist_n[i] = c.hist_n[i];
         }
         for (int i = 0; i < 8; ++i) o.phase_ticks[i] = c.phase_ticks[i];
-        A.out[blockIdx.x] = o;
+        A.out[cell] = o;
     }
 }
 
@@ -1659,6 +1662,12 @@ __global__ __launch_bounds__(CT) void k_cell(CellArgs A) {
 __global__ void k_cell_pack(CellArgs A, int* bad) {
     for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x; p < A.m2; p += (long long)gridDim.x * blockDim.x) {
         const Pos q = ld_pos(A.pos + p);
+        if (q.head >= A.cells[A.ncells - 1].cb[CELL_NCLS]) {
+            // a spare slot past the partition (no cell's node): its positions are inert and
+            // no workgroup reads them; the record only carries the residual for the unpack
+            A.cp[p] = CellPos{(int)q.rcap, (int)q.ucap, CELL_DEAD, 0u};
+            continue;
+        }
         int lo = 0, hi = A.ncells;
         while (hi - lo > 1) {
             const int mid = (lo + hi) >> 1;
@@ -1713,7 +1722,8 @@ int cell_max_nodes(size_t limit) {
 hipError_t cell_launch(const CellArgs& a, int* bad, size_t lds_limit, hipStream_t st, bool* refused) {
     *refused = false;
     const size_t lds = cell_lds_bytes(a.max_nodes, lds_limit);
-    if (!lds || a.ncells <= 0) {
+    const int grid = a.list ? a.nlist : a.ncells;
+    if (!lds || a.ncells <= 0 || grid <= 0 || grid > a.ncells) {
         *refused = true;
         return hipErrorInvalidValue;
     }
@@ -1729,7 +1739,7 @@ hipError_t cell_launch(const CellArgs& a, int* bad, size_t lds_limit, hipStream_
     hipLaunchKernelGGL(k_cell_pack, dim3(pg), dim3(256), 0, st, a, bad);
     CellArgs b = a;
     b.bad = bad;
-    hipLaunchKernelGGL(k_cell, dim3(a.ncells), dim3(CT), lds, st, b);
+    hipLaunchKernelGGL(k_cell, dim3(grid), dim3(CT), lds, st, b);
     hipLaunchKernelGGL(k_cell_unpack, dim3(pg), dim3(256), 0, st, a, (const int*)bad);
     return hipGetLastError();
 }

@@ -42,6 +42,8 @@ struct ks_ctx {
     bool map_fresh = false;                // map_dense holds the current solve's task→PU vector
     std::vector<uint64_t> map_dense;       // per live task slot in slot order: its PU (0: none)
     bool store_bad = false;                // a load / apply failed on the device: reload first
+    bool every_sink = false;               // a ks_batch union: one sink per graph, and a commit's capacity
+                                           //   refresh starts from all of them (a lone context refuses that)
     std::vector<ks_flow> flows;
 
     int fail(int code, const std::string& msg) {

@@ -43,6 +43,10 @@ public:
     // solver holds are then solved one workgroup each in ONE launch (ks_cell.h);
     // k = 0 forgets the partition (the whole graph is one cell).
     void set_cells(const int64_t* off, size_t k);
+    // Deltas will follow the load (ks_batch_reserve): node slots [0, nslots) are in use from
+    // now on (ids reserved past the highest loaded one) and the next build lays the
+    // residual CSR out with an edited graph's slack, so the first stream lands in place.
+    int expect_deltas(int64_t nslots, std::string& err);
 
     // Node state changes outside a stream (the auto-sink demand).
     int set_nodes(const NodeEdit* edits, size_t ne, std::string& err);
@@ -87,7 +91,10 @@ public:
     int topology_stats(uint64_t mtpp, const uint64_t* pu_ids, const uint64_t* pu_running, size_t k, int64_t sink_slot,
                        uint64_t* slots_below, uint64_t* running_below, std::string& err);
     // ks_commit_schedule: *out receives the deltas (cap: the caller's room for them);
-    // sink_slot < 0: no single sink. *dirty: device state was touched before a failure.
+    // sink_slot < 0: no single sink; kEverySink: a cell partition's sinks, one per cell (the
+    // capacity refresh then starts from every live sink; refused without a partition).
+    // *dirty: device state was touched before a failure.
+    static constexpr int64_t kEverySink = -2;
     int commit_schedule(int flags, int64_t ccost, const uint64_t* ids, size_t k, int64_t sink_slot, int64_t n_tasks,
                         size_t cap, std::vector<ks_sched_delta>* out, size_t* count, ks_commit_stats* stats,
                         bool* dirty, std::string& err);

@@ -2941,8 +2941,37 @@ void Engine::set_cells(const int64_t* off, size_t k) {
     if (off && k) v.assign(off, off + k + 1);
     if (v != s.cell_off) {
         s.cell_off.swap(v);
+        s.cell_first_valid = false;               // the dirty flags belong to the old partition
+        s.cells_kept = false;
         if (s.cell_layout) s.csr_valid = false;   // the cells are laid out anew by the next build
     }
+}
+
+// A PU's segment must hold the running arcs of the tasks a round pins to it: up to the
+// capacity of its arc into the sink, which its degree at the load (two arcs) does not
+// show. The build takes the larger of its own estimate and this hint (k_capacity).
+__global__ void k_hint_pu_slots(int hi, const unsigned char* __restrict__ alive, const int* __restrict__ src,
+                                const int* __restrict__ dst, const long long* __restrict__ cap,
+                                const unsigned char* __restrict__ type, int* __restrict__ hint) {
+    for (long long a = blockIdx.x * (long long)BLK + threadIdx.x; a < hi; a += (long long)gridDim.x * BLK)
+        if (alive[a] && type[src[a]] == KS_NODE_PU && type[dst[a]] == KS_NODE_SINK)
+            hint[src[a]] = (int)(cap[a] < 4092 ? cap[a] : 4092) + 4;
+}
+
+int Engine::expect_deltas(int64_t nslots, std::string& err) {
+    EngineImpl& s = *p_;
+    KS_CHECK(hipSetDevice(s.device));
+    if (int rc = ensure_nodes(s, std::max<int64_t>(nslots, 1), err)) return rc;
+    s.nslots = std::max(s.nslots, nslots);
+    s.incremental = true;
+    s.csr_valid = false;
+    if (const int hi = s.hi()) {
+        hipLaunchKernelGGL(k_hint_pu_slots, dim3(grid_for(hi)), dim3(BLK), 0, s.stream, hi,
+                           (const unsigned char*)s.a_alive.p, (const int*)s.a_src.p, (const int*)s.a_dst.p,
+                           (const long long*)s.a_cap.p, (const unsigned char*)s.n_type.p, s.n_hint.p);
+        KS_CHECK(hipGetLastError());
+    }
+    return KS_OK;
 }
 
 // The cell solver runs when every cell (the ks_batch partition, else the whole
@@ -2960,10 +2989,14 @@ static bool want_cells(const EngineImpl& s) {
     const int64_t ncap =
         s.csr_valid ? s.ncap : s.nslots + (s.incremental ? std::max<int64_t>(64, s.nslots / 16) : 0);
     if (ncap <= 0) return false;
-    const size_t k = s.cell_off.size() >= 2 ? s.cell_off.size() - 1 : 1;
+    // a partition's last cell ends where the partition does: the spare slots the store
+    // keeps past it once deltas arrive (max(64, nslots/16), tens of thousands on a config-5
+    // union) belong to no cell and must not push the union off the cell solver
+    const bool part = s.cell_off.size() >= 2;
+    const size_t k = part ? s.cell_off.size() - 1 : 1;
     int64_t prev = 0;
     for (size_t i = 1; i <= k; ++i) {
-        const int64_t b = i == k ? ncap : std::min<int64_t>(ncap, std::max<int64_t>(prev, s.cell_off[i]));
+        const int64_t b = i == k && !part ? ncap : std::min<int64_t>(ncap, std::max<int64_t>(prev, s.cell_off[i]));
         if (b - prev > lim) return false;
         prev = b;
     }
@@ -3000,6 +3033,9 @@ struct SolveRun {
     const bool fb;
     const bool use_warm;
     Retry retry = RETRY_NONE;
+    bool run_all = true;         // every cell runs (prepare(): which cells run)
+    std::vector<int> run_list;   //   else these, ascending
+    int cells_run = 0;           // cells the cell solver launched
 
     // ---- the graph as prepare() leaves it
     int hi = 0, nn = 0, ncells = 0;
@@ -3122,6 +3158,14 @@ struct SolveRun {
                 s.csr_valid = false;
             }
         }
+        // Which cells run: a warm solve of a partition whose last solve ended
+        // on the cell path, with the residual state still in place (no build since, none
+        // now, no fallback running), launches only the cells a record touched since.
+        // Anything else runs every cell: skipping is only an optimisation.
+        run_all = !(s.cell_off.size() >= 2 && o.warm_start >= 1 && use_warm && !fb && s.cells_kept && s.csr_valid &&
+                    s.cell_layout);
+        s.cells_kept = false;   // (until this solve ends well: report())
+        run_list.clear();
         res.warm_started = use_warm ? 1 : 0;
         res.rebuilt = s.csr_valid ? 0 : 1;
         res.recoveries = 0;
@@ -3165,7 +3209,18 @@ struct SolveRun {
             hipLaunchKernelGGL(k_pack_pos, dim3(grid_for(m2, 4096)), dim3(BLK), 0, st, (long long)m2,
                                (const Pos*)s.pos.p, s.cpos.p, s.crev.p, &s.ctl.p->cp_bad);
         }
+        // the cells' dirty flags come back with the control block (no sync of their own);
+        // a partition no stream has marked yet has none set
+        const bool flags = !run_all && s.cell_first_valid;
+        if (flags) {
+            s.h_cell_dirty.assign(ncells, 1);
+            KS_CHECK(hipMemcpyAsync(s.h_cell_dirty.data(), s.cell_dirty.p, ncells * sizeof(int), hipMemcpyDeviceToHost,
+                                    st));
+        }
         KS_CHECK(read_ctl());
+        if (flags)
+            for (int c = 0; c < ncells; ++c)
+                if (s.h_cell_dirty[c]) run_list.push_back(c);
         maxc = s.h_ctl->gu_L;
         cpv = want_cp && !s.h_ctl->cp_bad;
         cp_dirty = false;
@@ -3902,6 +3957,10 @@ struct SolveRun {
     int cell_solve() {
         KS_CHECK(s.cl_pos.ensure(std::max<int64_t>(m2, 1)));
         KS_CHECK(hipEventRecord(s.ev[3], st));
+        if (!run_all && run_list.empty()) {   // no cell changed since its last solve: no launch,
+            eps = 1;                          // verification reports the flow in place again
+            return KS_OK;
+        }
         const int cs = run_cells(0);
         if (cs < 0) return cs;
         if (cs == CS_RANGE) {
@@ -3931,6 +3990,21 @@ struct SolveRun {
         a.excess = s.excess.p;
         a.cells = s.cells.p;
         a.ncells = ncells;
+        // the solve launches the listed cells only; the certificate recovery, every cell
+        const bool part = mode == 0 && !run_all;
+        a.list = nullptr;
+        a.nlist = ncells;
+        if (part) {
+            s.h_cell_list = run_list;   // (the copy's source outlives the stream's use of it)
+            KS_CHECK(s.cell_list.ensure(run_list.size()));
+            KS_CHECK(hipMemcpyAsync(s.cell_list.p, s.h_cell_list.data(), run_list.size() * sizeof(int),
+                                    hipMemcpyHostToDevice, st));
+            // a skipped cell reports "ok, zero work"
+            KS_CHECK(hipMemsetAsync(s.cl_out.p, 0, ncells * sizeof(CellOut), st));
+            a.list = s.cell_list.p;
+            a.nlist = (int)run_list.size();
+        }
+        cells_run = part ? (int)run_list.size() : ncells;
         a.nn = nn;
         a.lists = s.cl_lists.p;
         a.rl_node = s.cl_rln.p;
@@ -3956,6 +4030,10 @@ struct SolveRun {
         a.diag = cycle_log ? 1 : 0;
         // TESTS ONLY (fault_inject bit 4): the middle cell gives up after 40 operations
         a.fault_cell = (o.fault_inject & 16) && mode == 0 ? ncells / 2 : -1;
+        if (part && a.fault_cell >= 0) {   // (the kernel compares its workgroup index: the cell's place in the list)
+            const auto it = std::find(run_list.begin(), run_list.end(), a.fault_cell);
+            a.fault_cell = it == run_list.end() ? -1 : (int)(it - run_list.begin());
+        }
         a.fault_ops = 40;
         a.cyc_lg = cyc_lg;
         KS_CHECK(hipEventRecord(s.kev[2], st));
@@ -4214,6 +4292,7 @@ struct SolveRun {
         res.fwd_updates = fwd_updates;
         res.solver = s.cell_layout ? 1 : 0;
         res.cells = s.cell_layout ? ncells : 0;
+        res.cells_run = s.cell_layout ? cells_run : 0;
         res.ms_cell_kernel = ms_cell;
         res.cell_ticks_max = cticks_max;
         res.cell_ticks_sum = cticks_sum;
@@ -4223,11 +4302,16 @@ struct SolveRun {
         KS_CHECK(hipMemsetAsync(s.n_cshift.p, 0, s.nstore * sizeof(unsigned long long), st));
         if (status == KS_OK) {
             KS_CHECK(hipMemsetAsync(s.n_fresh.p, 0, s.nstore, st));
+            // every cell now holds its optimum: the dirty flags start over
+            if (s.cell_first_valid && s.cell_dirty.p)
+                KS_CHECK(hipMemsetAsync(s.cell_dirty.p, 0, (s.cell_off.size() - 1) * sizeof(int), st));
             KS_CHECK(hipStreamSynchronize(st));
             s.solved = true;
             s.has_prev = true;
+            s.cells_kept = s.cell_layout;
         } else {
             s.has_prev = false;   // a failed solve leaves no usable warm state
+            s.cells_kept = false;
         }
         return status;
     }
@@ -4270,6 +4354,7 @@ int Engine::solve(ks_result& res, bool warm, std::string& err) {
         res.cell_fallbacks = bad.size();
         res.solver = 1;
         res.cells = run.ncells;
+        res.cells_run = run.cells_run;
         return rc2;
     }
     return rc;

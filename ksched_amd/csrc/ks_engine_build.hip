@@ -212,8 +212,9 @@ struct ClassIs {
 
 // Cell-major internal ids for the cell solver (ks_cell.h): every cell (a ks_batch
 // graph, or the whole graph) is one contiguous id range, its nodes grouped by the
-// cell solver's degree classes (cell_class of the segment capacity). Slots past the
-// partition belong to the last cell. Computed on the host from the capacities.
+// cell solver's degree classes (cell_class of the segment capacity). Without a partition
+// the one cell covers every slot; slots past a partition belong to no cell. Computed on
+// the host from the capacities.
 static int cell_order(EngineImpl& s, int64_t ncap, std::string& err) {
     hipStream_t st = s.stream;
     std::vector<int> capv(ncap);
@@ -222,7 +223,9 @@ static int cell_order(EngineImpl& s, int64_t ncap, std::string& err) {
     const size_t k = s.cell_off.size() >= 2 ? s.cell_off.size() - 1 : 1;
     std::vector<int64_t> bound(k + 1, 0);   // slot bounds of each cell
     for (size_t i = 1; i < k; ++i) bound[i] = std::min<int64_t>(ncap, std::max<int64_t>(0, s.cell_off[i]));
-    bound[k] = ncap;
+    // a partition ends at its last offset: the store's spare slots past it belong to no
+    // cell (they take the internal ids after the last cell; no arc can reach them)
+    bound[k] = s.cell_off.size() >= 2 ? std::min<int64_t>(ncap, std::max<int64_t>(bound[k - 1], s.cell_off[k])) : ncap;
     std::vector<int> cnt(k * CELL_NCLS, 0);
     std::vector<unsigned char> cls(ncap);
     for (size_t c = 0; c < k; ++c)
@@ -246,6 +249,7 @@ static int cell_order(EngineImpl& s, int64_t ncap, std::string& err) {
     std::vector<int> perm(ncap);
     for (size_t c = 0; c < k; ++c)
         for (int64_t v = bound[c]; v < bound[c + 1]; ++v) perm[v] = next[c * CELL_NCLS + cls[v]]++;
+    for (int64_t v = bound[k]; v < ncap; ++v) perm[v] = o++;   // slots past the partition: after the last cell
     if (ncap) KS_CHECK(hipMemcpyAsync(s.perm.p, perm.data(), ncap * sizeof(int), hipMemcpyHostToDevice, st));
     s.cell_max = mx;
     for (int c = 0; c <= NGC; ++c) s.ncls[c] = 0;
@@ -272,6 +276,7 @@ int impl::build(EngineImpl& s, std::string& err) {
     const int hi = s.hi();
     const int64_t spare = s.incremental ? std::max<int64_t>(64, s.nslots / 16) : 0;
     const int64_t ncap = s.nslots + spare;
+    s.cells_kept = false;   // positions and internal ids move: every cell runs in the next solve
     int rc = ensure_nodes(s, ncap, err);
     if (rc) return rc;
     s.ncap = ncap;

@@ -344,6 +344,15 @@ struct EngineImpl {
     DBuf<long long> fb_rng;             // their node-slot ranges on the device
     DBuf<unsigned long long> fb_cnt;    // arc + node slots k_fb_reset restarted cold
     std::vector<CellOut> h_cell_out;
+    // which cells run: one flag per cell of a partition, set on the device over
+    // every record stream that reaches store_apply and cleared by a successful solve
+    std::vector<int> h_cell_first;      // the cells' first node slots (k + 1: the last one ends the partition)
+    bool cell_first_valid = false;      // cell_first / cell_dirty hold the current partition
+    DBuf<int> cell_first, cell_dirty;
+    DBuf<int> cell_list;                // the cells of a partial launch
+    std::vector<int> h_cell_dirty, h_cell_list;
+    bool cells_kept = false;            // the last solve ended OK on the cell path and no build ran since:
+                                        //   a cell no record touched still holds its optimum
     // ---- scheduler-side sweeps (ks_sched.hip)
     DBuf<int> sched_i;                  // int scratch
     DBuf<unsigned long long> sched_u;   // u64 scratch
@@ -520,6 +529,8 @@ int read_sctl(EngineImpl& s, std::string& err);
 int ensure_arcs(EngineImpl& s, int64_t need, std::string& err);
 int ensure_hash(EngineImpl& s, int64_t extra, std::string& err);
 int applied(EngineImpl& s, std::string& err);
+// the cells a record stream (device memory) touches, before it reaches store_apply
+int mark_cells(EngineImpl& s, const ks_delta* recs, size_t k, const NodeEdit* edits, size_t ne, std::string& err);
 
 inline double ev_ms(hipEvent_t a, hipEvent_t b) {
     float ms = 0.f;

@@ -155,7 +155,73 @@ __global__ void k_flow_records(int cnt, const int* __restrict__ sel, const int* 
     }
 }
 
+// One flag per cell of a partition, set for every cell a record stream touches (DESIGN
+// §3.5 "which cells run"). A record's node — an arc's tail: no arc crosses two cells — is
+// bisected over the cells' first slots, as k_cell_pack bisects heads. The lanes of a
+// wave then agree on their distinct cells and ONE lane per cell issues the atomic: a
+// stream is grouped by graph, so a wave sets one or two words instead of sending 64
+// atomics to the same one. Slots outside the partition (the store's spare
+// slots) belong to no cell.
+__global__ void k_mark_cells(const ks_delta* __restrict__ recs, int k, const NodeEdit* __restrict__ edits, int ne,
+                             const int* __restrict__ first, int ncells, int* __restrict__ dirty) {
+    const long long total = (long long)k + ne;
+    const int lane = threadIdx.x & (WAVE - 1);
+    // (i − lane is the wave's first index: the trip count is wave-uniform)
+    for (long long i = blockIdx.x * (long long)BLK + threadIdx.x; i - lane < total; i += (long long)gridDim.x * BLK) {
+        int cell = -1;
+        if (i < total) {
+            long long slot;
+            if (i < k) {
+                const bool arc = recs[i].kind == KS_ADD_ARC || recs[i].kind == KS_UPDATE_ARC;
+                slot = (long long)(arc ? recs[i].src : recs[i].id) - 1;
+            } else {
+                slot = edits[i - k].slot;
+            }
+            if (slot >= first[0] && slot < first[ncells]) {
+                int lo = 0, hi = ncells;   // the last cell with first[cell] <= slot
+                while (hi - lo > 1) {
+                    const int mid = (lo + hi) >> 1;
+                    if (first[mid] <= slot) lo = mid;
+                    else hi = mid;
+                }
+                cell = lo;
+            }
+        }
+        for (;;) {
+            const unsigned long long m = __ballot(cell >= 0);
+            if (!m) break;
+            const int leader = __ffsll((long long)m) - 1;
+            const int c = __shfl(cell, leader);
+            if (lane == leader) atomicOr(&dirty[c], 1);
+            if (cell == c) cell = -1;
+        }
+    }
+}
+
 }  // namespace
+
+// The flags of k_mark_cells for a stream in device memory (the host's, uploaded by
+// run_apply, or a commit's, generated there). Without a partition there is nothing to mark.
+int impl::mark_cells(EngineImpl& s, const ks_delta* recs, size_t k, const NodeEdit* edits, size_t ne,
+                     std::string& err) {
+    if (s.cell_off.size() < 2 || k + ne == 0) return KS_OK;
+    hipStream_t st = s.stream;
+    const int ncells = (int)s.cell_off.size() - 1;
+    if (!s.cell_first_valid) {
+        s.h_cell_first.assign(s.cell_off.begin(), s.cell_off.end());   // cell i: slots [off[i], off[i+1])
+        KS_CHECK(s.cell_first.ensure(ncells + 1));
+        KS_CHECK(s.cell_dirty.ensure(ncells));
+        KS_CHECK(hipMemcpyAsync(s.cell_first.p, s.h_cell_first.data(), (ncells + 1) * sizeof(int),
+                                hipMemcpyHostToDevice, st));
+        KS_CHECK(hipMemsetAsync(s.cell_dirty.p, 0, ncells * sizeof(int), st));
+        KS_CHECK(hipStreamSynchronize(st));
+        s.cell_first_valid = true;
+    }
+    hipLaunchKernelGGL(k_mark_cells, dim3(grid_for((long long)(k + ne), 1024)), dim3(BLK), 0, st, recs, (int)k, edits,
+                       (int)ne, (const int*)s.cell_first.p, ncells, s.cell_dirty.p);
+    KS_CHECK(hipGetLastError());
+    return KS_OK;
+}
 
 // ------------------------------------------------------------------ store ---
 int impl::read_sctl(EngineImpl& s, std::string& err) {
@@ -253,6 +319,8 @@ static int run_apply(EngineImpl& s, const NodeEdit* edits, size_t ne, const ks_d
     if (k) KS_CHECK(hipMemcpyAsync(s.d_recs.p, recs, k * sizeof(ks_delta), hipMemcpyHostToDevice, st));
     if (ne) KS_CHECK(hipMemcpyAsync(s.d_edits.p, edits, ne * sizeof(NodeEdit), hipMemcpyHostToDevice, st));
     const auto t1 = std::chrono::steady_clock::now();
+    rc = mark_cells(s, s.d_recs.p, k, s.d_edits.p, ne, err);
+    if (rc) return rc;
     KS_CHECK(store_apply(s.sd(), s.d_recs.p, (int)k, s.rec_ent.p, s.d_edits.p, (int)ne, st));
     rc = read_sctl(s, err);
     if (rc) return rc;
@@ -310,6 +378,7 @@ int Engine::load(int64_t nslots, const int64_t* supply, const uint8_t* type, con
     s.rebuilds = 0;
     s.solved = false;
     s.has_prev = false;
+    s.cells_kept = false;
     s.cell_refused = s.cell_refused_values = false;
     rc = ensure_arcs(s, (int64_t)m, err);
     if (rc) return rc;

@@ -42,6 +42,21 @@ struct Carve {
         return p;
     }
 };
+
+// Level 0 of the topology BFS over a cell partition: every live sink, one per cell. A
+// union's sinks are few (one per graph) and far apart in slot space, so each is its
+// own returning atomic on the frontier's counter (nothing to aggregate per wave). With
+// one sink the frontier is that sink alone, as the single-graph seed writes it.
+__global__ void k_seed_sinks(int ncap, const unsigned char* __restrict__ alive, const unsigned char* __restrict__ type,
+                             const int* __restrict__ perm, int* __restrict__ lvl, int* __restrict__ front,
+                             int* __restrict__ nfront) {
+    for (long long v = blockIdx.x * (long long)BLK + threadIdx.x; v < ncap; v += (long long)gridDim.x * BLK)
+        if (alive[v] && type[v] == KS_NODE_SINK) {
+            const int x = perm[v];
+            lvl[x] = 0;
+            front[atomicAdd(nfront, 1)] = x;
+        }
+}
 }  // namespace
 
 // ------------------------------------------------- scheduler-side sweeps ---
@@ -149,7 +164,10 @@ int Engine::unsched_costs(const uint64_t* ids, size_t k, int mode, int64_t ucost
     KS_CHECK(hipMemcpyAsync(&h, s.sched_i.p, sizeof(int), hipMemcpyDeviceToHost, st));
     KS_CHECK(hipStreamSynchronize(st));
     if (changed) *changed = (size_t)h;
-    if (h) s.solved = false;
+    if (h) {
+        s.solved = false;
+        s.cells_kept = false;   // costs changed in place, past the dirty flags: every cell runs next
+    }
     return KS_OK;
 }
 
@@ -167,13 +185,23 @@ static int topo_bfs(EngineImpl& s, const SchedDev& d, int64_t sink_slot, uint64_
     int* fb = fa + (nn + 1);
     int* nnext = fb + (nn + 1);
     KS_CHECK(hipMemsetAsync(lvl, 0xff, (nn + 1) * sizeof(int), st));
-    int sink_x = 0;
-    KS_CHECK(hipMemcpyAsync(&sink_x, s.perm.p + sink_slot, sizeof(int), hipMemcpyDeviceToHost, st));
-    KS_CHECK(hipStreamSynchronize(st));
-    const int zero = 0;
-    KS_CHECK(hipMemcpyAsync(lvl + sink_x, &zero, sizeof(int), hipMemcpyHostToDevice, st));
-    KS_CHECK(hipMemcpyAsync(fa, &sink_x, sizeof(int), hipMemcpyHostToDevice, st));
     int nfront = 1;
+    if (sink_slot == Engine::kEverySink) {   // a partition: every live sink at level 0
+        KS_CHECK(hipMemsetAsync(nnext, 0, sizeof(int), st));
+        hipLaunchKernelGGL(k_seed_sinks, dim3(grid_for(s.ncap, 1024)), dim3(BLK), 0, st, (int)s.ncap,
+                           (const unsigned char*)s.n_alive.p, (const unsigned char*)s.n_type.p, (const int*)s.perm.p,
+                           lvl, fa, nnext);
+        KS_CHECK(hipGetLastError());
+        KS_CHECK(hipMemcpyAsync(&nfront, nnext, sizeof(int), hipMemcpyDeviceToHost, st));
+        KS_CHECK(hipStreamSynchronize(st));
+    } else {
+        int sink_x = 0;
+        KS_CHECK(hipMemcpyAsync(&sink_x, s.perm.p + sink_slot, sizeof(int), hipMemcpyDeviceToHost, st));
+        KS_CHECK(hipStreamSynchronize(st));
+        const int zero = 0;
+        KS_CHECK(hipMemcpyAsync(lvl + sink_x, &zero, sizeof(int), hipMemcpyHostToDevice, st));
+        KS_CHECK(hipMemcpyAsync(fa, &sink_x, sizeof(int), hipMemcpyHostToDevice, st));
+    }
     for (int level = 0; nfront > 0 && level <= nn; ++level) {
         KS_CHECK(hipMemsetAsync(nnext, 0, sizeof(int), st));
         KS_CHECK(sched_topo_level(d, fa, nfront, level, lvl, fb, nnext, mtpp, pu_slots, cnt, slots, run, st));
@@ -277,7 +305,8 @@ int Engine::commit(bool preempt, int flags, int64_t ccost, int64_t pcost, const 
     c.pcost = pcost;
     c.np = (int)np;
     c.ni_max = (int)(np + s.m2cap / 64 + 1);
-    if (c.resource_caps && (sink_slot < 0 || sink_slot >= ncap)) {
+    const bool every_sink = sink_slot == kEverySink && s.cell_off.size() >= 2;   // a partition: one sink per cell
+    if (c.resource_caps && !every_sink && (sink_slot < 0 || sink_slot >= ncap)) {
         err = "resource capacities need exactly one sink";
         return KS_E_INVALID;
     }
@@ -364,6 +393,9 @@ int Engine::commit(bool preempt, int flags, int64_t ccost, int64_t pcost, const 
     d = s.schd();   // (the arc table may have moved)
     *dirty = true;
     KS_CHECK(sched_commit_emit(d, c, s.d_recs.p, st));
+    // the records exist only here, in HBM: their cells are marked on the device
+    rc = mark_cells(s, s.d_recs.p, (size_t)nrec, nullptr, 0, err);
+    if (rc) return rc;
     KS_CHECK(store_apply(s.sd(), s.d_recs.p, (int)nrec, s.rec_ent.p, s.d_edits.p, 0, st));
     if (log) KS_CHECK(hipEventRecord(s.kev[1], st));
     rc = read_sctl(s, err);

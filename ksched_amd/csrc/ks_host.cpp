@@ -242,6 +242,7 @@ int ks_load_graph(ks_ctx* c, const ks_node* nodes, size_t n, const ks_arc* arcs,
     }
     c->dev_sink_supply = (c->n_sinks == 1) ? c->nodes[c->sink_id].excess : 0;
     c->eng.set_cells(nullptr, 0);   // a plain load is one graph (ks_batch_load sets its cells after)
+    c->every_sink = false;
     const int rc = c->eng.load((int64_t)maxid, supply.data(), type.data(), alive.data(), arcs, m, c->err);
     c->store_bad = rc != KS_OK;   // the upload failed part-way: nothing may read the store
     return rc;
@@ -674,7 +675,8 @@ static int commit_call(ks_ctx* c, int32_t flags, int64_t continuation_cost, int6
         *count = n;
         return rc;
     }
-    const int64_t sink = c->n_sinks == 1 ? (int64_t)c->sink_id - 1 : -1;
+    const int64_t sink = c->n_sinks == 1 ? (int64_t)c->sink_id - 1
+                         : (c->every_sink && c->n_sinks > 1) ? ks::Engine::kEverySink : -1;
     std::vector<ks_sched_delta> v;
     bool dirty = false;
     const int rc = run(sink, &v, &dirty);

@@ -25,6 +25,8 @@ EXPORTED_SYMBOLS = (
     "ks_batch_create", "ks_batch_create_rank", "ks_batch_unique_id", "ks_batch_destroy", "ks_batch_last_error",
     "ks_batch_load", "ks_batch_solve", "ks_batch_gather",
     "ks_batch_slots", "ks_batch_owner", "ks_batch_block_len", "ks_batch_unpack",
+    "ks_batch_node_offsets", "ks_batch_translate_deltas", "ks_batch_reserve", "ks_batch_apply_deltas",
+    "ks_batch_get_graph", "ks_batch_set_bindings", "ks_batch_commit_schedule", "ks_batch_commit_preemptive",
 )
 ABI_VERSION = 5
 KS_DELTA_PLACE, KS_DELTA_PREEMPT, KS_DELTA_MIGRATE, KS_DELTA_NOOP = 0, 1, 2, 3
@@ -40,6 +42,8 @@ DELTA_DT = np.dtype({"names": ["kind", "type", "id", "src", "dst", "low", "cap",
                      "formats": ["<i4", "<i4", "<u8", "<u8", "<u8", "<u8", "<u8", "<i8", "<i8", "<i8"],
                      "offsets": [0, 4, 8, 16, 24, 32, 40, 48, 56, 64], "itemsize": 72})
 SCHED_DELTA_DT = np.dtype({"names": ["type", "_pad", "task", "pu"], "formats": ["<i4", "<i4", "<u8", "<u8"],
+                           "offsets": [0, 4, 8, 16], "itemsize": 24})
+BATCH_DELTA_DT = np.dtype({"names": ["type", "graph", "task", "pu"], "formats": ["<i4", "<i4", "<u8", "<u8"],
                            "offsets": [0, 4, 8, 16], "itemsize": 24})
 FLOW_DT = np.dtype({"names": ["src", "dst", "flow"], "formats": ["<u8", "<u8", "<i8"],
                     "offsets": [0, 8, 16], "itemsize": 24})
@@ -72,10 +76,11 @@ class KsResult(C.Structure):
                 ("cells", C.c_int32), ("compact", C.c_int32), ("ms_cell_kernel", C.c_double),
                 ("cell_ticks_max", C.c_uint64), ("cell_ticks_sum", C.c_uint64), ("fs_arc_scans", C.c_uint64),
                 ("cell_fallbacks", C.c_uint64), ("cycles_cancelled", C.c_uint64), ("fb_resets", C.c_uint64),
-                ("cycles_rejected", C.c_uint64), ("gu_leaf_scans", C.c_uint64), ("reserved3", C.c_uint64 * 2)]
+                ("cycles_rejected", C.c_uint64), ("gu_leaf_scans", C.c_uint64), ("cells_run", C.c_int32),
+                ("reserved4", C.c_int32), ("reserved3", C.c_uint64 * 1)]
 
     def as_dict(self) -> dict:
-        d = {k: getattr(self, k) for k, _ in self._fields_ if k not in ("ms_phase", "reserved3")}
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k not in ("ms_phase", "reserved3", "reserved4")}
         names = ("build", "saturate", "cycles", "price_refine", "verify", "total")
         d["ms"] = dict(zip(names, list(self.ms_phase)))
         return d
@@ -198,6 +203,15 @@ def _bind(path: str):
     L.ks_batch_block_len.argtypes = [C.c_size_t, C.c_int, C.c_size_t]
     L.ks_batch_block_len.restype = C.c_size_t
     L.ks_batch_unpack.argtypes = [V, C.c_size_t, C.c_int, C.c_size_t, V, V, V]
+    L.ks_batch_node_offsets.argtypes = [V, C.c_size_t, C.c_size_t, V]
+    L.ks_batch_translate_deltas.argtypes = [C.c_int64, C.c_int64, V, C.c_size_t, V]
+    L.ks_batch_reserve.argtypes = [V, C.c_size_t]
+    L.ks_batch_apply_deltas.argtypes = [V, C.c_size_t, P(V), P(C.c_size_t)]
+    L.ks_batch_get_graph.argtypes = [V, C.c_size_t, V, C.c_size_t, P(C.c_size_t), V, C.c_size_t, P(C.c_size_t)]
+    L.ks_batch_set_bindings.argtypes = [V, C.c_size_t, V, V, C.c_size_t]
+    L.ks_batch_commit_schedule.argtypes = [V, C.c_int32, C.c_int64, V, C.c_size_t, P(C.c_size_t), P(KsCommitStats)]
+    L.ks_batch_commit_preemptive.argtypes = [V, C.c_int32, C.c_int64, C.c_int64, V, C.c_size_t, P(C.c_size_t),
+                                             P(KsPreemptStats)]
     L.ks_set_bindings.argtypes = [V, V, V, C.c_size_t]
     L.ks_scheduling_deltas.argtypes = [V, C.c_int, V, C.c_size_t, P(C.c_size_t)]
     L.ks_update_unsched_costs.argtypes = [V, V, C.c_size_t, C.c_int32, C.c_int64, C.c_int64, P(C.c_size_t)]
@@ -469,7 +483,10 @@ class Batch:
             pass
 
     def load(self, graphs):
-        arrs = [graph_arrays(g) for g in graphs]
+        self.load_arrays([graph_arrays(g) for g in graphs])
+
+    def load_arrays(self, arrs):
+        """ks_batch_load of prebuilt (nodes NODE_DT, arcs ARC_DT) pairs, one per graph."""
         k = len(arrs)
         self._keep = arrs
         npt = (C.c_void_p * max(1, k))(*[a[0].ctypes.data for a in arrs])
@@ -478,6 +495,60 @@ class Batch:
         ms = (C.c_size_t * max(1, k))(*[a[1].shape[0] for a in arrs])
         self._check(self._L.ks_batch_load(self._h, k, npt, ns, apt, ms))
         self.ngraphs = k
+
+    # -- rounds: deltas, the graph as it stands, bindings, commits ------------
+    def reserve(self, spare_ids: int):
+        """ks_batch_reserve: node ids every graph may grow by; takes effect at the next load."""
+        self._check(self._L.ks_batch_reserve(self._h, spare_ids))
+
+    def apply_deltas(self, streams):
+        """ks_batch_apply_deltas: one DELTA_DT array (graph-local ids) or None per graph."""
+        if len(streams) != self.ngraphs:
+            raise ValueError("one stream (or None) per loaded graph")
+        arrs = [None if d is None else np.ascontiguousarray(d, DELTA_DT) for d in streams]
+        k = max(1, len(arrs))
+        ptr = (C.c_void_p * k)(*[None if a is None or a.shape[0] == 0 else a.ctypes.data for a in arrs])
+        cnt = (C.c_size_t * k)(*[0 if a is None else a.shape[0] for a in arrs])
+        self._check(self._L.ks_batch_apply_deltas(self._h, len(arrs), ptr, cnt))
+
+    def get_graph(self, g: int):
+        """ks_batch_get_graph: graph g as it stands, graph-local ids → (nodes NODE_DT, arcs ARC_DT)."""
+        n, m = C.c_size_t(), C.c_size_t()
+        self._check(self._L.ks_batch_get_graph(self._h, g, None, 0, C.byref(n), None, 0, C.byref(m)))
+        nodes = np.zeros(n.value, NODE_DT)
+        arcs = np.zeros(m.value, ARC_DT)
+        self._check(self._L.ks_batch_get_graph(self._h, g, nodes.ctypes.data, n.value, C.byref(n), arcs.ctypes.data,
+                                               m.value, C.byref(m)))
+        return nodes, arcs
+
+    def set_bindings(self, g: int, bindings: dict[int, int]):
+        t = np.fromiter(bindings.keys(), np.uint64, len(bindings))
+        p = np.fromiter(bindings.values(), np.uint64, len(bindings))
+        self._check(self._L.ks_batch_set_bindings(self._h, g, t.ctypes.data, p.ctypes.data, t.shape[0]))
+
+    def commit_schedule(self, continuation: int = 0, resource_caps: bool = True):
+        """ks_batch_commit_schedule → (deltas BATCH_DELTA_DT grouped by graph, stats summed
+        over the local devices). Invalidates the solution: gather first."""
+        flags = KS_COMMIT_RESOURCE_CAPS if resource_caps else 0
+        cnt = C.c_size_t()
+        self._check(self._L.ks_batch_commit_schedule(self._h, flags, continuation, None, 0, C.byref(cnt), None))
+        out = np.zeros(max(cnt.value, 1), BATCH_DELTA_DT)
+        st = KsCommitStats()
+        self._check(self._L.ks_batch_commit_schedule(self._h, flags, continuation, out.ctypes.data, cnt.value,
+                                                     C.byref(cnt), C.byref(st)))
+        return out[:cnt.value], st.as_dict()
+
+    def commit_preemptive(self, continuation: int = 0, preemption: int = 0, resource_caps: bool = True):
+        """ks_batch_commit_preemptive → (deltas BATCH_DELTA_DT grouped by graph, stats)."""
+        flags = KS_COMMIT_RESOURCE_CAPS if resource_caps else 0
+        cnt = C.c_size_t()
+        self._check(self._L.ks_batch_commit_preemptive(self._h, flags, continuation, preemption, None, 0,
+                                                       C.byref(cnt), None))
+        out = np.zeros(max(cnt.value, 1), BATCH_DELTA_DT)
+        st = KsPreemptStats()
+        self._check(self._L.ks_batch_commit_preemptive(self._h, flags, continuation, preemption, out.ctypes.data,
+                                                       cnt.value, C.byref(cnt), C.byref(st)))
+        return out[:cnt.value], st.as_dict()
 
     def solve(self) -> list[SolveResult]:
         rs = (KsResult * self.local)()
@@ -500,6 +571,28 @@ def batch_owner(g: int, world: int) -> tuple[int, int]:
     if load().ks_batch_owner(g, world, C.byref(r), C.byref(sl)) != KS_OK:
         raise KsError(KS_E_INVALID, "ks_batch_owner")
     return r.value, sl.value
+
+
+def batch_node_offsets(maxids, spare: int = 0) -> np.ndarray:
+    """ks_batch_node_offsets: the k + 1 node-id offsets of k graphs in a device's union."""
+    mx = np.ascontiguousarray(maxids, np.uint64)
+    off = np.zeros(mx.shape[0] + 1, np.int64)
+    rc = load().ks_batch_node_offsets(mx.ctypes.data, mx.shape[0], spare, off.ctypes.data)
+    if rc != KS_OK:
+        raise KsError(rc, "ks_batch_node_offsets")
+    return off
+
+
+def batch_translate_deltas(lo: int, hi: int, deltas: np.ndarray, out: np.ndarray | None = None) -> np.ndarray:
+    """ks_batch_translate_deltas: a graph-local stream into the id range (lo, hi] of a union
+    (out may be the input array itself). KsError(KS_E_RANGE) when an id leaves the range."""
+    d = np.ascontiguousarray(deltas, DELTA_DT)
+    if out is None:
+        out = np.zeros(d.shape[0], DELTA_DT)
+    rc = load().ks_batch_translate_deltas(lo, hi, d.ctypes.data, d.shape[0], out.ctypes.data)
+    if rc != KS_OK:
+        raise KsError(rc, "ks_batch_translate_deltas: an id outside the graph's range")
+    return out
 
 
 def batch_block_len(ngraphs: int, world: int, max_tasks: int) -> int:
