@@ -34,6 +34,10 @@
  *                            updateRunningTaskToUnscheduledAggArc (:1164-1181), TaskEvicted
  *                            (:412-433), TaskMigrated (:407-410) and capacityFromResNodeToParent
  *                            returning NumSlotsBelow (:662-667)
+ *   ks_remove_resources      DeregisterResource (flowscheduler/scheduler.go:162-210): dfsEvictTasks
+ *                            (:533-566) → TaskEvicted, RemoveResourceTopology (:362-387) with
+ *                            traverseAndRemoveTopology (graph_manager.go:829-844) and the
+ *                            ancestors' capacities, generated and applied on device
  *   ks_last_error            the panics of solver.go:97-108, 148-153, 175-178, 223-225
  *                            become status codes + a message
  *
@@ -88,7 +92,8 @@ extern "C" {
                                   ks_batch_commit_* calls, the layout helpers
                                   ks_batch_node_offsets / ks_batch_translate_deltas, and
                                   ks_result.cells_run (half of a reserved word: the struct
-                                  keeps its size).
+                                  keeps its size). ks_remove_resources (still 5: an
+                                  entry point and its stats struct were added).
                                   ks_opts (96 B) CHANGED SIZE in ABI 2 and ks_result in
                                   ABI 2, 3 and 5: a caller must check
                                   ks_abi_version() == KSMCMF_ABI_VERSION before ks_create. */
@@ -590,6 +595,80 @@ int ks_commit_preemptive(ks_ctx* ctx, int32_t flags, int64_t continuation_cost, 
                          const uint64_t* unsched_ids, size_t k,
                          ks_sched_delta* out, size_t cap, size_t* count,
                          ks_preempt_stats* stats /* may be NULL */);
+
+#define KS_REMOVE_RESOURCE_CAPS 1   /* refresh the surviving resource arcs' capacities      */
+#define KS_REMOVE_PREEMPTIVE    2   /* capacity rule of ks_commit_preemptive (slots), else
+                                       that of ks_commit_schedule (slots − running)         */
+
+typedef struct ks_remove_stats {    /* 96 B */
+    int64_t roots;             /* distinct roots                                         */
+    int64_t nodes_removed;     /* nodes of the subtree (the REMOVE_NODE records)         */
+    int64_t pus_removed;       /* of those, PUs                                          */
+    int64_t tasks_evicted;     /* PREEMPT deltas written to evicted                      */
+    int64_t arcs_removed;      /* arcs that left the graph: those with an endpoint in the
+                                  subtree and the resource arcs whose capacity fell to 0
+                                  (ks_store_stats.killed of the stream)                  */
+    int64_t cap_updates;       /* resource arcs whose capacity changed                   */
+    int64_t records;           /* delta records generated on device and applied:
+                                  nodes_removed + cap_updates                            */
+    int64_t reserved[5];
+} ks_remove_stats;
+
+/* A machine, a rack or any resource subtree leaves the cluster, on device:
+ * DeregisterResource (flowscheduler/scheduler.go:162-210) — dfsEvictTasks (:533-566) →
+ * HandleTaskEviction → TaskEvicted (flowmanager/graph_manager.go:412-433) for every task
+ * bound anywhere in the subtree, then RemoveResourceTopology (:362-387) with
+ * traverseAndRemoveTopology (:829-844) for its nodes, and updateResourceStatsUpToRoot for
+ * the ancestors' capacities. The REMOVE_NODE records and the capacity records are
+ * generated in device memory and applied as ONE stream with the semantics of
+ * ks_apply_deltas (all or nothing, in place, store counters, warm-start bookkeeping, the
+ * dirty-cell marks of a partition); only the roots, the removed ids, the evictions and
+ * the host's node edits cross PCIe.
+ *   - Subtree: the roots plus every node reached from them along arcs u → v whose head v
+ *     is a PU, a machine or an intermediate node. The walk never enters the sink, a task
+ *     or a type-0 node. A root may be a PU, a machine, an intermediate node or a type-0
+ *     node: a Quincy rack is type 0, and so is an unscheduled aggregator, which then goes
+ *     alone (JobCompleted's removeUnscheduledAggNode). A root that is dead, beyond the
+ *     graph, a task or a sink: KS_E_INVALID, the error names the id, nothing changes. A
+ *     root listed twice, or one inside another root's subtree, is removed once. A node
+ *     that a surviving parent also reaches is still removed (the reference assumes a tree).
+ *     The walk follows the arcs the store holds, and a capacity of 0 removes an arc: under
+ *     ks_commit_schedule's rule (slots − running) a full machine has no arc into its PU and
+ *     a rack none into a full machine, so after pinned commits name such PUs and machines
+ *     as roots too (a root inside another root's subtree costs nothing).
+ *   - removed receives the removed NodeIDs in ascending order (rcap: its room): the caller
+ *     owns id reuse (flowgraph/graph.go:169-182) and needs the removed PUs.
+ *   - evicted receives one KS_DELTA_PREEMPT (task, the PU it leaves) per task whose
+ *     device-kept binding (ks_set_bindings, the commits) is a removed node, in task-id
+ *     order (ecap: its room), and the task is unbound. Nothing else of the task changes:
+ *     its running arc goes with the PU and its other arcs into removed nodes go with them;
+ *     its surviving arcs and their costs are the host's business before the next solve
+ *     (:432), as ks_commit_preemptive says of a PREEMPT. After ks_commit_schedule (pinned
+ *     mode) an evicted task has NO out-arc left: the caller re-adds its arcs, and the +1
+ *     on its aggregator → sink arc, through ks_apply_deltas — the device cannot know the
+ *     job of a task whose aggregator arc the pin deleted.
+ *   - removed == NULL and evicted == NULL: a probe, *nremoved and *nevicted only, nothing
+ *     changes. rcap < *nremoved or ecap < *nevicted: KS_E_INVALID, the counts are
+ *     written, nothing changes.
+ *   - KS_REMOVE_RESOURCE_CAPS: the BFS and sums of ks_topology_stats over the graph
+ *     without the subtree, a PU's slots being the capacity of its arc into the sink and
+ *     its running count the running arcs (type 1) into it; every surviving arc that is a
+ *     resource arc under ks_commit_schedule's rule is set to slots_below − running_below
+ *     of its head, or with KS_REMOVE_PREEMPTIVE to slots_below (ks_commit_preemptive's
+ *     rule). Only changed arcs get a record; 0 removes the arc; a capacity below the arc's
+ *     lower bound: KS_E_VERIFY, nothing changes. A context with other than one sink
+ *     refuses the flag (KS_E_INVALID), as the commits do.
+ *   - KS_REMOVE_PREEMPTIVE without KS_REMOVE_RESOURCE_CAPS, or any other flag bit:
+ *     KS_E_INVALID.
+ * Needs no previous solve (a pending rebuild of the residual CSR runs first, as in
+ * ks_topology_stats). On success the solution and the mapping are invalid, exactly as
+ * after ks_apply_deltas. A device failure after the records were emitted leaves the store
+ * unusable until the next ks_load_graph; the host's node table is rolled back. stats may
+ * be NULL; records == nodes_removed + cap_updates. */
+int ks_remove_resources(ks_ctx* ctx, int32_t flags, const uint64_t* roots, size_t k,
+                        uint64_t* removed, size_t rcap, size_t* nremoved,
+                        ks_sched_delta* evicted, size_t ecap, size_t* nevicted,
+                        ks_remove_stats* stats /* may be NULL */);
 
 /* ---- config 5: independent graphs sharded over GPUs (SURVEY §7 step 6, §8 row e) --
  * No reference counterpart (ksched solves one graph per round,

@@ -8,6 +8,7 @@
 #pragma once
 
 #include <cstdint>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -102,6 +103,16 @@ public:
     int commit_preemptive(int flags, int64_t ccost, int64_t pcost, const uint64_t* ids, size_t k, int64_t sink_slot,
                           int64_t n_tasks, size_t cap, std::vector<ks_sched_delta>* out, size_t* count,
                           ks_preempt_stats* stats, bool* dirty, std::string& err);
+    // ks_remove_resources (the subtree of the k roots, its evictions, the capacities of what
+    // stays). probe: the counts only. Otherwise *removed receives the ids ascending and
+    // *evicted the PREEMPTs; make_edits is called once with the removed ids, before anything
+    // changes on the device: the host checks them against its node table, takes them out of
+    // it and returns the node edits of the stream (a failure there changes nothing).
+    using RemoveEdits = std::function<int(const uint64_t* ids, size_t n, std::vector<NodeEdit>* edits, std::string& err)>;
+    int remove_resources(int flags, const uint64_t* roots, size_t k, int64_t sink_slot, bool probe, size_t rcap,
+                         size_t ecap, std::vector<uint64_t>* removed, std::vector<ks_sched_delta>* evicted,
+                         size_t* nremoved, size_t* nevicted, ks_remove_stats* stats, const RemoveEdits& make_edits,
+                         bool* dirty, std::string& err);
     int device() const;
 
 private:

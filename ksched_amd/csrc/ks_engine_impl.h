@@ -362,6 +362,7 @@ struct EngineImpl {
     DBuf<unsigned long long> cm_u;      //   per node slot: aggregator / PU counts, slots and running below
     DBuf<unsigned char> cm_b;           //   per node slot: aggregator / placed flags
     DBuf<CommitCtl> cm_ctl;
+    DBuf<RemoveCtl> rm_ctl;             // ks_remove_resources: its counters (the scratch is the commit's)
 
     SchedDev schd() const {
         SchedDev d{};

@@ -452,5 +452,190 @@ int Engine::commit_preemptive(int flags, int64_t ccost, int64_t pcost, const uin
     return rc;
 }
 
+// ks_remove_resources: the third body beside commit. The subtree is marked level by level
+// (one host sync each: the depth is the topology's height below the roots), the evictions
+// and the ascending id list come from two flag scans, the capacities from the commit's
+// passes over the graph without the subtree. One control copy brings the counts; then the
+// removed ids go to the host, which checks them against its node table and returns the
+// node edits (make_edits), and the REMOVE_NODE records (stream positions 0 … nremoved − 1)
+// with the capacity records behind them reach store_apply as one stream.
+int Engine::remove_resources(int flags, const uint64_t* roots, size_t k, int64_t sink_slot, bool probe, size_t rcap,
+                             size_t ecap, std::vector<uint64_t>* removed, std::vector<ks_sched_delta>* evicted,
+                             size_t* nremoved, size_t* nevicted, ks_remove_stats* stats, const RemoveEdits& make_edits,
+                             bool* dirty, std::string& err) {
+    EngineImpl& s = *p_;
+    *dirty = false;
+    *nremoved = *nevicted = 0;
+    KS_CHECK(hipSetDevice(s.device));
+    hipStream_t st = s.stream;
+    if (!s.csr_valid) {   // the descent and the BFS walk the residual CSR
+        int rc = build(s, err);
+        if (rc) return rc;
+        s.has_prev = false;
+        s.solved = false;
+    }
+    const bool log = s.opts.log_cycles != 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    const bool caps = (flags & KS_REMOVE_RESOURCE_CAPS) != 0;
+    const int64_t ncap = s.ncap, nst = s.nstore;
+    const int hi = s.hi();
+    const bool every_sink = sink_slot == kEverySink && s.cell_off.size() >= 2;
+    if (caps && !every_sink && (sink_slot < 0 || sink_slot >= ncap)) {
+        err = "resource capacities need exactly one sink";
+        return KS_E_INVALID;
+    }
+    if (k > (size_t)INT32_MAX) {
+        err = "too many roots";
+        return KS_E_RANGE;
+    }
+    CommitDev c{};
+    c.preempt = (flags & KS_REMOVE_PREEMPTIVE) ? 1 : 0;
+    c.resource_caps = 1;
+    c.removing = 1;
+    RemoveDev r{};
+    r.k = (int)k;
+    unsigned long long *d_roots = nullptr, *d_ids = nullptr;
+    auto carve = [&](Carve<int> ci, Carve<unsigned long long> cu) {
+        for (int** a : {&r.front, &r.next, &r.nch, &r.ch_off, &r.rm, &r.rm_pos, &r.ev, &r.ev_pos}) *a = ci.take(ncap + 1);
+        for (int** a : {&c.aflag, &c.a_off}) *a = ci.take((int64_t)hi + 1);
+        for (unsigned long long** a : {&c.agg_cnt, &c.pu_slots, &c.pu_run, &c.slots, &c.running}) *a = cu.take(nst + 1);
+        d_roots = cu.take(k);
+        d_ids = cu.take(ncap + 1);
+        return std::make_pair(ci.n, cu.n);
+    };
+    const auto [n_i, n_u] = carve({nullptr}, {nullptr});
+    const int64_t nb = (nst + 4) & ~3LL;
+    KS_CHECK(s.cm_i.ensure(n_i));
+    KS_CHECK(s.cm_u.ensure(n_u));
+    KS_CHECK(s.cm_b.ensure(nb));
+    KS_CHECK(s.cm_ctl.ensure(1));
+    KS_CHECK(s.rm_ctl.ensure(1));
+    carve({s.cm_i.p}, {s.cm_u.p});
+    c.fl = r.fl = s.cm_b.p;
+    c.ctl = s.cm_ctl.p;
+    r.ctl = s.rm_ctl.p;
+    r.roots = d_roots;
+    KS_CHECK(hipMemsetAsync(s.cm_i.p, 0, n_i * sizeof(int), st));
+    KS_CHECK(hipMemsetAsync(s.cm_u.p, 0, n_u * 8, st));
+    KS_CHECK(hipMemsetAsync(s.cm_b.p, 0, nb, st));
+    KS_CHECK(hipMemsetAsync(s.cm_ctl.p, 0, sizeof(CommitCtl), st));
+    KS_CHECK(hipMemsetAsync(s.rm_ctl.p, 0, sizeof(RemoveCtl), st));
+    if (k) KS_CHECK(hipMemcpyAsync(d_roots, roots, k * 8, hipMemcpyHostToDevice, st));
+    SchedDev d = s.schd();
+    RemoveCtl h{};
+    // ---- 1. the subtree
+    KS_CHECK(sched_remove_seed(d, r, st));
+    KS_CHECK(hipMemcpyAsync(&h, r.ctl, sizeof(RemoveCtl), hipMemcpyDeviceToHost, st));
+    KS_CHECK(hipStreamSynchronize(st));
+    if (h.bad_root) {
+        const uint64_t id = roots[k - (size_t)h.bad_root];
+        err = "root " + std::to_string(id) + " is not a live resource or type-0 node (dead, beyond the graph, a task or a sink)";
+        return KS_E_INVALID;
+    }
+    const int64_t nroots = h.nfront;
+    int levels = 0;
+    for (int nf = h.nfront; nf > 0 && levels <= s.nn; ++levels) {
+        std::swap(r.front, r.next);
+        KS_CHECK(hipMemsetAsync(&r.ctl->nfront, 0, sizeof(int), st));
+        KS_CHECK(sched_remove_chunks(d, r, nf, st));
+        KS_CHECK(exclusive_sum(s, (const int*)r.nch, r.ch_off, (int64_t)nf + 1, st));
+        KS_CHECK(sched_remove_level(d, r, nf, (int)(nf + s.m2cap / 64 + 1), st));
+        KS_CHECK(hipMemcpyAsync(&h.nfront, &r.ctl->nfront, sizeof(int), hipMemcpyDeviceToHost, st));
+        KS_CHECK(hipStreamSynchronize(st));
+        nf = h.nfront;
+        if (nf < 0 || nf > ncap) {
+            err = "inconsistent frontier length";
+            return KS_E_DEVICE;
+        }
+    }
+    const auto t1 = std::chrono::steady_clock::now();
+    // ---- 2, 3. the evictions and the removed list: two flag scans over the node slots
+    KS_CHECK(sched_remove_flags(d, r, st));
+    KS_CHECK(exclusive_sum(s, (const int*)r.rm, r.rm_pos, ncap + 1, st));
+    KS_CHECK(exclusive_sum(s, (const int*)r.ev, r.ev_pos, ncap + 1, st));
+    if (log) KS_CHECK(hipStreamSynchronize(st));   // (only to split the log line's times)
+    const auto t2 = std::chrono::steady_clock::now();
+    // ---- 4. the capacities over the graph without the subtree
+    if (caps) {
+        KS_CHECK(sched_commit_pu(d, c, st));
+        KS_CHECK(sched_remove_zero_pus(d, r, c, st));
+        int rc = topo_bfs(s, d, sink_slot, 0, c.pu_slots, c.pu_run, c.slots, c.running, err);
+        if (rc) return rc;
+        KS_CHECK(sched_commit_arc_flags(d, c, st));
+        KS_CHECK(exclusive_sum(s, (const int*)c.aflag, c.a_off, (int64_t)hi + 1, st));
+    }
+    KS_CHECK(sched_remove_totals(d, r, c, caps ? 1 : 0, st));
+    KS_CHECK(hipMemcpyAsync(&h, r.ctl, sizeof(RemoveCtl), hipMemcpyDeviceToHost, st));
+    KS_CHECK(hipStreamSynchronize(st));
+    const auto t3 = std::chrono::steady_clock::now();
+    if (h.nremoved < nroots || h.nremoved > ncap || h.nevicted < 0 || h.nevicted > ncap || h.rec_arc < 0 ||
+        h.rec_arc > hi) {
+        err = "inconsistent record counts";
+        return KS_E_DEVICE;
+    }
+    *nremoved = (size_t)h.nremoved;
+    *nevicted = (size_t)h.nevicted;
+    if (probe) return KS_OK;
+    if (rcap < *nremoved || ecap < *nevicted) {
+        err = rcap < *nremoved ? "removed buffer smaller than the " + std::to_string(h.nremoved) + " removed nodes"
+                               : "evicted buffer smaller than the " + std::to_string(h.nevicted) + " evicted tasks";
+        return KS_E_INVALID;
+    }
+    if (h.bad) {
+        err = "a capacity would fall below its arc's lower bound";
+        return KS_E_VERIFY;
+    }
+    const int64_t nrec = (int64_t)h.nremoved + h.rec_arc;
+    KS_CHECK(s.d_recs.ensure(std::max<size_t>(nrec, 1)));
+    KS_CHECK(s.rec_ent.ensure(std::max<size_t>(nrec, 1)));
+    KS_CHECK(s.d_edits.ensure(std::max<size_t>(h.nremoved, 1)));
+    KS_CHECK(s.sched_d.ensure(std::max(1, h.nevicted)));
+    KS_CHECK(sched_remove_emit_nodes(d, r, d_ids, s.d_recs.p, st));
+    removed->resize(h.nremoved);
+    if (h.nremoved) KS_CHECK(hipMemcpyAsync(removed->data(), d_ids, h.nremoved * 8, hipMemcpyDeviceToHost, st));
+    KS_CHECK(hipStreamSynchronize(st));
+    // the host's node table follows (and names an id it does not know as alive); from here
+    // on a failure leaves the device state unknown
+    std::vector<NodeEdit> edits;
+    int rc = make_edits(removed->data(), removed->size(), &edits, err);
+    if (rc) return rc;
+    *dirty = true;
+    if (!edits.empty())
+        KS_CHECK(hipMemcpyAsync(s.d_edits.p, edits.data(), edits.size() * sizeof(NodeEdit), hipMemcpyHostToDevice, st));
+    KS_CHECK(sched_remove_emit_evictions(d, r, s.sched_d.p, st));
+    if (caps) KS_CHECK(sched_commit_emit(d, c, s.d_recs.p, st));
+    rc = mark_cells(s, s.d_recs.p, (size_t)nrec, s.d_edits.p, edits.size(), err);
+    if (rc) return rc;
+    KS_CHECK(store_apply(s.sd(), s.d_recs.p, (int)nrec, s.rec_ent.p, s.d_edits.p, (int)edits.size(), st));
+    evicted->resize(h.nevicted);
+    if (h.nevicted)
+        KS_CHECK(hipMemcpyAsync(evicted->data(), s.sched_d.p, h.nevicted * sizeof(ks_sched_delta), hipMemcpyDeviceToHost,
+                                st));
+    rc = read_sctl(s, err);
+    if (rc == KS_OK) rc = applied(s, err);
+    if (rc) return rc;
+    if (log) {
+        const auto t4 = std::chrono::steady_clock::now();
+        auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+        std::fprintf(stderr,
+                     "remove: %lld nodes, %lld evictions, %lld records, %d levels, mark %.3f ms, evict %.3f ms, "
+                     "caps %.3f ms, emit + apply %.3f ms\n",
+                     (long long)h.nremoved, (long long)h.nevicted, (long long)nrec, levels, ms(t0, t1), ms(t1, t2),
+                     ms(t2, t3), ms(t3, t4));
+    }
+    s.incremental = true;
+    s.solved = false;
+    if (h.rec_arc && s.cell_refused_values) s.cell_refused = s.cell_refused_values = false;   // (as run_apply)
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        stats->roots = nroots;
+        stats->nodes_removed = h.nremoved;
+        stats->tasks_evicted = h.nevicted;
+        stats->arcs_removed = s.h_sctl->killed;
+        stats->cap_updates = h.rec_arc;
+        stats->records = nrec;
+    }
+    return KS_OK;
+}
 
 }  // namespace ks

@@ -20,6 +20,7 @@
 #include <cstdint>
 #include <cstring>
 #include <new>
+#include <optional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -165,6 +166,70 @@ int store_guard(ks_ctx* c) {
                                  "reload the graph (ks_load_graph)");
 }
 
+// The node table's side of one record stream (ks_apply_deltas, ks_remove_resources). Every
+// node the stream touches is saved at its first touch, so the stream applies entirely or
+// not at all; edits() turns the touched nodes into the store's node edits and moves the
+// aggregates, rollback_applied() undoes both after a device failure.
+struct NodeTxn {
+    ks_ctx* c;
+    std::vector<std::pair<uint64_t, NodeRec>> saved;   // first-touch state of every touched node
+    int64_t sum0 = 0, sinks0 = 0, tasks0 = 0, dsink0 = 0;
+    uint64_t sink0 = 0;
+
+    explicit NodeTxn(ks_ctx* ctx) : c(ctx) {
+        if (++c->epoch == 0) {   // epoch wrapped: forget old stamps
+            for (auto& st : c->ids) st.epoch = 0;
+            c->epoch = 1;
+        }
+    }
+    void touch(uint64_t id) {
+        ensure_node(c, id);
+        if (c->ids[id].epoch != c->epoch) {
+            c->ids[id].epoch = c->epoch;
+            c->ids[id].lastrm = -1;
+            saved.emplace_back(id, c->nodes[id]);
+        }
+    }
+    void remove(uint64_t id, int32_t pos) {   // REMOVE_NODE at stream position pos
+        touch(id);
+        c->nodes[id] = NodeRec{};
+        c->ids[id].lastrm = pos;
+    }
+    void rollback_nodes() {
+        for (auto it = saved.rbegin(); it != saved.rend(); ++it) c->nodes[it->first] = it->second;
+    }
+    void edits(std::vector<ks::NodeEdit>& out) {
+        out.reserve(saved.size());
+        sum0 = c->sum_others, sinks0 = c->n_sinks, tasks0 = c->n_tasks, dsink0 = c->dev_sink_supply;
+        sink0 = c->sink_id;
+        for (const auto& sv : saved) {
+            const uint64_t id = sv.first;
+            const NodeRec& now = c->nodes[id];
+            account(c, id, sv.second, -1);
+            account(c, id, now, 1);
+            ks::NodeEdit e;
+            std::memset(&e, 0, sizeof(e));
+            e.slot = (int32_t)(id - 1);
+            e.last_rm = c->ids[id].lastrm;
+            e.supply = now.alive ? now.excess : 0;
+            e.alive = now.alive ? 1 : 0;
+            e.type = (uint8_t)std::min<int32_t>(std::max<int32_t>(now.type, 0), 255);
+            e.was_alive = sv.second.alive ? 1 : 0;
+            out.push_back(e);
+            if (now.alive && now.type == KS_NODE_SINK) c->dev_sink_supply = now.excess;
+        }
+    }
+    void rollback_applied() {
+        rollback_nodes();
+        c->sum_others = sum0;
+        c->n_sinks = sinks0;
+        c->n_tasks = tasks0;
+        c->sink_id = sink0;
+        c->dev_sink_supply = dsink0;
+        c->store_bad = true;
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -257,19 +322,8 @@ int ks_apply_deltas(ks_ctx* c, const ks_delta* d, size_t k) {
     if (k > (size_t)INT32_MAX) return c->fail(KS_E_RANGE, "delta stream too long");
     if (int g = store_guard(c)) return g;
     const auto t_in = std::chrono::steady_clock::now();
-    if (++c->epoch == 0) {   // epoch wrapped: forget old stamps
-        for (auto& st : c->ids) st.epoch = 0;
-        c->epoch = 1;
-    }
-    std::vector<std::pair<uint64_t, NodeRec>> saved;   // first-touch state of every touched node
-    auto touch = [&](uint64_t id) {
-        ensure_node(c, id);
-        if (c->ids[id].epoch != c->epoch) {
-            c->ids[id].epoch = c->epoch;
-            c->ids[id].lastrm = -1;
-            saved.emplace_back(id, c->nodes[id]);
-        }
-    };
+    NodeTxn txn(c);
+    auto touch = [&](uint64_t id) { txn.touch(id); };
     int rc = KS_OK;
     for (size_t i = 0; i < k && rc == KS_OK; ++i) {
         const ks_delta& x = d[i];
@@ -291,9 +345,7 @@ int ks_apply_deltas(ks_ctx* c, const ks_delta* d, size_t k) {
                     rc = c->fail(KS_E_INVALID, "remove of missing node " + std::to_string(x.id));
                     break;
                 }
-                touch(x.id);
-                c->nodes[x.id] = NodeRec{};
-                c->ids[x.id].lastrm = (int32_t)i;
+                txn.remove(x.id, (int32_t)i);
                 break;
             case KS_ADD_ARC:
                 rc = check_arc(c, x.src, x.dst, x.low, x.cap, x.cost);
@@ -321,29 +373,11 @@ int ks_apply_deltas(ks_ctx* c, const ks_delta* d, size_t k) {
         }
     }
     if (rc) {   // roll back: the stream is applied entirely or not at all
-        for (auto it = saved.rbegin(); it != saved.rend(); ++it) c->nodes[it->first] = it->second;
+        txn.rollback_nodes();
         return rc;
     }
     std::vector<ks::NodeEdit> edits;
-    edits.reserve(saved.size());
-    const int64_t sum0 = c->sum_others, sinks0 = c->n_sinks, tasks0 = c->n_tasks, dsink0 = c->dev_sink_supply;
-    const uint64_t sink0 = c->sink_id;
-    for (const auto& sv : saved) {
-        const uint64_t id = sv.first;
-        const NodeRec& now = c->nodes[id];
-        account(c, id, sv.second, -1);
-        account(c, id, now, 1);
-        ks::NodeEdit e;
-        std::memset(&e, 0, sizeof(e));
-        e.slot = (int32_t)(id - 1);
-        e.last_rm = c->ids[id].lastrm;
-        e.supply = now.alive ? now.excess : 0;
-        e.alive = now.alive ? 1 : 0;
-        e.type = (uint8_t)std::min<int32_t>(std::max<int32_t>(now.type, 0), 255);
-        e.was_alive = sv.second.alive ? 1 : 0;
-        edits.push_back(e);
-        if (now.alive && now.type == KS_NODE_SINK) c->dev_sink_supply = now.excess;
-    }
+    txn.edits(edits);
     c->have_solution = false;
     c->map_fresh = false;
     c->flows_fresh = false;
@@ -359,13 +393,7 @@ int ks_apply_deltas(ks_ctx* c, const ks_delta* d, size_t k) {
         // the device may have applied part of the stream: the host goes back to its
         // state before the call (nodes and aggregates) and the store is marked
         // unusable until the next ks_load_graph
-        for (auto it = saved.rbegin(); it != saved.rend(); ++it) c->nodes[it->first] = it->second;
-        c->sum_others = sum0;
-        c->n_sinks = sinks0;
-        c->n_tasks = tasks0;
-        c->sink_id = sink0;
-        c->dev_sink_supply = dsink0;
-        c->store_bad = true;
+        txn.rollback_applied();
     }
     return rc;
 }
@@ -711,6 +739,66 @@ int ks_commit_preemptive(ks_ctx* c, int32_t flags, int64_t continuation_cost, in
                                                            ids ? k : 0, sink, c->n_tasks, cap, v, count, stats, dirty,
                                                            c->err);
                        });
+}
+
+// DeregisterResource (flowscheduler/scheduler.go:162-210). The device finds the subtree, the
+// evictions and the capacity records; the host's part is the node table: the removed ids
+// come back before anything changes, each must be a live node that is no task and no sink
+// (the roots were checked on the device, and the walk enters resources only), and they
+// leave the table as the REMOVE_NODE records at stream positions 0 … n − 1 would make them.
+int ks_remove_resources(ks_ctx* c, int32_t flags, const uint64_t* roots, size_t k, uint64_t* removed, size_t rcap,
+                        size_t* nremoved, ks_sched_delta* evicted, size_t ecap, size_t* nevicted,
+                        ks_remove_stats* stats) {
+    if (!c || !nremoved || !nevicted) return KS_E_INVALID;
+    if (int g = store_guard(c)) return g;
+    if (k && !roots) return c->fail(KS_E_INVALID, "null root array");
+    if (flags & ~(KS_REMOVE_RESOURCE_CAPS | KS_REMOVE_PREEMPTIVE)) return c->fail(KS_E_INVALID, "unknown remove flag");
+    if ((flags & KS_REMOVE_PREEMPTIVE) && !(flags & KS_REMOVE_RESOURCE_CAPS))
+        return c->fail(KS_E_INVALID, "KS_REMOVE_PREEMPTIVE selects a capacity rule: it needs KS_REMOVE_RESOURCE_CAPS");
+    const bool probe = !removed && !evicted;
+    if (!probe && ((!removed && rcap) || (!evicted && ecap)))
+        return c->fail(KS_E_INVALID, "a null output buffer with room in it");
+    const int64_t sink = c->n_sinks == 1 ? (int64_t)c->sink_id - 1
+                         : (c->every_sink && c->n_sinks > 1) ? ks::Engine::kEverySink : -1;
+    std::optional<NodeTxn> txn;
+    int64_t pus = 0;
+    auto make_edits = [&](const uint64_t* ids, size_t n, std::vector<ks::NodeEdit>* edits, std::string& err) {
+        for (size_t i = 0; i < n; ++i) {
+            const uint64_t id = ids[i];
+            if (!node_alive(c, id) || c->nodes[id].type == KS_NODE_TASK || c->nodes[id].type == KS_NODE_SINK ||
+                (i && ids[i - 1] >= id)) {
+                err = "the device removes node " + std::to_string(id) + ", which the host's node table does not hold as a "
+                      "live resource";
+                return KS_E_DEVICE;
+            }
+        }
+        txn.emplace(c);
+        for (size_t i = 0; i < n; ++i) {
+            pus += c->nodes[ids[i]].type == KS_NODE_PU;
+            txn->remove(ids[i], (int32_t)i);
+        }
+        txn->edits(*edits);
+        return KS_OK;
+    };
+    std::vector<uint64_t> rm;
+    std::vector<ks_sched_delta> ev;
+    bool dirty = false;
+    const int rc = c->eng.remove_resources(flags, roots, k, sink, probe, removed ? rcap : 0, evicted ? ecap : 0, &rm,
+                                           &ev, nremoved, nevicted, stats, make_edits, &dirty, c->err);
+    if (!c->eng.solved()) c->have_solution = c->flows_fresh = c->map_fresh = false;   // a pending CSR rebuild ran
+    if (rc) {
+        if (txn) txn->rollback_applied();   // (the edits were made: the stream may be half applied, reload first)
+        else if (dirty) c->store_bad = true;
+        return rc;
+    }
+    if (probe) return KS_OK;
+    if (!rm.empty()) std::memcpy(removed, rm.data(), rm.size() * sizeof(uint64_t));
+    if (!ev.empty()) std::memcpy(evicted, ev.data(), ev.size() * sizeof(ks_sched_delta));
+    if (stats) stats->pus_removed = pus;
+    c->have_solution = false;   // as after ks_apply_deltas
+    c->map_fresh = false;
+    c->flows_fresh = false;
+    return KS_OK;
 }
 
 int ks_get_graph(ks_ctx* c, ks_node* nodes, size_t ncap, size_t* n, ks_arc* arcs, size_t acap, size_t* m) {

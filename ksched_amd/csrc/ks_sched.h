@@ -104,6 +104,8 @@ struct CommitDev {
     unsigned long long* slots;     // per node slot: slots_below (resource caps)
     unsigned long long* running;   // per node slot: running_below
     CommitCtl* ctl;
+    int removing;                  // ks_remove_resources: fl bit 4 marks a removed node; the capacity pass
+                                   //   skips every arc with such an endpoint
 };
 
 // The items of the delta kinds (sched_delta_kinds) in delta order, their chunk counts, and
@@ -125,5 +127,63 @@ hipError_t sched_commit_totals(const SchedDev& d, const CommitDev& c, hipStream_
 // Emit pass: the records into recs (item records, then new running arcs, then capacities) and
 // the bindings of every item.
 hipError_t sched_commit_emit(const SchedDev& d, const CommitDev& c, ks_delta* recs, hipStream_t st);
+
+// ---- ks_remove_resources: a resource subtree leaves the graph. DeregisterResource
+// (flowscheduler/scheduler.go:162-210): dfsEvictTasks (:533-566) → TaskEvicted
+// (graph_manager.go:412-433) for every task bound in the subtree, RemoveResourceTopology
+// (:362-387) with traverseAndRemoveTopology (:829-844) for its nodes, and the ancestors'
+// capacities (updateResourceStatsUpToRoot) through the commit's capacity pass over the
+// graph without the subtree. The REMOVE_NODE records and the capacity records are
+// generated in device memory for store_apply, as a commit's.
+constexpr unsigned char RM_FLAG = 4;   // CommitDev::fl bit of a node in the removed subtree
+
+// Device counters of one removal; the host reads them in one 32-byte copy.
+struct RemoveCtl {
+    int nfront;      // nodes the seed or the running level claimed: the next frontier's length
+    int bad_root;    // k − the index of the first illegal root (dead, out of range, a task or a sink), 0 none
+    int nremoved;    // flagged node slots (the REMOVE_NODE records, stream positions 0 … nremoved − 1)
+    int nevicted;    // live tasks whose binding names a flagged slot
+    int rec_arc;     // capacity records (resource arcs whose capacity changes)
+    int bad;         // 1: a capacity would fall below its arc's lower bound
+    int reserved[2];
+};
+
+// Scratch of one removal (device pointers; ncap node slots).
+struct RemoveDev {
+    const unsigned long long* roots;   // [k] the caller's root ids, unchecked
+    int k;
+    unsigned char* fl;                 // per node slot (word-aligned length): RM_FLAG
+    int* front;                        // [ncap + 1] node slots of the level being expanded
+    int* next;                         // [ncap + 1] node slots it claims
+    int* nch;                          // [ncap + 1] 64-position chunks of a frontier node's segment; ch_off its scan
+    int* ch_off;                       // [ncap + 1]
+    int* rm;                           // [ncap + 1] 1: the slot is removed; rm_pos its scan
+    int* rm_pos;                       // [ncap + 1]
+    int* ev;                           // [ncap + 1] 1: a live task bound to a removed slot; ev_pos its scan
+    int* ev_pos;                       // [ncap + 1]
+    RemoveCtl* ctl;
+};
+
+// Check and flag the roots; the distinct legal ones are the first frontier (next, ctl->nfront).
+hipError_t sched_remove_seed(const SchedDev& d, const RemoveDev& r, hipStream_t st);
+// Chunk counts of the nf frontier nodes (before the scan nch → ch_off).
+hipError_t sched_remove_chunks(const SchedDev& d, const RemoveDev& r, int nf, hipStream_t st);
+// One level of the descent: one wave per 64-position chunk item of the frontier's segments
+// follows the live forward arcs into PUs, machines and intermediate nodes and claims them
+// (next, ctl->nfront; the caller zeroes nfront first). ni_max bounds the chunk items.
+hipError_t sched_remove_level(const SchedDev& d, const RemoveDev& r, int nf, int ni_max, hipStream_t st);
+// Per node slot: removed (rm), a live task whose binding is removed (ev).
+hipError_t sched_remove_flags(const SchedDev& d, const RemoveDev& r, hipStream_t st);
+// A removed PU has no slots and runs nothing: the capacity sums are those of the graph
+// without the subtree (after sched_commit_pu, before the level BFS).
+hipError_t sched_remove_zero_pus(const SchedDev& d, const RemoveDev& r, const CommitDev& c, hipStream_t st);
+// Totals into r.ctl after the scans (caps: also a_off and the capacity pass's bad word),
+// and the capacity records' base into c.ctl (they follow the REMOVE_NODE records).
+hipError_t sched_remove_totals(const SchedDev& d, const RemoveDev& r, const CommitDev& c, int caps, hipStream_t st);
+// The removed ids ascending and their REMOVE_NODE records at stream positions 0 … nremoved − 1.
+hipError_t sched_remove_emit_nodes(const SchedDev& d, const RemoveDev& r, unsigned long long* ids, ks_delta* recs,
+                                   hipStream_t st);
+// One PREEMPT (task, the PU it leaves) per evicted task in task order; the task is unbound.
+hipError_t sched_remove_emit_evictions(const SchedDev& d, const RemoveDev& r, ks_sched_delta* out, hipStream_t st);
 
 }  // namespace ks

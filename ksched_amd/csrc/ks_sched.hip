@@ -24,6 +24,12 @@
 //                       updateRunningTaskToUnscheduledAggArc (:1164-1181), TaskEvicted
 //                       (:412-433), TaskMigrated (:407-410) and
 //                       capacityFromResNodeToParent returning NumSlotsBelow
+//   remove resources    DeregisterResource (flowscheduler/scheduler.go:162-210): the subtree of
+//                       a machine or a rack marked by a chunked level descent over the
+//                       residual CSR (traverseAndRemoveTopology, graph_manager.go:829-844),
+//                       the tasks bound in it evicted (dfsEvictTasks, scheduler.go:533-566),
+//                       its REMOVE_NODE records and, through the commit's capacity pass, the
+//                       ancestors' capacity records generated for store_apply
 #include "ks_sched.h"
 
 namespace ks {
@@ -374,6 +380,9 @@ __global__ void k_commit_pu_places(CommitDev c) {
 __device__ __forceinline__ int commit_arc_cap(const SchedDev& d, const CommitDev& c, int s, long long* cap) {
     if (!d.a_alive[s]) return 0;
     const int u = d.a_src[s], v = d.a_dst[s];
+    // ks_remove_resources: an arc with an endpoint in the subtree goes with it (no record may
+    // name a removed node after its removal)
+    if (c.removing && ((c.fl[u] | c.fl[v]) & RM_FLAG)) return 0;
     const unsigned char tu = d.n_type[u], tv = d.n_type[v];
     if (tv == KS_NODE_SINK) {
         if (c.preempt || !(c.fl[u] & 1) || c.agg_cnt[u] == 0) return 0;
@@ -470,6 +479,151 @@ __global__ void k_commit_emit_arcs(SchedDev d, CommitDev c, ks_delta* __restrict
     }
 }
 
+// ------------------------------------------------------------- remove resources ---
+// DeregisterResource (flowscheduler/scheduler.go:162-210) on the device-resident graph.
+// The subtree is marked by a level-synchronous descent from the roots along forward arcs
+// whose head is a PU, a machine or an intermediate resource (traverseAndRemoveTopology,
+// graph_manager.go:829-844); the sink, tasks and type-0 nodes are never entered. A frontier
+// node's residual segment is cut into 64-position chunk items (chunk counts → scan →
+// bisection, as k_commit_items / commit_item), one wave per item: a rack's thousands of
+// preference in-arcs cost it their chunks, not one wave walking them. A node is claimed by
+// an atomicOr of its flag byte's word; the claiming lanes of a wave take their places in
+// the next frontier with one atomic on its counter.
+
+// True for the one caller that sets slot v's RM_FLAG.
+__device__ __forceinline__ bool rm_claim(unsigned char* fl, int v) {
+    const unsigned bit = (unsigned)RM_FLAG << (8 * (v & 3));
+    return !(atomicOr((unsigned*)&fl[v & ~3], bit) & bit);
+}
+
+// list[*ctr ...] = v on the pred lanes, in lane order (every lane of the wave calls it).
+__device__ __forceinline__ void wave_push(int* list, int* ctr, int v, bool pred) {
+    const unsigned long long m = __ballot(pred);
+    if (!m) return;
+    const int me = (int)__lane_id(), lead = __ffsll((long long)m) - 1;
+    int base = 0;
+    if (me == lead) base = atomicAdd(ctr, __popcll(m));
+    base = __shfl(base, lead);
+    if (pred) list[base + __popcll(m & ((1ULL << me) - 1))] = v;
+}
+
+// A root must be a live node that is neither a task nor a sink: a PU, a machine, an
+// intermediate resource, or a type-0 node (a Quincy rack; an unscheduled aggregator, which
+// then goes alone: removeUnscheduledAggNode). A root listed twice is claimed once.
+__global__ void k_remove_seed(SchedDev d, RemoveDev r) {
+    for (long long i0 = blockIdx.x * (long long)SB; i0 < r.k; i0 += (long long)gridDim.x * SB) {   // (uniform per workgroup)
+        const long long i = i0 + threadIdx.x;
+        bool claim = false;
+        int v = 0;
+        if (i < r.k) {
+            const unsigned long long id = r.roots[i];
+            bool ok = id >= 1 && id <= (unsigned long long)d.ncap;
+            if (ok) {
+                v = (int)(id - 1);
+                const unsigned char t = d.n_type[v];
+                ok = d.n_alive[v] && d.perm[v] >= 0 && t != KS_NODE_TASK && t != KS_NODE_SINK;
+            }
+            if (ok) claim = rm_claim(r.fl, v);
+            else atomicMax(&r.ctl->bad_root, (int)(r.k - i));
+        }
+        wave_push(r.next, &r.ctl->nfront, v, claim);
+    }
+}
+
+__device__ __forceinline__ int remove_seg_len(const SchedDev& d, int x) {
+    return max(min(d.used[x], d.first[x + 1] - d.first[x]), 0);
+}
+
+__global__ void k_remove_chunks(SchedDev d, RemoveDev r, int nf) {
+    for (long long i = blockIdx.x * (long long)SB + threadIdx.x; i <= nf; i += (long long)gridDim.x * SB)
+        r.nch[i] = i < nf ? (remove_seg_len(d, d.perm[r.front[i]]) + 63) >> 6 : 0;
+}
+
+__global__ void k_remove_level(SchedDev d, RemoveDev r, int nf, int ni_max) {
+    const int lane = threadIdx.x & 63;
+    const int wave = (blockIdx.x * SB + threadIdx.x) >> 6;
+    const int nwaves = (gridDim.x * SB) >> 6;
+    const int ni = min(r.ch_off[nf], ni_max);
+    for (int w = wave; w < ni; w += nwaves) {
+        int lo = 0, hi = nf - 1;   // the frontier node i with ch_off[i] ≤ w < ch_off[i + 1]
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (r.ch_off[mid] <= w) lo = mid;
+            else hi = mid - 1;
+        }
+        const int x = d.perm[r.front[lo]];
+        const int b = d.first[x];
+        const int p = b + ((w - r.ch_off[lo]) << 6) + lane;
+        bool claim = false;
+        int us = 0;
+        if (p < b + remove_seg_len(d, x)) {
+            const int e = d.ent[p];
+            if (e >= 0 && !(e & 1)) {   // forward positions only: the node's live out-arcs
+                us = d.iperm[d.pos[p].head];
+                if (us >= 0) {
+                    const unsigned char t = d.n_type[us];
+                    if (t == KS_NODE_PU || t == KS_NODE_MACHINE || t == KS_NODE_INTERMEDIATE) claim = rm_claim(r.fl, us);
+                }
+            }
+        }
+        wave_push(r.next, &r.ctl->nfront, us, claim);
+    }
+}
+
+// dfsEvictTasks (scheduler.go:533-566): the tasks to evict are those the device-kept
+// bindings place on a removed node.
+__global__ void k_remove_flags(SchedDev d, RemoveDev r) {
+    for (long long v = blockIdx.x * (long long)SB + threadIdx.x; v <= d.ncap; v += (long long)gridDim.x * SB) {
+        int rm = 0, ev = 0;
+        if (v < d.ncap) {
+            rm = (r.fl[v] & RM_FLAG) != 0;
+            if (d.n_alive[v] && d.n_type[v] == KS_NODE_TASK) {
+                const unsigned long long b = d.n_bind[v];
+                ev = b >= 1 && b <= (unsigned long long)d.ncap && (r.fl[b - 1] & RM_FLAG);
+            }
+        }
+        r.rm[v] = rm;
+        r.ev[v] = ev;
+    }
+}
+
+__global__ void k_remove_zero_pus(SchedDev d, RemoveDev r, CommitDev c) {
+    for (long long v = blockIdx.x * (long long)SB + threadIdx.x; v < d.ncap; v += (long long)gridDim.x * SB)
+        if (r.fl[v] & RM_FLAG) c.pu_slots[v] = c.pu_run[v] = 0;
+}
+
+__global__ void k_remove_totals(SchedDev d, RemoveDev r, CommitDev c, int caps) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        r.ctl->nremoved = r.rm_pos[d.ncap];
+        r.ctl->nevicted = r.ev_pos[d.ncap];
+        r.ctl->rec_arc = caps ? c.a_off[d.hi] : 0;
+        r.ctl->bad = caps ? c.ctl->bad : 0;
+        c.ctl->rec_pin = r.rm_pos[d.ncap];   // k_commit_emit_arcs writes behind the REMOVE_NODE records
+        c.ctl->rec_add = 0;
+    }
+}
+
+__global__ void k_remove_emit_nodes(SchedDev d, RemoveDev r, unsigned long long* __restrict__ ids,
+                                    ks_delta* __restrict__ recs) {
+    for (long long v = blockIdx.x * (long long)SB + threadIdx.x; v < d.ncap; v += (long long)gridDim.x * SB) {
+        if (!r.rm[v]) continue;
+        const int i = r.rm_pos[v];
+        ids[i] = (unsigned long long)v + 1;
+        ks_delta x{};
+        x.kind = KS_REMOVE_NODE;
+        x.id = (uint64_t)v + 1;
+        recs[i] = x;
+    }
+}
+
+__global__ void k_remove_emit_evictions(SchedDev d, RemoveDev r, ks_sched_delta* __restrict__ out) {
+    for (long long v = blockIdx.x * (long long)SB + threadIdx.x; v < d.ncap; v += (long long)gridDim.x * SB) {
+        if (!r.ev[v]) continue;
+        out[r.ev_pos[v]] = ks_sched_delta{KS_DELTA_PREEMPT, 0, (uint64_t)v + 1, d.n_bind[v]};
+        d.n_bind[v] = 0;   // TaskEvicted: the task is unbound, nothing else of it changes here
+    }
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------ launchers ---
@@ -561,6 +715,47 @@ hipError_t sched_commit_emit(const SchedDev& d, const CommitDev& c, ks_delta* re
     // (preemptive without resource capacities: no arc slot is flagged)
     if (d.hi && (!c.preempt || c.resource_caps))
         hipLaunchKernelGGL(k_commit_emit_arcs, dim3(grid(d.hi)), dim3(SB), 0, st, d, c, recs);
+    return hipGetLastError();
+}
+
+hipError_t sched_remove_seed(const SchedDev& d, const RemoveDev& r, hipStream_t st) {
+    if (r.k) hipLaunchKernelGGL(k_remove_seed, dim3(grid(r.k)), dim3(SB), 0, st, d, r);
+    return hipGetLastError();
+}
+
+hipError_t sched_remove_chunks(const SchedDev& d, const RemoveDev& r, int nf, hipStream_t st) {
+    hipLaunchKernelGGL(k_remove_chunks, dim3(grid(nf + 1)), dim3(SB), 0, st, d, r, nf);
+    return hipGetLastError();
+}
+
+hipError_t sched_remove_level(const SchedDev& d, const RemoveDev& r, int nf, int ni_max, hipStream_t st) {
+    hipLaunchKernelGGL(k_remove_level, dim3(grid(64LL * ni_max)), dim3(SB), 0, st, d, r, nf, ni_max);
+    return hipGetLastError();
+}
+
+hipError_t sched_remove_flags(const SchedDev& d, const RemoveDev& r, hipStream_t st) {
+    hipLaunchKernelGGL(k_remove_flags, dim3(grid(d.ncap + 1)), dim3(SB), 0, st, d, r);
+    return hipGetLastError();
+}
+
+hipError_t sched_remove_zero_pus(const SchedDev& d, const RemoveDev& r, const CommitDev& c, hipStream_t st) {
+    if (d.ncap) hipLaunchKernelGGL(k_remove_zero_pus, dim3(grid(d.ncap)), dim3(SB), 0, st, d, r, c);
+    return hipGetLastError();
+}
+
+hipError_t sched_remove_totals(const SchedDev& d, const RemoveDev& r, const CommitDev& c, int caps, hipStream_t st) {
+    hipLaunchKernelGGL(k_remove_totals, dim3(1), dim3(64), 0, st, d, r, c, caps);
+    return hipGetLastError();
+}
+
+hipError_t sched_remove_emit_nodes(const SchedDev& d, const RemoveDev& r, unsigned long long* ids, ks_delta* recs,
+                                   hipStream_t st) {
+    if (d.ncap) hipLaunchKernelGGL(k_remove_emit_nodes, dim3(grid(d.ncap)), dim3(SB), 0, st, d, r, ids, recs);
+    return hipGetLastError();
+}
+
+hipError_t sched_remove_emit_evictions(const SchedDev& d, const RemoveDev& r, ks_sched_delta* out, hipStream_t st) {
+    if (d.ncap) hipLaunchKernelGGL(k_remove_emit_evictions, dim3(grid(d.ncap)), dim3(SB), 0, st, d, r, out);
     return hipGetLastError();
 }
 

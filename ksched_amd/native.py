@@ -21,7 +21,7 @@ EXPORTED_SYMBOLS = (
     "ks_apply_deltas", "ks_solve", "ks_get_flows", "ks_get_task_mapping", "ks_get_task_pu_device", "ks_solve_many",
     "ks_coalesce_deltas", "ks_get_store_stats", "ks_set_bindings", "ks_scheduling_deltas",
     "ks_update_unsched_costs", "ks_topology_stats", "ks_get_graph", "ks_commit_schedule",
-    "ks_commit_preemptive",
+    "ks_commit_preemptive", "ks_remove_resources",
     "ks_batch_create", "ks_batch_create_rank", "ks_batch_unique_id", "ks_batch_destroy", "ks_batch_last_error",
     "ks_batch_load", "ks_batch_solve", "ks_batch_gather",
     "ks_batch_slots", "ks_batch_owner", "ks_batch_block_len", "ks_batch_unpack",
@@ -32,6 +32,7 @@ ABI_VERSION = 5
 KS_DELTA_PLACE, KS_DELTA_PREEMPT, KS_DELTA_MIGRATE, KS_DELTA_NOOP = 0, 1, 2, 3
 KS_COST_SET, KS_COST_ADD = 0, 1
 KS_COMMIT_RESOURCE_CAPS = 1
+KS_REMOVE_RESOURCE_CAPS, KS_REMOVE_PREEMPTIVE = 1, 2
 
 NODE_DT = np.dtype({"names": ["id", "excess", "type", "_pad"],
                     "formats": ["<u8", "<i8", "<i4", "<i4"], "offsets": [0, 8, 16, 20], "itemsize": 24})
@@ -111,6 +112,16 @@ class KsPreemptStats(C.Structure):
                 ("running_added", C.c_int64), ("running_converted", C.c_int64), ("running_removed", C.c_int64),
                 ("unsched_cost_updates", C.c_int64), ("cap_updates", C.c_int64), ("records", C.c_int64),
                 ("reserved", C.c_int64 * 3)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class KsRemoveStats(C.Structure):
+    """ks_remove_stats: what one ks_remove_resources removed and generated on device."""
+    _fields_ = [("roots", C.c_int64), ("nodes_removed", C.c_int64), ("pus_removed", C.c_int64),
+                ("tasks_evicted", C.c_int64), ("arcs_removed", C.c_int64), ("cap_updates", C.c_int64),
+                ("records", C.c_int64), ("reserved", C.c_int64 * 5)]
 
     def as_dict(self) -> dict:
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
@@ -220,6 +231,8 @@ def _bind(path: str):
                                      P(KsCommitStats)]
     L.ks_commit_preemptive.argtypes = [V, C.c_int32, C.c_int64, C.c_int64, V, C.c_size_t, V, C.c_size_t,
                                        P(C.c_size_t), P(KsPreemptStats)]
+    L.ks_remove_resources.argtypes = [V, C.c_int32, V, C.c_size_t, V, C.c_size_t, P(C.c_size_t), V, C.c_size_t,
+                                      P(C.c_size_t), P(KsRemoveStats)]
     return L
 
 
@@ -412,6 +425,26 @@ class Context:
         self._check(self._L.ks_commit_preemptive(self._h, flags, continuation, preemption, pid, k, out.ctypes.data,
                                                  cnt.value, C.byref(cnt), C.byref(st)))
         return out[:cnt.value], st.as_dict()
+
+    def remove_resources(self, roots, resource_caps: bool = True, preemptive: bool = False):
+        """ks_remove_resources: the subtrees of the root ids (machines, racks, PUs, or an
+        unscheduled aggregator, which goes alone) leave the device-resident graph; every
+        task bound in them is evicted and unbound and, with resource_caps, the surviving
+        resource arcs get their capacities (preemptive: the rule of commit_preemptive).
+        → (removed ids ascending uint64, evicted SCHED_DELTA_DT PREEMPTs in task order,
+        stats dict). Needs no solve; invalidates the solution."""
+        ids = np.ascontiguousarray(roots, np.uint64).reshape(-1)
+        flags = (KS_REMOVE_RESOURCE_CAPS if resource_caps else 0) | (KS_REMOVE_PREEMPTIVE if preemptive else 0)
+        nr, ne = C.c_size_t(), C.c_size_t()
+        self._check(self._L.ks_remove_resources(self._h, flags, ids.ctypes.data, ids.shape[0], None, 0, C.byref(nr),
+                                                None, 0, C.byref(ne), None))
+        removed = np.zeros(max(nr.value, 1), np.uint64)
+        evicted = np.zeros(max(ne.value, 1), SCHED_DELTA_DT)
+        st = KsRemoveStats()
+        self._check(self._L.ks_remove_resources(self._h, flags, ids.ctypes.data, ids.shape[0], removed.ctypes.data,
+                                                nr.value, C.byref(nr), evicted.ctypes.data, ne.value, C.byref(ne),
+                                                C.byref(st)))
+        return removed[:nr.value], evicted[:ne.value], st.as_dict()
 
     def task_pu_device(self, dev_ptr: int, cap: int) -> int:
         cnt = C.c_size_t()
