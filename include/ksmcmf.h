@@ -38,6 +38,11 @@
  *                            (:533-566) → TaskEvicted, RemoveResourceTopology (:362-387) with
  *                            traverseAndRemoveTopology (graph_manager.go:829-844) and the
  *                            ancestors' capacities, generated and applied on device
+ *   ks_complete_tasks        HandleTaskCompletion (flowscheduler/scheduler.go:106-132) →
+ *                            TaskCompleted (graph_manager.go:389-405) → removeTaskNode
+ *                            (:803-813) and updateUnscheduledAggNode(−1) (:1291-1305); also
+ *                            TaskFailed / TaskKilled (:435-452), generated and applied on device
+ *   ks_get_bindings          the TaskBindings the device keeps (ks_set_bindings, the commits)
  *   ks_last_error            the panics of solver.go:97-108, 148-153, 175-178, 223-225
  *                            become status codes + a message
  *
@@ -94,6 +99,8 @@ extern "C" {
                                   ks_result.cells_run (half of a reserved word: the struct
                                   keeps its size). ks_remove_resources (still 5: an
                                   entry point and its stats struct were added).
+                                  ks_complete_tasks and ks_get_bindings (still 5: two
+                                  entry points and one stats struct were added).
                                   ks_opts (96 B) CHANGED SIZE in ABI 2 and ks_result in
                                   ABI 2, 3 and 5: a caller must check
                                   ks_abi_version() == KSMCMF_ABI_VERSION before ks_create. */
@@ -669,6 +676,82 @@ int ks_remove_resources(ks_ctx* ctx, int32_t flags, const uint64_t* roots, size_
                         uint64_t* removed, size_t rcap, size_t* nremoved,
                         ks_sched_delta* evicted, size_t ecap, size_t* nevicted,
                         ks_remove_stats* stats /* may be NULL */);
+
+#define KS_COMPLETE_RESOURCE_CAPS 1   /* refresh the resource arcs' capacities            */
+#define KS_COMPLETE_PREEMPTIVE    2   /* capacity rule of ks_commit_preemptive (slots),
+                                         else ks_commit_schedule's (slots − running)     */
+
+typedef struct ks_complete_stats {    /* 96 B */
+    int64_t tasks;            /* distinct tasks removed (the REMOVE_NODE records)         */
+    int64_t bound;            /* of those, tasks that were bound to a PU                  */
+    int64_t arcs_removed;     /* arcs that left the graph (ks_store_stats.killed)         */
+    int64_t unsched_updates;  /* aggregator → sink arcs whose capacity changed            */
+    int64_t cap_updates;      /* resource arcs whose capacity changed                     */
+    int64_t records;          /* tasks + unsched_updates + cap_updates                    */
+    int64_t reserved[6];
+} ks_complete_stats;
+
+/* Finished tasks leave the graph, on device: HandleTaskCompletion
+ * (flowscheduler/scheduler.go:106-132) → TaskCompleted (flowmanager/graph_manager.go:389-405)
+ * → removeTaskNode (:803-813), with updateUnscheduledAggNode(−1) (:396, :1291-1305).
+ * TaskFailed and TaskKilled (:435-452, scheduler.go:272-306) are the same graph edit. The
+ * records are generated in device memory and applied as ONE stream with the semantics of
+ * ks_apply_deltas (all or nothing, in place, store counters, warm-start bookkeeping, the
+ * dirty-cell marks of a partition): one REMOVE_NODE per distinct task in ascending id order
+ * at stream positions 0 … n − 1, then the capacity records in arc-slot order. No (src, dst)
+ * appears twice (ks_store_stats.superseded stays 0). Only the task ids, left and the host's
+ * node edits cross PCIe.
+ *   - Every id must be a live task node. The first id that is 0, beyond the graph, dead or
+ *     not of type task: KS_E_INVALID, the error names the id, nothing changes. An id listed
+ *     twice is removed once.
+ *   - left (k entries, may be NULL): left[i] is the PU tasks[i] was bound to on the device
+ *     (ks_set_bindings, the commits), 0 if unbound, aligned with the input (duplicates get
+ *     the same value). It is read before the store unbinds the removed task; the caller
+ *     needs it for unbindTaskFromResource (scheduler.go:106-132).
+ *   - Aggregators: unsched_ids, nu of them; NULL: every type-0 node with an arc into the
+ *     sink, as in the commits. On its arc into the sink an aggregator loses one unit of
+ *     capacity per completed task that still had an arc into it; capacity 0 removes the
+ *     arc. One rule for both modes: after ks_commit_preemptive every task keeps that arc and
+ *     loses the unit (TaskCompleted's −1); after ks_commit_schedule a pinned task has no such
+ *     arc and nothing moves (the pin already took the unit, :393-396). In pinned mode a task
+ *     that was never placed does lose the unit here, where the reference leaves the
+ *     capacity one too high: there this call has no reference counterpart. A capacity that
+ *     would fall below its arc's lower bound: KS_E_VERIFY, nothing changes.
+ *   - KS_COMPLETE_RESOURCE_CAPS: the BFS and sums of ks_topology_stats over the graph
+ *     without the completed tasks, a PU's slots being the capacity of its arc into the sink
+ *     and its running count the running arcs (type 1) into it whose tail is not a completed
+ *     task; every arc that is a resource arc under ks_commit_schedule's rule is set to
+ *     slots_below − running_below of its head, or with KS_COMPLETE_PREEMPTIVE to
+ *     slots_below. Only changed arcs get a record; 0 removes the arc; a capacity below the
+ *     arc's lower bound: KS_E_VERIFY, nothing changes. A context with other than one sink
+ *     refuses the flag (KS_E_INVALID), as the commits do. Under ks_commit_preemptive's rule
+ *     a completion changes no resource capacity: such callers leave the flag off, the BFS
+ *     is the expensive part of the call.
+ *   - k == 0 is legal: without KS_COMPLETE_RESOURCE_CAPS nothing happens and the solution
+ *     stays valid; with it the call is a plain refresh of the resource capacities (and
+ *     keeps the solution when every capacity already stands).
+ *   - KS_COMPLETE_PREEMPTIVE without KS_COMPLETE_RESOURCE_CAPS, or any other flag bit:
+ *     KS_E_INVALID.
+ *   - Pinned mode (slots − running): a full PU has no arc from its machine and a full
+ *     machine none from its rack, since a capacity of 0 removes an arc, and the device
+ *     cannot re-create an arc the store no longer holds. Before completing tasks that ran
+ *     on full PUs: ks_get_bindings for the finishing tasks, ks_apply_deltas with ADD_ARC
+ *     upserts of those PUs' parent chains (any positive capacity), then this call with
+ *     KS_COMPLETE_RESOURCE_CAPS, which sets every one of them to its right value.
+ * Needs no previous solve (a pending rebuild of the residual CSR runs first, as in
+ * ks_remove_resources). On success with k > 0 or any record the solution and the mapping
+ * are invalid, exactly as after ks_apply_deltas. A device failure after the records were
+ * emitted leaves the store unusable until the next ks_load_graph; the host's node table is
+ * rolled back. stats may be NULL; records == tasks + unsched_updates + cap_updates. */
+int ks_complete_tasks(ks_ctx* ctx, int32_t flags, const uint64_t* tasks, size_t k,
+                      const uint64_t* unsched_ids, size_t nu,
+                      uint64_t* left /* k entries, may be NULL */,
+                      ks_complete_stats* stats /* may be NULL */);
+
+/* pu[i] = the PU task[i] is bound to on the device (ks_set_bindings, the commits), 0 =
+ * unbound: for the pinned recipe above and for checkpoints. A task id that is not a live
+ * task: KS_E_INVALID. */
+int ks_get_bindings(ks_ctx* ctx, const uint64_t* task, uint64_t* pu, size_t k);
 
 /* ---- config 5: independent graphs sharded over GPUs (SURVEY §7 step 6, §8 row e) --
  * No reference counterpart (ksched solves one graph per round,

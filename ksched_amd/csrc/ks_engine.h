@@ -113,6 +113,16 @@ public:
                          size_t ecap, std::vector<uint64_t>* removed, std::vector<ks_sched_delta>* evicted,
                          size_t* nremoved, size_t* nevicted, ks_remove_stats* stats, const RemoveEdits& make_edits,
                          bool* dirty, std::string& err);
+    // ks_complete_tasks (the k task ids leave the graph; the aggregators' and, with the caps
+    // flag, the resource arcs' capacities follow). left (k entries, may be null) receives the
+    // bindings read before anything changes. make_edits is called once with the distinct ids
+    // ascending, as in remove_resources. *changed: records were applied (the solution is
+    // invalid); a call with k == 0 whose refresh finds every capacity right changes nothing.
+    int complete_tasks(int flags, const uint64_t* tasks, size_t k, const uint64_t* unsched_ids, size_t nu,
+                       int64_t sink_slot, uint64_t* left, ks_complete_stats* stats, const RemoveEdits& make_edits,
+                       bool* dirty, bool* changed, std::string& err);
+    // ks_get_bindings: pu[i] = the device-kept binding of task[i] (ids checked by the caller).
+    int get_bindings(const uint64_t* task, uint64_t* pu, size_t k, std::string& err);
     int device() const;
 
 private:

@@ -1,5 +1,6 @@
 // ks_engine_sched.hip — the engine's scheduler glue: bindings, scheduling deltas,
-// unscheduled costs, topology statistics, ks_commit_schedule and ks_commit_preemptive. It launches the
+// unscheduled costs, topology statistics, ks_commit_schedule and ks_commit_preemptive,
+// ks_remove_resources, ks_complete_tasks and ks_get_bindings. It launches the
 // kernels of ks_sched.hip and ks_store.hip through their launchers, none of the engine's.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -635,6 +636,208 @@ int Engine::remove_resources(int flags, const uint64_t* roots, size_t k, int64_t
         stats->cap_updates = h.rec_arc;
         stats->records = nrec;
     }
+    return KS_OK;
+}
+
+// ks_complete_tasks: the fourth body. The ids are checked and claimed in the flag bytes (one
+// host sync: the first illegal id, the distinct count, left), their segments' chunk items
+// count the aggregators' losses, the ascending id list comes from the removal's flag scan and
+// the capacities from the commit's passes in their completing mode. One more sync brings the
+// counts; then the ids go to the host for its node edits (make_edits) and the REMOVE_NODE
+// records (stream positions 0 … n − 1) with the capacity records behind them reach store_apply
+// as one stream.
+int Engine::complete_tasks(int flags, const uint64_t* tasks, size_t k, const uint64_t* unsched_ids, size_t nu,
+                           int64_t sink_slot, uint64_t* left, ks_complete_stats* stats, const RemoveEdits& make_edits,
+                           bool* dirty, bool* changed, std::string& err) {
+    EngineImpl& s = *p_;
+    *dirty = *changed = false;
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    const bool caps = (flags & KS_COMPLETE_RESOURCE_CAPS) != 0;
+    if (!k && !caps) return KS_OK;
+    KS_CHECK(hipSetDevice(s.device));
+    hipStream_t st = s.stream;
+    if (!s.csr_valid) {   // the chunk items and the BFS walk the residual CSR
+        int rc = build(s, err);
+        if (rc) return rc;
+        s.has_prev = false;
+        s.solved = false;
+    }
+    const bool log = s.opts.log_cycles != 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int64_t ncap = s.ncap, nst = s.nstore;
+    const int hi = s.hi();
+    const bool every_sink = sink_slot == kEverySink && s.cell_off.size() >= 2;
+    if (caps && !every_sink && (sink_slot < 0 || sink_slot >= ncap)) {
+        err = "resource capacities need exactly one sink";
+        return KS_E_INVALID;
+    }
+    if (k > (size_t)INT32_MAX || nu > (size_t)INT32_MAX) {
+        err = "too many ids";
+        return KS_E_RANGE;
+    }
+    for (size_t i = 0; unsched_ids && i < nu; ++i)
+        if (unsched_ids[i] == 0 || (int64_t)unsched_ids[i] > nst) {
+            err = "unscheduled aggregator id beyond the graph";
+            return KS_E_INVALID;
+        }
+    CommitDev c{};
+    c.preempt = (flags & KS_COMPLETE_PREEMPTIVE) ? 1 : 0;
+    c.resource_caps = caps ? 1 : 0;
+    c.removing = 1;   // (no capacity record names a completed task)
+    c.completing = 1;
+    RemoveDev r{};
+    r.k = (int)k;
+    unsigned long long *d_tasks = nullptr, *d_left = nullptr, *d_agg = nullptr, *d_ids = nullptr;
+    auto carve = [&](Carve<int> ci, Carve<unsigned long long> cu) {
+        for (int** a : {&r.front, &r.next, &r.nch, &r.ch_off, &r.rm, &r.rm_pos, &r.ev, &r.ev_pos}) *a = ci.take(ncap + 1);
+        for (int** a : {&c.aflag, &c.a_off}) *a = ci.take((int64_t)hi + 1);
+        for (unsigned long long** a : {&c.agg_cnt, &c.pu_slots, &c.pu_run, &c.slots, &c.running}) *a = cu.take(nst + 1);
+        d_tasks = cu.take(k);
+        d_left = cu.take(k);
+        d_agg = cu.take(nu);
+        d_ids = cu.take(ncap + 1);
+        return std::make_pair(ci.n, cu.n);
+    };
+    const auto [n_i, n_u] = carve({nullptr}, {nullptr});
+    const int64_t nb = (nst + 4) & ~3LL;
+    KS_CHECK(s.cm_i.ensure(n_i));
+    KS_CHECK(s.cm_u.ensure(n_u));
+    KS_CHECK(s.cm_b.ensure(nb));
+    KS_CHECK(s.cm_ctl.ensure(1));
+    KS_CHECK(s.rm_ctl.ensure(1));
+    carve({s.cm_i.p}, {s.cm_u.p});
+    c.fl = r.fl = s.cm_b.p;
+    c.ctl = s.cm_ctl.p;
+    r.ctl = s.rm_ctl.p;
+    r.roots = d_tasks;
+    KS_CHECK(hipMemsetAsync(s.cm_i.p, 0, n_i * sizeof(int), st));
+    KS_CHECK(hipMemsetAsync(s.cm_u.p, 0, n_u * 8, st));
+    KS_CHECK(hipMemsetAsync(s.cm_b.p, 0, nb, st));
+    KS_CHECK(hipMemsetAsync(s.cm_ctl.p, 0, sizeof(CommitCtl), st));
+    KS_CHECK(hipMemsetAsync(s.rm_ctl.p, 0, sizeof(RemoveCtl), st));
+    if (k) KS_CHECK(hipMemcpyAsync(d_tasks, tasks, k * 8, hipMemcpyHostToDevice, st));
+    if (unsched_ids && nu) KS_CHECK(hipMemcpyAsync(d_agg, unsched_ids, nu * 8, hipMemcpyHostToDevice, st));
+    SchedDev d = s.schd();
+    RemoveCtl h{};
+    std::vector<uint64_t> h_left(k);
+    // ---- 1. the ids: checked, claimed, their bindings read
+    int np = 0;
+    if (k) {
+        KS_CHECK(sched_complete_seed(d, r, unsched_ids ? d_agg : nullptr, (int)nu, d_left, st));
+        KS_CHECK(hipMemcpyAsync(&h, r.ctl, sizeof(RemoveCtl), hipMemcpyDeviceToHost, st));
+        KS_CHECK(hipMemcpyAsync(h_left.data(), d_left, k * 8, hipMemcpyDeviceToHost, st));
+        KS_CHECK(hipStreamSynchronize(st));
+        if (h.bad_root) {
+            const uint64_t id = tasks[k - (size_t)h.bad_root];
+            err = "task " + std::to_string(id) + " is not a live task node (0, beyond the graph, dead or of another type)";
+            return KS_E_INVALID;
+        }
+        np = h.nfront;
+        if (np < 1 || np > ncap || (size_t)np > k || h.nbound < 0 || h.nbound > np) {
+            err = "inconsistent task count";
+            return KS_E_DEVICE;
+        }
+    }
+    const int nbound = h.nbound;
+    const auto t1 = std::chrono::steady_clock::now();
+    // ---- 2. the aggregators' losses, from the completed tasks' own segments
+    if (np) {
+        std::swap(r.front, r.next);
+        KS_CHECK(sched_remove_chunks(d, r, np, st));
+        KS_CHECK(exclusive_sum(s, (const int*)r.nch, r.ch_off, (int64_t)np + 1, st));
+        KS_CHECK(sched_complete_count(d, r, c, np, (int)(np + s.m2cap / 64 + 1), st));
+    }
+    // the ascending id list: a flag scan over the node slots
+    KS_CHECK(sched_remove_flags(d, r, st));
+    KS_CHECK(exclusive_sum(s, (const int*)r.rm, r.rm_pos, ncap + 1, st));
+    if (log) KS_CHECK(hipStreamSynchronize(st));   // (only to split the log line's times)
+    const auto t2 = std::chrono::steady_clock::now();
+    // ---- 3. the capacities over the graph without the completed tasks
+    if (caps) {
+        KS_CHECK(sched_commit_pu(d, c, st));
+        int rc = topo_bfs(s, d, sink_slot, 0, c.pu_slots, c.pu_run, c.slots, c.running, err);
+        if (rc) return rc;
+    }
+    KS_CHECK(sched_commit_arc_flags(d, c, st));
+    KS_CHECK(exclusive_sum(s, (const int*)c.aflag, c.a_off, (int64_t)hi + 1, st));
+    KS_CHECK(sched_remove_totals(d, r, c, 1, st));
+    CommitCtl hc{};
+    KS_CHECK(hipMemcpyAsync(&h, r.ctl, sizeof(RemoveCtl), hipMemcpyDeviceToHost, st));
+    KS_CHECK(hipMemcpyAsync(&hc, c.ctl, sizeof(CommitCtl), hipMemcpyDeviceToHost, st));
+    KS_CHECK(hipStreamSynchronize(st));
+    const auto t3 = std::chrono::steady_clock::now();
+    if (h.nremoved != np || h.nevicted != 0 || h.rec_arc < 0 || h.rec_arc > hi ||
+        hc.unsched + hc.caps != h.rec_arc) {
+        err = "inconsistent record counts";
+        return KS_E_DEVICE;
+    }
+    if (h.bad) {
+        err = "a capacity would fall below its arc's lower bound";
+        return KS_E_VERIFY;
+    }
+    const int64_t nrec = (int64_t)np + h.rec_arc;
+    if (left && k) std::memcpy(left, h_left.data(), k * 8);
+    if (!nrec) return KS_OK;   // (k == 0 and every capacity stands: the solution stays valid)
+    KS_CHECK(s.d_recs.ensure(std::max<size_t>(nrec, 1)));
+    KS_CHECK(s.rec_ent.ensure(std::max<size_t>(nrec, 1)));
+    KS_CHECK(s.d_edits.ensure(std::max<size_t>(np, 1)));
+    KS_CHECK(sched_remove_emit_nodes(d, r, d_ids, s.d_recs.p, st));
+    std::vector<uint64_t> ids(np);
+    if (np) KS_CHECK(hipMemcpyAsync(ids.data(), d_ids, (size_t)np * 8, hipMemcpyDeviceToHost, st));
+    KS_CHECK(hipStreamSynchronize(st));
+    // the host's node table follows (and names an id it does not hold as a live task); from
+    // here on a failure leaves the device state unknown
+    std::vector<NodeEdit> edits;
+    int rc = make_edits(ids.data(), ids.size(), &edits, err);
+    if (rc) return rc;
+    *dirty = true;
+    if (!edits.empty())
+        KS_CHECK(hipMemcpyAsync(s.d_edits.p, edits.data(), edits.size() * sizeof(NodeEdit), hipMemcpyHostToDevice, st));
+    KS_CHECK(sched_commit_emit(d, c, s.d_recs.p, st));
+    rc = mark_cells(s, s.d_recs.p, (size_t)nrec, s.d_edits.p, edits.size(), err);
+    if (rc) return rc;
+    KS_CHECK(store_apply(s.sd(), s.d_recs.p, (int)nrec, s.rec_ent.p, s.d_edits.p, (int)edits.size(), st));
+    rc = read_sctl(s, err);
+    if (rc == KS_OK) rc = applied(s, err);
+    if (rc) return rc;
+    if (log) {
+        const auto t4 = std::chrono::steady_clock::now();
+        auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+        std::fprintf(stderr,
+                     "complete: %d tasks, %lld records, seed %.3f ms, aggregator counts %.3f ms, caps %.3f ms, "
+                     "emit + apply %.3f ms\n",
+                     np, (long long)nrec, ms(t0, t1), ms(t1, t2), ms(t2, t3), ms(t3, t4));
+    }
+    s.incremental = true;
+    s.solved = false;
+    if (h.rec_arc && s.cell_refused_values) s.cell_refused = s.cell_refused_values = false;   // (as run_apply)
+    *changed = true;
+    if (stats) {
+        stats->tasks = np;
+        stats->bound = nbound;
+        stats->arcs_removed = s.h_sctl->killed;
+        stats->unsched_updates = hc.unsched;
+        stats->cap_updates = hc.caps;
+        stats->records = nrec;
+    }
+    return KS_OK;
+}
+
+int Engine::get_bindings(const uint64_t* task, uint64_t* pu, size_t k, std::string& err) {
+    EngineImpl& s = *p_;
+    KS_CHECK(hipSetDevice(s.device));
+    if (!k) return KS_OK;
+    for (size_t i = 0; i < k; ++i)
+        if (task[i] == 0 || (int64_t)task[i] > s.nstore) {
+            err = "binding of a task id beyond the graph";
+            return KS_E_INVALID;
+        }
+    KS_CHECK(s.sched_u.ensure(2 * k));
+    hipStream_t st = s.stream;
+    KS_CHECK(hipMemcpyAsync(s.sched_u.p, task, k * 8, hipMemcpyHostToDevice, st));
+    KS_CHECK(sched_gather_bindings(s.schd(), s.sched_u.p, (int)k, s.sched_u.p + k, st));
+    KS_CHECK(hipMemcpyAsync(pu, s.sched_u.p + k, k * 8, hipMemcpyDeviceToHost, st));
+    KS_CHECK(hipStreamSynchronize(st));
     return KS_OK;
 }
 

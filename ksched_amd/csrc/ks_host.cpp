@@ -801,6 +801,67 @@ int ks_remove_resources(ks_ctx* c, int32_t flags, const uint64_t* roots, size_t 
     return KS_OK;
 }
 
+// HandleTaskCompletion (flowscheduler/scheduler.go:106-132) → TaskCompleted
+// (flowmanager/graph_manager.go:389-405). The device checks the ids, reads their bindings and
+// generates the records; the host's part is the node table: the distinct ids come back
+// ascending before anything changes, each must be a live task here too, and they leave the
+// table as the REMOVE_NODE records at stream positions 0 … n − 1 would make them (n_tasks and
+// the sink's auto demand follow through the edits).
+int ks_complete_tasks(ks_ctx* c, int32_t flags, const uint64_t* tasks, size_t k, const uint64_t* unsched_ids, size_t nu,
+                      uint64_t* left, ks_complete_stats* stats) {
+    if (!c) return KS_E_INVALID;
+    if (int g = store_guard(c)) return g;
+    if (k && !tasks) return c->fail(KS_E_INVALID, "null task array");
+    if (flags & ~(KS_COMPLETE_RESOURCE_CAPS | KS_COMPLETE_PREEMPTIVE)) return c->fail(KS_E_INVALID, "unknown complete flag");
+    if ((flags & KS_COMPLETE_PREEMPTIVE) && !(flags & KS_COMPLETE_RESOURCE_CAPS))
+        return c->fail(KS_E_INVALID, "KS_COMPLETE_PREEMPTIVE selects a capacity rule: it needs KS_COMPLETE_RESOURCE_CAPS");
+    for (size_t i = 0; unsched_ids && i < nu; ++i)
+        if (!node_alive(c, unsched_ids[i]))
+            return c->fail(KS_E_INVALID, "unscheduled aggregator " + std::to_string(unsched_ids[i]) + " is not a live node");
+    const int64_t sink = c->n_sinks == 1 ? (int64_t)c->sink_id - 1
+                         : (c->every_sink && c->n_sinks > 1) ? ks::Engine::kEverySink : -1;
+    std::optional<NodeTxn> txn;
+    auto make_edits = [&](const uint64_t* ids, size_t n, std::vector<ks::NodeEdit>* edits, std::string& err) {
+        for (size_t i = 0; i < n; ++i) {
+            const uint64_t id = ids[i];
+            if (!node_alive(c, id) || c->nodes[id].type != KS_NODE_TASK || (i && ids[i - 1] >= id)) {
+                err = "the device completes node " + std::to_string(id) + ", which the host's node table does not hold as a "
+                      "live task";
+                return KS_E_DEVICE;
+            }
+        }
+        txn.emplace(c);
+        for (size_t i = 0; i < n; ++i) txn->remove(ids[i], (int32_t)i);
+        txn->edits(*edits);
+        return KS_OK;
+    };
+    bool dirty = false, changed = false;
+    const int rc = c->eng.complete_tasks(flags, tasks, k, unsched_ids, unsched_ids ? nu : 0, sink, left, stats, make_edits,
+                                         &dirty, &changed, c->err);
+    if (!c->eng.solved()) c->have_solution = c->flows_fresh = c->map_fresh = false;   // a pending CSR rebuild ran
+    if (rc) {
+        if (txn) txn->rollback_applied();   // (the edits were made: the stream may be half applied, reload first)
+        else if (dirty) c->store_bad = true;
+        return rc;
+    }
+    if (changed) {
+        c->have_solution = false;   // as after ks_apply_deltas
+        c->map_fresh = false;
+        c->flows_fresh = false;
+    }
+    return KS_OK;
+}
+
+int ks_get_bindings(ks_ctx* c, const uint64_t* task, uint64_t* pu, size_t k) {
+    if (!c) return KS_E_INVALID;
+    if (int g = store_guard(c)) return g;
+    if (k && (!task || !pu)) return c->fail(KS_E_INVALID, "null binding array");
+    for (size_t i = 0; i < k; ++i)
+        if (!node_alive(c, task[i]) || c->nodes[task[i]].type != KS_NODE_TASK)
+            return c->fail(KS_E_INVALID, "binding of a node that is not a live task: " + std::to_string(task[i]));
+    return c->eng.get_bindings(task, pu, k, c->err);
+}
+
 int ks_get_graph(ks_ctx* c, ks_node* nodes, size_t ncap, size_t* n, ks_arc* arcs, size_t acap, size_t* m) {
     if (!c || !n || !m) return KS_E_INVALID;
     if (int g = store_guard(c)) return g;

@@ -106,6 +106,8 @@ struct CommitDev {
     CommitCtl* ctl;
     int removing;                  // ks_remove_resources: fl bit 4 marks a removed node; the capacity pass
                                    //   skips every arc with such an endpoint
+    int completing;                // ks_complete_tasks: fl bit 4 marks a completed task; its running arc no
+                                   //   longer counts, and the aggregator → sink kind fires in both rule modes
 };
 
 // The items of the delta kinds (sched_delta_kinds) in delta order, their chunk counts, and
@@ -145,7 +147,8 @@ struct RemoveCtl {
     int nevicted;    // live tasks whose binding names a flagged slot
     int rec_arc;     // capacity records (resource arcs whose capacity changes)
     int bad;         // 1: a capacity would fall below its arc's lower bound
-    int reserved[2];
+    int nbound;      // ks_complete_tasks: of the claimed tasks, those bound to a PU
+    int reserved;
 };
 
 // Scratch of one removal (device pointers; ncap node slots).
@@ -185,5 +188,28 @@ hipError_t sched_remove_emit_nodes(const SchedDev& d, const RemoveDev& r, unsign
                                    hipStream_t st);
 // One PREEMPT (task, the PU it leaves) per evicted task in task order; the task is unbound.
 hipError_t sched_remove_emit_evictions(const SchedDev& d, const RemoveDev& r, ks_sched_delta* out, hipStream_t st);
+
+// ---- ks_complete_tasks: finished tasks leave the graph. HandleTaskCompletion
+// (flowscheduler/scheduler.go:106-132) → TaskCompleted (flowmanager/graph_manager.go:389-405)
+// → removeTaskNode (:803-813) with updateUnscheduledAggNode(−1) (:396, :1291-1305); TaskFailed
+// and TaskKilled (:435-452) are the same edit. The scratch is the removal's (RemoveDev: roots
+// are the caller's task ids, RM_FLAG marks a completed task) and the commit's in its
+// completing mode; the flag scan, the REMOVE_NODE records and the capacity records are
+// sched_remove_flags / _totals / _emit_nodes and sched_commit_arc_flags / _emit.
+
+// The aggregator flags (ids: nu node ids, or nullptr for every type-0 node with an arc into
+// the sink) into r.fl, then the check of the k ids: each must be a live task, else
+// ctl->bad_root = k − its index (the first one wins). left[i] = the PU ids[i] is bound to;
+// the distinct tasks are claimed (next, ctl->nfront), ctl->nbound of them bound.
+hipError_t sched_complete_seed(const SchedDev& d, const RemoveDev& r, const unsigned long long* ids, int nu,
+                               unsigned long long* left, hipStream_t st);
+// One wave per 64-position chunk item of the nf claimed tasks' segments (r.front, after
+// sched_remove_chunks and the scan nch → ch_off): c.agg_cnt[a] += 1 per live out-arc into a
+// flagged aggregator a. ni_max bounds the chunk items.
+hipError_t sched_complete_count(const SchedDev& d, const RemoveDev& r, const CommitDev& c, int nf, int ni_max,
+                                hipStream_t st);
+// ks_get_bindings: out[i] = the PU ids[i] is bound to (ids checked by the caller).
+hipError_t sched_gather_bindings(const SchedDev& d, const unsigned long long* ids, int k, unsigned long long* out,
+                                 hipStream_t st);
 
 }  // namespace ks

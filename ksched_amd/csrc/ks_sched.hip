@@ -30,6 +30,12 @@
 //                       the tasks bound in it evicted (dfsEvictTasks, scheduler.go:533-566),
 //                       its REMOVE_NODE records and, through the commit's capacity pass, the
 //                       ancestors' capacity records generated for store_apply
+//   complete tasks      HandleTaskCompletion (flowscheduler/scheduler.go:106-132) → TaskCompleted
+//                       (graph_manager.go:389-405) → removeTaskNode (:803-813): the ids checked and
+//                       claimed in the flag bytes, their bindings read, the aggregators' losses
+//                       (updateUnscheduledAggNode(−1), :1291-1305) counted from the tasks' own chunked
+//                       segments, the REMOVE_NODE records and, through the commit's capacity pass in
+//                       its completing mode, the capacity records generated for store_apply
 #include "ks_sched.h"
 
 namespace ks {
@@ -359,7 +365,8 @@ __global__ void k_commit_pu_arcs(SchedDev d, CommitDev c) {
             const int src = d.a_src[s];
             dst = d.a_dst[s];
             if (d.n_type[dst] == KS_NODE_SINK && d.n_type[src] == KS_NODE_PU) c.pu_slots[src] = (unsigned long long)d.a_cap[s];
-            run = !c.preempt && d.a_type[s] == 1 && !(c.fl[src] & 2);
+            // (completing: a completed task's running arc goes with it)
+            run = !c.preempt && d.a_type[s] == 1 && !(c.fl[src] & (c.completing ? 2 | RM_FLAG : 2));
         }
         wave_add_distinct(c.pu_run, dst, run);
     }
@@ -385,7 +392,8 @@ __device__ __forceinline__ int commit_arc_cap(const SchedDev& d, const CommitDev
     if (c.removing && ((c.fl[u] | c.fl[v]) & RM_FLAG)) return 0;
     const unsigned char tu = d.n_type[u], tv = d.n_type[v];
     if (tv == KS_NODE_SINK) {
-        if (c.preempt || !(c.fl[u] & 1) || c.agg_cnt[u] == 0) return 0;
+        // (completing: TaskCompleted's −1 holds under both capacity rules)
+        if ((c.preempt && !c.completing) || !(c.fl[u] & 1) || c.agg_cnt[u] == 0) return 0;
         *cap = d.a_cap[s] - (long long)c.agg_cnt[u];
         return 1;
     }
@@ -539,24 +547,31 @@ __global__ void k_remove_chunks(SchedDev d, RemoveDev r, int nf) {
         r.nch[i] = i < nf ? (remove_seg_len(d, d.perm[r.front[i]]) + 63) >> 6 : 0;
 }
 
+// Chunk item w → the frontier node i with ch_off[i] ≤ w < ch_off[i + 1]; the position this
+// lane reads in its segment, −1 past the positions handed out.
+__device__ __forceinline__ int remove_item_pos(const SchedDev& d, const RemoveDev& r, int nf, int w, int lane) {
+    int lo = 0, hi = nf - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (r.ch_off[mid] <= w) lo = mid;
+        else hi = mid - 1;
+    }
+    const int x = d.perm[r.front[lo]];
+    const int b = d.first[x];
+    const int p = b + ((w - r.ch_off[lo]) << 6) + lane;
+    return p < b + remove_seg_len(d, x) ? p : -1;
+}
+
 __global__ void k_remove_level(SchedDev d, RemoveDev r, int nf, int ni_max) {
     const int lane = threadIdx.x & 63;
     const int wave = (blockIdx.x * SB + threadIdx.x) >> 6;
     const int nwaves = (gridDim.x * SB) >> 6;
     const int ni = min(r.ch_off[nf], ni_max);
     for (int w = wave; w < ni; w += nwaves) {
-        int lo = 0, hi = nf - 1;   // the frontier node i with ch_off[i] ≤ w < ch_off[i + 1]
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (r.ch_off[mid] <= w) lo = mid;
-            else hi = mid - 1;
-        }
-        const int x = d.perm[r.front[lo]];
-        const int b = d.first[x];
-        const int p = b + ((w - r.ch_off[lo]) << 6) + lane;
+        const int p = remove_item_pos(d, r, nf, w, lane);
         bool claim = false;
         int us = 0;
-        if (p < b + remove_seg_len(d, x)) {
+        if (p >= 0) {
             const int e = d.ent[p];
             if (e >= 0 && !(e & 1)) {   // forward positions only: the node's live out-arcs
                 us = d.iperm[d.pos[p].head];
@@ -622,6 +637,66 @@ __global__ void k_remove_emit_evictions(SchedDev d, RemoveDev r, ks_sched_delta*
         out[r.ev_pos[v]] = ks_sched_delta{KS_DELTA_PREEMPT, 0, (uint64_t)v + 1, d.n_bind[v]};
         d.n_bind[v] = 0;   // TaskEvicted: the task is unbound, nothing else of it changes here
     }
+}
+
+// --------------------------------------------------------------- complete tasks ---
+// HandleTaskCompletion (flowscheduler/scheduler.go:106-132) → TaskCompleted
+// (graph_manager.go:389-405) → removeTaskNode (:803-813) on the device-resident graph; TaskFailed
+// and TaskKilled (:435-452) are the same edit. The seed is k_remove_seed with the type test
+// inverted; a completed task's out-arcs are found in its residual segment, one wave per
+// 64-position chunk item (k_remove_chunks → scan → remove_item_pos), so the work follows the
+// completions and not the aggregators' in-degree.
+
+// An id must be a live task. left[i] is read here, before the store unbinds the removed
+// task. An id listed twice is claimed once; both entries of left get its binding.
+__global__ void k_complete_seed(SchedDev d, RemoveDev r, unsigned long long* __restrict__ left) {
+    for (long long i0 = blockIdx.x * (long long)SB; i0 < r.k; i0 += (long long)gridDim.x * SB) {   // (uniform per workgroup)
+        const long long i = i0 + threadIdx.x;
+        bool claim = false, bound = false;
+        int v = 0;
+        if (i < r.k) {
+            const unsigned long long id = r.roots[i];
+            bool ok = id >= 1 && id <= (unsigned long long)d.ncap;
+            if (ok) {
+                v = (int)(id - 1);
+                ok = d.n_alive[v] && d.perm[v] >= 0 && d.n_type[v] == KS_NODE_TASK;
+            }
+            unsigned long long b = 0;
+            if (ok) {
+                b = d.n_bind[v];
+                claim = rm_claim(r.fl, v);
+                bound = claim && b != 0;
+            } else {
+                atomicMax(&r.ctl->bad_root, (int)(r.k - i));
+            }
+            left[i] = b;
+        }
+        wave_push(r.next, &r.ctl->nfront, v, claim);
+        wave_count(&r.ctl->nbound, bound);
+    }
+}
+
+// updateUnscheduledAggNode(−1) (:396, :1291-1305): an aggregator loses one unit per completed
+// task that still has an arc into it. The lanes of a wave read one task's arcs, at most one
+// per (src, dst): their aggregators are distinct words; waves of one job meet on its word.
+__global__ void k_complete_count(SchedDev d, RemoveDev r, CommitDev c, int nf, int ni_max) {
+    const int lane = threadIdx.x & 63;
+    const int wave = (blockIdx.x * SB + threadIdx.x) >> 6;
+    const int nwaves = (gridDim.x * SB) >> 6;
+    const int ni = min(r.ch_off[nf], ni_max);
+    for (int w = wave; w < ni; w += nwaves) {
+        const int p = remove_item_pos(d, r, nf, w, lane);
+        const int e = p >= 0 ? d.ent[p] : -1;
+        if (e < 0 || (e & 1)) continue;   // forward positions only: the task's live out-arcs
+        const int dst = d.a_dst[e >> 1];
+        if (c.fl[dst] & 1) atomicAdd(&c.agg_cnt[dst], 1ULL);
+    }
+}
+
+__global__ void k_gather_bindings(int k, const unsigned long long* __restrict__ ids,
+                                  const unsigned long long* __restrict__ bind, unsigned long long* __restrict__ out) {
+    for (long long i = blockIdx.x * (long long)SB + threadIdx.x; i < k; i += (long long)gridDim.x * SB)
+        out[i] = bind[ids[i] - 1];
 }
 
 }  // namespace
@@ -756,6 +831,29 @@ hipError_t sched_remove_emit_nodes(const SchedDev& d, const RemoveDev& r, unsign
 
 hipError_t sched_remove_emit_evictions(const SchedDev& d, const RemoveDev& r, ks_sched_delta* out, hipStream_t st) {
     if (d.ncap) hipLaunchKernelGGL(k_remove_emit_evictions, dim3(grid(d.ncap)), dim3(SB), 0, st, d, r, out);
+    return hipGetLastError();
+}
+
+hipError_t sched_complete_seed(const SchedDev& d, const RemoveDev& r, const unsigned long long* ids, int nu,
+                               unsigned long long* left, hipStream_t st) {
+    if (!r.k) return hipSuccess;
+    // (the byte stores of the aggregator marks come first: the claims are atomicOrs on top of them)
+    mark_aggregators(d, ids, nu, r.fl, st);
+    hipLaunchKernelGGL(k_complete_seed, dim3(grid(r.k)), dim3(SB), 0, st, d, r, left);
+    return hipGetLastError();
+}
+
+hipError_t sched_complete_count(const SchedDev& d, const RemoveDev& r, const CommitDev& c, int nf, int ni_max,
+                                hipStream_t st) {
+    if (nf) hipLaunchKernelGGL(k_complete_count, dim3(grid(64LL * ni_max)), dim3(SB), 0, st, d, r, c, nf, ni_max);
+    return hipGetLastError();
+}
+
+hipError_t sched_gather_bindings(const SchedDev& d, const unsigned long long* ids, int k, unsigned long long* out,
+                                 hipStream_t st) {
+    if (k)
+        hipLaunchKernelGGL(k_gather_bindings, dim3(grid(k)), dim3(SB), 0, st, k, ids,
+                           (const unsigned long long*)d.n_bind, out);
     return hipGetLastError();
 }
 

@@ -21,7 +21,7 @@ EXPORTED_SYMBOLS = (
     "ks_apply_deltas", "ks_solve", "ks_get_flows", "ks_get_task_mapping", "ks_get_task_pu_device", "ks_solve_many",
     "ks_coalesce_deltas", "ks_get_store_stats", "ks_set_bindings", "ks_scheduling_deltas",
     "ks_update_unsched_costs", "ks_topology_stats", "ks_get_graph", "ks_commit_schedule",
-    "ks_commit_preemptive", "ks_remove_resources",
+    "ks_commit_preemptive", "ks_remove_resources", "ks_complete_tasks", "ks_get_bindings",
     "ks_batch_create", "ks_batch_create_rank", "ks_batch_unique_id", "ks_batch_destroy", "ks_batch_last_error",
     "ks_batch_load", "ks_batch_solve", "ks_batch_gather",
     "ks_batch_slots", "ks_batch_owner", "ks_batch_block_len", "ks_batch_unpack",
@@ -33,6 +33,7 @@ KS_DELTA_PLACE, KS_DELTA_PREEMPT, KS_DELTA_MIGRATE, KS_DELTA_NOOP = 0, 1, 2, 3
 KS_COST_SET, KS_COST_ADD = 0, 1
 KS_COMMIT_RESOURCE_CAPS = 1
 KS_REMOVE_RESOURCE_CAPS, KS_REMOVE_PREEMPTIVE = 1, 2
+KS_COMPLETE_RESOURCE_CAPS, KS_COMPLETE_PREEMPTIVE = 1, 2
 
 NODE_DT = np.dtype({"names": ["id", "excess", "type", "_pad"],
                     "formats": ["<u8", "<i8", "<i4", "<i4"], "offsets": [0, 8, 16, 20], "itemsize": 24})
@@ -122,6 +123,16 @@ class KsRemoveStats(C.Structure):
     _fields_ = [("roots", C.c_int64), ("nodes_removed", C.c_int64), ("pus_removed", C.c_int64),
                 ("tasks_evicted", C.c_int64), ("arcs_removed", C.c_int64), ("cap_updates", C.c_int64),
                 ("records", C.c_int64), ("reserved", C.c_int64 * 5)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class KsCompleteStats(C.Structure):
+    """ks_complete_stats: what one ks_complete_tasks removed and generated on device."""
+    _fields_ = [("tasks", C.c_int64), ("bound", C.c_int64), ("arcs_removed", C.c_int64),
+                ("unsched_updates", C.c_int64), ("cap_updates", C.c_int64), ("records", C.c_int64),
+                ("reserved", C.c_int64 * 6)]
 
     def as_dict(self) -> dict:
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
@@ -233,6 +244,8 @@ def _bind(path: str):
                                        P(C.c_size_t), P(KsPreemptStats)]
     L.ks_remove_resources.argtypes = [V, C.c_int32, V, C.c_size_t, V, C.c_size_t, P(C.c_size_t), V, C.c_size_t,
                                       P(C.c_size_t), P(KsRemoveStats)]
+    L.ks_complete_tasks.argtypes = [V, C.c_int32, V, C.c_size_t, V, C.c_size_t, V, P(KsCompleteStats)]
+    L.ks_get_bindings.argtypes = [V, V, V, C.c_size_t]
     return L
 
 
@@ -445,6 +458,34 @@ class Context:
                                                 nr.value, C.byref(nr), evicted.ctypes.data, ne.value, C.byref(ne),
                                                 C.byref(st)))
         return removed[:nr.value], evicted[:ne.value], st.as_dict()
+
+    def complete_tasks(self, tasks, resource_caps: bool = True, preemptive: bool = False, unsched_ids=None):
+        """ks_complete_tasks: the finished (failed, killed) task ids leave the device-resident
+        graph; each unscheduled aggregator loses one unit on its arc into the sink per
+        completed task that still had an arc into it and, with resource_caps, the resource
+        arcs get their capacities (preemptive: the rule of commit_preemptive, under which a
+        completion changes none: such callers pass resource_caps=False).
+        → (left: the PU each input id was bound to, 0 = unbound, uint64 aligned with tasks;
+        stats dict). Needs no solve; invalidates the solution."""
+        ids = np.ascontiguousarray(tasks, np.uint64).reshape(-1)
+        agg = None if unsched_ids is None else np.ascontiguousarray(unsched_ids, np.uint64).reshape(-1)
+        nu = 0 if agg is None else agg.shape[0]
+        if agg is not None and nu == 0:
+            agg = np.zeros(1, np.uint64)   # an empty list names no aggregator: not NULL, which is the auto rule
+        flags = (KS_COMPLETE_RESOURCE_CAPS if resource_caps else 0) | (KS_COMPLETE_PREEMPTIVE if preemptive else 0)
+        left = np.zeros(max(ids.shape[0], 1), np.uint64)
+        st = KsCompleteStats()
+        self._check(self._L.ks_complete_tasks(self._h, flags, ids.ctypes.data, ids.shape[0],
+                                              None if agg is None else agg.ctypes.data,
+                                              nu, left.ctypes.data, C.byref(st)))
+        return left[:ids.shape[0]], st.as_dict()
+
+    def bindings(self, tasks) -> np.ndarray:
+        """ks_get_bindings: the PU each task id is bound to on the device, 0 = unbound."""
+        ids = np.ascontiguousarray(tasks, np.uint64).reshape(-1)
+        pu = np.zeros(max(ids.shape[0], 1), np.uint64)
+        self._check(self._L.ks_get_bindings(self._h, ids.ctypes.data, pu.ctypes.data, ids.shape[0]))
+        return pu[:ids.shape[0]]
 
     def task_pu_device(self, dev_ptr: int, cap: int) -> int:
         cnt = C.c_size_t()
