@@ -101,6 +101,8 @@ extern "C" {
                                   entry point and its stats struct were added).
                                   ks_complete_tasks and ks_get_bindings (still 5: two
                                   entry points and one stats struct were added).
+                                  ks_add_tasks (still 5: one entry point and two structs
+                                  were added, nothing was resized).
                                   ks_opts (96 B) CHANGED SIZE in ABI 2 and ks_result in
                                   ABI 2, 3 and 5: a caller must check
                                   ks_abi_version() == KSMCMF_ABI_VERSION before ks_create. */
@@ -747,6 +749,81 @@ int ks_complete_tasks(ks_ctx* ctx, int32_t flags, const uint64_t* tasks, size_t 
                       const uint64_t* unsched_ids, size_t nu,
                       uint64_t* left /* k entries, may be NULL */,
                       ks_complete_stats* stats /* may be NULL */);
+
+typedef struct ks_task_arc {          /* 16 B: one out-arc of an arriving task            */
+    uint64_t dst;             /* the head: a live node that is no task                    */
+    int64_t  cost;
+} ks_task_arc;
+
+typedef struct ks_add_stats {         /* 96 B */
+    int64_t tasks;            /* ADD_NODE records                                          */
+    int64_t arcs_added;       /* task out-arc records (ADD_ARC)                            */
+    int64_t unsched_updates;  /* aggregator → sink arcs whose capacity rose (UPDATE_ARC)   */
+    int64_t unsched_added;    /* aggregator → sink arcs the store no longer held (ADD_ARC) */
+    int64_t records;          /* the sum of the four above                                 */
+    int64_t reserved[7];
+} ks_add_stats;
+
+/* Arriving tasks enter the graph, on device: AddOrUpdateJobNodes
+ * (flowmanager/graph_manager.go:166-208) → addTaskNode (:632-648), updateUnscheduledAggNode(+1)
+ * (:194, :1291-1305) and updateTaskNode (:1183-1192) with its three arc writers,
+ * updateTaskToUnscheduledAggArc (:1270-1285), updateTaskToEquivArcs (:1197-1226) and
+ * updateTaskToResArcs (:1229-1264), each of which calls AddArc(task, head, 0, 1, cost,
+ * ArcTypeOther). The records are generated in device memory and applied as ONE stream with
+ * the semantics of ks_apply_deltas (all or nothing, in place, store counters, warm-start
+ * bookkeeping, the dirty-cell marks of a partition). The stream's order is fixed, so a host
+ * restatement produces the identical stream: k ADD_NODE records at positions 0 … k − 1 in
+ * input order; the task arcs in input order, arc arc_off[i] + j at position k + arc_off[i] + j;
+ * then one record per aggregator that gains a unit, in ascending aggregator id. Only the ids,
+ * the offsets, the 16-byte arcs and the host's node edits cross PCIe.
+ *   - Task ids: tasks[i] is the NodeID the caller allocated; the caller owns id reuse, as for
+ *     ks_remove_resources. It must be in 1 … 2^30 − 1 (KS_E_RANGE) and must not be a live
+ *     node; an id listed twice is "already present", as a second ADD_NODE would be. The
+ *     first offending id is named: KS_E_INVALID, nothing changes. A reused dead id, the next
+ *     id or any id beyond the highest in use is legal, dead slots in between too. The node
+ *     is of type task with supply 1; the task count and the sink's auto demand follow
+ *     through the host's node table, as after an ADD_NODE. A new task is unbound, also when
+ *     its id belonged to a bound task that left earlier.
+ *   - Arcs: task i gets arcs[arc_off[i] .. arc_off[i + 1]), each with low 0, cap 1, type 0
+ *     and its cost. arc_off[0] == 0 and the offsets never decrease, else KS_E_INVALID; a
+ *     task with no arc is legal. Every head must be a node that was live before the call
+ *     and is no task (a task of this same call is therefore refused): a head that is 0,
+ *     beyond the graph, dead or a task is KS_E_INVALID, the error names the task and the
+ *     head, nothing changes. |cost| > 2^40: KS_E_RANGE, nothing changes. The first offending
+ *     arc in input order is the one reported. A head listed twice for one task, other than
+ *     an aggregator, is the upsert it is in ks_apply_deltas: the later record stands and
+ *     ks_store_stats.superseded counts the other. This is the one place where a generated
+ *     stream may supersede.
+ *   - Aggregators: unsched_ids, nu of them; NULL: every type-0 node with an arc into the
+ *     sink, as in the commits. On its arc into the sink an aggregator gains one unit of
+ *     capacity per arriving task with an arc into it. If the store holds that arc: one
+ *     UPDATE_ARC, low, cost and type kept, cap raised. If it does not (a new job's
+ *     aggregator, or one whose capacity fell to 0): one ADD_ARC aggregator → sink with low 0,
+ *     cap = the count, cost unsched_sink_cost, type 0 (the AddArc branch of
+ *     updateUnscheduledAggNode, :1300-1304). A task with arcs into more than one marked
+ *     aggregator, or twice into the same one, is KS_E_INVALID (a task has one job), the
+ *     error names the task. With explicit ids a task with no aggregator arc is legal and
+ *     moves no capacity. With unsched_ids == NULL an aggregator that has lost its arc into
+ *     the sink is invisible, so a task with no arc into a recognised aggregator is
+ *     KS_E_INVALID with a message that asks for the ids: the call never silently leaves a
+ *     capacity one short. After a pinned commit or ks_complete_tasks may have drained an
+ *     aggregator to 0, pass the ids. A context with other than one sink refuses any call in
+ *     which an aggregator gains a unit (KS_E_INVALID). unsched_sink_cost beyond ±2^40:
+ *     KS_E_RANGE. An aggregator id that is no live node: KS_E_INVALID.
+ *   - flags must be 0 (reserved); anything else is KS_E_INVALID.
+ * Needs no previous solve and no residual CSR (no BFS runs: arrivals change no resource
+ * capacity). k == 0 does nothing and keeps the solution. Success with k > 0 invalidates the
+ * solution and the mapping, exactly as ks_apply_deltas does; a node beyond the built CSR or a
+ * full segment takes the store's rebuild path (ks_store_stats.rebuilds). Every refusal is
+ * found before anything changes on the device, and the host's node table is rolled back. A
+ * device failure after the records were emitted leaves the store unusable until the next
+ * ks_load_graph; the host's node table is rolled back. stats may be NULL; records == tasks +
+ * arcs_added + unsched_updates + unsched_added. */
+int ks_add_tasks(ks_ctx* ctx, int32_t flags,
+                 const uint64_t* tasks, size_t k,
+                 const uint64_t* arc_off /* k + 1 */, const ks_task_arc* arcs,
+                 const uint64_t* unsched_ids, size_t nu, int64_t unsched_sink_cost,
+                 ks_add_stats* stats /* may be NULL */);
 
 /* pu[i] = the PU task[i] is bound to on the device (ks_set_bindings, the commits), 0 =
  * unbound: for the pinned recipe above and for checkpoints. A task id that is not a live

@@ -121,6 +121,14 @@ public:
     int complete_tasks(int flags, const uint64_t* tasks, size_t k, const uint64_t* unsched_ids, size_t nu,
                        int64_t sink_slot, uint64_t* left, ks_complete_stats* stats, const RemoveEdits& make_edits,
                        bool* dirty, bool* changed, std::string& err);
+    // ks_add_tasks (the k new task ids, checked and already entered in the host's node table,
+    // with their arcs; the aggregators gain a unit per task). nslots: the node slots in use
+    // with the new ids. Every refusal is found before make_edits is called, once, for the node
+    // edits of the stream (the host's aggregates move there); *dirty is set from then on.
+    using AddEdits = std::function<void(std::vector<NodeEdit>* edits)>;
+    int add_tasks(const uint64_t* tasks, size_t k, const uint64_t* arc_off, const ks_task_arc* arcs,
+                  const uint64_t* unsched_ids, size_t nu, int64_t sink_slot, int64_t sink_cost, int64_t nslots,
+                  ks_add_stats* stats, const AddEdits& make_edits, bool* dirty, std::string& err);
     // ks_get_bindings: pu[i] = the device-kept binding of task[i] (ids checked by the caller).
     int get_bindings(const uint64_t* task, uint64_t* pu, size_t k, std::string& err);
     int device() const;

@@ -1,6 +1,6 @@
 // ks_engine_sched.hip — the engine's scheduler glue: bindings, scheduling deltas,
 // unscheduled costs, topology statistics, ks_commit_schedule and ks_commit_preemptive,
-// ks_remove_resources, ks_complete_tasks and ks_get_bindings. It launches the
+// ks_remove_resources, ks_complete_tasks, ks_add_tasks and ks_get_bindings. It launches the
 // kernels of ks_sched.hip and ks_store.hip through their launchers, none of the engine's.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -818,6 +818,173 @@ int Engine::complete_tasks(int flags, const uint64_t* tasks, size_t k, const uin
         stats->arcs_removed = s.h_sctl->killed;
         stats->unsched_updates = hc.unsched;
         stats->cap_updates = hc.caps;
+        stats->records = nrec;
+    }
+    return KS_OK;
+}
+
+// ks_add_tasks: the fifth body. The ids were checked against the host's node table; the ids,
+// the offsets and the 16-byte arcs go up, one lane per arc checks its head and cost and counts
+// the aggregators' gains, the store's index says which gaining aggregator still has its arc
+// into the sink, and ONE host sync brings every refusal and the record counts (no step before
+// it changes anything, so the checks need no sync of their own). Then the host's node edits,
+// the sizing of the node store, the arc table and the index, and the ADD_NODE records (stream
+// positions 0 … k − 1), the task arcs (k …) and the aggregator records behind them reach
+// store_apply as one stream. Neither the residual CSR nor the topology BFS is needed.
+int Engine::add_tasks(const uint64_t* tasks, size_t k, const uint64_t* arc_off, const ks_task_arc* arcs,
+                      const uint64_t* unsched_ids, size_t nu, int64_t sink_slot, int64_t sink_cost, int64_t nslots,
+                      ks_add_stats* stats, const AddEdits& make_edits, bool* dirty, std::string& err) {
+    EngineImpl& s = *p_;
+    *dirty = false;
+    if (!k) return KS_OK;
+    KS_CHECK(hipSetDevice(s.device));
+    hipStream_t st = s.stream;
+    const bool log = s.opts.log_cycles != 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int64_t nst = s.nstore;
+    const size_t na = (size_t)arc_off[k];
+    if (k > (size_t)INT32_MAX / 4 || na > (size_t)INT32_MAX / 4 || nu > (size_t)INT32_MAX) {
+        err = "too many tasks, arcs or aggregator ids";
+        return KS_E_RANGE;
+    }
+    for (size_t i = 0; unsched_ids && i < nu; ++i)
+        if (unsched_ids[i] == 0 || (int64_t)unsched_ids[i] > nst) {
+            err = "unscheduled aggregator id beyond the graph";
+            return KS_E_INVALID;
+        }
+    AddDev a{};
+    a.k = (int)k;
+    a.na = (int)na;
+    a.nst = nst;
+    a.null_rule = unsched_ids ? 0 : 1;
+    a.sink = sink_slot >= 0 && sink_slot < nst ? sink_slot : -1;
+    a.sink_cost = sink_cost;
+    unsigned long long *d_tasks = nullptr, *d_off = nullptr, *d_arcs = nullptr, *d_agg = nullptr;
+    auto carve = [&](Carve<int> ci, Carve<unsigned long long> cu) {
+        a.t_agg = ci.take((int64_t)k + 1);
+        for (int** x : {&a.aflag, &a.a_off, &a.a_slot}) *x = ci.take(nst + 1);
+        a.agg_cnt = cu.take(nst + 1);   // (first: the only u64 array that starts zeroed)
+        d_tasks = cu.take(k);
+        d_off = cu.take(k + 1);
+        d_arcs = cu.take(2 * na);
+        d_agg = cu.take(nu);
+        return std::make_pair(ci.n, cu.n);
+    };
+    const auto [n_i, n_u] = carve({nullptr}, {nullptr});
+    const int64_t nb = (nst + 4) & ~3LL;
+    KS_CHECK(s.cm_i.ensure(n_i));
+    KS_CHECK(s.cm_u.ensure(n_u));
+    KS_CHECK(s.cm_b.ensure(nb));
+    KS_CHECK(s.add_ctl.ensure(1));
+    carve({s.cm_i.p}, {s.cm_u.p});
+    a.fl = s.cm_b.p;
+    a.ctl = s.add_ctl.p;
+    a.tasks = d_tasks;
+    a.arc_off = d_off;
+    a.arcs = (const ks_task_arc*)d_arcs;
+    a.hkey = s.hkey.p;
+    a.hval = s.hval.p;
+    a.hmask = s.hcap ? (int)(s.hcap - 1) : -1;
+    KS_CHECK(hipMemsetAsync(s.cm_i.p, 0, n_i * sizeof(int), st));
+    KS_CHECK(hipMemsetAsync(a.agg_cnt, 0, (nst + 1) * 8, st));
+    KS_CHECK(hipMemsetAsync(s.cm_b.p, 0, nb, st));
+    KS_CHECK(hipMemsetAsync(s.add_ctl.p, 0, sizeof(AddCtl), st));
+    KS_CHECK(hipMemcpyAsync(d_tasks, tasks, k * 8, hipMemcpyHostToDevice, st));
+    KS_CHECK(hipMemcpyAsync(d_off, arc_off, (k + 1) * 8, hipMemcpyHostToDevice, st));
+    if (na) KS_CHECK(hipMemcpyAsync(d_arcs, arcs, na * sizeof(ks_task_arc), hipMemcpyHostToDevice, st));
+    if (unsched_ids && nu) KS_CHECK(hipMemcpyAsync(d_agg, unsched_ids, nu * 8, hipMemcpyHostToDevice, st));
+    SchedDev d = s.schd();
+    // ---- 1. heads, costs, the aggregators' gains and their arcs into the sink: one sync
+    KS_CHECK(sched_add_check(d, a, unsched_ids ? d_agg : nullptr, (int)nu, st));
+    KS_CHECK(exclusive_sum(s, (const int*)a.aflag, a.a_off, nst + 1, st));
+    KS_CHECK(sched_add_totals(a, st));
+    AddCtl h{};
+    KS_CHECK(hipMemcpyAsync(&h, a.ctl, sizeof(AddCtl), hipMemcpyDeviceToHost, st));
+    KS_CHECK(hipStreamSynchronize(st));
+    const auto t1 = std::chrono::steady_clock::now();
+    auto task_of = [&](size_t j) {   // the last i with arc_off[i] ≤ j
+        return (size_t)(std::upper_bound(arc_off, arc_off + k, (uint64_t)j) - arc_off) - 1;
+    };
+    if (h.bad_head || h.bad_cost) {   // the first offending arc in input order; on one arc the head comes first
+        if (h.bad_head < 0 || h.bad_cost < 0 || (size_t)h.bad_head > na || (size_t)h.bad_cost > na) {
+            err = "inconsistent arc index";
+            return KS_E_DEVICE;
+        }
+        const bool head = h.bad_head >= h.bad_cost;
+        const size_t j = na - (size_t)(head ? h.bad_head : h.bad_cost);
+        const std::string who = "task " + std::to_string(tasks[task_of(j)]) + ": ";
+        if (head) {
+            err = who + "head " + std::to_string(arcs[j].dst) + " is not a node that was live before the call and is no "
+                  "task (0, beyond the graph, dead, a task, or a task of this call)";
+            return KS_E_INVALID;
+        }
+        err = who + "the cost of its arc into " + std::to_string(arcs[j].dst) + " is outside the supported range";
+        return KS_E_RANGE;
+    }
+    if (h.bad_multi || h.bad_none) {
+        if (h.bad_multi < 0 || h.bad_none < 0 || (size_t)h.bad_multi > k || (size_t)h.bad_none > k) {
+            err = "inconsistent task index";
+            return KS_E_DEVICE;
+        }
+        const bool multi = h.bad_multi >= h.bad_none;
+        const uint64_t id = tasks[k - (size_t)(multi ? h.bad_multi : h.bad_none)];
+        err = multi ? "task " + std::to_string(id) + " has more than one arc into unscheduled aggregators: a task has one job"
+                    : "task " + std::to_string(id) + " has no arc into a node with an arc into the sink; an aggregator "
+                      "whose capacity fell to 0 has lost that arc: pass the aggregators' ids (unsched_ids)";
+        return KS_E_INVALID;
+    }
+    if (h.units && a.sink < 0) {
+        err = "an unscheduled aggregator's capacity needs exactly one sink";
+        return KS_E_INVALID;
+    }
+    if (h.units < 0 || (size_t)h.units > na || h.rec_upd < 0 || h.rec_add < 0 || h.rec_upd + h.rec_add != h.rec_agg ||
+        h.rec_agg > h.units || (h.units > 0) != (h.rec_agg > 0)) {
+        err = "inconsistent record counts";
+        return KS_E_DEVICE;
+    }
+    // ---- 2. room for the new nodes and arcs; the host's node table follows
+    const int64_t nrec = (int64_t)k + (int64_t)na + h.rec_agg;
+    int rc = ensure_nodes(s, std::max<int64_t>(nslots, 1), err);
+    if (rc == KS_OK) rc = ensure_arcs(s, (int64_t)s.hi() + (int64_t)na + h.rec_add, err);
+    if (rc == KS_OK) rc = ensure_hash(s, (int64_t)na + h.rec_add, err);
+    if (rc) return rc;
+    KS_CHECK(s.d_recs.ensure((size_t)nrec));
+    KS_CHECK(s.rec_ent.ensure((size_t)nrec));
+    KS_CHECK(s.d_edits.ensure(k));
+    std::vector<NodeEdit> edits;
+    make_edits(&edits);
+    // from here on a failure leaves the device state unknown
+    *dirty = true;
+    s.nslots = std::max(s.nslots, nslots);
+    s.incremental = true;
+    d = s.schd();   // (the node store and the arc table may have moved)
+    const auto t2 = std::chrono::steady_clock::now();
+    // ---- 3. the records, at their fixed positions, and the apply
+    if (!edits.empty())
+        KS_CHECK(hipMemcpyAsync(s.d_edits.p, edits.data(), edits.size() * sizeof(NodeEdit), hipMemcpyHostToDevice, st));
+    KS_CHECK(sched_add_emit(d, a, s.d_recs.p, st));
+    rc = mark_cells(s, s.d_recs.p, (size_t)nrec, s.d_edits.p, edits.size(), err);
+    if (rc) return rc;
+    KS_CHECK(store_apply(s.sd(), s.d_recs.p, (int)nrec, s.rec_ent.p, s.d_edits.p, (int)edits.size(), st));
+    rc = read_sctl(s, err);
+    if (rc == KS_OK) rc = applied(s, err);
+    if (rc) return rc;
+    if (log) {
+        const auto t3 = std::chrono::steady_clock::now();
+        auto ms = [](auto x, auto y) { return std::chrono::duration<double, std::milli>(y - x).count(); };
+        std::fprintf(stderr,
+                     "add: %zu tasks, %zu arcs, %lld records, upload + checks + counts %.3f ms, node table + sizing "
+                     "%.3f ms, emit + apply %.3f ms\n",
+                     k, na, (long long)nrec, ms(t0, t1), ms(t1, t2), ms(t2, t3));
+    }
+    s.solved = false;
+    if (nrec > (int64_t)k && s.cell_refused_values) s.cell_refused = s.cell_refused_values = false;   // (as run_apply)
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        stats->tasks = (int64_t)k;
+        stats->arcs_added = (int64_t)na;
+        stats->unsched_updates = h.rec_upd;
+        stats->unsched_added = h.rec_add;
         stats->records = nrec;
     }
     return KS_OK;

@@ -190,6 +190,14 @@ struct NodeTxn {
             saved.emplace_back(id, c->nodes[id]);
         }
     }
+    // ADD_NODE (ks_apply_deltas, ks_add_tasks): the id in range and not a live node (graph.go:95-98)
+    int add(uint64_t id, int64_t excess, int32_t type) {
+        if (id == 0 || id >= kMaxId) return c->fail(KS_E_RANGE, "node id " + std::to_string(id) + " out of range");
+        if (node_alive(c, id)) return c->fail(KS_E_INVALID, "node " + std::to_string(id) + " already present");
+        touch(id);
+        c->nodes[id] = NodeRec{excess, type, true, true};
+        return KS_OK;
+    }
     void remove(uint64_t id, int32_t pos) {   // REMOVE_NODE at stream position pos
         touch(id);
         c->nodes[id] = NodeRec{};
@@ -329,16 +337,7 @@ int ks_apply_deltas(ks_ctx* c, const ks_delta* d, size_t k) {
         const ks_delta& x = d[i];
         switch (x.kind) {
             case KS_ADD_NODE:
-                if (x.id == 0 || x.id >= kMaxId) {
-                    rc = c->fail(KS_E_RANGE, "node id " + std::to_string(x.id) + " out of range");
-                    break;
-                }
-                if (node_alive(c, x.id)) {   // graph.go:95-98
-                    rc = c->fail(KS_E_INVALID, "node " + std::to_string(x.id) + " already present");
-                    break;
-                }
-                touch(x.id);
-                c->nodes[x.id] = NodeRec{x.excess, x.type, true, true};
+                rc = txn.add(x.id, x.excess, x.type);
                 break;
             case KS_REMOVE_NODE:
                 if (!node_alive(c, x.id)) {
@@ -849,6 +848,53 @@ int ks_complete_tasks(ks_ctx* c, int32_t flags, const uint64_t* tasks, size_t k,
         c->map_fresh = false;
         c->flows_fresh = false;
     }
+    return KS_OK;
+}
+
+// AddOrUpdateJobNodes (flowmanager/graph_manager.go:166-208). The ids are the host's part: each
+// enters the node table through the ADD_NODE rule of ks_apply_deltas (NodeTxn::add), so a live
+// id and an id listed twice are refused alike. The device checks the arcs' heads and costs,
+// counts the aggregators' gains and generates the records; a refusal it finds takes the new
+// nodes out of the table again.
+int ks_add_tasks(ks_ctx* c, int32_t flags, const uint64_t* tasks, size_t k, const uint64_t* arc_off,
+                 const ks_task_arc* arcs, const uint64_t* unsched_ids, size_t nu, int64_t unsched_sink_cost,
+                 ks_add_stats* stats) {
+    if (!c) return KS_E_INVALID;
+    if (int g = store_guard(c)) return g;
+    if (flags) return c->fail(KS_E_INVALID, "unknown add flag (flags is reserved: pass 0)");
+    if (k && (!tasks || !arc_off)) return c->fail(KS_E_INVALID, "null task or offset array");
+    if (unsched_sink_cost > (int64_t(1) << 40) || unsched_sink_cost < -(int64_t(1) << 40))
+        return c->fail(KS_E_RANGE, "unscheduled sink cost outside the supported range");
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (!k) return KS_OK;   // nothing arrives: the solution stands
+    if (arc_off[0] != 0) return c->fail(KS_E_INVALID, "arc_off[0] must be 0");
+    for (size_t i = 0; i < k; ++i)
+        if (arc_off[i + 1] < arc_off[i])
+            return c->fail(KS_E_INVALID, "arc_off decreases at task " + std::to_string(tasks[i]));
+    if (arc_off[k] && !arcs) return c->fail(KS_E_INVALID, "null arc array");
+    for (size_t i = 0; unsched_ids && i < nu; ++i)
+        if (!node_alive(c, unsched_ids[i]))
+            return c->fail(KS_E_INVALID, "unscheduled aggregator " + std::to_string(unsched_ids[i]) + " is not a live node");
+    const int64_t sink = c->n_sinks == 1 ? (int64_t)c->sink_id - 1 : -1;
+    NodeTxn txn(c);
+    for (size_t i = 0; i < k; ++i)
+        if (int rc = txn.add(tasks[i], 1, KS_NODE_TASK)) {
+            txn.rollback_nodes();
+            return rc;
+        }
+    bool dirty = false;
+    auto make_edits = [&](std::vector<ks::NodeEdit>* edits) { txn.edits(*edits); };
+    const int rc = c->eng.add_tasks(tasks, k, arc_off, arcs, unsched_ids, unsched_ids ? nu : 0, sink, unsched_sink_cost,
+                                    c->nslots(), stats, make_edits, &dirty, c->err);
+    if (rc) {
+        if (dirty) txn.rollback_applied();   // (the edits were made: the stream may be half applied, reload first)
+        else txn.rollback_nodes();
+        if (stats) std::memset(stats, 0, sizeof(*stats));
+        return rc;
+    }
+    c->have_solution = false;   // as after ks_apply_deltas
+    c->map_fresh = false;
+    c->flows_fresh = false;
     return KS_OK;
 }
 

@@ -212,4 +212,60 @@ hipError_t sched_complete_count(const SchedDev& d, const RemoveDev& r, const Com
 hipError_t sched_gather_bindings(const SchedDev& d, const unsigned long long* ids, int k, unsigned long long* out,
                                  hipStream_t st);
 
+// ---- ks_add_tasks: arriving tasks enter the graph. AddOrUpdateJobNodes
+// (flowmanager/graph_manager.go:166-208) → addTaskNode (:632-648), updateUnscheduledAggNode(+1)
+// (:194, :1291-1305) and updateTaskNode (:1183-1192) with its arc writers (:1197-1285), each an
+// AddArc(task, head, 0, 1, cost, ArcTypeOther). The ids are the host's business (its node
+// table); the device checks every arc's head against node liveness and types, counts the
+// aggregators' gains, asks the store's (src, dst) index whether each gaining aggregator still
+// has its arc into the sink, and writes the ADD_NODE, ADD_ARC and aggregator records at fixed
+// stream positions for store_apply. Only the node store, the arc table and the index are
+// read: no residual CSR is needed and no BFS runs.
+
+// Device counters of one arrival; the host reads them in one 32-byte copy.
+struct AddCtl {
+    int bad_head;    // na − the index of the first arc whose head is 0, beyond the graph, dead or a task, 0 none
+    int bad_cost;    // na − the index of the first arc whose cost is beyond ±2^40, 0 none
+    int bad_multi;   // k − the index of the first task with more than one arc into flagged aggregators, 0 none
+    int bad_none;    // k − the index of the first task with none (counted under the NULL rule only), 0 none
+    int units;       // arcs into flagged aggregators: the capacity the aggregators gain
+    int rec_upd;     // gaining aggregators whose arc into the sink the store holds (UPDATE_ARC)
+    int rec_add;     // gaining aggregators without it (ADD_ARC)
+    int rec_agg;     // the scan's total: rec_upd + rec_add
+};
+
+// Inputs and scratch of one arrival (device pointers; nst node slots before the call).
+struct AddDev {
+    int k;                             // tasks
+    int na;                            // arcs
+    const unsigned long long* tasks;   // [k] the new ids, checked by the host
+    const unsigned long long* arc_off; // [k + 1] checked by the host: 0 first, never decreasing, na last
+    const ks_task_arc* arcs;           // [na] unchecked
+    long long nst;                     // node slots the head pass may read
+    unsigned char* fl;                 // per node slot: 1 unscheduled aggregator
+    int* t_agg;                        // [k + 1] arcs of task i into flagged aggregators
+    unsigned long long* agg_cnt;       // [nst + 1] per node slot: arriving tasks with an arc into the aggregator
+    int* aflag;                        // [nst + 1] 1: the aggregator gains and gets a record; a_off its scan
+    int* a_off;                        // [nst + 1]
+    int* a_slot;                       // [nst + 1] arc slot of aggregator → sink, −1: the store does not hold it
+    int null_rule;                     // unsched_ids == NULL: a task without an aggregator arc is refused
+    long long sink;                    // the sink's node slot, −1: other than one sink
+    long long sink_cost;               // cost of a re-created aggregator → sink arc
+    const unsigned long long* hkey;    // the store's (src, dst) index (ks_store.h)
+    const int* hval;
+    int hmask;                         // capacity − 1, −1: no index yet
+    AddCtl* ctl;
+};
+
+// The aggregator flags (ids: nu node ids, or nullptr for every type-0 node with an arc into the
+// sink) into a.fl; the head pass, one lane per arc (head and cost checks, t_agg, agg_cnt with one
+// atomic per distinct aggregator per wave, ctl->units); the per-task count check; the
+// per-aggregator lookup (aflag, a_slot, ctl->rec_upd / rec_add). The caller scans aflag → a_off.
+hipError_t sched_add_check(const SchedDev& d, const AddDev& a, const unsigned long long* ids, int nu, hipStream_t st);
+// ctl->rec_agg after the scan.
+hipError_t sched_add_totals(const AddDev& a, hipStream_t st);
+// The records: ADD_NODE at 0 … k − 1, the task arcs at k + their index, the aggregator records
+// in ascending id behind them (d: the arc table as it is now, after any growth).
+hipError_t sched_add_emit(const SchedDev& d, const AddDev& a, ks_delta* recs, hipStream_t st);
+
 }  // namespace ks

@@ -36,7 +36,14 @@
 //                       (updateUnscheduledAggNode(−1), :1291-1305) counted from the tasks' own chunked
 //                       segments, the REMOVE_NODE records and, through the commit's capacity pass in
 //                       its completing mode, the capacity records generated for store_apply
+//   add tasks           AddOrUpdateJobNodes (graph_manager.go:166-208): addTaskNode (:632-648) and the
+//                       arcs of updateTaskNode (:1183-1285) as ADD_NODE and ADD_ARC records at fixed
+//                       stream positions, every head checked against node liveness and types, and
+//                       updateUnscheduledAggNode(+1) (:194, :1291-1305): the gains counted with one
+//                       atomic per aggregator per wave, the store's (src, dst) index telling a capacity
+//                       rise from an arc to re-create. No residual CSR is read and no BFS runs
 #include "ks_sched.h"
+#include "ks_store.h"
 
 namespace ks {
 namespace {
@@ -699,6 +706,127 @@ __global__ void k_gather_bindings(int k, const unsigned long long* __restrict__ 
         out[i] = bind[ids[i] - 1];
 }
 
+// -------------------------------------------------------------------- add tasks ---
+// AddOrUpdateJobNodes (graph_manager.go:166-208) on the device-resident graph: addTaskNode
+// (:632-648), the arcs of updateTaskNode (:1183-1285) and updateUnscheduledAggNode(+1) (:194,
+// :1291-1305). The work follows the arrivals: one lane per input arc, one per new task, and a
+// pass over the node slots for the aggregators that gain; nothing walks a segment.
+
+// The task of input arc j: the last i with arc_off[i] ≤ j (a task without arcs shares its
+// offset with its successor, which owns the arc).
+__device__ __forceinline__ int add_task_of(const AddDev& a, long long j) {
+    int lo = 0, hi = a.k - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (a.arc_off[mid] <= (unsigned long long)j) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// A head must be a node that was live before the call and is no task (the new tasks are dead
+// slots here: an arc into one of them is refused with the rest). Arrivals of one job meet on
+// their aggregator's word, 64 to a wave: the lanes combine into one atomic per distinct
+// aggregator (wave_add_distinct), so a job's 5,000 arrivals cost ~80 same-word atomics, not 5,000.
+__global__ void k_add_heads(SchedDev d, AddDev a) {
+    for (long long j0 = blockIdx.x * (long long)SB; j0 < a.na; j0 += (long long)gridDim.x * SB) {   // (uniform per workgroup)
+        const long long j = j0 + threadIdx.x;
+        bool agg = false;
+        int v = 0;
+        if (j < a.na) {
+            const ks_task_arc x = a.arcs[j];
+            bool ok = x.dst >= 1 && x.dst <= (unsigned long long)a.nst;
+            if (ok) {
+                v = (int)(x.dst - 1);
+                ok = d.n_alive[v] && d.n_type[v] != KS_NODE_TASK;
+            }
+            if (!ok) {
+                v = 0;
+                atomicMax(&a.ctl->bad_head, (int)(a.na - j));
+            } else if (x.cost > (1LL << 40) || x.cost < -(1LL << 40)) {
+                atomicMax(&a.ctl->bad_cost, (int)(a.na - j));
+            } else if (a.fl[v] & 1) {
+                agg = true;
+                atomicAdd(&a.t_agg[add_task_of(a, j)], 1);   // (a task's own word: one arc per task in a legal call)
+            }
+        }
+        wave_add_distinct(a.agg_cnt, v, agg);
+        wave_count(&a.ctl->units, agg);
+    }
+}
+
+// A task has one job: more than one arc into the flagged aggregators (two of them, or one
+// twice) is refused, and under the NULL rule so is none (its aggregator may have lost the arc
+// into the sink that would have flagged it).
+__global__ void k_add_task_check(AddDev a) {
+    for (long long i = blockIdx.x * (long long)SB + threadIdx.x; i < a.k; i += (long long)gridDim.x * SB) {
+        const int c = a.t_agg[i];
+        if (c > 1) atomicMax(&a.ctl->bad_multi, (int)(a.k - i));
+        else if (c == 0 && a.null_rule) atomicMax(&a.ctl->bad_none, (int)(a.k - i));
+    }
+}
+
+// updateUnscheduledAggNode(+1) (:1291-1305): the store's (src, dst) index tells "raise the
+// capacity" (the arc is there) from "the arc is gone, re-create it" (:1300-1304).
+__global__ void k_add_agg_flags(SchedDev d, AddDev a) {
+    for (long long v0 = blockIdx.x * (long long)SB; v0 <= a.nst; v0 += (long long)gridDim.x * SB) {   // (uniform per workgroup)
+        const long long v = v0 + threadIdx.x;
+        int f = 0, slot = -1;
+        if (v < a.nst && a.agg_cnt[v] > 0) {
+            f = 1;
+            if (a.sink >= 0 && a.hmask >= 0) {
+                const int e = store_hfind(a.hkey, a.hmask, arc_hkey(v + 1, a.sink + 1));
+                const int s = e >= 0 ? a.hval[e] : -1;
+                if (s >= 0 && s < d.hi && d.a_alive[s]) slot = s;
+            }
+        }
+        if (v <= a.nst) {
+            a.aflag[v] = f;
+            a.a_slot[v] = slot;
+        }
+        wave_count(&a.ctl->rec_upd, f && slot >= 0);
+        wave_count(&a.ctl->rec_add, f && slot < 0);
+    }
+}
+
+__global__ void k_add_totals(AddDev a) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) a.ctl->rec_agg = a.a_off[a.nst];
+}
+
+// Stream positions 0 … k − 1: the ADD_NODE records in input order; k … k + na − 1: the task
+// arcs in input order (AddArc(task, head, 0, 1, cost, ArcTypeOther)).
+__global__ void k_add_emit_tasks(AddDev a, ks_delta* __restrict__ recs) {
+    const long long n = (long long)a.k + a.na;
+    for (long long i = blockIdx.x * (long long)SB + threadIdx.x; i < n; i += (long long)gridDim.x * SB) {
+        if (i < a.k) {
+            ks_delta x{};
+            x.kind = KS_ADD_NODE;
+            x.type = KS_NODE_TASK;
+            x.id = a.tasks[i];
+            x.excess = 1;
+            recs[i] = x;
+        } else {
+            const long long j = i - a.k;
+            const ks_task_arc t = a.arcs[j];
+            recs[i] = arc_record(KS_ADD_ARC, 0, (int)(a.tasks[add_task_of(a, j)] - 1), (int)(t.dst - 1), 0, 1, t.cost, 0);
+        }
+    }
+}
+
+// The aggregator records behind them, in ascending aggregator id (the scan over the node slots).
+__global__ void k_add_emit_aggs(SchedDev d, AddDev a, ks_delta* __restrict__ recs) {
+    const long long base = (long long)a.k + a.na;
+    for (long long v = blockIdx.x * (long long)SB + threadIdx.x; v < a.nst; v += (long long)gridDim.x * SB) {
+        if (!a.aflag[v]) continue;
+        const long long cnt = (long long)a.agg_cnt[v];
+        const int s = a.a_slot[v];
+        recs[base + a.a_off[v]] =
+            s >= 0 ? arc_record(KS_UPDATE_ARC, d.a_type[s], (int)v, (int)a.sink, d.a_low[s], d.a_cap[s] + cnt, d.a_cost[s],
+                                d.a_cost[s])
+                   : arc_record(KS_ADD_ARC, 0, (int)v, (int)a.sink, 0, cnt, a.sink_cost, 0);
+    }
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------ launchers ---
@@ -854,6 +982,25 @@ hipError_t sched_gather_bindings(const SchedDev& d, const unsigned long long* id
     if (k)
         hipLaunchKernelGGL(k_gather_bindings, dim3(grid(k)), dim3(SB), 0, st, k, ids,
                            (const unsigned long long*)d.n_bind, out);
+    return hipGetLastError();
+}
+
+hipError_t sched_add_check(const SchedDev& d, const AddDev& a, const unsigned long long* ids, int nu, hipStream_t st) {
+    mark_aggregators(d, ids, nu, a.fl, st);
+    if (a.na) hipLaunchKernelGGL(k_add_heads, dim3(grid(a.na)), dim3(SB), 0, st, d, a);
+    if (a.k) hipLaunchKernelGGL(k_add_task_check, dim3(grid(a.k)), dim3(SB), 0, st, a);
+    hipLaunchKernelGGL(k_add_agg_flags, dim3(grid(a.nst + 1)), dim3(SB), 0, st, d, a);
+    return hipGetLastError();
+}
+
+hipError_t sched_add_totals(const AddDev& a, hipStream_t st) {
+    hipLaunchKernelGGL(k_add_totals, dim3(1), dim3(64), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t sched_add_emit(const SchedDev& d, const AddDev& a, ks_delta* recs, hipStream_t st) {
+    hipLaunchKernelGGL(k_add_emit_tasks, dim3(grid((long long)a.k + a.na)), dim3(SB), 0, st, a, recs);
+    if (a.nst) hipLaunchKernelGGL(k_add_emit_aggs, dim3(grid(a.nst)), dim3(SB), 0, st, d, a, recs);
     return hipGetLastError();
 }
 

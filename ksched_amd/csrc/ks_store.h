@@ -100,6 +100,31 @@ __host__ __device__ inline unsigned long long arc_hkey(long long src_id, long lo
     return ((unsigned long long)src_id << 32) | (unsigned long long)dst_id;
 }
 
+#if defined(__HIP__)
+// The index's hash and its read-only lookup, shared with the kernels of other sources that
+// only ask whether the store holds an arc (ks_sched.hip: ks_add_tasks). No apply may run
+// beside them: the lookup takes no part in the insert protocol of ks_store.hip.
+__device__ __forceinline__ unsigned store_hslot(unsigned long long k, int mask) {
+    k ^= k >> 33;
+    k *= 0xff51afd7ed558ccdULL;
+    k ^= k >> 33;
+    k *= 0xc4ceb9fe1a85ec53ULL;
+    k ^= k >> 33;
+    return (unsigned)k & (unsigned)mask;
+}
+
+// Index of key k's entry (its arc slot is hval[entry], −1 while a record is pending), −1 absent.
+__device__ inline int store_hfind(const unsigned long long* hkey, int hmask, unsigned long long k) {
+    unsigned i = store_hslot(k, hmask);
+    for (int probe = 0; probe <= hmask; ++probe, i = (i + 1) & (unsigned)hmask) {
+        const unsigned long long cur = hkey[i];
+        if (cur == k) return (int)i;
+        if (cur == HKEY_EMPTY) return -1;
+    }
+    return -1;
+}
+#endif
+
 // Launchers (ks_store.hip). All run on `st` and return hipGetLastError().
 // Apply k device-resident delta records (recs) and ne node edits; rec_ent is
 // scratch of k ints. The StoreCtl counters killed..superseded are reset first.

@@ -32,14 +32,7 @@ namespace {
 
 constexpr int SBLK = 256;
 
-__device__ __forceinline__ unsigned hslot(unsigned long long k, int mask) {
-    k ^= k >> 33;
-    k *= 0xff51afd7ed558ccdULL;
-    k ^= k >> 33;
-    k *= 0xc4ceb9fe1a85ec53ULL;
-    k ^= k >> 33;
-    return (unsigned)k & (unsigned)mask;
-}
+__device__ __forceinline__ unsigned hslot(unsigned long long k, int mask) { return store_hslot(k, mask); }
 
 // Index of key k's entry, inserting it (value −1) when absent. −1 if the table is full.
 __device__ int h_find_or_insert(const StoreDev& d, unsigned long long k) {
@@ -55,15 +48,7 @@ __device__ int h_find_or_insert(const StoreDev& d, unsigned long long k) {
     return -1;
 }
 
-__device__ int h_find(const StoreDev& d, unsigned long long k) {
-    unsigned i = hslot(k, d.hmask);
-    for (int probe = 0; probe <= d.hmask; ++probe, i = (i + 1) & (unsigned)d.hmask) {
-        const unsigned long long cur = d.hkey[i];
-        if (cur == k) return (int)i;
-        if (cur == HKEY_EMPTY) return -1;
-    }
-    return -1;
-}
+__device__ int h_find(const StoreDev& d, unsigned long long k) { return store_hfind(d.hkey, d.hmask, k); }
 
 // Wave-aggregated counter updates and slot allocation. A round's delta stream
 // deletes and inserts tens of thousands of arcs (config 4: ~25k of each), and

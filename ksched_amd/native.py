@@ -22,6 +22,7 @@ EXPORTED_SYMBOLS = (
     "ks_coalesce_deltas", "ks_get_store_stats", "ks_set_bindings", "ks_scheduling_deltas",
     "ks_update_unsched_costs", "ks_topology_stats", "ks_get_graph", "ks_commit_schedule",
     "ks_commit_preemptive", "ks_remove_resources", "ks_complete_tasks", "ks_get_bindings",
+    "ks_add_tasks",
     "ks_batch_create", "ks_batch_create_rank", "ks_batch_unique_id", "ks_batch_destroy", "ks_batch_last_error",
     "ks_batch_load", "ks_batch_solve", "ks_batch_gather",
     "ks_batch_slots", "ks_batch_owner", "ks_batch_block_len", "ks_batch_unpack",
@@ -138,6 +139,18 @@ class KsCompleteStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
+class KsAddStats(C.Structure):
+    """ks_add_stats: what one ks_add_tasks generated on device."""
+    _fields_ = [("tasks", C.c_int64), ("arcs_added", C.c_int64), ("unsched_updates", C.c_int64),
+                ("unsched_added", C.c_int64), ("records", C.c_int64), ("reserved", C.c_int64 * 7)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+TASK_ARC_DT = np.dtype({"names": ["dst", "cost"], "formats": ["<u8", "<i8"], "offsets": [0, 8], "itemsize": 16})
+
+
 class KsError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"ksmcmf error {code}: {msg}")
@@ -245,6 +258,7 @@ def _bind(path: str):
     L.ks_remove_resources.argtypes = [V, C.c_int32, V, C.c_size_t, V, C.c_size_t, P(C.c_size_t), V, C.c_size_t,
                                       P(C.c_size_t), P(KsRemoveStats)]
     L.ks_complete_tasks.argtypes = [V, C.c_int32, V, C.c_size_t, V, C.c_size_t, V, P(KsCompleteStats)]
+    L.ks_add_tasks.argtypes = [V, C.c_int32, V, C.c_size_t, V, V, V, C.c_size_t, C.c_int64, P(KsAddStats)]
     L.ks_get_bindings.argtypes = [V, V, V, C.c_size_t]
     return L
 
@@ -479,6 +493,31 @@ class Context:
                                               None if agg is None else agg.ctypes.data,
                                               nu, left.ctypes.data, C.byref(st)))
         return left[:ids.shape[0]], st.as_dict()
+
+    def add_tasks(self, tasks, arc_off, dst, cost, unsched_ids=None, unsched_sink_cost: int = 0) -> dict:
+        """ks_add_tasks: the arriving task ids enter the device-resident graph as task nodes with
+        supply 1; task i gets the arcs (dst[j], cost[j]) for arc_off[i] <= j < arc_off[i + 1]
+        (low 0, cap 1, type 0), and each unscheduled aggregator gains one unit on its arc into
+        the sink per arriving task with an arc into it (the arc is re-created with
+        unsched_sink_cost when the store no longer holds it). unsched_ids=None: every type-0
+        node with an arc into the sink; a task without an arc into one of those is then
+        refused. → stats dict. Needs no solve; invalidates the solution when a task arrives."""
+        ids = np.ascontiguousarray(tasks, np.uint64).reshape(-1)
+        off = np.ascontiguousarray(arc_off, np.uint64).reshape(-1)
+        if off.shape[0] != ids.shape[0] + 1:
+            raise ValueError("arc_off has one entry more than tasks")
+        arcs = np.zeros(max(np.asarray(dst).size, 1), TASK_ARC_DT)
+        arcs["dst"][:np.asarray(dst).size] = np.asarray(dst, np.uint64).reshape(-1)
+        arcs["cost"][:np.asarray(cost).size] = np.asarray(cost, np.int64).reshape(-1)
+        agg = None if unsched_ids is None else np.ascontiguousarray(unsched_ids, np.uint64).reshape(-1)
+        nu = 0 if agg is None else agg.shape[0]
+        if agg is not None and nu == 0:
+            agg = np.zeros(1, np.uint64)   # an empty list names no aggregator: not NULL, which is the auto rule
+        st = KsAddStats()
+        self._check(self._L.ks_add_tasks(self._h, 0, ids.ctypes.data, ids.shape[0], off.ctypes.data, arcs.ctypes.data,
+                                         None if agg is None else agg.ctypes.data, nu, int(unsched_sink_cost),
+                                         C.byref(st)))
+        return st.as_dict()
 
     def bindings(self, tasks) -> np.ndarray:
         """ks_get_bindings: the PU each task id is bound to on the device, 0 = unbound."""
