@@ -103,6 +103,8 @@ extern "C" {
                                   entry points and one stats struct were added).
                                   ks_add_tasks (still 5: one entry point and two structs
                                   were added, nothing was resized).
+                                  ks_add_resources (still 5: one entry point and three
+                                  structs were added).
                                   ks_opts (96 B) CHANGED SIZE in ABI 2 and ks_result in
                                   ABI 2, 3 and 5: a caller must check
                                   ks_abi_version() == KSMCMF_ABI_VERSION before ks_create. */
@@ -824,6 +826,104 @@ int ks_add_tasks(ks_ctx* ctx, int32_t flags,
                  const uint64_t* arc_off /* k + 1 */, const ks_task_arc* arcs,
                  const uint64_t* unsched_ids, size_t nu, int64_t unsched_sink_cost,
                  ks_add_stats* stats /* may be NULL */);
+
+typedef struct ks_res_node {          /* 32 B: one new resource node                        */
+    uint64_t id;              /* caller-allocated NodeID (id reuse is the caller's, as in ks_add_tasks) */
+    int32_t  type;            /* KS_NODE_PU, _MACHINE, _INTERMEDIATE or _OTHER (a rack)     */
+    int32_t  _pad;
+    uint64_t slots;           /* PU: capacity of its arc into the sink (MaxTasksPerPu), >= 1; others: 0 */
+    int64_t  sink_cost;       /* PU: cost of that arc (LeafResourceNodeToSinkCost); others: 0 */
+} ks_res_node;
+
+#define KS_RES_TREE  0   /* the ParentId edge: each child has at most one; slots sum up along it */
+#define KS_RES_EXTRA 1   /* any other arc into a node of the call (an equivalence class or cluster
+                            aggregator -> machine): gets the head's capacity, sums nothing      */
+#define KS_RES_MAX_DEPTH 32   /* KS_RES_TREE edges between a new PU and the topology's root, at most */
+typedef struct ks_res_arc {           /* 32 B */
+    uint64_t parent, child;
+    int64_t  cost;            /* ResourceNodeToResourceNodeCost; used when the arc is created */
+    int32_t  kind;            /* KS_RES_TREE / KS_RES_EXTRA */
+    int32_t  _pad;
+} ks_res_arc;
+
+typedef struct ks_grow_stats {        /* 96 B */
+    int64_t nodes, pus, slots;        /* ADD_NODE records; of those PUs; their slots summed      */
+    int64_t sink_arcs;                /* PU -> sink ADD_ARC records (== pus)                     */
+    int64_t arcs_added;               /* edge records that are ADD_ARC (new head, or arc not held) */
+    int64_t cap_updates;              /* edge records that are UPDATE_ARC (held arc, cap raised)  */
+    int64_t arcs_skipped;             /* edges that get no record (no new slot beneath the head)  */
+    int64_t records;                  /* nodes + sink_arcs + arcs_added + cap_updates             */
+    int64_t reserved[4];
+} ks_grow_stats;
+
+/* Machines, racks and PUs join the graph, on device: AddResourceTopology
+ * (flowmanager/graph_manager.go:238-251) through addResourceTopologyDFS (:557-630),
+ * addResourceNode (:528-551), updateResToSinkArc (:1116-1129) and capacityFromResNodeToParent
+ * (:662-667), and updateResourceStatsUpToRoot (:1041-1061) for the arcs above the attach
+ * point. The records are generated in device memory and applied as ONE stream with the
+ * semantics of ks_apply_deltas (all or nothing, in place, store counters, warm-start
+ * bookkeeping, the dirty-cell marks of a partition). The stream's order is fixed, so a host
+ * restatement produces the identical stream: n ADD_NODE records at positions 0 … n − 1 in
+ * input order; the PU → sink arcs in input order of the PUs; then one record per edge that
+ * gets one, in input order. No (src, dst) appears twice: ks_store_stats.superseded stays 0.
+ * Only the two 32-byte arrays and the host's node edits cross PCIe; the caller keeps no shadow
+ * of the ancestors' capacities and need not know which ancestor arc the store still holds.
+ *   - Nodes: each enters with supply 0 and its type. The ids follow the ADD_NODE rule of
+ *     ks_apply_deltas, as in ks_add_tasks: in 1 … 2^30 − 1 (KS_E_RANGE), no live node, an id
+ *     listed twice is "already present" (KS_E_INVALID); a reused dead id or any id beyond the
+ *     highest in use is legal. A type of task or sink, or an unknown one: KS_E_INVALID. A PU
+ *     with slots == 0, or another node with slots or sink_cost other than 0: KS_E_INVALID.
+ *     slots > 2^53 or |sink_cost| > 2^40: KS_E_RANGE. The first offending node in input order
+ *     is named (on one node: the id, the type, then the values); nothing changes. The new
+ *     slots of one call summed beyond 2^53: KS_E_RANGE. Each new PU gets ADD_ARC PU → sink
+ *     (low 0, cap slots, cost sink_cost, type 0); a call with a PU needs exactly one sink
+ *     (KS_E_INVALID).
+ *   - Edges: parent and child must each be a node of this call or a node that was live before
+ *     it; the parent no task, no sink and no PU, the child no task and no sink; parent ==
+ *     child: KS_E_INVALID. An unknown kind: KS_E_INVALID. A KS_RES_TREE edge from a new parent
+ *     to a node that was live before the call: KS_E_INVALID (a live node does not move).
+ *     |cost| > 2^40: KS_E_RANGE. A (parent, child) pair listed twice: KS_E_INVALID. A child
+ *     named by two KS_RES_TREE edges: KS_E_INVALID, the error names the child (a resource has
+ *     one parent). The first offending edge in input order is the one reported, on one edge in
+ *     the order of this list; nothing changes. The KS_RES_TREE edges whose child was live
+ *     before the call are the chain: the caller lists the ancestors of each attach point up to
+ *     the topology's root (rack → machine, root → rack, …; Go's nodeToParentNode has them).
+ *   - New slots beneath a node: S(v) = the slots of the new PUs from which v is reached going
+ *     up KS_RES_TREE edges, a new PU counting itself. A PU whose walk has not ended after
+ *     KS_RES_MAX_DEPTH edges (a cycle, or a topology too deep): KS_E_INVALID, the first such PU
+ *     in input order is named; nothing changes.
+ *   - Capacities: a function of the edge's head v only, for both kinds. New resources run
+ *     nothing, so slots − running (ks_commit_schedule's rule) and slots (ks_commit_preemptive's)
+ *     both rise by exactly S(v): one rule serves both, which is why flags is reserved.
+ *       S(v) == 0                      no record (arcs_skipped): a capacity of 0 is an absent
+ *                                      arc. An empty rack's arc is created by the later call
+ *                                      that attaches beneath it and lists the edge as chain.
+ *       v new, S(v) > 0                ADD_ARC (low 0, cap S(v), the edge's cost, type 0)
+ *       v live, the store holds        UPDATE_ARC: low, cost and type kept, cap = old + S(v)
+ *         parent → v                   (beyond 2^53: KS_E_RANGE, nothing changes)
+ *       v live, the store does not     ADD_ARC (low 0, cap S(v), the edge's cost, type 0): the
+ *         hold it                      capacity had fallen to 0 (a full machine under the
+ *                                      pinned rule), which removed the arc
+ *     The store's (src, dst) index tells the last two apart; the pinned recipe of
+ *     ks_complete_tasks is not needed here.
+ *   - What the device cannot check: that the chain reaches the root, and that every arc into
+ *     a chain node is listed. A chain cut short leaves the arcs above it one subtree short, an
+ *     unlisted KS_RES_EXTRA arc into a chain node likewise. ks_complete_tasks(k = 0,
+ *     KS_COMPLETE_RESOURCE_CAPS[ | KS_COMPLETE_PREEMPTIVE]) repairs both (arcs that fell to 0
+ *     first re-created by the pinned recipe).
+ *   - flags must be 0 (reserved); anything else is KS_E_INVALID.
+ * Needs no previous solve, no residual CSR and no BFS. n == 0 && m == 0 does nothing and
+ * keeps the solution, as does a call that generates no record. Success with a record
+ * invalidates the solution and the mapping, exactly as ks_apply_deltas does; a node beyond the
+ * built CSR or a full segment takes the store's rebuild path (ks_store_stats.rebuilds). Every
+ * refusal is found before anything changes on the device, and the host's node table is rolled
+ * back. A device failure after the records were emitted leaves the store unusable until the
+ * next ks_load_graph; the host's node table is rolled back. stats may be NULL. No batch twin.
+ * UpdateResourceTopology (:217-236, a resource's slots change) is not covered. */
+int ks_add_resources(ks_ctx* ctx, int32_t flags /* must be 0 */,
+                     const ks_res_node* nodes, size_t n,
+                     const ks_res_arc* arcs, size_t m,
+                     ks_grow_stats* stats /* may be NULL */);
 
 /* pu[i] = the PU task[i] is bound to on the device (ks_set_bindings, the commits), 0 =
  * unbound: for the pinned recipe above and for checkpoints. A task id that is not a live

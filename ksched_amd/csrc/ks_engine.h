@@ -129,6 +129,12 @@ public:
     int add_tasks(const uint64_t* tasks, size_t k, const uint64_t* arc_off, const ks_task_arc* arcs,
                   const uint64_t* unsched_ids, size_t nu, int64_t sink_slot, int64_t sink_cost, int64_t nslots,
                   ks_add_stats* stats, const AddEdits& make_edits, bool* dirty, std::string& err);
+    // ks_add_resources (the n new resource nodes, checked and already entered in the host's node
+    // table, and the m edges; first_pair: the first edge that repeats an earlier (parent, child),
+    // m when none does). make_edits and *dirty as in add_tasks; *changed: records were applied.
+    int add_resources(const ks_res_node* nodes, size_t n, const ks_res_arc* arcs, size_t m, size_t first_pair,
+                      int64_t sink_slot, int64_t nslots, ks_grow_stats* stats, const AddEdits& make_edits, bool* dirty,
+                      bool* changed, std::string& err);
     // ks_get_bindings: pu[i] = the device-kept binding of task[i] (ids checked by the caller).
     int get_bindings(const uint64_t* task, uint64_t* pu, size_t k, std::string& err);
     int device() const;

@@ -1,7 +1,7 @@
 // ks_engine_sched.hip — the engine's scheduler glue: bindings, scheduling deltas,
 // unscheduled costs, topology statistics, ks_commit_schedule and ks_commit_preemptive,
-// ks_remove_resources, ks_complete_tasks, ks_add_tasks and ks_get_bindings. It launches the
-// kernels of ks_sched.hip and ks_store.hip through their launchers, none of the engine's.
+// ks_remove_resources, ks_complete_tasks, ks_add_tasks, ks_add_resources and ks_get_bindings. It
+// launches the kernels of ks_sched.hip and ks_store.hip through their launchers, none of the engine's.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -985,6 +985,191 @@ int Engine::add_tasks(const uint64_t* tasks, size_t k, const uint64_t* arc_off, 
         stats->arcs_added = (int64_t)na;
         stats->unsched_updates = h.rec_upd;
         stats->unsched_added = h.rec_add;
+        stats->records = nrec;
+    }
+    return KS_OK;
+}
+
+// ks_add_resources: the sixth body, on the scratch carve of add_tasks. The nodes were checked
+// against the host's node table and entered there; the two 32-byte arrays go up, one lane per
+// edge checks it and claims the child's parent word, the new PUs' slots climb the parent words,
+// the store's index says which edge into a live head is still held, and ONE host sync brings
+// every refusal and the record counts (no step before it writes anything but scratch). Then the
+// host's node edits, the sizing of the node store, the arc table and the index, and the
+// ADD_NODE records (stream positions 0 … n − 1), the PU → sink arcs and the edge records behind
+// them reach store_apply as one stream. Neither the residual CSR nor the topology BFS is needed.
+// first_pair: the first edge that repeats an earlier (parent, child), m: none (the host's sort).
+int Engine::add_resources(const ks_res_node* nodes, size_t n, const ks_res_arc* arcs, size_t m, size_t first_pair,
+                          int64_t sink_slot, int64_t nslots, ks_grow_stats* stats, const AddEdits& make_edits,
+                          bool* dirty, bool* changed, std::string& err) {
+    EngineImpl& s = *p_;
+    *dirty = *changed = false;
+    if (!n && !m) return KS_OK;
+    KS_CHECK(hipSetDevice(s.device));
+    hipStream_t st = s.stream;
+    const bool log = s.opts.log_cycles != 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int64_t nst = s.nstore;
+    if (n > (size_t)INT32_MAX / 16 || m > (size_t)INT32_MAX / 16) {
+        err = "too many resource nodes or edges";
+        return KS_E_RANGE;
+    }
+    int64_t ntot = nst, pus = 0, slots = 0;
+    for (size_t i = 0; i < n; ++i) {
+        ntot = std::max<int64_t>(ntot, (int64_t)nodes[i].id);
+        if (nodes[i].type == KS_NODE_PU) {
+            ++pus;
+            slots += (int64_t)nodes[i].slots;
+        }
+    }
+    GrowDev g{};
+    g.n = (int)n;
+    g.m = (int)m;
+    g.nst = nst;
+    g.ntot = ntot;
+    g.sink = sink_slot >= 0 && sink_slot < nst ? sink_slot : -1;
+    unsigned long long *d_nodes = nullptr, *d_arcs = nullptr;
+    auto carve = [&](Carve<int> ci, Carve<unsigned long long> cu) {
+        for (int** x : {&g.newt, &g.par}) *x = ci.take(ntot + 1);
+        for (int** x : {&g.nflag, &g.n_off}) *x = ci.take((int64_t)n + 1);
+        for (int** x : {&g.eflag, &g.e_off, &g.e_slot}) *x = ci.take((int64_t)m + 1);
+        g.S = cu.take(ntot + 1);   // (first: the only u64 array that starts zeroed)
+        d_nodes = cu.take(4 * (int64_t)n);
+        d_arcs = cu.take(4 * (int64_t)m);
+        return std::make_pair(ci.n, cu.n);
+    };
+    const auto [n_i, n_u] = carve({nullptr}, {nullptr});
+    KS_CHECK(s.cm_i.ensure(n_i));
+    KS_CHECK(s.cm_u.ensure(n_u));
+    KS_CHECK(s.grow_ctl.ensure(1));
+    carve({s.cm_i.p}, {s.cm_u.p});
+    g.ctl = s.grow_ctl.p;
+    g.nodes = (const ks_res_node*)d_nodes;
+    g.arcs = (const ks_res_arc*)d_arcs;
+    g.hkey = s.hkey.p;
+    g.hval = s.hval.p;
+    g.hmask = s.hcap ? (int)(s.hcap - 1) : -1;
+    KS_CHECK(hipMemsetAsync(s.cm_i.p, 0, n_i * sizeof(int), st));
+    KS_CHECK(hipMemsetAsync(g.S, 0, (ntot + 1) * 8, st));
+    KS_CHECK(hipMemsetAsync(s.grow_ctl.p, 0, sizeof(GrowCtl), st));
+    if (n) KS_CHECK(hipMemcpyAsync(d_nodes, nodes, n * sizeof(ks_res_node), hipMemcpyHostToDevice, st));
+    if (m) KS_CHECK(hipMemcpyAsync(d_arcs, arcs, m * sizeof(ks_res_arc), hipMemcpyHostToDevice, st));
+    SchedDev d = s.schd();
+    // ---- 1. the edges, the sums and the arcs the store still holds: one sync
+    KS_CHECK(sched_grow_check(d, g, st));
+    KS_CHECK(exclusive_sum(s, (const int*)g.nflag, g.n_off, (int64_t)n + 1, st));
+    KS_CHECK(exclusive_sum(s, (const int*)g.eflag, g.e_off, (int64_t)m + 1, st));
+    KS_CHECK(sched_grow_totals(g, st));
+    GrowCtl h{};
+    KS_CHECK(hipMemcpyAsync(&h, g.ctl, sizeof(GrowCtl), hipMemcpyDeviceToHost, st));
+    KS_CHECK(hipStreamSynchronize(st));
+    const auto t1 = std::chrono::steady_clock::now();
+    if (h.bad_edge || first_pair < m) {   // the first offending edge in input order; on one edge the lowest class
+        if (h.bad_edge < 0 || (size_t)(h.bad_edge >> 3) > m || (h.bad_edge && ((h.bad_edge & 7) == 0 || h.bad_edge < 8))) {
+            err = "inconsistent edge index";
+            return KS_E_DEVICE;
+        }
+        size_t j = h.bad_edge ? m - (size_t)(h.bad_edge >> 3) : m;
+        int cls = h.bad_edge ? 7 - (h.bad_edge & 7) : 7;
+        if (first_pair < j || (first_pair == j && cls == 6)) {   // (the repeated pair ranks before the second parent)
+            j = first_pair;
+            cls = 7;
+        }
+        const ks_res_arc& e = arcs[j];
+        const std::string who = "edge " + std::to_string(e.parent) + " -> " + std::to_string(e.child) + ": ";
+        switch (cls) {
+            case 0:
+                err = who + "parent " + std::to_string(e.parent) + " is not a node of this call or a live node that is no task, "
+                      "no sink and no PU";
+                break;
+            case 1:
+                err = who + "child " + std::to_string(e.child) + " is not a node of this call or a live node that is no task and "
+                      "no sink";
+                break;
+            case 2: err = who + "parent and child are node " + std::to_string(e.child); break;
+            case 3: err = who + "unknown kind " + std::to_string(e.kind); break;
+            case 4:
+                err = who + "a tree edge from a new parent to live node " + std::to_string(e.child) + ": a live node does not move";
+                break;
+            case 5: err = who + "the cost is outside the supported range"; return KS_E_RANGE;
+            case 6: err = who + "child " + std::to_string(e.child) + " has a second tree edge: a resource has one parent"; break;
+            default: err = who + "the pair is listed twice"; break;
+        }
+        return KS_E_INVALID;
+    }
+    if (h.bad_depth) {
+        if (h.bad_depth < 0 || (size_t)h.bad_depth > n) {
+            err = "inconsistent node index";
+            return KS_E_DEVICE;
+        }
+        err = "PU " + std::to_string(nodes[n - (size_t)h.bad_depth].id) + ": its tree edges do not end after " +
+              std::to_string(KS_RES_MAX_DEPTH) + " steps (a cycle, or a topology too deep)";
+        return KS_E_INVALID;
+    }
+    if (h.bad_cap) {
+        if (h.bad_cap < 0 || (size_t)h.bad_cap > m) {
+            err = "inconsistent edge index";
+            return KS_E_DEVICE;
+        }
+        const ks_res_arc& e = arcs[m - (size_t)h.bad_cap];
+        err = "edge " + std::to_string(e.parent) + " -> " + std::to_string(e.child) + ": the raised capacity is outside the "
+              "supported range";
+        return KS_E_RANGE;
+    }
+    if (h.rec_upd < 0 || h.rec_add < 0 || h.skipped < 0 || h.rec_upd + h.rec_add != h.rec_edge ||
+        (int64_t)h.rec_edge + h.skipped != (int64_t)m || h.rec_pu != pus) {
+        err = "inconsistent record counts";
+        return KS_E_DEVICE;
+    }
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        stats->arcs_skipped = h.skipped;
+    }
+    const int64_t nrec = (int64_t)n + h.rec_pu + h.rec_edge;
+    if (!nrec) return KS_OK;   // chain edges alone with no new slot beneath them: nothing to write
+    // ---- 2. room for the new nodes and arcs; the host's node table follows
+    int rc = ensure_nodes(s, std::max<int64_t>(nslots, 1), err);
+    if (rc == KS_OK) rc = ensure_arcs(s, (int64_t)s.hi() + h.rec_pu + h.rec_add, err);
+    if (rc == KS_OK) rc = ensure_hash(s, (int64_t)h.rec_pu + h.rec_add, err);
+    if (rc) return rc;
+    KS_CHECK(s.d_recs.ensure((size_t)nrec));
+    KS_CHECK(s.rec_ent.ensure((size_t)nrec));
+    KS_CHECK(s.d_edits.ensure(std::max<size_t>(n, 1)));
+    std::vector<NodeEdit> edits;
+    make_edits(&edits);
+    // from here on a failure leaves the device state unknown
+    *dirty = *changed = true;
+    s.nslots = std::max(s.nslots, nslots);
+    s.incremental = true;
+    d = s.schd();   // (the node store and the arc table may have moved)
+    const auto t2 = std::chrono::steady_clock::now();
+    // ---- 3. the records, at their fixed positions, and the apply
+    if (!edits.empty())
+        KS_CHECK(hipMemcpyAsync(s.d_edits.p, edits.data(), edits.size() * sizeof(NodeEdit), hipMemcpyHostToDevice, st));
+    KS_CHECK(sched_grow_emit(d, g, h.rec_pu, s.d_recs.p, st));
+    rc = mark_cells(s, s.d_recs.p, (size_t)nrec, s.d_edits.p, edits.size(), err);
+    if (rc) return rc;
+    KS_CHECK(store_apply(s.sd(), s.d_recs.p, (int)nrec, s.rec_ent.p, s.d_edits.p, (int)edits.size(), st));
+    rc = read_sctl(s, err);
+    if (rc == KS_OK) rc = applied(s, err);
+    if (rc) return rc;
+    if (log) {
+        const auto t3 = std::chrono::steady_clock::now();
+        auto ms = [](auto x, auto y) { return std::chrono::duration<double, std::milli>(y - x).count(); };
+        std::fprintf(stderr,
+                     "grow: %zu nodes, %zu edges, %lld records, upload + checks + sums %.3f ms, node table + sizing "
+                     "%.3f ms, emit + apply %.3f ms\n",
+                     n, m, (long long)nrec, ms(t0, t1), ms(t1, t2), ms(t2, t3));
+    }
+    s.solved = false;
+    if (nrec > (int64_t)n && s.cell_refused_values) s.cell_refused = s.cell_refused_values = false;   // (as run_apply)
+    if (stats) {
+        stats->nodes = (int64_t)n;
+        stats->pus = pus;
+        stats->slots = slots;
+        stats->sink_arcs = h.rec_pu;
+        stats->arcs_added = h.rec_add;
+        stats->cap_updates = h.rec_upd;
         stats->records = nrec;
     }
     return KS_OK;

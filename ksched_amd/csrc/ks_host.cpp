@@ -898,6 +898,77 @@ int ks_add_tasks(ks_ctx* c, int32_t flags, const uint64_t* tasks, size_t k, cons
     return KS_OK;
 }
 
+// AddResourceTopology (flowmanager/graph_manager.go:238-251). The nodes are the host's part: each
+// id enters the node table through the ADD_NODE rule of ks_apply_deltas (NodeTxn::add), then its
+// type and values are checked; a repeated (parent, child) pair is found by a sort. The device
+// checks the edges, sums the new slots up the tree edges and generates the records; a refusal
+// it finds takes the new nodes out of the table again.
+int ks_add_resources(ks_ctx* c, int32_t flags, const ks_res_node* nodes, size_t n, const ks_res_arc* arcs, size_t m,
+                     ks_grow_stats* stats) {
+    if (!c) return KS_E_INVALID;
+    if (int g = store_guard(c)) return g;
+    if (flags) return c->fail(KS_E_INVALID, "unknown flag (flags is reserved: pass 0)");
+    if ((n && !nodes) || (m && !arcs)) return c->fail(KS_E_INVALID, "null node or edge array");
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (!n && !m) return KS_OK;   // nothing joins: the solution stands
+    NodeTxn txn(c);
+    auto refuse = [&](int code, const std::string& msg) {
+        txn.rollback_nodes();
+        return c->fail(code, msg);
+    };
+    uint64_t total = 0;
+    bool pu = false;
+    for (size_t i = 0; i < n; ++i) {
+        const ks_res_node& x = nodes[i];
+        if (int rc = txn.add(x.id, 0, x.type)) {
+            txn.rollback_nodes();
+            return rc;
+        }
+        const std::string who = "resource node " + std::to_string(x.id);
+        if (x.type != KS_NODE_PU && x.type != KS_NODE_MACHINE && x.type != KS_NODE_INTERMEDIATE && x.type != KS_NODE_OTHER)
+            return refuse(KS_E_INVALID, who + " has type " + std::to_string(x.type) + ": not a resource type");
+        if (x.type == KS_NODE_PU ? x.slots == 0 : (x.slots != 0 || x.sink_cost != 0))
+            return refuse(KS_E_INVALID, x.type == KS_NODE_PU ? who + " is a PU without slots"
+                                                             : who + " is no PU: its slots and sink cost must be 0");
+        if (x.slots > (uint64_t(1) << 53) || x.sink_cost > (int64_t(1) << 40) || x.sink_cost < -(int64_t(1) << 40))
+            return refuse(KS_E_RANGE, who + ": slots or sink cost outside the supported range");
+        total += x.slots;
+        if (total > (uint64_t(1) << 53)) return refuse(KS_E_RANGE, who + ": the new slots summed exceed the supported range");
+        pu |= x.type == KS_NODE_PU;
+    }
+    if (pu && c->n_sinks != 1) return refuse(KS_E_INVALID, "a new PU's arc into the sink needs exactly one sink");
+    size_t first_pair = m;   // the first edge in input order that repeats an earlier (parent, child)
+    {
+        std::vector<size_t> order(m);
+        for (size_t j = 0; j < m; ++j) order[j] = j;
+        std::sort(order.begin(), order.end(), [&](size_t a, size_t b) {
+            if (arcs[a].parent != arcs[b].parent) return arcs[a].parent < arcs[b].parent;
+            if (arcs[a].child != arcs[b].child) return arcs[a].child < arcs[b].child;
+            return a < b;
+        });
+        for (size_t q = 1; q < m; ++q)
+            if (arcs[order[q]].parent == arcs[order[q - 1]].parent && arcs[order[q]].child == arcs[order[q - 1]].child)
+                first_pair = std::min(first_pair, order[q]);
+    }
+    const int64_t sink = c->n_sinks == 1 ? (int64_t)c->sink_id - 1 : -1;
+    bool dirty = false, changed = false;
+    auto make_edits = [&](std::vector<ks::NodeEdit>* edits) { txn.edits(*edits); };
+    const int rc = c->eng.add_resources(nodes, n, arcs, m, first_pair, sink, c->nslots(), stats, make_edits, &dirty,
+                                        &changed, c->err);
+    if (rc) {
+        if (dirty) txn.rollback_applied();   // (the edits were made: the stream may be half applied, reload first)
+        else txn.rollback_nodes();
+        if (stats) std::memset(stats, 0, sizeof(*stats));
+        return rc;
+    }
+    if (changed) {   // as after ks_apply_deltas
+        c->have_solution = false;
+        c->map_fresh = false;
+        c->flows_fresh = false;
+    }
+    return KS_OK;
+}
+
 int ks_get_bindings(ks_ctx* c, const uint64_t* task, uint64_t* pu, size_t k) {
     if (!c) return KS_E_INVALID;
     if (int g = store_guard(c)) return g;

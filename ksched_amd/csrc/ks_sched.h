@@ -268,4 +268,66 @@ hipError_t sched_add_totals(const AddDev& a, hipStream_t st);
 // in ascending id behind them (d: the arc table as it is now, after any growth).
 hipError_t sched_add_emit(const SchedDev& d, const AddDev& a, ks_delta* recs, hipStream_t st);
 
+// ---- ks_add_resources: machines, racks and PUs join the graph. AddResourceTopology
+// (flowmanager/graph_manager.go:238-251) → addResourceTopologyDFS (:557-630) with addResourceNode
+// (:528-551), updateResToSinkArc (:1116-1129) and capacityFromResNodeToParent (:662-667), and
+// updateResourceStatsUpToRoot (:1041-1061) above the attach point. The ids and the nodes'
+// values are the host's business (its node table); the device checks every edge's endpoints
+// against node liveness and types, sums the new PUs' slots up the KS_RES_TREE edges, asks the
+// store's (src, dst) index whether each edge into a live head is still held, and writes the
+// ADD_NODE, PU → sink and edge records at fixed stream positions for store_apply. Only the node
+// store, the arc table and the index are read: no residual CSR is needed and no BFS runs.
+
+// Device counters of one growth; the host reads them in one 32-byte copy.
+struct GrowCtl {
+    int bad_edge;    // 8·(m − j) + (7 − class) of the first offending edge j, lowest class first; 0 none.
+                     // class 0 parent, 1 child, 2 parent == child, 3 kind, 4 a live node would move,
+                     // 5 cost, 6 a second KS_RES_TREE edge into the child
+    int bad_depth;   // n − the index of the first new PU whose walk has not ended after KS_RES_MAX_DEPTH
+                     // edges, 0 none
+    int bad_cap;     // m − the index of the first edge whose raised capacity exceeds 2^53, 0 none
+    int rec_upd;     // edges whose arc the store holds (UPDATE_ARC)
+    int rec_add;     // edges that create their arc (ADD_ARC)
+    int skipped;     // edges without a record (no new slot beneath the head)
+    int rec_pu;      // the node scan's total: PU → sink records
+    int rec_edge;    // the edge scan's total: rec_upd + rec_add
+};
+
+// Inputs and scratch of one growth (device pointers). nst node slots before the call, ntot ≥
+// nst slots with the highest new id: the per-slot scratch covers ids beyond the store.
+struct GrowDev {
+    int n;                             // new nodes
+    int m;                             // edges
+    const ks_res_node* nodes;          // [n] checked by the host
+    const ks_res_arc* arcs;            // [m] unchecked
+    long long nst;                     // node slots whose liveness and type may be read
+    long long ntot;                    // node slots of the scratch
+    int* newt;                         // [ntot + 1] per node slot: 1 + the type of a new node, 0: not of this call
+    int* par;                          // [ntot + 1] per node slot: m − j of the first KS_RES_TREE edge j into it, 0
+                                       //   none (claimed with atomicMax, so the array starts zeroed)
+    unsigned long long* S;             // [ntot + 1] per node slot: the new slots beneath it
+    int* nflag;                        // [n + 1] 1: node i is a PU (its arc into the sink); n_off its scan
+    int* n_off;                        // [n + 1]
+    int* eflag;                        // [m + 1] 1: edge j gets a record; e_off its scan
+    int* e_off;                        // [m + 1]
+    int* e_slot;                       // [m + 1] arc slot of parent → child, −1: the store does not hold it
+    long long sink;                    // the sink's node slot, −1: other than one sink
+    const unsigned long long* hkey;    // the store's (src, dst) index (ks_store.h)
+    const int* hval;
+    int hmask;                         // capacity − 1, −1: no index yet
+    GrowCtl* ctl;
+};
+
+// The new nodes into the per-slot scratch (newt, S of the PUs, nflag); the edge pass, one lane
+// per edge (endpoints, kind, cost, the claim of par); the second-parent check; the sums, one
+// lane per new PU walking par with one atomic per distinct ancestor per wave and step; the
+// per-edge lookup (eflag, e_slot, ctl->rec_upd / rec_add / skipped / bad_cap). Nothing outside
+// the scratch is written. The caller scans nflag → n_off and eflag → e_off.
+hipError_t sched_grow_check(const SchedDev& d, const GrowDev& g, hipStream_t st);
+// ctl->rec_pu and ctl->rec_edge after the scans.
+hipError_t sched_grow_totals(const GrowDev& g, hipStream_t st);
+// The records: ADD_NODE at 0 … n − 1, the PU → sink arcs at n + n_off, the edge records at
+// n + rec_pu + e_off (d: the arc table as it is now, after any growth).
+hipError_t sched_grow_emit(const SchedDev& d, const GrowDev& g, int rec_pu, ks_delta* recs, hipStream_t st);
+
 }  // namespace ks

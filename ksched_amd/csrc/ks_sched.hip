@@ -42,6 +42,12 @@
 //                       updateUnscheduledAggNode(+1) (:194, :1291-1305): the gains counted with one
 //                       atomic per aggregator per wave, the store's (src, dst) index telling a capacity
 //                       rise from an arc to re-create. No residual CSR is read and no BFS runs
+//   add resources       AddResourceTopology (graph_manager.go:238-251): addResourceTopologyDFS (:557-630)
+//                       as ADD_NODE, PU → sink and resource-arc records at fixed stream positions, every
+//                       edge checked against node liveness and types; the new PUs' slots summed up the
+//                       parent edges with one atomic per ancestor per wave and step, and
+//                       updateResourceStatsUpToRoot (:1041-1061) for the arcs above the attach point, the
+//                       store's index again telling a capacity rise from an arc to re-create
 #include "ks_sched.h"
 #include "ks_store.h"
 
@@ -827,6 +833,190 @@ __global__ void k_add_emit_aggs(SchedDev d, AddDev a, ks_delta* __restrict__ rec
     }
 }
 
+// ---------------------------------------------------------------- add resources ---
+// AddResourceTopology (graph_manager.go:238-251) on the device-resident graph:
+// addResourceTopologyDFS (:557-630) for the new nodes and their arcs, updateResourceStatsUpToRoot
+// (:1041-1061) for the arcs above the attach point. The work follows the input: one lane per
+// new node, one per edge; the per-slot scratch (newt, par, S) is the only thing written before
+// the host has read every refusal.
+
+// wave_add_distinct with a value per lane: one atomicAdd of the summed val per distinct idx
+// among the pred lanes of a wave. Every lane of the wave calls it.
+__device__ __forceinline__ void wave_sum_distinct(unsigned long long* base, int idx, unsigned long long val, bool pred) {
+    const int me = (int)__lane_id();
+    unsigned long long rem = __ballot(pred);
+    while (rem) {
+        const int l = __ffsll((long long)rem) - 1;
+        const int il = __shfl(idx, l);
+        const bool mine = pred && idx == il;
+        const unsigned long long same = __ballot(mine) & rem;
+        unsigned long long sum = mine ? val : 0;
+        for (int o = 32; o; o >>= 1) sum += __shfl_xor(sum, o);
+        if (me == l) atomicAdd(&base[il], sum);
+        rem &= ~same;
+    }
+}
+
+// The first offending edge in input order, on one edge the lowest class: one word, one atomicMax.
+__device__ __forceinline__ void grow_bad_edge(const GrowDev& g, long long j, int cls) {
+    atomicMax(&g.ctl->bad_edge, (int)(8 * (g.m - j) + (7 - cls)));
+}
+
+// The type of node id as this call sees it: a node of the call (its slot may be a dead one the
+// store still remembers otherwise), else a node that was live before it; −1: neither.
+__device__ __forceinline__ int grow_type(const SchedDev& d, const GrowDev& g, unsigned long long id, bool* is_new) {
+    *is_new = false;
+    if (id < 1 || id > (unsigned long long)g.ntot) return -1;
+    const long long v = (long long)id - 1;
+    const int t = g.newt[v];
+    if (t) {
+        *is_new = true;
+        return t - 1;
+    }
+    return v < g.nst && d.n_alive[v] ? (int)d.n_type[v] : -1;
+}
+
+// addResourceNode (:528-551): the new nodes into the per-slot scratch. The host checked the
+// ids (in range, distinct), so every lane owns its slot's words.
+__global__ void k_grow_nodes(GrowDev g) {
+    for (long long i = blockIdx.x * (long long)SB + threadIdx.x; i < g.n; i += (long long)gridDim.x * SB) {
+        const ks_res_node x = g.nodes[i];
+        const long long v = (long long)x.id - 1;
+        const int pu = x.type == KS_NODE_PU;
+        g.newt[v] = 1 + x.type;
+        g.nflag[i] = pu;
+        if (pu) g.S[v] = x.slots;
+    }
+}
+
+// One lane per edge: the endpoints, the kind, the cost; a legal KS_RES_TREE edge claims its
+// child's parent word for the first such edge in input order (nodeToParentNode, :618-622).
+__global__ void k_grow_edges(SchedDev d, GrowDev g) {
+    for (long long j = blockIdx.x * (long long)SB + threadIdx.x; j < g.m; j += (long long)gridDim.x * SB) {
+        const ks_res_arc e = g.arcs[j];
+        bool pnew, cnew;
+        const int tp = grow_type(d, g, e.parent, &pnew), tc = grow_type(d, g, e.child, &cnew);
+        int cls = -1;
+        if (tp < 0 || tp == KS_NODE_TASK || tp == KS_NODE_SINK || tp == KS_NODE_PU) cls = 0;
+        else if (tc < 0 || tc == KS_NODE_TASK || tc == KS_NODE_SINK) cls = 1;
+        else if (e.parent == e.child) cls = 2;
+        else if (e.kind != KS_RES_TREE && e.kind != KS_RES_EXTRA) cls = 3;
+        else if (e.kind == KS_RES_TREE && pnew && !cnew) cls = 4;
+        else if (e.cost > (1LL << 40) || e.cost < -(1LL << 40)) cls = 5;
+        if (cls >= 0) grow_bad_edge(g, j, cls);
+        else if (e.kind == KS_RES_TREE) atomicMax(&g.par[e.child - 1], (int)(g.m - j));
+    }
+}
+
+// A resource has one parent: a KS_RES_TREE edge whose child an earlier one claimed. (A refused
+// edge claims nothing and its own class outranks this one, so it may be tested like the rest.)
+__global__ void k_grow_second_parent(GrowDev g) {
+    for (long long j = blockIdx.x * (long long)SB + threadIdx.x; j < g.m; j += (long long)gridDim.x * SB) {
+        const ks_res_arc e = g.arcs[j];
+        if (e.kind == KS_RES_TREE && e.child >= 1 && e.child <= (unsigned long long)g.ntot &&
+            g.par[e.child - 1] > (int)(g.m - j))
+            grow_bad_edge(g, j, 6);
+    }
+}
+
+// S(v): every new PU adds its slots to each of its ancestors, the whole wave one step up par at
+// a time. The 64 PUs of one machine, or 64 machines of one rack, meet on one word and same-word
+// atomics serialise, so each step first combines the lanes: one atomic per
+// distinct ancestor per wave (wave_sum_distinct). No PU is an ancestor (a parent is never a PU),
+// so the words k_grow_nodes wrote are not touched. Only legal edges claimed par: their parent
+// ids are slots of the scratch. A lane whose ancestor after KS_RES_MAX_DEPTH steps still has
+// a parent is on a cycle or too deep.
+__global__ void k_grow_sums(GrowDev g) {
+    for (long long i0 = blockIdx.x * (long long)SB; i0 < g.n; i0 += (long long)gridDim.x * SB) {   // (uniform per workgroup)
+        const long long i = i0 + threadIdx.x;
+        long long cur = -1;
+        unsigned long long w = 0;
+        if (i < g.n) {
+            const ks_res_node x = g.nodes[i];
+            if (x.type == KS_NODE_PU) {
+                cur = (long long)x.id - 1;
+                w = x.slots;
+            }
+        }
+        for (int step = 0; step < KS_RES_MAX_DEPTH; ++step) {
+            if (cur >= 0) {
+                const int c = g.par[cur];
+                cur = c ? (long long)g.arcs[g.m - c].parent - 1 : -1;
+            }
+            if (!__ballot(cur >= 0)) break;   // (uniform per wave)
+            wave_sum_distinct(g.S, cur >= 0 ? (int)cur : 0, w, cur >= 0);
+        }
+        if (cur >= 0 && g.par[cur]) atomicMax(&g.ctl->bad_depth, (int)(g.n - i));
+    }
+}
+
+// capacityFromResNodeToParent (:662-667) and updateResourceStatsUpToRoot (:1049-1055): an edge
+// whose head has new slots beneath it gets a record. The store's (src, dst) index tells "raise
+// the capacity" (the arc is there) from "the arc is gone, re-create it" (its capacity fell to 0).
+__global__ void k_grow_edge_flags(SchedDev d, GrowDev g) {
+    for (long long j0 = blockIdx.x * (long long)SB; j0 < g.m; j0 += (long long)gridDim.x * SB) {   // (uniform per workgroup)
+        const long long j = j0 + threadIdx.x;
+        int f = 0, slot = -1;
+        if (j < g.m) {
+            const ks_res_arc e = g.arcs[j];
+            const bool in = e.child >= 1 && e.child <= (unsigned long long)g.ntot;   // (a refused edge holds anything)
+            const unsigned long long sv = in ? g.S[e.child - 1] : 0;
+            if (sv > 0) {
+                f = 1;
+                if (!g.newt[e.child - 1] && e.parent >= 1 && e.parent < (1ULL << 30) && g.hmask >= 0) {
+                    const int h = store_hfind(g.hkey, g.hmask, arc_hkey((long long)e.parent, (long long)e.child));
+                    const int s = h >= 0 ? g.hval[h] : -1;
+                    if (s >= 0 && s < d.hi && d.a_alive[s]) slot = s;
+                }
+                if (slot >= 0 && (unsigned long long)d.a_cap[slot] + sv > (1ULL << 53))
+                    atomicMax(&g.ctl->bad_cap, (int)(g.m - j));
+            }
+            g.eflag[j] = f;
+            g.e_slot[j] = slot;
+        }
+        wave_count(&g.ctl->rec_upd, f && slot >= 0);
+        wave_count(&g.ctl->rec_add, f && slot < 0);
+        wave_count(&g.ctl->skipped, j < g.m && !f);
+    }
+}
+
+__global__ void k_grow_totals(GrowDev g) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        g.ctl->rec_pu = g.n_off[g.n];
+        g.ctl->rec_edge = g.e_off[g.m];
+    }
+}
+
+// Stream positions 0 … n − 1: the ADD_NODE records in input order; behind them the PU → sink
+// arcs in input order of the PUs (updateResToSinkArc, :1124); behind those the edge records in
+// input order (AddArc, :624-627, or ChangeArcCapacity, :1054-1055).
+__global__ void k_grow_emit(SchedDev d, GrowDev g, int rec_pu, ks_delta* __restrict__ recs) {
+    const long long tot = (long long)g.n + g.m;
+    for (long long i = blockIdx.x * (long long)SB + threadIdx.x; i < tot; i += (long long)gridDim.x * SB) {
+        if (i < g.n) {
+            const ks_res_node x = g.nodes[i];
+            ks_delta r{};
+            r.kind = KS_ADD_NODE;
+            r.type = x.type;
+            r.id = x.id;
+            recs[i] = r;
+            if (g.nflag[i])
+                recs[g.n + g.n_off[i]] =
+                    arc_record(KS_ADD_ARC, 0, (int)(x.id - 1), (int)g.sink, 0, (long long)x.slots, x.sink_cost, 0);
+        } else {
+            const long long j = i - g.n;
+            if (!g.eflag[j]) continue;
+            const ks_res_arc e = g.arcs[j];
+            const long long sv = (long long)g.S[e.child - 1];
+            const int s = g.e_slot[j];
+            recs[(long long)g.n + rec_pu + g.e_off[j]] =
+                s >= 0 ? arc_record(KS_UPDATE_ARC, d.a_type[s], (int)(e.parent - 1), (int)(e.child - 1), d.a_low[s],
+                                    d.a_cap[s] + sv, d.a_cost[s], d.a_cost[s])
+                       : arc_record(KS_ADD_ARC, 0, (int)(e.parent - 1), (int)(e.child - 1), 0, sv, e.cost, 0);
+        }
+    }
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------ launchers ---
@@ -1001,6 +1191,25 @@ hipError_t sched_add_totals(const AddDev& a, hipStream_t st) {
 hipError_t sched_add_emit(const SchedDev& d, const AddDev& a, ks_delta* recs, hipStream_t st) {
     hipLaunchKernelGGL(k_add_emit_tasks, dim3(grid((long long)a.k + a.na)), dim3(SB), 0, st, a, recs);
     if (a.nst) hipLaunchKernelGGL(k_add_emit_aggs, dim3(grid(a.nst)), dim3(SB), 0, st, d, a, recs);
+    return hipGetLastError();
+}
+
+hipError_t sched_grow_check(const SchedDev& d, const GrowDev& g, hipStream_t st) {
+    if (g.n) hipLaunchKernelGGL(k_grow_nodes, dim3(grid(g.n)), dim3(SB), 0, st, g);
+    if (g.m) hipLaunchKernelGGL(k_grow_edges, dim3(grid(g.m)), dim3(SB), 0, st, d, g);
+    if (g.m) hipLaunchKernelGGL(k_grow_second_parent, dim3(grid(g.m)), dim3(SB), 0, st, g);
+    if (g.n) hipLaunchKernelGGL(k_grow_sums, dim3(grid(g.n)), dim3(SB), 0, st, g);
+    if (g.m) hipLaunchKernelGGL(k_grow_edge_flags, dim3(grid(g.m)), dim3(SB), 0, st, d, g);
+    return hipGetLastError();
+}
+
+hipError_t sched_grow_totals(const GrowDev& g, hipStream_t st) {
+    hipLaunchKernelGGL(k_grow_totals, dim3(1), dim3(64), 0, st, g);
+    return hipGetLastError();
+}
+
+hipError_t sched_grow_emit(const SchedDev& d, const GrowDev& g, int rec_pu, ks_delta* recs, hipStream_t st) {
+    hipLaunchKernelGGL(k_grow_emit, dim3(grid((long long)g.n + g.m)), dim3(SB), 0, st, d, g, rec_pu, recs);
     return hipGetLastError();
 }
 

@@ -22,7 +22,7 @@ EXPORTED_SYMBOLS = (
     "ks_coalesce_deltas", "ks_get_store_stats", "ks_set_bindings", "ks_scheduling_deltas",
     "ks_update_unsched_costs", "ks_topology_stats", "ks_get_graph", "ks_commit_schedule",
     "ks_commit_preemptive", "ks_remove_resources", "ks_complete_tasks", "ks_get_bindings",
-    "ks_add_tasks",
+    "ks_add_tasks", "ks_add_resources",
     "ks_batch_create", "ks_batch_create_rank", "ks_batch_unique_id", "ks_batch_destroy", "ks_batch_last_error",
     "ks_batch_load", "ks_batch_solve", "ks_batch_gather",
     "ks_batch_slots", "ks_batch_owner", "ks_batch_block_len", "ks_batch_unpack",
@@ -151,6 +151,23 @@ class KsAddStats(C.Structure):
 TASK_ARC_DT = np.dtype({"names": ["dst", "cost"], "formats": ["<u8", "<i8"], "offsets": [0, 8], "itemsize": 16})
 
 
+class KsGrowStats(C.Structure):
+    """ks_grow_stats: what one ks_add_resources generated on device."""
+    _fields_ = [("nodes", C.c_int64), ("pus", C.c_int64), ("slots", C.c_int64), ("sink_arcs", C.c_int64),
+                ("arcs_added", C.c_int64), ("cap_updates", C.c_int64), ("arcs_skipped", C.c_int64),
+                ("records", C.c_int64), ("reserved", C.c_int64 * 4)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+RES_NODE_DT = np.dtype({"names": ["id", "type", "slots", "sink_cost"], "formats": ["<u8", "<i4", "<u8", "<i8"],
+                        "offsets": [0, 8, 16, 24], "itemsize": 32})
+RES_ARC_DT = np.dtype({"names": ["parent", "child", "cost", "kind"], "formats": ["<u8", "<u8", "<i8", "<i4"],
+                       "offsets": [0, 8, 16, 24], "itemsize": 32})
+KS_RES_TREE, KS_RES_EXTRA, KS_RES_MAX_DEPTH = 0, 1, 32
+
+
 class KsError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"ksmcmf error {code}: {msg}")
@@ -259,6 +276,7 @@ def _bind(path: str):
                                       P(C.c_size_t), P(KsRemoveStats)]
     L.ks_complete_tasks.argtypes = [V, C.c_int32, V, C.c_size_t, V, C.c_size_t, V, P(KsCompleteStats)]
     L.ks_add_tasks.argtypes = [V, C.c_int32, V, C.c_size_t, V, V, V, C.c_size_t, C.c_int64, P(KsAddStats)]
+    L.ks_add_resources.argtypes = [V, C.c_int32, V, C.c_size_t, V, C.c_size_t, P(KsGrowStats)]
     L.ks_get_bindings.argtypes = [V, V, V, C.c_size_t]
     return L
 
@@ -517,6 +535,27 @@ class Context:
         self._check(self._L.ks_add_tasks(self._h, 0, ids.ctypes.data, ids.shape[0], off.ctypes.data, arcs.ctypes.data,
                                          None if agg is None else agg.ctypes.data, nu, int(unsched_sink_cost),
                                          C.byref(st)))
+        return st.as_dict()
+
+    def add_resources(self, nodes, arcs) -> dict:
+        """ks_add_resources: new resource nodes (RES_NODE_DT rows, or (id, type, slots, sink_cost)
+        tuples) join the device-resident graph with supply 0; each PU gets its arc into the sink.
+        arcs (RES_ARC_DT rows, or (parent, child, cost, kind) tuples): the KS_RES_TREE edges of the
+        new subtree and of the chain from each attach point up to the root, and KS_RES_EXTRA arcs
+        into nodes of the call. An edge whose head has S new slots beneath it is created with
+        capacity S or, where the store still holds it, has its capacity raised by S. -> stats
+        dict. Needs no solve; invalidates the solution when a record is applied."""
+        def rows(x, dt):
+            if isinstance(x, np.ndarray) and x.dtype == dt:
+                return np.ascontiguousarray(x).reshape(-1)
+            out = np.zeros(len(x), dt)
+            for name, col in zip(dt.names, zip(*x)):
+                out[name] = np.asarray(col, dtype=dt[name])
+            return out
+        nd, ar = rows(nodes, RES_NODE_DT), rows(arcs, RES_ARC_DT)
+        st = KsGrowStats()
+        self._check(self._L.ks_add_resources(self._h, 0, nd.ctypes.data if nd.shape[0] else None, nd.shape[0],
+                                             ar.ctypes.data if ar.shape[0] else None, ar.shape[0], C.byref(st)))
         return st.as_dict()
 
     def bindings(self, tasks) -> np.ndarray:
