@@ -42,8 +42,12 @@
  *                            TaskCompleted (graph_manager.go:389-405) → removeTaskNode
  *                            (:803-813) and updateUnscheduledAggNode(−1) (:1291-1305); also
  *                            TaskFailed / TaskKilled (:435-452), generated and applied on device
+ *   ks_update_tasks          UpdateTimeDependentCosts (graph_manager.go:211-213) → updateTaskNode
+ *                            (:1183-1192) for tasks that have their node: arcs added, re-costed
+ *                            and dropped as the cost model lists them, generated and applied on
+ *                            device
  *   ks_get_bindings          the TaskBindings the device keeps (ks_set_bindings, the commits)
- *   ks_last_error            the panics of solver.go:97-108, 148-153, 175-178, 223-225
+ *   ks_last_error           the panics of solver.go:97-108, 148-153, 175-178, 223-225
  *                            become status codes + a message
  *
  * Semantics (flowgraph/graph.go:25-41, arc.go:26-36, node.go:76-106):
@@ -105,6 +109,8 @@ extern "C" {
                                   were added, nothing was resized).
                                   ks_add_resources (still 5: one entry point and three
                                   structs were added).
+                                  ks_update_tasks (still 5: one entry point and one
+                                  struct were added, nothing was resized).
                                   ks_opts (96 B) CHANGED SIZE in ABI 2 and ks_result in
                                   ABI 2, 3 and 5: a caller must check
                                   ks_abi_version() == KSMCMF_ABI_VERSION before ks_create. */
@@ -655,9 +661,10 @@ typedef struct ks_remove_stats {    /* 96 B */
  *     its running arc goes with the PU and its other arcs into removed nodes go with them;
  *     its surviving arcs and their costs are the host's business before the next solve
  *     (:432), as ks_commit_preemptive says of a PREEMPT. After ks_commit_schedule (pinned
- *     mode) an evicted task has NO out-arc left: the caller re-adds its arcs, and the +1
- *     on its aggregator → sink arc, through ks_apply_deltas — the device cannot know the
- *     job of a task whose aggregator arc the pin deleted.
+ *     mode) an evicted task has NO out-arc left: the caller lists its arcs, the one into
+ *     its aggregator among them, in ks_update_tasks, which adds them and the +1 on the
+ *     aggregator → sink arc — the device cannot know the job of a task whose aggregator
+ *     arc the pin deleted.
  *   - removed == NULL and evicted == NULL: a probe, *nremoved and *nevicted only, nothing
  *     changes. rcap < *nremoved or ecap < *nevicted: KS_E_INVALID, the counts are
  *     written, nothing changes.
@@ -924,6 +931,97 @@ int ks_add_resources(ks_ctx* ctx, int32_t flags /* must be 0 */,
                      const ks_res_node* nodes, size_t n,
                      const ks_res_arc* arcs, size_t m,
                      ks_grow_stats* stats /* may be NULL */);
+
+#define KS_UPDATE_KEEP_UNLISTED 1   /* no arc is deleted: additions and cost changes only */
+
+typedef struct ks_update_stats {      /* 96 B */
+    int64_t tasks;            /* tasks listed                                              */
+    int64_t arcs_added;       /* listed arcs the store did not hold (ADD_ARC)              */
+    int64_t cost_updates;     /* held arcs whose cost changed (UPDATE_ARC)                 */
+    int64_t arcs_unchanged;   /* listed, held, same cost: no record                        */
+    int64_t running_kept;     /* listed heads whose held arc is a running arc: no record   */
+    int64_t arcs_removed;     /* held, unlisted, deleted (UPDATE_ARC 0/0)                  */
+    int64_t unsched_updates;  /* aggregator → sink arcs whose capacity rose (UPDATE_ARC)   */
+    int64_t unsched_added;    /* aggregator → sink arcs re-created (ADD_ARC)               */
+    int64_t records;          /* arcs_added + cost_updates + arcs_removed + the two above  */
+    int64_t reserved[3];
+} ks_update_stats;
+
+/* Live tasks' arcs follow the cost model, on device: UpdateTimeDependentCosts =
+ * AddOrUpdateJobNodes (flowmanager/graph_manager.go:211-213, :166-208), which for a task that
+ * already has its node runs updateTaskNode (:1183-1192) with its three arc writers,
+ * updateTaskToUnscheduledAggArc (:1270-1285), updateTaskToEquivArcs (:1197-1226) and
+ * updateTaskToResArcs (:1229-1264). Each adds the arc the graph does not hold or calls
+ * ChangeArcCost, which logs a record only when the cost differs (graph_change_manager.go:171-182),
+ * and then removeInvalidECPrefArcs / removeInvalidPrefResArcs (:732-790) delete the arcs that are
+ * no longer preferred; updateRunningTaskNode (:1140-1158) does the same for a running task under
+ * preemption. The caller lists, per task, the non-running out-arcs the task should have; the
+ * device diffs each list against the arcs the store holds, so the caller keeps no shadow of the
+ * tasks' arcs and costs (which ks_update_unsched_costs and the commits change on the device
+ * alone). The records are generated in device memory and applied as ONE stream with the
+ * semantics of ks_apply_deltas (all or nothing, in place, store counters, warm-start bookkeeping,
+ * the dirty-cell marks of a partition). The stream's order is fixed, so a host restatement
+ * produces the identical stream: the records on held arcs (cost changes and deletions) in
+ * ascending arc-slot order, the order in which ks_get_graph lists arcs; the ADD_ARC records of
+ * the listed arcs the store did not hold, in input order; then one record per aggregator that
+ * gains a unit, in ascending aggregator id. No (src, dst) appears twice
+ * (ks_store_stats.superseded stays 0). Only the ids, the offsets and the 16-byte arcs cross PCIe.
+ *   - Task ids: every id must be a live task node. The first id that is 0, beyond the graph,
+ *     dead, of another type or listed a second time: KS_E_INVALID, the error names the id,
+ *     nothing changes (two lists for one task have no meaning: a repeat is refused, not
+ *     merged). No node is added or removed; the host's node table is only read.
+ *   - Listed arcs: task i's list is arcs[arc_off[i] .. arc_off[i + 1]), the offsets as in
+ *     ks_add_tasks (arc_off[0] == 0, never decreasing, else KS_E_INVALID); an empty list is
+ *     legal. Every head must be a live node that is no task: a head that is 0, beyond the
+ *     graph, dead or a task is KS_E_INVALID, the error names the task and the head.
+ *     |cost| > 2^40: KS_E_RANGE. A head listed twice for one task: KS_E_INVALID (the diff needs
+ *     a set; in ks_add_tasks a repeat is an upsert). The first offending arc in input order is
+ *     the one reported; on one arc the head comes before the repeat and the repeat before the
+ *     cost. Nothing changes. Per listed arc (t, h):
+ *       the store does not hold it     ADD_ARC (low 0, cap 1, the listed cost, type 0)
+ *       held, type 0, another cost     UPDATE_ARC: low, cap and type kept, the listed cost,
+ *                                      old_cost the cost it had
+ *       held, type 0, the same cost    no record (ChangeArcCost logs nothing then)
+ *       held as a running arc (type 1) no record and its cost stays (:1250-1255): that cost
+ *                                      belongs to ks_update_unsched_costs and the commits
+ *   - Held arcs of a listed task that its list does not name: a running arc is kept. This is a
+ *     deliberate deviation: the reference's removeInvalidPrefResArcs deletes a running arc
+ *     whose PU left the preferences and then panics at the next updateRunningTaskNode. An arc
+ *     into a marked aggregator is kept with its cost (the reference never deletes it, and
+ *     ks_update_unsched_costs may have aged the cost on the device). Every other arc is deleted
+ *     (UPDATE_ARC with low == cap == 0). With KS_UPDATE_KEEP_UNLISTED nothing is deleted.
+ *   - Aggregators: unsched_ids, nu of them; NULL: every type-0 node with an arc into the
+ *     sink, as in the commits. On its arc into the sink an aggregator gains one unit of
+ *     capacity per listed task whose listed arc into it the store did not hold: the mirror of
+ *     ks_complete_tasks' loss rule, and the +1 of a task evicted after a pinned commit (after a
+ *     preemptive commit the task still has the arc, only its cost moves and nothing is gained).
+ *     The record is that of ks_add_tasks: if the store holds aggregator → sink, one UPDATE_ARC,
+ *     low, cost and type kept, cap raised; if not, one ADD_ARC with low 0, cap = the count, cost
+ *     unsched_sink_cost, type 0 (:1300-1304). A task that would end with arcs into two marked
+ *     aggregators, listed, held or one of each: KS_E_INVALID, the error names the task (a task
+ *     does not change its job). With unsched_ids == NULL a drained aggregator is invisible, so
+ *     a task without a device-kept binding that would end with no arc into a recognised
+ *     aggregator is KS_E_INVALID with a message that asks for the ids: the call never silently
+ *     leaves a capacity one short. A bound task may have none (a pinned running task has no
+ *     aggregator arc). A context with other than one sink refuses any call in which an
+ *     aggregator gains a unit (KS_E_INVALID). unsched_sink_cost beyond ±2^40: KS_E_RANGE. An
+ *     aggregator id that is no live node: KS_E_INVALID.
+ *   - flags: KS_UPDATE_KEEP_UNLISTED or 0; any other bit is KS_E_INVALID.
+ * Needs no previous solve. Without the flag the tasks' segments of the residual CSR are walked
+ * (a pending rebuild runs first, as in ks_complete_tasks); with it only the node store, the arc
+ * table and the (src, dst) index are read, as in ks_add_tasks. k == 0 does nothing and keeps the
+ * solution, as does a call that generates no record (the solution and the mapping stay valid);
+ * a call that generates any record invalidates them, exactly as ks_apply_deltas does. A full
+ * segment takes the store's rebuild path (ks_store_stats.rebuilds). Every refusal is found before
+ * anything changes on the device. A device failure after the records were emitted leaves the
+ * store unusable until the next ks_load_graph. stats may be NULL; records == arcs_added +
+ * cost_updates + arcs_removed + unsched_updates + unsched_added. No batch twin.
+ * UpdateResourceTopology (:217-236) stays with ks_apply_deltas. */
+int ks_update_tasks(ks_ctx* ctx, int32_t flags,
+                    const uint64_t* tasks, size_t k,
+                    const uint64_t* arc_off /* k + 1 */, const ks_task_arc* arcs,
+                    const uint64_t* unsched_ids, size_t nu, int64_t unsched_sink_cost,
+                    ks_update_stats* stats /* may be NULL */);
 
 /* pu[i] = the PU task[i] is bound to on the device (ks_set_bindings, the commits), 0 =
  * unbound: for the pinned recipe above and for checkpoints. A task id that is not a live

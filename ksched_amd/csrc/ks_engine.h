@@ -135,6 +135,13 @@ public:
     int add_resources(const ks_res_node* nodes, size_t n, const ks_res_arc* arcs, size_t m, size_t first_pair,
                       int64_t sink_slot, int64_t nslots, ks_grow_stats* stats, const AddEdits& make_edits, bool* dirty,
                       bool* changed, std::string& err);
+    // ks_update_tasks (the k live task ids with the arcs each should have; offsets checked by the
+    // caller). first_pair: the first arc that repeats an earlier head of its own task, arc_off[k]
+    // when none does. No node is edited. *dirty: records were emitted (a failure from then on
+    // leaves the device state unknown); *changed: records were applied.
+    int update_tasks(int flags, const uint64_t* tasks, size_t k, const uint64_t* arc_off, const ks_task_arc* arcs,
+                     size_t first_pair, const uint64_t* unsched_ids, size_t nu, int64_t sink_slot, int64_t sink_cost,
+                     ks_update_stats* stats, bool* dirty, bool* changed, std::string& err);
     // ks_get_bindings: pu[i] = the device-kept binding of task[i] (ids checked by the caller).
     int get_bindings(const uint64_t* task, uint64_t* pu, size_t k, std::string& err);
     int device() const;

@@ -1,7 +1,8 @@
 // ks_engine_sched.hip — the engine's scheduler glue: bindings, scheduling deltas,
 // unscheduled costs, topology statistics, ks_commit_schedule and ks_commit_preemptive,
-// ks_remove_resources, ks_complete_tasks, ks_add_tasks, ks_add_resources and ks_get_bindings. It
-// launches the kernels of ks_sched.hip and ks_store.hip through their launchers, none of the engine's.
+// ks_remove_resources, ks_complete_tasks, ks_add_tasks, ks_add_resources, ks_update_tasks and
+// ks_get_bindings. It launches the kernels of ks_sched.hip and ks_store.hip through their
+// launchers, none of the engine's.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -1172,6 +1173,219 @@ int Engine::add_resources(const ks_res_node* nodes, size_t n, const ks_res_arc* 
         stats->cap_updates = h.rec_upd;
         stats->records = nrec;
     }
+    return KS_OK;
+}
+
+// ks_update_tasks: the seventh body, on the scratch carve of add_tasks. The ids, the offsets and
+// the 16-byte arcs go up; one lane per id checks and claims it, one lane per listed arc checks its
+// head and cost and asks the store's index for the arc's slot, the tasks' segments (or, with
+// KS_UPDATE_KEEP_UNLISTED, the arc table: no CSR is needed then) give the held arcs nobody listed,
+// the aggregators' part is that of add_tasks, and ONE host sync brings every refusal and the
+// record counts (no step before it writes anything but scratch). Then the sizing of the arc table
+// and the index, and the records on held arcs (ascending arc slot), the new arcs (input order)
+// and the aggregator records (ascending id) reach store_apply as one stream. No node is edited.
+int Engine::update_tasks(int flags, const uint64_t* tasks, size_t k, const uint64_t* arc_off, const ks_task_arc* arcs,
+                         size_t first_pair, const uint64_t* unsched_ids, size_t nu, int64_t sink_slot,
+                         int64_t sink_cost, ks_update_stats* stats, bool* dirty, bool* changed, std::string& err) {
+    EngineImpl& s = *p_;
+    *dirty = *changed = false;
+    if (!k) return KS_OK;
+    KS_CHECK(hipSetDevice(s.device));
+    hipStream_t st = s.stream;
+    const bool walk = !(flags & KS_UPDATE_KEEP_UNLISTED);
+    if (walk && !s.csr_valid) {   // the chunk items walk the residual CSR
+        int rc = build(s, err);
+        if (rc) return rc;
+        s.has_prev = false;
+        s.solved = false;
+    }
+    const bool log = s.opts.log_cycles != 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int64_t nst = s.nstore;
+    const int hi = s.hi();
+    const size_t na = (size_t)arc_off[k];
+    if (k > (size_t)INT32_MAX / 4 || na > (size_t)INT32_MAX / 4 || nu > (size_t)INT32_MAX) {
+        err = "too many tasks, arcs or aggregator ids";
+        return KS_E_RANGE;
+    }
+    for (size_t i = 0; unsched_ids && i < nu; ++i)
+        if (unsched_ids[i] == 0 || (int64_t)unsched_ids[i] > nst) {
+            err = "unscheduled aggregator id beyond the graph";
+            return KS_E_INVALID;
+        }
+    UpdDev u{};
+    u.k = (int)k;
+    u.na = (int)na;
+    u.hi = hi;
+    u.keep = walk ? 0 : 1;
+    u.null_rule = unsched_ids ? 0 : 1;
+    u.nst = nst;
+    AddDev a{};   // the aggregators' gains: the lookup and the records of add_tasks
+    a.nst = nst;
+    a.sink = sink_slot >= 0 && sink_slot < nst ? sink_slot : -1;
+    a.sink_cost = sink_cost;
+    unsigned long long *d_tasks = nullptr, *d_off = nullptr, *d_arcs = nullptr, *d_agg = nullptr;
+    auto carve = [&](Carve<int> ci, Carve<unsigned long long> cu) {
+        for (int** x : {&u.t_own, &a.aflag, &a.a_off, &a.a_slot}) *x = ci.take(nst + 1);
+        for (int** x : {&u.t_slot, &u.t_agg, &u.nch, &u.ch_off}) *x = ci.take((int64_t)k + 1);
+        for (int** x : {&u.seen, &u.sflag, &u.s_off}) *x = ci.take((int64_t)hi + 1);
+        for (int** x : {&u.lflag, &u.l_off}) *x = ci.take((int64_t)na + 1);
+        u.agg_cnt = cu.take(nst + 1);   // (first: the only u64 array that starts zeroed)
+        d_tasks = cu.take(k);
+        d_off = cu.take(k + 1);
+        d_arcs = cu.take(2 * na);
+        d_agg = cu.take(nu);
+        return std::make_pair(ci.n, cu.n);
+    };
+    const auto [n_i, n_u] = carve({nullptr}, {nullptr});
+    const int64_t nb = (nst + 4) & ~3LL;
+    KS_CHECK(s.cm_i.ensure(n_i));
+    KS_CHECK(s.cm_u.ensure(n_u));
+    KS_CHECK(s.cm_b.ensure(nb));
+    KS_CHECK(s.upd_ctl.ensure(1));
+    KS_CHECK(s.add_ctl.ensure(1));
+    carve({s.cm_i.p}, {s.cm_u.p});
+    u.fl = a.fl = s.cm_b.p;
+    a.agg_cnt = u.agg_cnt;
+    u.ctl = s.upd_ctl.p;
+    a.ctl = s.add_ctl.p;
+    u.tasks = d_tasks;
+    u.arc_off = d_off;
+    u.arcs = (const ks_task_arc*)d_arcs;
+    u.hkey = a.hkey = s.hkey.p;
+    u.hval = a.hval = s.hval.p;
+    u.hmask = a.hmask = s.hcap ? (int)(s.hcap - 1) : -1;
+    KS_CHECK(hipMemsetAsync(s.cm_i.p, 0, n_i * sizeof(int), st));
+    KS_CHECK(hipMemsetAsync(u.agg_cnt, 0, (nst + 1) * 8, st));
+    KS_CHECK(hipMemsetAsync(s.cm_b.p, 0, nb, st));
+    KS_CHECK(hipMemsetAsync(s.upd_ctl.p, 0, sizeof(UpdCtl), st));
+    KS_CHECK(hipMemsetAsync(s.add_ctl.p, 0, sizeof(AddCtl), st));
+    KS_CHECK(hipMemcpyAsync(d_tasks, tasks, k * 8, hipMemcpyHostToDevice, st));
+    KS_CHECK(hipMemcpyAsync(d_off, arc_off, (k + 1) * 8, hipMemcpyHostToDevice, st));
+    if (na) KS_CHECK(hipMemcpyAsync(d_arcs, arcs, na * sizeof(ks_task_arc), hipMemcpyHostToDevice, st));
+    if (unsched_ids && nu) KS_CHECK(hipMemcpyAsync(d_agg, unsched_ids, nu * 8, hipMemcpyHostToDevice, st));
+    SchedDev d = s.schd();
+    // ---- 1. ids, heads, costs, the diff, the aggregators' gains and their arcs into the sink: one sync
+    KS_CHECK(sched_upd_check(d, u, unsched_ids ? d_agg : nullptr, (int)nu, walk, st));
+    if (walk) KS_CHECK(exclusive_sum(s, (const int*)u.nch, u.ch_off, (int64_t)k + 1, st));
+    KS_CHECK(sched_upd_unlisted(d, u, walk, (int)(k + s.m2cap / 64 + 1), st));
+    KS_CHECK(sched_add_agg_flags(d, a, st));
+    KS_CHECK(exclusive_sum(s, (const int*)u.sflag, u.s_off, (int64_t)hi + 1, st));
+    KS_CHECK(exclusive_sum(s, (const int*)u.lflag, u.l_off, (int64_t)na + 1, st));
+    KS_CHECK(exclusive_sum(s, (const int*)a.aflag, a.a_off, nst + 1, st));
+    KS_CHECK(sched_upd_totals(u, st));
+    KS_CHECK(sched_add_totals(a, st));
+    UpdCtl h{};
+    AddCtl ha{};
+    KS_CHECK(hipMemcpyAsync(&h, u.ctl, sizeof(UpdCtl), hipMemcpyDeviceToHost, st));
+    KS_CHECK(hipMemcpyAsync(&ha, a.ctl, sizeof(AddCtl), hipMemcpyDeviceToHost, st));
+    KS_CHECK(hipStreamSynchronize(st));
+    const auto t1 = std::chrono::steady_clock::now();
+    if (h.bad_task) {
+        if (h.bad_task < 0 || (size_t)h.bad_task > k) {
+            err = "inconsistent task index";
+            return KS_E_DEVICE;
+        }
+        err = "task " + std::to_string(tasks[k - (size_t)h.bad_task]) + " is not a live task node listed once (0, beyond "
+              "the graph, dead, of another type, or listed before)";
+        return KS_E_INVALID;
+    }
+    auto task_of = [&](size_t j) {   // the last i with arc_off[i] ≤ j
+        return (size_t)(std::upper_bound(arc_off, arc_off + k, (uint64_t)j) - arc_off) - 1;
+    };
+    // the first offending arc in input order; on one arc the head, then the repeat, then the cost
+    if (h.bad_head || h.bad_cost || first_pair < na) {
+        if (h.bad_head < 0 || h.bad_cost < 0 || (size_t)h.bad_head > na || (size_t)h.bad_cost > na) {
+            err = "inconsistent arc index";
+            return KS_E_DEVICE;
+        }
+        const size_t jh = h.bad_head ? na - (size_t)h.bad_head : na, jc = h.bad_cost ? na - (size_t)h.bad_cost : na;
+        const size_t j = std::min({jh, first_pair, jc});
+        const std::string who = "task " + std::to_string(tasks[task_of(j)]) + ": ";
+        if (j == jh) {
+            err = who + "head " + std::to_string(arcs[j].dst) + " is not a live node that is no task (0, beyond the graph, "
+                  "dead or a task)";
+            return KS_E_INVALID;
+        }
+        if (j == first_pair) {
+            err = who + "head " + std::to_string(arcs[j].dst) + " is listed twice: the list is the set of arcs the task "
+                  "should have";
+            return KS_E_INVALID;
+        }
+        err = who + "the cost of its arc into " + std::to_string(arcs[j].dst) + " is outside the supported range";
+        return KS_E_RANGE;
+    }
+    if (h.bad_multi || h.bad_none) {
+        if (h.bad_multi < 0 || h.bad_none < 0 || (size_t)h.bad_multi > k || (size_t)h.bad_none > k) {
+            err = "inconsistent task index";
+            return KS_E_DEVICE;
+        }
+        const bool multi = h.bad_multi >= h.bad_none;
+        const uint64_t id = tasks[k - (size_t)(multi ? h.bad_multi : h.bad_none)];
+        err = multi ? "task " + std::to_string(id) + " would have arcs into two unscheduled aggregators: a task does not "
+                      "change its job"
+                    : "task " + std::to_string(id) + " is unbound and would have no arc into a node with an arc into the "
+                      "sink; an aggregator whose capacity fell to 0 has lost that arc: pass the aggregators' ids "
+                      "(unsched_ids)";
+        return KS_E_INVALID;
+    }
+    if (h.units && a.sink < 0) {
+        err = "an unscheduled aggregator's capacity needs exactly one sink";
+        return KS_E_INVALID;
+    }
+    if (h.units < 0 || h.n_cost < 0 || h.n_same < 0 || h.n_run < 0 || h.n_del < 0 || h.rec_add < 0 ||
+        (int64_t)h.rec_add + h.n_cost + h.n_same + h.n_run != (int64_t)na || h.n_cost + h.n_del != h.rec_held ||
+        h.rec_held > hi || h.units > h.rec_add || (!walk && h.n_del) || ha.rec_upd < 0 || ha.rec_add < 0 ||
+        ha.rec_upd + ha.rec_add != ha.rec_agg || ha.rec_agg > h.units || (h.units > 0) != (ha.rec_agg > 0)) {
+        err = "inconsistent record counts";
+        return KS_E_DEVICE;
+    }
+    const int64_t nrec = (int64_t)h.rec_held + h.rec_add + ha.rec_agg;
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        stats->tasks = (int64_t)k;
+        stats->arcs_added = h.rec_add;
+        stats->cost_updates = h.n_cost;
+        stats->arcs_unchanged = h.n_same;
+        stats->running_kept = h.n_run;
+        stats->arcs_removed = h.n_del;
+        stats->unsched_updates = ha.rec_upd;
+        stats->unsched_added = ha.rec_add;
+        stats->records = nrec;
+    }
+    if (!nrec) return KS_OK;   // every list is what the store holds: the solution stands
+    // ---- 2. room for the new arcs
+    int rc = ensure_arcs(s, (int64_t)hi + h.rec_add + ha.rec_add, err);
+    if (rc == KS_OK) rc = ensure_hash(s, (int64_t)h.rec_add + ha.rec_add, err);
+    if (rc) return rc;
+    KS_CHECK(s.d_recs.ensure((size_t)nrec));
+    KS_CHECK(s.rec_ent.ensure((size_t)nrec));
+    KS_CHECK(s.d_edits.ensure(1));
+    // from here on a failure leaves the device state unknown
+    *dirty = true;
+    s.incremental = true;
+    d = s.schd();   // (the arc table may have moved)
+    const auto t2 = std::chrono::steady_clock::now();
+    // ---- 3. the records, at their fixed positions, and the apply
+    KS_CHECK(sched_upd_emit(d, u, h.rec_held, s.d_recs.p, st));
+    KS_CHECK(sched_add_emit_aggs(d, a, (int64_t)h.rec_held + h.rec_add, s.d_recs.p, st));
+    rc = mark_cells(s, s.d_recs.p, (size_t)nrec, s.d_edits.p, 0, err);
+    if (rc) return rc;
+    KS_CHECK(store_apply(s.sd(), s.d_recs.p, (int)nrec, s.rec_ent.p, s.d_edits.p, 0, st));
+    rc = read_sctl(s, err);
+    if (rc == KS_OK) rc = applied(s, err);
+    if (rc) return rc;
+    if (log) {
+        const auto t3 = std::chrono::steady_clock::now();
+        auto ms = [](auto x, auto y) { return std::chrono::duration<double, std::milli>(y - x).count(); };
+        std::fprintf(stderr,
+                     "update: %zu tasks, %zu arcs, %lld records, upload + checks + diff %.3f ms, sizing %.3f ms, "
+                     "emit + apply %.3f ms\n",
+                     k, na, (long long)nrec, ms(t0, t1), ms(t1, t2), ms(t2, t3));
+    }
+    s.solved = false;
+    if (s.cell_refused_values) s.cell_refused = s.cell_refused_values = false;   // (as run_apply)
+    *changed = true;
     return KS_OK;
 }
 

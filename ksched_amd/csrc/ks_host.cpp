@@ -969,6 +969,62 @@ int ks_add_resources(ks_ctx* c, int32_t flags, const ks_res_node* nodes, size_t 
     return KS_OK;
 }
 
+// UpdateTimeDependentCosts (flowmanager/graph_manager.go:211-213) → updateTaskNode (:1183-1192).
+// No node is edited, so there is no NodeTxn: the host's part is the argument, flag and range
+// checks, the offsets, and the one refusal the device's index cannot see, a head listed twice
+// for one task whose arc the store does not hold (found by a sort of each task's heads, as
+// ks_add_resources finds a repeated pair). The device checks the ids, the heads and the costs
+// and generates the records.
+int ks_update_tasks(ks_ctx* c, int32_t flags, const uint64_t* tasks, size_t k, const uint64_t* arc_off,
+                    const ks_task_arc* arcs, const uint64_t* unsched_ids, size_t nu, int64_t unsched_sink_cost,
+                    ks_update_stats* stats) {
+    if (!c) return KS_E_INVALID;
+    if (int g = store_guard(c)) return g;
+    if (flags & ~KS_UPDATE_KEEP_UNLISTED) return c->fail(KS_E_INVALID, "unknown update flag");
+    if (k && (!tasks || !arc_off)) return c->fail(KS_E_INVALID, "null task or offset array");
+    if (unsched_sink_cost > (int64_t(1) << 40) || unsched_sink_cost < -(int64_t(1) << 40))
+        return c->fail(KS_E_RANGE, "unscheduled sink cost outside the supported range");
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (!k) return KS_OK;   // nothing is refreshed: the solution stands
+    if (arc_off[0] != 0) return c->fail(KS_E_INVALID, "arc_off[0] must be 0");
+    for (size_t i = 0; i < k; ++i)
+        if (arc_off[i + 1] < arc_off[i])
+            return c->fail(KS_E_INVALID, "arc_off decreases at task " + std::to_string(tasks[i]));
+    const size_t na = (size_t)arc_off[k];
+    if (na && !arcs) return c->fail(KS_E_INVALID, "null arc array");
+    for (size_t i = 0; unsched_ids && i < nu; ++i)
+        if (!node_alive(c, unsched_ids[i]))
+            return c->fail(KS_E_INVALID, "unscheduled aggregator " + std::to_string(unsched_ids[i]) + " is not a live node");
+    size_t first_pair = na;   // the first arc in input order that repeats an earlier head of its own task
+    {
+        std::vector<std::pair<uint64_t, size_t>> heads;
+        for (size_t i = 0; i < k; ++i) {
+            heads.clear();
+            for (size_t j = (size_t)arc_off[i]; j < (size_t)arc_off[i + 1]; ++j) heads.emplace_back(arcs[j].dst, j);
+            std::sort(heads.begin(), heads.end());
+            for (size_t q = 1; q < heads.size(); ++q)
+                if (heads[q].first == heads[q - 1].first) first_pair = std::min(first_pair, heads[q].second);
+            if (first_pair < na) break;   // (a later task's arcs come later in input order)
+        }
+    }
+    const int64_t sink = c->n_sinks == 1 ? (int64_t)c->sink_id - 1 : -1;
+    bool dirty = false, changed = false;
+    const int rc = c->eng.update_tasks(flags, tasks, k, arc_off, arcs, first_pair, unsched_ids, unsched_ids ? nu : 0, sink,
+                                       unsched_sink_cost, stats, &dirty, &changed, c->err);
+    if (!c->eng.solved()) c->have_solution = c->flows_fresh = c->map_fresh = false;   // a pending CSR rebuild ran
+    if (rc) {
+        if (dirty) c->store_bad = true;   // (the stream may be half applied: reload first)
+        if (stats) std::memset(stats, 0, sizeof(*stats));
+        return rc;
+    }
+    if (changed) {   // as after ks_apply_deltas
+        c->have_solution = false;
+        c->map_fresh = false;
+        c->flows_fresh = false;
+    }
+    return KS_OK;
+}
+
 int ks_get_bindings(ks_ctx* c, const uint64_t* task, uint64_t* pu, size_t k) {
     if (!c) return KS_E_INVALID;
     if (int g = store_guard(c)) return g;

@@ -330,4 +330,86 @@ hipError_t sched_grow_totals(const GrowDev& g, hipStream_t st);
 // n + rec_pu + e_off (d: the arc table as it is now, after any growth).
 hipError_t sched_grow_emit(const SchedDev& d, const GrowDev& g, int rec_pu, ks_delta* recs, hipStream_t st);
 
+// ---- ks_update_tasks: live tasks' arcs follow the cost model. UpdateTimeDependentCosts =
+// AddOrUpdateJobNodes (flowmanager/graph_manager.go:211-213, :166-208) → updateTaskNode
+// (:1183-1192) with its arc writers (:1197-1285), each AddArc or ChangeArcCost
+// (graph_change_manager.go:171-182) followed by removeInvalidECPrefArcs /
+// removeInvalidPrefResArcs (:732-790), and updateRunningTaskNode (:1140-1158). The device
+// diffs each listed task's list against the arcs the store holds: a listed arc is found
+// through the store's (src, dst) index, a held arc nobody listed in the task's own residual
+// segment (or, with KS_UPDATE_KEEP_UNLISTED, in a pass over the arc table: no CSR is needed
+// then). The aggregators' part (aflag, a_off, a_slot, the lookup and the records) is that of
+// ks_add_tasks on an AddDev that shares fl and agg_cnt.
+
+// Device counters of one refresh; the host reads them in one 64-byte copy.
+struct UpdCtl {
+    int bad_task;    // k − the index of the first id that is 0, beyond the graph, dead, no task or listed before, 0 none
+    int bad_head;    // na − the index of the first arc whose head is 0, beyond the graph, dead or a task, 0 none
+    int bad_cost;    // na − the index of the first arc whose cost is beyond ±2^40, 0 none
+    int bad_multi;   // k − the index of the first task that would end with arcs into two flagged aggregators, 0 none
+    int bad_none;    // k − the index of the first unbound task that would end with none (NULL rule only), 0 none
+    int units;       // listed arcs into flagged aggregators that the store did not hold: the aggregators' gain
+    int n_cost;      // listed, held with type 0, another cost (UPDATE_ARC)
+    int n_same;      // listed, held with type 0, the same cost
+    int n_run;       // listed, held as a running arc
+    int n_del;       // held, unlisted, deleted
+    int rec_held;    // the arc-slot scan's total: n_cost + n_del
+    int rec_add;     // the listed-arc scan's total: listed arcs the store did not hold (ADD_ARC)
+    int reserved[4];
+};
+
+// Inputs and scratch of one refresh (device pointers; nst node slots, hi arc slots).
+struct UpdDev {
+    int k;                             // tasks
+    int na;                            // listed arcs
+    int hi;                            // arc slots handed out when the call began
+    int keep;                          // KS_UPDATE_KEEP_UNLISTED: nothing is deleted, no segment is walked
+    int null_rule;                     // unsched_ids == NULL: an unbound task without an aggregator arc is refused
+    const unsigned long long* tasks;   // [k] unchecked
+    const unsigned long long* arc_off; // [k + 1] checked by the host: 0 first, never decreasing, na last
+    const ks_task_arc* arcs;           // [na] unchecked (a head repeated within one task: the host's sort)
+    long long nst;                     // node slots the passes may read
+    unsigned char* fl;                 // per node slot: 1 unscheduled aggregator
+    int* t_own;                        // [nst + 1] per node slot: k − i of the first listing i of the task, 0: not
+                                       //   listed (claimed with atomicMax, so the array starts zeroed)
+    int* t_slot;                       // [k + 1] node slot of task i, −1: the id is refused
+    int* t_agg;                        // [k + 1] arcs into flagged aggregators task i would end with
+    int* nch;                          // [k + 1] 64-position chunks of task i's segment; ch_off its scan
+    int* ch_off;                       // [k + 1]
+    int* seen;                         // [hi + 1] per arc slot: na − j of the listed arc j that names it, 0 none
+    int* sflag;                        // [hi + 1] 1: the arc slot gets a record (a cost change where seen, else a
+                                       //   deletion); s_off its scan
+    int* s_off;                        // [hi + 1]
+    int* lflag;                        // [na + 1] 1: the store does not hold listed arc j (ADD_ARC); l_off its scan
+    int* l_off;                        // [na + 1]
+    unsigned long long* agg_cnt;       // [nst + 1] per node slot: the aggregator's gain
+    const unsigned long long* hkey;    // the store's (src, dst) index (ks_store.h)
+    const int* hval;
+    int hmask;                         // capacity − 1, −1: no index yet
+    UpdCtl* ctl;
+};
+
+// The aggregator flags (ids: nu node ids, or nullptr for every type-0 node with an arc into the
+// sink) into u.fl; the task seed, one lane per id (liveness, type, the claim of t_own, t_slot,
+// nch; walk: the id must lie in the built CSR, whose segments are walked); the listed-arc pass,
+// one lane per arc (head and cost checks, the index lookup, seen, sflag / lflag, t_agg, agg_cnt
+// with one atomic per distinct aggregator per wave). Nothing outside the scratch is written.
+// The caller scans nch → ch_off when it walks.
+hipError_t sched_upd_check(const SchedDev& d, const UpdDev& u, const unsigned long long* ids, int nu, bool walk,
+                           hipStream_t st);
+// The held arcs nobody listed (kept: running arcs and arcs into flagged aggregators, which count
+// into t_agg; else sflag, n_del): walk, one wave per 64-position chunk item of the tasks'
+// segments (ni_max bounds the items), else one lane per arc slot. Then the per-task check
+// (bad_multi, bad_none). The caller scans sflag → s_off and lflag → l_off.
+hipError_t sched_upd_unlisted(const SchedDev& d, const UpdDev& u, bool walk, int ni_max, hipStream_t st);
+// ctl->rec_held and ctl->rec_add after the scans.
+hipError_t sched_upd_totals(const UpdDev& u, hipStream_t st);
+// The records on held arcs at s_off (ascending arc slot), the ADD_ARC records of the listed
+// arcs at rec_held + l_off (input order); d: the arc table as it is now, after any growth.
+hipError_t sched_upd_emit(const SchedDev& d, const UpdDev& u, int rec_held, ks_delta* recs, hipStream_t st);
+// The aggregator part of ks_add_tasks alone: the per-aggregator lookup (a.aflag, a.a_slot,
+// ctl->rec_upd / rec_add), and the aggregator records at base + a.a_off.
+hipError_t sched_add_agg_flags(const SchedDev& d, const AddDev& a, hipStream_t st);
+hipError_t sched_add_emit_aggs(const SchedDev& d, const AddDev& a, long long base, ks_delta* recs, hipStream_t st);
+
 }  // namespace ks

@@ -48,6 +48,13 @@
 //                       parent edges with one atomic per ancestor per wave and step, and
 //                       updateResourceStatsUpToRoot (:1041-1061) for the arcs above the attach point, the
 //                       store's index again telling a capacity rise from an arc to re-create
+//   update tasks        UpdateTimeDependentCosts (graph_manager.go:211-213) → updateTaskNode (:1183-1192)
+//                       for tasks that have their node: each task's list of arcs diffed against the
+//                       store. A listed arc finds its slot through the (src, dst) index (AddArc, or
+//                       ChangeArcCost when the cost differs); the held arcs nobody listed are found in the
+//                       task's own chunked segment and deleted (removeInvalid*Arcs, :732-790) unless
+//                       running or into an aggregator; an evicted task's unit returns to its aggregator
+//                       with one atomic per aggregator per wave
 #include "ks_sched.h"
 #include "ks_store.h"
 
@@ -720,15 +727,17 @@ __global__ void k_gather_bindings(int k, const unsigned long long* __restrict__ 
 
 // The task of input arc j: the last i with arc_off[i] ≤ j (a task without arcs shares its
 // offset with its successor, which owns the arc).
-__device__ __forceinline__ int add_task_of(const AddDev& a, long long j) {
-    int lo = 0, hi = a.k - 1;
+__device__ __forceinline__ int task_of_arc(const unsigned long long* arc_off, int k, long long j) {
+    int lo = 0, hi = k - 1;
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
-        if (a.arc_off[mid] <= (unsigned long long)j) lo = mid;
+        if (arc_off[mid] <= (unsigned long long)j) lo = mid;
         else hi = mid - 1;
     }
     return lo;
 }
+
+__device__ __forceinline__ int add_task_of(const AddDev& a, long long j) { return task_of_arc(a.arc_off, a.k, j); }
 
 // A head must be a node that was live before the call and is no task (the new tasks are dead
 // slots here: an arc into one of them is refused with the rest). Arrivals of one job meet on
@@ -819,9 +828,9 @@ __global__ void k_add_emit_tasks(AddDev a, ks_delta* __restrict__ recs) {
     }
 }
 
-// The aggregator records behind them, in ascending aggregator id (the scan over the node slots).
-__global__ void k_add_emit_aggs(SchedDev d, AddDev a, ks_delta* __restrict__ recs) {
-    const long long base = (long long)a.k + a.na;
+// The aggregator records behind them (base: the records before), in ascending aggregator id
+// (the scan over the node slots).
+__global__ void k_add_emit_aggs(SchedDev d, AddDev a, long long base, ks_delta* __restrict__ recs) {
     for (long long v = blockIdx.x * (long long)SB + threadIdx.x; v < a.nst; v += (long long)gridDim.x * SB) {
         if (!a.aflag[v]) continue;
         const long long cnt = (long long)a.agg_cnt[v];
@@ -1017,6 +1026,186 @@ __global__ void k_grow_emit(SchedDev d, GrowDev g, int rec_pu, ks_delta* __restr
     }
 }
 
+// ----------------------------------------------------------------- update tasks ---
+// UpdateTimeDependentCosts = AddOrUpdateJobNodes (graph_manager.go:211-213, :166-208) for tasks
+// that have their node: updateTaskNode (:1183-1192). Each arc writer (:1197-1285) adds the arc the
+// graph lacks or calls ChangeArcCost, which logs only a cost that differs
+// (graph_change_manager.go:171-182), and then drops the arcs that are no longer preferred
+// (removeInvalidECPrefArcs / removeInvalidPrefResArcs, :732-790). Here that is a diff of each
+// task's list against the store: a listed arc asks the (src, dst) index for its slot and marks it
+// seen; the task's held arcs that nobody marked are found in its own residual segment, one wave
+// per 64-position chunk item as in k_complete_count, or with KS_UPDATE_KEEP_UNLISTED (nothing to
+// delete, only the aggregator counts to complete) by a pass over the arc table. Three record
+// families at fixed positions: held arcs by slot, new arcs in input order, aggregators by id.
+
+// The arc slot of src → dst (node slots), −1: the store does not hold it.
+__device__ __forceinline__ int upd_held_slot(const SchedDev& d, const UpdDev& u, int src, int dst) {
+    if (u.hmask < 0) return -1;
+    const int e = store_hfind(u.hkey, u.hmask, arc_hkey((long long)src + 1, (long long)dst + 1));
+    const int s = e >= 0 ? u.hval[e] : -1;
+    return s >= 0 && s < u.hi && d.a_alive[s] ? s : -1;
+}
+
+// An id must be a live task and listed once: the first listing holds t_own (atomicMax of k − i),
+// every other one loses a comparison there exactly once, as the arriving or the displaced value,
+// and is reported then. walk: the task's segment is read, so the id must lie in the built CSR.
+__global__ void k_upd_seed(SchedDev d, UpdDev u, int walk) {
+    const unsigned long long lim = walk ? (unsigned long long)d.ncap : (unsigned long long)u.nst;
+    for (long long i = blockIdx.x * (long long)SB + threadIdx.x; i < u.k; i += (long long)gridDim.x * SB) {
+        const unsigned long long id = u.tasks[i];
+        bool ok = id >= 1 && id <= lim;
+        int v = -1, nch = 0;
+        if (ok) {
+            v = (int)(id - 1);
+            ok = d.n_alive[v] && d.n_type[v] == KS_NODE_TASK && (!walk || d.perm[v] >= 0);
+        }
+        if (ok) {
+            const int mine = (int)(u.k - i);
+            const int old = atomicMax(&u.t_own[v], mine);
+            if (old) atomicMax(&u.ctl->bad_task, min(old, mine));
+            if (walk) nch = (remove_seg_len(d, d.perm[v]) + 63) >> 6;
+        } else {
+            v = -1;
+            atomicMax(&u.ctl->bad_task, (int)(u.k - i));
+        }
+        u.t_slot[i] = v;
+        u.nch[i] = nch;
+    }
+}
+
+// One lane per listed arc. A held arc is marked seen and compared: a running arc keeps its cost
+// (:1250-1255), any other gets a record only when the cost differs. An arc the store does not
+// hold is an AddArc; into a flagged aggregator it is the task's unit coming back
+// (updateUnscheduledAggNode(+1), :1291-1305): an eviction of one job's tasks puts 64 lanes on
+// one word, so the lanes combine into one atomic per distinct aggregator (wave_add_distinct).
+__global__ void k_upd_heads(SchedDev d, UpdDev u) {
+    for (long long j0 = blockIdx.x * (long long)SB; j0 < u.na; j0 += (long long)gridDim.x * SB) {   // (uniform per workgroup)
+        const long long j = j0 + threadIdx.x;
+        bool gain = false, cost = false, same = false, run = false;
+        int v = 0;
+        if (j < u.na) {
+            const ks_task_arc x = u.arcs[j];
+            bool ok = x.dst >= 1 && x.dst <= (unsigned long long)u.nst;
+            if (ok) {
+                v = (int)(x.dst - 1);
+                ok = d.n_alive[v] && d.n_type[v] != KS_NODE_TASK;
+            }
+            const int i = task_of_arc(u.arc_off, u.k, j);
+            const int t = u.t_slot[i];
+            if (!ok) {
+                v = 0;
+                atomicMax(&u.ctl->bad_head, (int)(u.na - j));
+            } else if (x.cost > (1LL << 40) || x.cost < -(1LL << 40)) {
+                atomicMax(&u.ctl->bad_cost, (int)(u.na - j));
+            } else if (t >= 0) {
+                const bool agg = (u.fl[v] & 1) != 0;
+                if (agg) atomicAdd(&u.t_agg[i], 1);   // (a task's own word: one such arc per task in a legal call)
+                const int s = upd_held_slot(d, u, t, v);
+                if (s < 0) {
+                    u.lflag[j] = 1;
+                    gain = agg;
+                } else {
+                    u.seen[s] = (int)(u.na - j);
+                    run = d.a_type[s] == 1;
+                    cost = !run && d.a_cost[s] != x.cost;
+                    same = !run && !cost;
+                    if (cost) u.sflag[s] = 1;
+                }
+            }
+        }
+        wave_add_distinct(u.agg_cnt, v, gain);
+        wave_count(&u.ctl->units, gain);
+        wave_count(&u.ctl->n_cost, cost);
+        wave_count(&u.ctl->n_same, same);
+        wave_count(&u.ctl->n_run, run);
+    }
+}
+
+// A held arc of a listed task that no listed arc named. A running arc stays (the reference's
+// removeInvalidPrefResArcs would drop one whose PU left the preferences and panic at the next
+// updateRunningTaskNode); an arc into a flagged aggregator stays with its cost, which may have
+// aged on the device, and counts as the task's job; any other is no longer preferred. → deleted.
+__device__ __forceinline__ bool upd_unlisted(const SchedDev& d, const UpdDev& u, int s) {
+    if (!d.a_alive[s] || u.seen[s]) return false;
+    const int own = u.t_own[d.a_src[s]];
+    if (!own) return false;
+    if (u.fl[d.a_dst[s]] & 1) {
+        atomicAdd(&u.t_agg[u.k - own], 1);
+        return false;
+    }
+    if (d.a_type[s] == 1 || u.keep) return false;
+    u.sflag[s] = 1;
+    return true;
+}
+
+__global__ void k_upd_walk(SchedDev d, UpdDev u, int ni_max) {
+    const int lane = threadIdx.x & 63;
+    const int wave = (blockIdx.x * SB + threadIdx.x) >> 6;
+    const int nwaves = (gridDim.x * SB) >> 6;
+    const int ni = min(u.ch_off[u.k], ni_max);
+    RemoveDev r{};   // (the chunk items of remove_item_pos: the tasks' node slots and their chunk scan)
+    r.front = u.t_slot;
+    r.ch_off = u.ch_off;
+    for (int w = wave; w < ni; w += nwaves) {
+        const int p = remove_item_pos(d, r, u.k, w, lane);
+        const int e = p >= 0 ? d.ent[p] : -1;
+        const bool del = e >= 0 && !(e & 1) && (e >> 1) < u.hi && upd_unlisted(d, u, e >> 1);   // forward positions only
+        wave_count(&u.ctl->n_del, del);
+    }
+}
+
+__global__ void k_upd_table(SchedDev d, UpdDev u) {
+    for (long long s0 = blockIdx.x * (long long)SB; s0 < u.hi; s0 += (long long)gridDim.x * SB) {   // (uniform per workgroup)
+        const long long s = s0 + threadIdx.x;
+        const bool del = s < u.hi && upd_unlisted(d, u, (int)s);
+        wave_count(&u.ctl->n_del, del);
+    }
+}
+
+// A task does not change its job: arcs into two flagged aggregators, listed, held or a mix, are
+// refused. Under the NULL rule an unbound task with none is refused too (its aggregator may have
+// lost the arc into the sink that would have flagged it, and its unit would be lost with it); a
+// bound task may have none (a pinned running task has no aggregator arc).
+__global__ void k_upd_task_check(SchedDev d, UpdDev u) {
+    for (long long i = blockIdx.x * (long long)SB + threadIdx.x; i < u.k; i += (long long)gridDim.x * SB) {
+        const int t = u.t_slot[i];
+        if (t < 0) continue;
+        const int c = u.t_agg[i];
+        if (c > 1) atomicMax(&u.ctl->bad_multi, (int)(u.k - i));
+        else if (c == 0 && u.null_rule && d.n_bind[t] == 0) atomicMax(&u.ctl->bad_none, (int)(u.k - i));
+    }
+}
+
+__global__ void k_upd_totals(UpdDev u) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        u.ctl->rec_held = u.s_off[u.hi];
+        u.ctl->rec_add = u.l_off[u.na];
+    }
+}
+
+// Stream part 1, ascending arc slot: ChangeArcCost (low, cap and type kept, the listed cost) on a
+// seen slot, else the delete (UPDATE_ARC 0/0, as the commit writes it).
+__global__ void k_upd_emit_held(SchedDev d, UpdDev u, ks_delta* __restrict__ recs) {
+    for (long long s = blockIdx.x * (long long)SB + threadIdx.x; s < u.hi; s += (long long)gridDim.x * SB) {
+        if (!u.sflag[s]) continue;
+        const long long co = d.a_cost[s];
+        const int sn = u.seen[s];
+        recs[u.s_off[s]] = sn ? arc_record(KS_UPDATE_ARC, d.a_type[s], d.a_src[s], d.a_dst[s], d.a_low[s], d.a_cap[s],
+                                           u.arcs[u.na - sn].cost, co)
+                              : arc_record(KS_UPDATE_ARC, d.a_type[s], d.a_src[s], d.a_dst[s], 0, 0, co, co);
+    }
+}
+
+// Stream part 2, input order: AddArc(task, head, 0, 1, cost, ArcTypeOther).
+__global__ void k_upd_emit_adds(UpdDev u, int rec_held, ks_delta* __restrict__ recs) {
+    for (long long j = blockIdx.x * (long long)SB + threadIdx.x; j < u.na; j += (long long)gridDim.x * SB) {
+        if (!u.lflag[j]) continue;
+        const ks_task_arc x = u.arcs[j];
+        recs[(long long)rec_held + u.l_off[j]] =
+            arc_record(KS_ADD_ARC, 0, u.t_slot[task_of_arc(u.arc_off, u.k, j)], (int)(x.dst - 1), 0, 1, x.cost, 0);
+    }
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------ launchers ---
@@ -1190,7 +1379,43 @@ hipError_t sched_add_totals(const AddDev& a, hipStream_t st) {
 
 hipError_t sched_add_emit(const SchedDev& d, const AddDev& a, ks_delta* recs, hipStream_t st) {
     hipLaunchKernelGGL(k_add_emit_tasks, dim3(grid((long long)a.k + a.na)), dim3(SB), 0, st, a, recs);
-    if (a.nst) hipLaunchKernelGGL(k_add_emit_aggs, dim3(grid(a.nst)), dim3(SB), 0, st, d, a, recs);
+    return sched_add_emit_aggs(d, a, (long long)a.k + a.na, recs, st);
+}
+
+hipError_t sched_add_agg_flags(const SchedDev& d, const AddDev& a, hipStream_t st) {
+    hipLaunchKernelGGL(k_add_agg_flags, dim3(grid(a.nst + 1)), dim3(SB), 0, st, d, a);
+    return hipGetLastError();
+}
+
+hipError_t sched_add_emit_aggs(const SchedDev& d, const AddDev& a, long long base, ks_delta* recs, hipStream_t st) {
+    if (a.nst) hipLaunchKernelGGL(k_add_emit_aggs, dim3(grid(a.nst)), dim3(SB), 0, st, d, a, base, recs);
+    return hipGetLastError();
+}
+
+hipError_t sched_upd_check(const SchedDev& d, const UpdDev& u, const unsigned long long* ids, int nu, bool walk,
+                           hipStream_t st) {
+    // (the byte stores of the aggregator marks come first, as in sched_complete_seed)
+    mark_aggregators(d, ids, nu, u.fl, st);
+    hipLaunchKernelGGL(k_upd_seed, dim3(grid(u.k)), dim3(SB), 0, st, d, u, walk ? 1 : 0);
+    if (u.na) hipLaunchKernelGGL(k_upd_heads, dim3(grid(u.na)), dim3(SB), 0, st, d, u);
+    return hipGetLastError();
+}
+
+hipError_t sched_upd_unlisted(const SchedDev& d, const UpdDev& u, bool walk, int ni_max, hipStream_t st) {
+    if (walk) hipLaunchKernelGGL(k_upd_walk, dim3(grid(64LL * ni_max)), dim3(SB), 0, st, d, u, ni_max);
+    else if (u.hi) hipLaunchKernelGGL(k_upd_table, dim3(grid(u.hi)), dim3(SB), 0, st, d, u);
+    hipLaunchKernelGGL(k_upd_task_check, dim3(grid(u.k)), dim3(SB), 0, st, d, u);
+    return hipGetLastError();
+}
+
+hipError_t sched_upd_totals(const UpdDev& u, hipStream_t st) {
+    hipLaunchKernelGGL(k_upd_totals, dim3(1), dim3(64), 0, st, u);
+    return hipGetLastError();
+}
+
+hipError_t sched_upd_emit(const SchedDev& d, const UpdDev& u, int rec_held, ks_delta* recs, hipStream_t st) {
+    if (u.hi) hipLaunchKernelGGL(k_upd_emit_held, dim3(grid(u.hi)), dim3(SB), 0, st, d, u, recs);
+    if (u.na) hipLaunchKernelGGL(k_upd_emit_adds, dim3(grid(u.na)), dim3(SB), 0, st, u, rec_held, recs);
     return hipGetLastError();
 }
 

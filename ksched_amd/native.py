@@ -22,7 +22,7 @@ EXPORTED_SYMBOLS = (
     "ks_coalesce_deltas", "ks_get_store_stats", "ks_set_bindings", "ks_scheduling_deltas",
     "ks_update_unsched_costs", "ks_topology_stats", "ks_get_graph", "ks_commit_schedule",
     "ks_commit_preemptive", "ks_remove_resources", "ks_complete_tasks", "ks_get_bindings",
-    "ks_add_tasks", "ks_add_resources",
+    "ks_add_tasks", "ks_add_resources", "ks_update_tasks",
     "ks_batch_create", "ks_batch_create_rank", "ks_batch_unique_id", "ks_batch_destroy", "ks_batch_last_error",
     "ks_batch_load", "ks_batch_solve", "ks_batch_gather",
     "ks_batch_slots", "ks_batch_owner", "ks_batch_block_len", "ks_batch_unpack",
@@ -35,6 +35,7 @@ KS_COST_SET, KS_COST_ADD = 0, 1
 KS_COMMIT_RESOURCE_CAPS = 1
 KS_REMOVE_RESOURCE_CAPS, KS_REMOVE_PREEMPTIVE = 1, 2
 KS_COMPLETE_RESOURCE_CAPS, KS_COMPLETE_PREEMPTIVE = 1, 2
+KS_UPDATE_KEEP_UNLISTED = 1
 
 NODE_DT = np.dtype({"names": ["id", "excess", "type", "_pad"],
                     "formats": ["<u8", "<i8", "<i4", "<i4"], "offsets": [0, 8, 16, 20], "itemsize": 24})
@@ -143,6 +144,17 @@ class KsAddStats(C.Structure):
     """ks_add_stats: what one ks_add_tasks generated on device."""
     _fields_ = [("tasks", C.c_int64), ("arcs_added", C.c_int64), ("unsched_updates", C.c_int64),
                 ("unsched_added", C.c_int64), ("records", C.c_int64), ("reserved", C.c_int64 * 7)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class KsUpdateStats(C.Structure):
+    """ks_update_stats: what one ks_update_tasks found and generated on device."""
+    _fields_ = [("tasks", C.c_int64), ("arcs_added", C.c_int64), ("cost_updates", C.c_int64),
+                ("arcs_unchanged", C.c_int64), ("running_kept", C.c_int64), ("arcs_removed", C.c_int64),
+                ("unsched_updates", C.c_int64), ("unsched_added", C.c_int64), ("records", C.c_int64),
+                ("reserved", C.c_int64 * 3)]
 
     def as_dict(self) -> dict:
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
@@ -277,6 +289,7 @@ def _bind(path: str):
     L.ks_complete_tasks.argtypes = [V, C.c_int32, V, C.c_size_t, V, C.c_size_t, V, P(KsCompleteStats)]
     L.ks_add_tasks.argtypes = [V, C.c_int32, V, C.c_size_t, V, V, V, C.c_size_t, C.c_int64, P(KsAddStats)]
     L.ks_add_resources.argtypes = [V, C.c_int32, V, C.c_size_t, V, C.c_size_t, P(KsGrowStats)]
+    L.ks_update_tasks.argtypes = [V, C.c_int32, V, C.c_size_t, V, V, V, C.c_size_t, C.c_int64, P(KsUpdateStats)]
     L.ks_get_bindings.argtypes = [V, V, V, C.c_size_t]
     return L
 
@@ -556,6 +569,37 @@ class Context:
         st = KsGrowStats()
         self._check(self._L.ks_add_resources(self._h, 0, nd.ctypes.data if nd.shape[0] else None, nd.shape[0],
                                              ar.ctypes.data if ar.shape[0] else None, ar.shape[0], C.byref(st)))
+        return st.as_dict()
+
+    def update_tasks(self, tasks, arc_off, dst, cost, unsched_ids=None, unsched_sink_cost: int = 0,
+                     keep_unlisted: bool = False) -> dict:
+        """ks_update_tasks: the live task ids get the arcs their lists name. Task i's list is
+        (dst[j], cost[j]) for arc_off[i] <= j < arc_off[i + 1]: an arc the store does not hold is
+        added (low 0, cap 1, type 0), a held one whose cost differs is re-costed, a held running
+        arc keeps its cost; a held arc the list does not name is deleted unless it is a running
+        arc or an arc into an unscheduled aggregator (keep_unlisted: nothing is deleted, and no
+        residual CSR is needed). An aggregator gains one unit on its arc into the sink per task
+        whose listed arc into it the store did not hold (the arc is re-created with
+        unsched_sink_cost when the store no longer holds it). unsched_ids=None: every type-0
+        node with an arc into the sink; an unbound task that would end without an arc into one
+        of those is then refused. → stats dict. Needs no solve; invalidates the solution when a
+        record is applied."""
+        ids = np.ascontiguousarray(tasks, np.uint64).reshape(-1)
+        off = np.ascontiguousarray(arc_off, np.uint64).reshape(-1)
+        if off.shape[0] != ids.shape[0] + 1:
+            raise ValueError("arc_off has one entry more than tasks")
+        arcs = np.zeros(max(np.asarray(dst).size, 1), TASK_ARC_DT)
+        arcs["dst"][:np.asarray(dst).size] = np.asarray(dst, np.uint64).reshape(-1)
+        arcs["cost"][:np.asarray(cost).size] = np.asarray(cost, np.int64).reshape(-1)
+        agg = None if unsched_ids is None else np.ascontiguousarray(unsched_ids, np.uint64).reshape(-1)
+        nu = 0 if agg is None else agg.shape[0]
+        if agg is not None and nu == 0:
+            agg = np.zeros(1, np.uint64)   # an empty list names no aggregator: not NULL, which is the auto rule
+        st = KsUpdateStats()
+        self._check(self._L.ks_update_tasks(self._h, KS_UPDATE_KEEP_UNLISTED if keep_unlisted else 0, ids.ctypes.data,
+                                            ids.shape[0], off.ctypes.data, arcs.ctypes.data,
+                                            None if agg is None else agg.ctypes.data, nu, int(unsched_sink_cost),
+                                            C.byref(st)))
         return st.as_dict()
 
     def bindings(self, tasks) -> np.ndarray:
