@@ -114,6 +114,13 @@ __device__ __forceinline__ long long atom_load(const long long* p) {
 __device__ __forceinline__ int atom_load_i(const int* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+// A wave-uniform 64-bit value that came from a vector load (one address for the
+// whole wave), moved to scalar registers.
+__device__ __forceinline__ long long uniform64(long long x) {
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)((unsigned long long)x & 0xffffffffULL));
+    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)((unsigned long long)x >> 32));
+    return (long long)(((unsigned long long)hi << 32) | lo);
+}
 __device__ __forceinline__ void drain_vm() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // One residual position (ks_pos.h) in two 16-byte loads issued together.
@@ -427,7 +434,7 @@ struct Scan {
 };
 
 __device__ __forceinline__ int wave_index_in_grid(int first_block) {
-    return ((int)blockIdx.x - first_block) * WPB + ((int)threadIdx.x >> 6);
+    return __builtin_amdgcn_readfirstlane(((int)blockIdx.x - first_block) * WPB + ((int)threadIdx.x >> 6));   // wave-uniform: a scalar register
 }
 
 // max |cost| over live arcs → *out (the first phase's ε).
@@ -1134,20 +1141,29 @@ __device__ __forceinline__ bool bf_enqueue(const BfQ& Q, int u, unsigned long lo
     return true;
 }
 
+// A leaf's arc records loaded together and held in registers: a task has five
+// arcs and a PU two, so five cover the scheduling graphs; a leaf of six to eight
+// arcs reads the rest one by one. Eight held 24 more VGPRs across the expansion
+// and kept k_bf_round at 4 waves per SIMD. -DKS_LEAF_REGS: tuning builds.
+#ifndef KS_LEAF_REGS
+#define KS_LEAF_REGS 5
+#endif
+constexpr int LEAF_REGS = KS_LEAF_REGS;
+
 // Relax the in-arcs of a low-degree node u (≤ 8 arcs: tasks, PUs) right after
 // its distance dropped to du: a second hop inside the same round.
 template <int PR, bool CP>
 __device__ __forceinline__ void expand_leaf(const DG& g, const Front& nf, const BfQ& Q, int u, long long du, long long pu,
                                             int b0, int b1, long long eps, long long B, long long* hub_min, int& out,
-                                            long long& lscan) {
+                                            int& lscan) {
     lscan += b1 - b0;   // the second hop's in-arc positions examined (ks_result.gu_leaf_scans)
-    // the records of all (≤ 8) arcs issued together; usually one in-arc carries
-    // flow (a task's assignment), so the dependent loads follow for it alone
+    // the records of the first LEAF_REGS arcs issued together; usually one in-arc
+    // carries flow (a task's assignment), so the dependent loads follow for it alone
     unsigned live = 0;
-    int hd[8];
-    long long cb[8];
+    int hd[LEAF_REGS];
+    long long cb[LEAF_REGS];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
+    for (int k = 0; k < LEAF_REGS; ++k) {
         hd[k] = 0;
         cb[k] = 0;
         if (b0 + k < b1) {
@@ -1157,7 +1173,7 @@ __device__ __forceinline__ void expand_leaf(const DG& g, const Front& nf, const 
             if (q.ucap - q.rcap > 0) live |= 1u << k;
         }
     }
-    for (int b = b1 - b0 > 8 ? b0 + 8 : b1; b < b1; ++b) {   // leaves have ≤ 8 arcs; kept for safety
+    for (int b = b1 - b0 > LEAF_REGS ? b0 + LEAF_REGS : b1; b < b1; ++b) {   // the arcs beyond the registers, one by one
         const Pos q = PL<CP>::ld_nr(g, b);
         if (q.ucap - q.rcap > 0) {
             const int u2 = q.head;
@@ -1177,7 +1193,7 @@ __device__ __forceinline__ void expand_leaf(const DG& g, const Front& nf, const 
         int u2 = 0;
         long long c2 = 0;
 #pragma unroll
-        for (int j = 0; j < 8; ++j)   // register select (no dynamic indexing into scratch)
+        for (int j = 0; j < LEAF_REGS; ++j)   // register select (no dynamic indexing into scratch)
             if (j == k) {
                 u2 = hd[j];
                 c2 = cb[j];
@@ -1201,7 +1217,7 @@ __device__ __forceinline__ void expand_leaf(const DG& g, const Front& nf, const 
 template <int PR, bool CP>
 __device__ __forceinline__ void relax_pos(const DG& g, const Front& nf, const BfQ& Q, const Pos& q, int a, long long dv,
                                           long long pv, long long eps, long long B, long long* hub_min, int& out,
-                                          long long& lscan) {
+                                          int& lscan) {
     const long long rin = q.ucap - q.rcap;
     // an arc that cannot relax reads node 0's (hot) record instead of its head's
     // random line: the loads stay unconditional (no branch join to wait at) and
@@ -1229,7 +1245,7 @@ __device__ __forceinline__ void relax_pos(const DG& g, const Front& nf, const Bf
 
 template <int PR, bool CP>
 __device__ __forceinline__ void relax_in(const DG& g, const Front& nf, const BfQ& Q, int v, int a, long long dv, long long pv,
-                                         long long eps, long long B, long long* hub_min, int& out, long long& lscan) {
+                                         long long eps, long long B, long long* hub_min, int& out, int& lscan) {
     relax_pos<PR, CP>(g, nf, Q, PL<CP>::ld_nr(g, a), a, dv, pv, eps, B, hub_min, out, lscan);
 }
 
@@ -1241,7 +1257,7 @@ __device__ __forceinline__ void relax_in(const DG& g, const Front& nf, const BfQ
 // Qn (the next level; cap 0: the frontier flags of the next launch).
 template <int PR, bool CP>
 __device__ __forceinline__ void bf_drain(const DG& g, const Front& nf, const QEnt* q, int n, const BfQ& Qn, long long eps,
-                                         long long B, long long* hub_min, int& out, long long& scans, long long& lscan) {
+                                         long long B, long long* hub_min, int& out, int& scans, int& lscan) {
     constexpr int QG = BFQ_GROUP;
     const int lig = threadIdx.x & (QG - 1);
     for (int i = threadIdx.x / QG; i < n; i += BLK / QG) {
@@ -1258,7 +1274,7 @@ __device__ __forceinline__ void bf_drain(const DG& g, const Front& nf, const QEn
 
 template <int G, int PR, bool CP>
 __device__ __forceinline__ void bf_group_pre(const DG& g, const Front& nf, const BfQ& Q, int v, long long dv, long long pv, int b0,
-                                             int en, long long eps, long long B, long long* hub_min, int& out, long long& scans, long long& lscan) {
+                                             int en, long long eps, long long B, long long* hub_min, int& out, int& scans, int& lscan) {
     const int lig = lane_id() & (G - 1);
     const bool act = v >= 0 && (PR || dv < INF64);
     if (!act) en = b0;
@@ -1275,7 +1291,7 @@ __device__ __forceinline__ void bf_group_pre(const DG& g, const Front& nf, const
 // Sparse Bellman-Ford pass over window w of class C (mask from window_mask).
 template <int C, int PR, bool CP>
 __device__ __forceinline__ void bf_win(const DG& g, const Front& N, const BfQ& Q, int w, unsigned long long mask, const WinFlag& f,
-                                       long long eps, long long B, long long* hub_min, int& out, long long& scans, long long& lscan) {
+                                       long long eps, long long B, long long* hub_min, int& out, int& scans, int& lscan) {
     constexpr int G = class_lanes(C);
     constexpr int PER = 64 / G;
     constexpr int WS = win_slots(C);
@@ -1297,7 +1313,7 @@ __device__ __forceinline__ void bf_win(const DG& g, const Front& N, const BfQ& Q
 // One 64-arc chunk of a chunked-class node (its flag already tested).
 template <int PR, bool CP>
 __device__ __forceinline__ void bf_chunk(const DG& g, const Front& N, const BfQ& Q, const CItem& ci, long long eps,
-                                         long long B, long long* hub_min, int& out, long long& scans, long long& lscan) {
+                                         long long B, long long* hub_min, int& out, int& scans, int& lscan) {
     const long long dv = atom_load(&g.dist[ni(ci.node)]);
     if (!PR && dv >= INF64) return;
     const int a = ci.begin + lane_id();
@@ -1309,7 +1325,7 @@ __device__ __forceinline__ void bf_chunk(const DG& g, const Front& N, const BfQ&
 
 template <int G, int PR, bool CP>
 __device__ __forceinline__ void bf_group(const DG& g, const Front& nf, const BfQ& Q, int v, long long eps, long long B, long long* hub_min,
-                                         int& out, long long& scans, long long& lscan) {
+                                         int& out, int& scans, int& lscan) {
     const int lig = lane_id() & (G - 1);
     long long dv = INF64;
     if (v >= 0) dv = atom_load(&g.dist[ni(v)]);
@@ -1336,7 +1352,7 @@ __device__ __forceinline__ void bf_group(const DG& g, const Front& nf, const BfQ
 template <int PR, bool CP>
 __global__ __launch_bounds__(BLK) void k_bf_round(DG g, int seq, int dense_arg) {
     const unsigned long long t_entry = PR == 2 ? __builtin_amdgcn_s_memrealtime() : 0;
-    const int dense = dense_arg >= 0 ? dense_arg : (seq == g.ctl->bf_seq0 ? 1 : 0);
+    const int dense = __builtin_amdgcn_readfirstlane(dense_arg >= 0 ? dense_arg : (seq == g.ctl->bf_seq0 ? 1 : 0));
     __shared__ long long hub_min[HUB_LDS];
     __shared__ QEnt bfq[BF_DEPTH][BFQ_CAP];   // the continuation queue (g.expand ≥ 2), one level per extra hop pair
     __shared__ int bfq_n[BF_DEPTH];
@@ -1360,12 +1376,16 @@ __global__ __launch_bounds__(BLK) void k_bf_round(DG g, int seq, int dense_arg) 
         done = g.ctl->bf_done;
         any = g.ctl->bfa[seq % 3];
     };
-    const long long eps = g.ctl->eps;
+    auto ctl_uniform = [&]() {   // the words are wave-uniform: scalar registers for the rest of the launch
+        done = __builtin_amdgcn_readfirstlane(done);
+        any = __builtin_amdgcn_readfirstlane(any);
+    };
+    const long long eps = uniform64(g.ctl->eps);
     // bounded update (tail): offers at or above the listed excess nodes' largest
     // tentative distance are dropped (that bound only falls, so a stale copy is safe)
-    const long long B = (!PR && g.bound) ? atom_load(&g.ctl->bf_bound) : INF64;
+    const long long B = (!PR && g.bound) ? uniform64(atom_load(&g.ctl->bf_bound)) : INF64;
     int out = 0;
-    long long scans = 0, lscan = 0;
+    int scans = 0, lscan = 0;   // per lane and launch: 32 bits, widened at the wave sum
     // Hub chunks are split over HSPLIT workgroups: a relaxation is a dependent
     // chain (arc, tail record, leaf expansion, atomic), and a thread that runs
     // several of them in a row made the hub the last block of its round.
@@ -1378,6 +1398,7 @@ __global__ __launch_bounds__(BLK) void k_bf_round(DG g, int seq, int dense_arg) 
         const long long pv = g.p0[ni(it.node)];
         ctl_words();
         KS_AFTER_LOADS(done, any, "v"(fl), "v"(dv), "v"(pv));
+        ctl_uniform();
         if (!done && (dense || any) && (dense || fl)) {
             if (PR || dv < INF64) {
 #pragma unroll
@@ -1393,6 +1414,7 @@ __global__ __launch_bounds__(BLK) void k_bf_round(DG g, int seq, int dense_arg) 
     } else if (dense) {
         const int w = wave_index_in_grid(nhb);
         ctl_words();
+        ctl_uniform();
         if (done) {
             // the update already converged
         } else if (w < g.wbeg[CCLS]) {
@@ -1415,6 +1437,7 @@ __global__ __launch_bounds__(BLK) void k_bf_round(DG g, int seq, int dense_arg) 
         }
         ctl_words();
         KS_AFTER_LOADS(done, any, "v"(any_raw));
+        ctl_uniform();
         const bool go = !done && any;
         unsigned long long mk[WPW];
 #pragma unroll

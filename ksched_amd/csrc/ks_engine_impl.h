@@ -29,7 +29,10 @@ constexpr int PER_T = CHUNK / 256; // arcs per thread in a hub chunk
 constexpr int HSPLIT = 4;          // Bellman-Ford: workgroups per hub chunk (one arc per thread at 4)
 constexpr int BF_PER_T = PER_T / HSPLIT;
 static_assert(PER_T % HSPLIT == 0, "a hub chunk splits into whole arcs per thread");
-constexpr int WPW = 2;             // windows per wave in sparse (grid-stride) passes
+#ifndef KS_WPW
+#define KS_WPW 2
+#endif
+constexpr int WPW = KS_WPW;        // windows per wave in sparse (grid-stride) passes (-DKS_WPW: tuning builds)
 constexpr int SHARDS = 16;         // inbox shards per heavy hub
 constexpr int MAXB = 64;           // max sweeps per cycle
 constexpr int HUB_LDS = 16;        // hubs whose Bellman-Ford minima are reduced in LDS

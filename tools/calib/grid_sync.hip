@@ -17,10 +17,15 @@
 // Every spin has a wall-clock deadline (s_memrealtime, 100 MHz), so a grid that
 // could not be co-resident ends instead of hanging.
 //
-//   hipcc --offload-arch=gfx950 -O3 tools/calib/grid_sync.hip -o /tmp/grid_sync && /tmp/grid_sync
+//   C  `grid_sync occupancy`: the floor of A at the config-3 sparse grids (2,350
+//      and 2,800 workgroups) and the engine kernels' register footprints, with
+//      working waves at the front or at the back of the grid (see mode C below).
+//
+//   hipcc --offload-arch=gfx950 -O3 tools/calib/grid_sync.hip -o /tmp/grid_sync && /tmp/grid_sync [occupancy]
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
+#include <string>
 #include <vector>
 
 #define CK(x)                                                                      \
@@ -141,7 +146,144 @@ __global__ __launch_bounds__(256) void k_persist(const unsigned char* flags, uns
     }
 }
 
-int main() {
+// ---------------------------------------------------------------- mode C ---
+//   C  (`grid_sync occupancy`) the floor of A at the engine's sparse grids and
+//      register footprints: does a launch whose grid exceeds what is resident at
+//      once pay for the second residency pass, and does it matter where in the
+//      grid the working waves sit? The kernel is the engine's sparse prologue:
+//      each wave loads the flag bytes of its WPW windows (strided across the
+//      grid, all loads issued together), ballots them and exits when none is set.
+//      NV pins the kernel's VGPR allocation (a write to v[NV-1]: registers, no
+//      scratch), so one source runs at occupancy 8, 5 and 4 waves/SIMD.
+//      A window whose flags are set makes its wave follow a chain of
+//      dependent loads per lane (random lines of a 16 MB table: a working
+//      window's arc → record → distance … chain). The host sets 1 % of the
+//      waves' first windows, at the front of the grid or at the back. The chain
+//      is 5 loads (a working window of the engine) and 20 loads: at 5 the kernel
+//      is shorter than the launch-to-launch floor, which hides it; at 20 the
+//      working waves outlast the floor as the engine's 11–20 µs launches do, and
+//      a wait for residency ahead of them would show.
+constexpr int OCC_TABLE = 1 << 22;   // ints
+
+template <int NV>
+__device__ __forceinline__ void pin_vgprs() {
+    static_assert(NV == 64 || NV == 96 || NV == 116, "one of the measured footprints");
+    if (NV == 64) asm volatile("v_mov_b32 v63, 0" ::: "v63");
+    if (NV == 96) asm volatile("v_mov_b32 v95, 0" ::: "v95");
+    if (NV == 116) asm volatile("v_mov_b32 v115, 0" ::: "v115");
+}
+
+template <int NV, int WPW>
+__global__ __launch_bounds__(256) void k_occ(const unsigned char* __restrict__ flags, int nwin,
+                                             const int* __restrict__ table, int chain, unsigned char* out) {
+    pin_vgprs<NV>();
+    const int lane = threadIdx.x & 63;
+    const int tw = gridDim.x * 4;
+    const int w0 = blockIdx.x * 4 + (threadIdx.x >> 6);
+    int f[WPW];
+#pragma unroll
+    for (int j = 0; j < WPW; ++j) {
+        const int w = w0 + j * tw;
+        f[j] = w < nwin ? flags[(size_t)w * 64 + lane] : 0;
+    }
+    unsigned long long mk[WPW];
+#pragma unroll
+    for (int j = 0; j < WPW; ++j) mk[j] = __ballot(f[j] != 0);
+    int acc = 0;
+#pragma unroll
+    for (int j = 0; j < WPW; ++j) {
+        if (!mk[j]) continue;
+        int i = (int)(((unsigned)(w0 + j * tw) * 64u + (unsigned)lane) * 2654435761u >> 10);   // < 2^22
+        for (int k = 0; k < chain; ++k) i = table[i];
+        acc |= i;
+    }
+    if (acc < 0) out[0] = 1;   // (never: table entries are indices; keeps the chain alive)
+}
+
+template <int NV, int WPW>
+static int occ_setting(const char* place, int G, int nwin, int nwork, const unsigned char* flags, const int* table,
+                       int chain, unsigned char* out, hipEvent_t a, hipEvent_t b, bool& first) {
+    int per_cu = 0;
+    CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k_occ<NV, WPW>, 256, 0));
+    const int L = 2000;
+    for (int rep = 0; rep < 3; ++rep) {
+        for (int i = 0; i < 50; ++i) hipLaunchKernelGGL((k_occ<NV, WPW>), dim3(G), dim3(256), 0, 0, flags, nwin, table, chain, out);
+        CK(hipEventRecord(a, 0));
+        for (int i = 0; i < L; ++i) hipLaunchKernelGGL((k_occ<NV, WPW>), dim3(G), dim3(256), 0, 0, flags, nwin, table, chain, out);
+        CK(hipEventRecord(b, 0));
+        CK(hipEventSynchronize(b));
+        float ms = 0;
+        CK(hipEventElapsedTime(&ms, a, b));
+        std::printf("%s {\"mode\": \"occupancy\", \"workgroups\": %d, \"windows_per_wave\": %d, \"vgprs\": %d, "
+                    "\"workgroups_per_cu\": %d, \"working_waves\": %d, \"chain\": %d, \"placement\": \"%s\", \"rep\": %d, "
+                    "\"us_per_launch\": %.3f}",
+                    first ? "" : ",\n", G, WPW, NV, per_cu, nwork, nwork ? chain : 0, place, rep, ms * 1000.0 / L);
+        first = false;
+    }
+    return 0;
+}
+
+static int occupancy_mode() {
+    int ncu = 0;
+    CK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, 0));
+    const int GMAX = 2800, NWIN = GMAX * 4 * 2;
+    unsigned char *flags, *out;
+    int* table;
+    CK(hipMalloc(&flags, (size_t)NWIN * 64));
+    CK(hipMalloc(&out, 64));
+    CK(hipMalloc(&table, (size_t)OCC_TABLE * sizeof(int)));
+    {
+        std::vector<int> h(OCC_TABLE);
+        unsigned x = 12345;
+        for (int i = 0; i < OCC_TABLE; ++i) {
+            x = x * 1664525u + 1013904223u;
+            h[i] = (int)(x >> 10);   // < 2^22
+        }
+        CK(hipMemcpy(table, h.data(), (size_t)OCC_TABLE * sizeof(int), hipMemcpyHostToDevice));
+    }
+    hipEvent_t a, b;
+    CK(hipEventCreate(&a));
+    CK(hipEventCreate(&b));
+    std::printf("{\"rows\": [\n");
+    bool first = true;
+    // the engine's config-3 sparse grids at WPW 2 (k_bf_round 2,350; k_sweep 2,800
+    // workgroups), and the same windows at WPW 4 (half the grid)
+    for (int G2 : {2350, 2800}) {
+        const int nwin = G2 * 4 * 2;
+        const int nwork = G2 * 4 / 100;   // 1 % of the waves of the WPW-2 grid, in every setting
+        for (int wpw : {2, 4}) {
+            const int G = G2 * 2 / wpw;
+            const int tw = G * 4;
+            for (int pc = 0; pc < 5; ++pc) {   // no working wave; front and back at each chain length
+                const int place = pc == 0 ? 0 : 1 + (pc - 1) % 2;
+                const int chain = pc < 3 ? 5 : 20;
+                CK(hipMemset(flags, 0, (size_t)NWIN * 64));
+                // a working wave's first window is flagged: windows [0, nwork) are the first
+                // windows of the grid's first waves, [tw − nwork, tw) of its last
+                if (place == 1) CK(hipMemset(flags, 1, (size_t)nwork * 64));
+                if (place == 2) CK(hipMemset(flags + (size_t)(tw - nwork) * 64, 1, (size_t)nwork * 64));
+                const char* pn = place == 0 ? "none" : place == 1 ? "front" : "back";
+                const int nw = place ? nwork : 0;
+#define OCC_RUN(NV, W) if (occ_setting<NV, W>(pn, G, nwin, nw, flags, table, chain, out, a, b, first)) return 1
+                if (wpw == 2) {
+                    OCC_RUN(64, 2);
+                    OCC_RUN(96, 2);
+                    OCC_RUN(116, 2);
+                } else {
+                    OCC_RUN(64, 4);
+                    OCC_RUN(96, 4);
+                    OCC_RUN(116, 4);
+                }
+#undef OCC_RUN
+            }
+        }
+    }
+    std::printf("\n], \"cus\": %d}\n", ncu);
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc > 1 && std::string(argv[1]) == "occupancy") return occupancy_mode();
     unsigned char *flags, *out;
     unsigned* sync;
     unsigned long long* tout;
