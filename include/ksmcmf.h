@@ -918,6 +918,17 @@ typedef struct ks_grow_stats {        /* 96 B */
  *     unlisted KS_RES_EXTRA arc into a chain node likewise. ks_complete_tasks(k = 0,
  *     KS_COMPLETE_RESOURCE_CAPS[ | KS_COMPLETE_PREEMPTIVE]) repairs both (arcs that fell to 0
  *     first re-created by the pinned recipe).
+ *   - A held capacity that was not the rule's value is raised all the same. The capacity rule
+ *     of the commits, ks_remove_resources and ks_complete_tasks treats a type-0 head (a rack)
+ *     as a resource only while slots_below[v] > 0: once the last machine beneath a rack has
+ *     left (or, under slots − running, the rack's only machine with a free slot has), the arc
+ *     into the rack KEEPS the capacity it had, which no flow can use. A machine that later
+ *     joins beneath that rack with the chain listed gets old + S(v) on that arc, S(v) being
+ *     the right value. The surplus admits no flow (the arcs beneath carry S(v)), but the
+ *     capacity is not the rule's any more: a round that adds resources beneath racks that may
+ *     have been emptied or filled follows ks_add_resources with the same refresh,
+ *     ks_complete_tasks(k = 0, KS_COMPLETE_RESOURCE_CAPS[ | KS_COMPLETE_PREEMPTIVE]), which
+ *     sets it (tests/round_ref.py does so after every call with an edge).
  *   - flags must be 0 (reserved); anything else is KS_E_INVALID.
  * Needs no previous solve, no residual CSR and no BFS. n == 0 && m == 0 does nothing and
  * keeps the solution, as does a call that generates no record. Success with a record

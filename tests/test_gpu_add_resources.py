@@ -237,6 +237,29 @@ def test_toy(state):
             assert after.table[(3, 5)] == (0, 1, 9, 0)
 
 
+@pytest.mark.parametrize("state", ["fresh", "preemptive"])
+def test_a_machine_under_a_rack_that_a_removal_emptied(state):
+    """The capacity rule takes a type-0 head for a resource only while slots lie beneath it: when a
+    rack's last machine leaves, the arc into the rack keeps the capacity it had (no flow can use
+    it), and the machine that joins later raises that value instead of starting from 0. The
+    refresh sets it: the recipe of include/ksmcmf.h (ks_add_resources) that the round test
+    (tests/test_gpu_rounds.py) showed to be needed."""
+    spec = Cluster(2, 1, 3, [1, 1] + [None] * 2)
+    with open_ctx(state) as ctx:
+        pre = bring(ctx, spec, state)
+        mach, pu = spec.M0, spec.P0
+        removed, _, _ = ctx.remove_resources([mach], resource_caps=True, preemptive=pre)
+        assert removed.tolist() == [mach, pu]
+        assert Snapshot(ctx).table[(spec.X, spec.R0)] == (0, 3, 0, 0)   # kept, with nothing beneath it
+        nodes = [(mach, 4, 0, 0), (pu, 2, 2, 0)]
+        edges = [(spec.R0, mach, 0, TREE), (mach, pu, 0, TREE), (spec.X, spec.R0, 0, TREE)]
+        ref, after, _ = grow_and_check(ctx, nodes, edges, pre, state, solve=False, full_chain=False)
+        assert after.table[(spec.X, spec.R0)] == (0, 5, 0, 0)           # raised from the stale 3
+        assert refresh(ctx, pre) == 1
+        assert Snapshot(ctx).table[(spec.X, spec.R0)] == (0, 2, 0, 0)
+        resolve_and_check(ctx)
+
+
 # ------------------------------------------------------------------ id reuse ---
 @pytest.mark.parametrize("state", ["fresh", "pinned", "preemptive"])
 def test_ids_freed_by_remove_resources_are_reused(state):
