@@ -538,6 +538,12 @@ int ensure_hash(EngineImpl& s, int64_t extra, std::string& err);
 int applied(EngineImpl& s, std::string& err);
 // the cells a record stream (device memory) touches, before it reaches store_apply
 int mark_cells(EngineImpl& s, const ks_delta* recs, size_t k, const NodeEdit* edits, size_t ne, std::string& err);
+// the tail of a record stream generated on the device: room for nrec records in
+// d_recs / rec_ent and nedits node edits in d_edits; then, the records emitted, the stream's way
+// into the store
+int size_stream(EngineImpl& s, int64_t nrec, size_t nedits, std::string& err);
+int apply_stream(EngineImpl& s, int64_t nrec, const std::vector<NodeEdit>& edits, bool arc_recs, std::string& err,
+                 hipEvent_t applied_ev = nullptr);
 
 inline double ev_ms(hipEvent_t a, hipEvent_t b) {
     float ms = 0.f;

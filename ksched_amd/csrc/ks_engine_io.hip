@@ -304,6 +304,38 @@ int impl::applied(EngineImpl& s, std::string& err) {
     return KS_OK;
 }
 
+// Room for a stream generated on the device: nrec records and nedits node edits (no buffer
+// below one element: store_apply takes the pointers of an empty stream too).
+int impl::size_stream(EngineImpl& s, int64_t nrec, size_t nedits, std::string& err) {
+    KS_CHECK(s.d_recs.ensure(std::max<size_t>(nrec, 1)));
+    KS_CHECK(s.rec_ent.ensure(std::max<size_t>(nrec, 1)));
+    KS_CHECK(s.d_edits.ensure(std::max<size_t>(nedits, 1)));
+    return KS_OK;
+}
+
+// The nrec records a scheduler call emitted into d_recs reach the store: the host's node edits
+// go up, the stream's cells are marked on the device (the records exist only there), store_apply
+// runs, and ONE sync brings the store's counters. A failure in here leaves the device state
+// unknown. arc_recs: the stream held arc records (costs or capacities changed, as in run_apply).
+// applied_ev: recorded behind store_apply, before the sync (the commit's device span).
+int impl::apply_stream(EngineImpl& s, int64_t nrec, const std::vector<NodeEdit>& edits, bool arc_recs,
+                       std::string& err, hipEvent_t applied_ev) {
+    hipStream_t st = s.stream;
+    if (!edits.empty())
+        KS_CHECK(hipMemcpyAsync(s.d_edits.p, edits.data(), edits.size() * sizeof(NodeEdit), hipMemcpyHostToDevice, st));
+    int rc = mark_cells(s, s.d_recs.p, (size_t)nrec, s.d_edits.p, edits.size(), err);
+    if (rc) return rc;
+    KS_CHECK(store_apply(s.sd(), s.d_recs.p, (int)nrec, s.rec_ent.p, s.d_edits.p, (int)edits.size(), st));
+    if (applied_ev) KS_CHECK(hipEventRecord(applied_ev, st));
+    rc = read_sctl(s, err);
+    if (rc == KS_OK) rc = applied(s, err);
+    if (rc) return rc;
+    s.incremental = true;
+    s.solved = false;
+    if (arc_recs && s.cell_refused_values) s.cell_refused = s.cell_refused_values = false;   // (as run_apply)
+    return KS_OK;
+}
+
 static int run_apply(EngineImpl& s, const NodeEdit* edits, size_t ne, const ks_delta* recs, size_t k,
                      std::string& err) {
     hipStream_t st = s.stream;

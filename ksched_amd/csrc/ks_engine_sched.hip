@@ -45,6 +45,87 @@ struct Carve {
     }
 };
 
+// The scratch of a delta call (the commit's buffers): carve(ci, cu), the call's own part, takes its
+// int arrays from cm_i and its u64 arrays from cm_u; it runs twice, to size and to hand out.
+// cm_i starts zeroed, cm_u in its first zero_u words (kAllU64: all of it), and with flags the
+// flag bytes per node slot, cm_b, too.
+constexpr int64_t kAllU64 = -1;
+template <class F>
+int carve_scratch(EngineImpl& s, F&& carve, int64_t zero_u, bool flags, std::string& err) {
+    hipStream_t st = s.stream;
+    Carve<int> ci{nullptr};
+    Carve<unsigned long long> cu{nullptr};
+    carve(ci, cu);
+    const int64_t n_i = ci.n, n_u = cu.n;
+    const int64_t nb = (s.nstore + 4) & ~3LL;   // byte flags, word-aligned for the atomics
+    KS_CHECK(s.cm_i.ensure(n_i));
+    KS_CHECK(s.cm_u.ensure(n_u));
+    if (flags) KS_CHECK(s.cm_b.ensure(nb));
+    ci = {s.cm_i.p};
+    cu = {s.cm_u.p};
+    carve(ci, cu);
+    KS_CHECK(hipMemsetAsync(s.cm_i.p, 0, n_i * sizeof(int), st));
+    KS_CHECK(hipMemsetAsync(s.cm_u.p, 0, (zero_u == kAllU64 ? n_u : zero_u) * 8, st));
+    if (flags) KS_CHECK(hipMemsetAsync(s.cm_b.p, 0, nb, st));
+    return KS_OK;
+}
+
+// A call's control word, zeroed on st.
+template <typename C>
+hipError_t clear_ctl(DBuf<C>& ctl, hipStream_t st) {
+    const hipError_t e = ctl.ensure(1);
+    return e == hipSuccess ? hipMemsetAsync(ctl.p, 0, sizeof(C), st) : e;
+}
+
+// The store's (src, dst) index as a call's kernels read it.
+template <typename Dev>
+void wire_hash(const EngineImpl& s, Dev& d) {
+    d.hkey = s.hkey.p;
+    d.hval = s.hval.p;
+    d.hmask = s.hcap ? (int)(s.hcap - 1) : -1;
+}
+
+// A stale residual CSR is rebuilt from the table (the solution in place goes with it).
+int fresh_csr(EngineImpl& s, std::string& err) {
+    if (s.csr_valid) return KS_OK;
+    const int rc = build(s, err);
+    if (rc) return rc;
+    s.has_prev = false;
+    s.solved = false;
+    return KS_OK;
+}
+
+int check_agg_ids(const EngineImpl& s, const uint64_t* ids, size_t k, std::string& err) {
+    for (size_t i = 0; ids && i < k; ++i)
+        if (ids[i] == 0 || (int64_t)ids[i] > s.nstore) {
+            err = "unscheduled aggregator id beyond the graph";
+            return KS_E_INVALID;
+        }
+    return KS_OK;
+}
+
+// The capacity passes climb from one sink, or, over a cell partition, from every cell's own.
+int check_one_sink(const EngineImpl& s, bool caps, int64_t sink_slot, std::string& err) {
+    const bool every_sink = sink_slot == Engine::kEverySink && s.cell_off.size() >= 2;
+    if (caps && !every_sink && (sink_slot < 0 || sink_slot >= s.ncap)) {
+        err = "resource capacities need exactly one sink";
+        return KS_E_INVALID;
+    }
+    return KS_OK;
+}
+
+// A refusal's control word holds count − index of the first offender in input order (the kernels
+// keep the largest), 0 when there is none: → its index, n for none; false: no such word.
+bool first_bad(int word, size_t n, size_t* idx) {
+    if (word < 0 || (size_t)word > n) return false;
+    *idx = n - (size_t)word;
+    return true;
+}
+
+double ms(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
+    return std::chrono::duration<double, std::milli>(b - a).count();
+}
+
 // Level 0 of the topology BFS over a cell partition: every live sink, one per cell. A
 // union's sinks are few (one per graph) and far apart in slot space, so each is its
 // own returning atomic on the frontier's counter (nothing to aggregate per wave). With
@@ -151,11 +232,7 @@ int Engine::unsched_costs(const uint64_t* ids, size_t k, int mode, int64_t ucost
     KS_CHECK(hipMemsetAsync(s.sched_i.p, 0, sizeof(int), st));
     const unsigned long long* dids = nullptr;
     if (ids && k) {
-        for (size_t i = 0; i < k; ++i)
-            if (ids[i] == 0 || (int64_t)ids[i] > s.nstore) {
-                err = "unscheduled aggregator id beyond the graph";
-                return KS_E_INVALID;
-            }
+        if (int rc = check_agg_ids(s, ids, k, err)) return rc;
         KS_CHECK(s.sched_u.ensure(k));
         KS_CHECK(hipMemcpyAsync(s.sched_u.p, ids, k * 8, hipMemcpyHostToDevice, st));
         dids = s.sched_u.p;
@@ -219,12 +296,7 @@ int Engine::topology_stats(uint64_t mtpp, const uint64_t* pu_ids, const uint64_t
     EngineImpl& s = *p_;
     KS_CHECK(hipSetDevice(s.device));
     hipStream_t st = s.stream;
-    if (!s.csr_valid) {   // the BFS walks the residual CSR's in-arcs
-        int rc = build(s, err);
-        if (rc) return rc;
-        s.has_prev = false;
-        s.solved = false;
-    }
+    if (int rc = fresh_csr(s, err)) return rc;   // the BFS walks the residual CSR's in-arcs
     const int64_t ncap = s.ncap;
     if (sink_slot < 0 || sink_slot >= ncap || ncap == 0) {
         std::memset(slots_below, 0, s.nslots * sizeof(uint64_t));
@@ -307,15 +379,12 @@ int Engine::commit(bool preempt, int flags, int64_t ccost, int64_t pcost, const 
     c.pcost = pcost;
     c.np = (int)np;
     c.ni_max = (int)(np + s.m2cap / 64 + 1);
-    const bool every_sink = sink_slot == kEverySink && s.cell_off.size() >= 2;   // a partition: one sink per cell
-    if (c.resource_caps && !every_sink && (sink_slot < 0 || sink_slot >= ncap)) {
-        err = "resource capacities need exactly one sink";
-        return KS_E_INVALID;
-    }
+    rc = check_one_sink(s, c.resource_caps, sink_slot, err);
+    if (rc) return rc;
     // scratch: int arrays per item, chunk item and arc slot in cm_i; counters per node slot
     // and the aggregator ids in cm_u; flags per node slot in cm_b
     unsigned long long* idbuf = nullptr;
-    auto carve = [&](Carve<int> ci, Carve<unsigned long long> cu) {
+    rc = carve_scratch(s, [&](Carve<int>& ci, Carve<unsigned long long>& cu) {
         for (int** a : {&c.pl_task, &c.pl_kind, &c.pl_pu, &c.pl_old, &c.pl_has, &c.pl_found, &c.pl_noarc, &c.add_off,
                         &c.nch, &c.ch_off})
             *a = ci.take(np + 1);
@@ -323,29 +392,14 @@ int Engine::commit(bool preempt, int flags, int64_t ccost, int64_t pcost, const 
         for (int** a : {&c.aflag, &c.a_off}) *a = ci.take((int64_t)hi + 1);
         for (unsigned long long** a : {&c.agg_cnt, &c.pu_slots, &c.pu_run, &c.slots, &c.running}) *a = cu.take(nst + 1);
         idbuf = cu.take(k);
-        return std::make_pair(ci.n, cu.n);
-    };
-    const auto [n_i, n_u] = carve({nullptr}, {nullptr});
-    const int64_t nb = (nst + 4) & ~3LL;
-    KS_CHECK(s.cm_i.ensure(n_i));
-    KS_CHECK(s.cm_u.ensure(n_u));
-    KS_CHECK(s.cm_b.ensure(nb));
-    KS_CHECK(s.cm_ctl.ensure(1));
-    carve({s.cm_i.p}, {s.cm_u.p});
+    }, kAllU64, true, err);
+    if (rc) return rc;
+    KS_CHECK(clear_ctl(s.cm_ctl, st));
     c.fl = s.cm_b.p;
     c.ctl = s.cm_ctl.p;
-    KS_CHECK(hipMemsetAsync(s.cm_i.p, 0, n_i * sizeof(int), st));
-    KS_CHECK(hipMemsetAsync(s.cm_u.p, 0, n_u * 8, st));
-    KS_CHECK(hipMemsetAsync(s.cm_b.p, 0, nb, st));
-    KS_CHECK(hipMemsetAsync(s.cm_ctl.p, 0, sizeof(CommitCtl), st));
-    if (ids) {
-        for (size_t i = 0; i < k; ++i)
-            if (ids[i] == 0 || (int64_t)ids[i] > nst) {
-                err = "unscheduled aggregator id beyond the graph";
-                return KS_E_INVALID;
-            }
-        if (k) KS_CHECK(hipMemcpyAsync(idbuf, ids, k * 8, hipMemcpyHostToDevice, st));
-    }
+    rc = check_agg_ids(s, ids, k, err);
+    if (rc) return rc;
+    if (ids && k) KS_CHECK(hipMemcpyAsync(idbuf, ids, k * 8, hipMemcpyHostToDevice, st));
     const unsigned long long* dids = ids ? idbuf : nullptr;
     SchedDev d = s.schd();
     {   // the kinds of sched_deltas: [pre | other | pre_pos | other_pos] × (ncap + 1)
@@ -388,31 +442,21 @@ int Engine::commit(bool preempt, int flags, int64_t ccost, int64_t pcost, const 
     }
     rc = ensure_arcs(s, (int64_t)hi + h.rec_add, err);   // the only new arcs: one running arc per placed task
     if (rc == KS_OK) rc = ensure_hash(s, h.rec_add, err);
+    if (rc == KS_OK) rc = size_stream(s, nrec, 0, err);
     if (rc) return rc;
-    KS_CHECK(s.d_recs.ensure(std::max<size_t>(nrec, 1)));
-    KS_CHECK(s.rec_ent.ensure(std::max<size_t>(nrec, 1)));
-    KS_CHECK(s.d_edits.ensure(1));
     d = s.schd();   // (the arc table may have moved)
     *dirty = true;
     KS_CHECK(sched_commit_emit(d, c, s.d_recs.p, st));
-    // the records exist only here, in HBM: their cells are marked on the device
-    rc = mark_cells(s, s.d_recs.p, (size_t)nrec, nullptr, 0, err);
-    if (rc) return rc;
-    KS_CHECK(store_apply(s.sd(), s.d_recs.p, (int)nrec, s.rec_ent.p, s.d_edits.p, 0, st));
-    if (log) KS_CHECK(hipEventRecord(s.kev[1], st));
-    rc = read_sctl(s, err);
-    if (rc == KS_OK) rc = applied(s, err);
+    // (arc_recs false although most records are UPDATE_ARC: the commit never reset cell_refused)
+    rc = apply_stream(s, nrec, {}, false, err, log ? s.kev[1] : nullptr);
     if (rc) return rc;
     if (log) {
         const auto t3 = std::chrono::steady_clock::now();
-        auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
         std::fprintf(stderr,
                      "commit: %lld records, deltas %.3f ms, count passes %.3f ms, emit + apply %.3f ms, "
                      "device span after the deltas %.3f ms\n",
                      (long long)nrec, ms(t0, t1), ms(t1, t2), ms(t2, t3), ev_ms(s.kev[0], s.kev[1]));
     }
-    s.incremental = true;
-    s.solved = false;
     return KS_OK;
 }
 
@@ -470,22 +514,15 @@ int Engine::remove_resources(int flags, const uint64_t* roots, size_t k, int64_t
     *nremoved = *nevicted = 0;
     KS_CHECK(hipSetDevice(s.device));
     hipStream_t st = s.stream;
-    if (!s.csr_valid) {   // the descent and the BFS walk the residual CSR
-        int rc = build(s, err);
-        if (rc) return rc;
-        s.has_prev = false;
-        s.solved = false;
-    }
+    int rc = fresh_csr(s, err);   // the descent and the BFS walk the residual CSR
+    if (rc) return rc;
     const bool log = s.opts.log_cycles != 0;
     const auto t0 = std::chrono::steady_clock::now();
     const bool caps = (flags & KS_REMOVE_RESOURCE_CAPS) != 0;
     const int64_t ncap = s.ncap, nst = s.nstore;
     const int hi = s.hi();
-    const bool every_sink = sink_slot == kEverySink && s.cell_off.size() >= 2;
-    if (caps && !every_sink && (sink_slot < 0 || sink_slot >= ncap)) {
-        err = "resource capacities need exactly one sink";
-        return KS_E_INVALID;
-    }
+    rc = check_one_sink(s, caps, sink_slot, err);
+    if (rc) return rc;
     if (k > (size_t)INT32_MAX) {
         err = "too many roots";
         return KS_E_RANGE;
@@ -497,31 +534,20 @@ int Engine::remove_resources(int flags, const uint64_t* roots, size_t k, int64_t
     RemoveDev r{};
     r.k = (int)k;
     unsigned long long *d_roots = nullptr, *d_ids = nullptr;
-    auto carve = [&](Carve<int> ci, Carve<unsigned long long> cu) {
+    rc = carve_scratch(s, [&](Carve<int>& ci, Carve<unsigned long long>& cu) {
         for (int** a : {&r.front, &r.next, &r.nch, &r.ch_off, &r.rm, &r.rm_pos, &r.ev, &r.ev_pos}) *a = ci.take(ncap + 1);
         for (int** a : {&c.aflag, &c.a_off}) *a = ci.take((int64_t)hi + 1);
         for (unsigned long long** a : {&c.agg_cnt, &c.pu_slots, &c.pu_run, &c.slots, &c.running}) *a = cu.take(nst + 1);
         d_roots = cu.take(k);
         d_ids = cu.take(ncap + 1);
-        return std::make_pair(ci.n, cu.n);
-    };
-    const auto [n_i, n_u] = carve({nullptr}, {nullptr});
-    const int64_t nb = (nst + 4) & ~3LL;
-    KS_CHECK(s.cm_i.ensure(n_i));
-    KS_CHECK(s.cm_u.ensure(n_u));
-    KS_CHECK(s.cm_b.ensure(nb));
-    KS_CHECK(s.cm_ctl.ensure(1));
-    KS_CHECK(s.rm_ctl.ensure(1));
-    carve({s.cm_i.p}, {s.cm_u.p});
+    }, kAllU64, true, err);
+    if (rc) return rc;
+    KS_CHECK(clear_ctl(s.cm_ctl, st));
+    KS_CHECK(clear_ctl(s.rm_ctl, st));
     c.fl = r.fl = s.cm_b.p;
     c.ctl = s.cm_ctl.p;
     r.ctl = s.rm_ctl.p;
     r.roots = d_roots;
-    KS_CHECK(hipMemsetAsync(s.cm_i.p, 0, n_i * sizeof(int), st));
-    KS_CHECK(hipMemsetAsync(s.cm_u.p, 0, n_u * 8, st));
-    KS_CHECK(hipMemsetAsync(s.cm_b.p, 0, nb, st));
-    KS_CHECK(hipMemsetAsync(s.cm_ctl.p, 0, sizeof(CommitCtl), st));
-    KS_CHECK(hipMemsetAsync(s.rm_ctl.p, 0, sizeof(RemoveCtl), st));
     if (k) KS_CHECK(hipMemcpyAsync(d_roots, roots, k * 8, hipMemcpyHostToDevice, st));
     SchedDev d = s.schd();
     RemoveCtl h{};
@@ -561,7 +587,7 @@ int Engine::remove_resources(int flags, const uint64_t* roots, size_t k, int64_t
     if (caps) {
         KS_CHECK(sched_commit_pu(d, c, st));
         KS_CHECK(sched_remove_zero_pus(d, r, c, st));
-        int rc = topo_bfs(s, d, sink_slot, 0, c.pu_slots, c.pu_run, c.slots, c.running, err);
+        rc = topo_bfs(s, d, sink_slot, 0, c.pu_slots, c.pu_run, c.slots, c.running, err);
         if (rc) return rc;
         KS_CHECK(sched_commit_arc_flags(d, c, st));
         KS_CHECK(exclusive_sum(s, (const int*)c.aflag, c.a_off, (int64_t)hi + 1, st));
@@ -588,9 +614,8 @@ int Engine::remove_resources(int flags, const uint64_t* roots, size_t k, int64_t
         return KS_E_VERIFY;
     }
     const int64_t nrec = (int64_t)h.nremoved + h.rec_arc;
-    KS_CHECK(s.d_recs.ensure(std::max<size_t>(nrec, 1)));
-    KS_CHECK(s.rec_ent.ensure(std::max<size_t>(nrec, 1)));
-    KS_CHECK(s.d_edits.ensure(std::max<size_t>(h.nremoved, 1)));
+    rc = size_stream(s, nrec, (size_t)h.nremoved, err);
+    if (rc) return rc;
     KS_CHECK(s.sched_d.ensure(std::max(1, h.nevicted)));
     KS_CHECK(sched_remove_emit_nodes(d, r, d_ids, s.d_recs.p, st));
     removed->resize(h.nremoved);
@@ -599,35 +624,25 @@ int Engine::remove_resources(int flags, const uint64_t* roots, size_t k, int64_t
     // the host's node table follows (and names an id it does not know as alive); from here
     // on a failure leaves the device state unknown
     std::vector<NodeEdit> edits;
-    int rc = make_edits(removed->data(), removed->size(), &edits, err);
+    rc = make_edits(removed->data(), removed->size(), &edits, err);
     if (rc) return rc;
     *dirty = true;
-    if (!edits.empty())
-        KS_CHECK(hipMemcpyAsync(s.d_edits.p, edits.data(), edits.size() * sizeof(NodeEdit), hipMemcpyHostToDevice, st));
     KS_CHECK(sched_remove_emit_evictions(d, r, s.sched_d.p, st));
     if (caps) KS_CHECK(sched_commit_emit(d, c, s.d_recs.p, st));
-    rc = mark_cells(s, s.d_recs.p, (size_t)nrec, s.d_edits.p, edits.size(), err);
-    if (rc) return rc;
-    KS_CHECK(store_apply(s.sd(), s.d_recs.p, (int)nrec, s.rec_ent.p, s.d_edits.p, (int)edits.size(), st));
-    evicted->resize(h.nevicted);
+    evicted->resize(h.nevicted);   // (on the stream before the tail's sync)
     if (h.nevicted)
         KS_CHECK(hipMemcpyAsync(evicted->data(), s.sched_d.p, h.nevicted * sizeof(ks_sched_delta), hipMemcpyDeviceToHost,
                                 st));
-    rc = read_sctl(s, err);
-    if (rc == KS_OK) rc = applied(s, err);
+    rc = apply_stream(s, nrec, edits, h.rec_arc != 0, err);
     if (rc) return rc;
     if (log) {
         const auto t4 = std::chrono::steady_clock::now();
-        auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
         std::fprintf(stderr,
                      "remove: %lld nodes, %lld evictions, %lld records, %d levels, mark %.3f ms, evict %.3f ms, "
                      "caps %.3f ms, emit + apply %.3f ms\n",
                      (long long)h.nremoved, (long long)h.nevicted, (long long)nrec, levels, ms(t0, t1), ms(t1, t2),
                      ms(t2, t3), ms(t3, t4));
     }
-    s.incremental = true;
-    s.solved = false;
-    if (h.rec_arc && s.cell_refused_values) s.cell_refused = s.cell_refused_values = false;   // (as run_apply)
     if (stats) {
         std::memset(stats, 0, sizeof(*stats));
         stats->roots = nroots;
@@ -657,30 +672,20 @@ int Engine::complete_tasks(int flags, const uint64_t* tasks, size_t k, const uin
     if (!k && !caps) return KS_OK;
     KS_CHECK(hipSetDevice(s.device));
     hipStream_t st = s.stream;
-    if (!s.csr_valid) {   // the chunk items and the BFS walk the residual CSR
-        int rc = build(s, err);
-        if (rc) return rc;
-        s.has_prev = false;
-        s.solved = false;
-    }
+    int rc = fresh_csr(s, err);   // the chunk items and the BFS walk the residual CSR
+    if (rc) return rc;
     const bool log = s.opts.log_cycles != 0;
     const auto t0 = std::chrono::steady_clock::now();
     const int64_t ncap = s.ncap, nst = s.nstore;
     const int hi = s.hi();
-    const bool every_sink = sink_slot == kEverySink && s.cell_off.size() >= 2;
-    if (caps && !every_sink && (sink_slot < 0 || sink_slot >= ncap)) {
-        err = "resource capacities need exactly one sink";
-        return KS_E_INVALID;
-    }
+    rc = check_one_sink(s, caps, sink_slot, err);
+    if (rc) return rc;
     if (k > (size_t)INT32_MAX || nu > (size_t)INT32_MAX) {
         err = "too many ids";
         return KS_E_RANGE;
     }
-    for (size_t i = 0; unsched_ids && i < nu; ++i)
-        if (unsched_ids[i] == 0 || (int64_t)unsched_ids[i] > nst) {
-            err = "unscheduled aggregator id beyond the graph";
-            return KS_E_INVALID;
-        }
+    rc = check_agg_ids(s, unsched_ids, nu, err);
+    if (rc) return rc;
     CommitDev c{};
     c.preempt = (flags & KS_COMPLETE_PREEMPTIVE) ? 1 : 0;
     c.resource_caps = caps ? 1 : 0;
@@ -689,7 +694,7 @@ int Engine::complete_tasks(int flags, const uint64_t* tasks, size_t k, const uin
     RemoveDev r{};
     r.k = (int)k;
     unsigned long long *d_tasks = nullptr, *d_left = nullptr, *d_agg = nullptr, *d_ids = nullptr;
-    auto carve = [&](Carve<int> ci, Carve<unsigned long long> cu) {
+    rc = carve_scratch(s, [&](Carve<int>& ci, Carve<unsigned long long>& cu) {
         for (int** a : {&r.front, &r.next, &r.nch, &r.ch_off, &r.rm, &r.rm_pos, &r.ev, &r.ev_pos}) *a = ci.take(ncap + 1);
         for (int** a : {&c.aflag, &c.a_off}) *a = ci.take((int64_t)hi + 1);
         for (unsigned long long** a : {&c.agg_cnt, &c.pu_slots, &c.pu_run, &c.slots, &c.running}) *a = cu.take(nst + 1);
@@ -697,25 +702,14 @@ int Engine::complete_tasks(int flags, const uint64_t* tasks, size_t k, const uin
         d_left = cu.take(k);
         d_agg = cu.take(nu);
         d_ids = cu.take(ncap + 1);
-        return std::make_pair(ci.n, cu.n);
-    };
-    const auto [n_i, n_u] = carve({nullptr}, {nullptr});
-    const int64_t nb = (nst + 4) & ~3LL;
-    KS_CHECK(s.cm_i.ensure(n_i));
-    KS_CHECK(s.cm_u.ensure(n_u));
-    KS_CHECK(s.cm_b.ensure(nb));
-    KS_CHECK(s.cm_ctl.ensure(1));
-    KS_CHECK(s.rm_ctl.ensure(1));
-    carve({s.cm_i.p}, {s.cm_u.p});
+    }, kAllU64, true, err);
+    if (rc) return rc;
+    KS_CHECK(clear_ctl(s.cm_ctl, st));
+    KS_CHECK(clear_ctl(s.rm_ctl, st));
     c.fl = r.fl = s.cm_b.p;
     c.ctl = s.cm_ctl.p;
     r.ctl = s.rm_ctl.p;
     r.roots = d_tasks;
-    KS_CHECK(hipMemsetAsync(s.cm_i.p, 0, n_i * sizeof(int), st));
-    KS_CHECK(hipMemsetAsync(s.cm_u.p, 0, n_u * 8, st));
-    KS_CHECK(hipMemsetAsync(s.cm_b.p, 0, nb, st));
-    KS_CHECK(hipMemsetAsync(s.cm_ctl.p, 0, sizeof(CommitCtl), st));
-    KS_CHECK(hipMemsetAsync(s.rm_ctl.p, 0, sizeof(RemoveCtl), st));
     if (k) KS_CHECK(hipMemcpyAsync(d_tasks, tasks, k * 8, hipMemcpyHostToDevice, st));
     if (unsched_ids && nu) KS_CHECK(hipMemcpyAsync(d_agg, unsched_ids, nu * 8, hipMemcpyHostToDevice, st));
     SchedDev d = s.schd();
@@ -756,7 +750,7 @@ int Engine::complete_tasks(int flags, const uint64_t* tasks, size_t k, const uin
     // ---- 3. the capacities over the graph without the completed tasks
     if (caps) {
         KS_CHECK(sched_commit_pu(d, c, st));
-        int rc = topo_bfs(s, d, sink_slot, 0, c.pu_slots, c.pu_run, c.slots, c.running, err);
+        rc = topo_bfs(s, d, sink_slot, 0, c.pu_slots, c.pu_run, c.slots, c.running, err);
         if (rc) return rc;
     }
     KS_CHECK(sched_commit_arc_flags(d, c, st));
@@ -779,9 +773,8 @@ int Engine::complete_tasks(int flags, const uint64_t* tasks, size_t k, const uin
     const int64_t nrec = (int64_t)np + h.rec_arc;
     if (left && k) std::memcpy(left, h_left.data(), k * 8);
     if (!nrec) return KS_OK;   // (k == 0 and every capacity stands: the solution stays valid)
-    KS_CHECK(s.d_recs.ensure(std::max<size_t>(nrec, 1)));
-    KS_CHECK(s.rec_ent.ensure(std::max<size_t>(nrec, 1)));
-    KS_CHECK(s.d_edits.ensure(std::max<size_t>(np, 1)));
+    rc = size_stream(s, nrec, (size_t)np, err);
+    if (rc) return rc;
     KS_CHECK(sched_remove_emit_nodes(d, r, d_ids, s.d_recs.p, st));
     std::vector<uint64_t> ids(np);
     if (np) KS_CHECK(hipMemcpyAsync(ids.data(), d_ids, (size_t)np * 8, hipMemcpyDeviceToHost, st));
@@ -789,29 +782,19 @@ int Engine::complete_tasks(int flags, const uint64_t* tasks, size_t k, const uin
     // the host's node table follows (and names an id it does not hold as a live task); from
     // here on a failure leaves the device state unknown
     std::vector<NodeEdit> edits;
-    int rc = make_edits(ids.data(), ids.size(), &edits, err);
+    rc = make_edits(ids.data(), ids.size(), &edits, err);
     if (rc) return rc;
     *dirty = true;
-    if (!edits.empty())
-        KS_CHECK(hipMemcpyAsync(s.d_edits.p, edits.data(), edits.size() * sizeof(NodeEdit), hipMemcpyHostToDevice, st));
     KS_CHECK(sched_commit_emit(d, c, s.d_recs.p, st));
-    rc = mark_cells(s, s.d_recs.p, (size_t)nrec, s.d_edits.p, edits.size(), err);
-    if (rc) return rc;
-    KS_CHECK(store_apply(s.sd(), s.d_recs.p, (int)nrec, s.rec_ent.p, s.d_edits.p, (int)edits.size(), st));
-    rc = read_sctl(s, err);
-    if (rc == KS_OK) rc = applied(s, err);
+    rc = apply_stream(s, nrec, edits, h.rec_arc != 0, err);
     if (rc) return rc;
     if (log) {
         const auto t4 = std::chrono::steady_clock::now();
-        auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
         std::fprintf(stderr,
                      "complete: %d tasks, %lld records, seed %.3f ms, aggregator counts %.3f ms, caps %.3f ms, "
                      "emit + apply %.3f ms\n",
                      np, (long long)nrec, ms(t0, t1), ms(t1, t2), ms(t2, t3), ms(t3, t4));
     }
-    s.incremental = true;
-    s.solved = false;
-    if (h.rec_arc && s.cell_refused_values) s.cell_refused = s.cell_refused_values = false;   // (as run_apply)
     *changed = true;
     if (stats) {
         stats->tasks = np;
@@ -848,11 +831,8 @@ int Engine::add_tasks(const uint64_t* tasks, size_t k, const uint64_t* arc_off, 
         err = "too many tasks, arcs or aggregator ids";
         return KS_E_RANGE;
     }
-    for (size_t i = 0; unsched_ids && i < nu; ++i)
-        if (unsched_ids[i] == 0 || (int64_t)unsched_ids[i] > nst) {
-            err = "unscheduled aggregator id beyond the graph";
-            return KS_E_INVALID;
-        }
+    int rc = check_agg_ids(s, unsched_ids, nu, err);
+    if (rc) return rc;
     AddDev a{};
     a.k = (int)k;
     a.na = (int)na;
@@ -861,7 +841,7 @@ int Engine::add_tasks(const uint64_t* tasks, size_t k, const uint64_t* arc_off, 
     a.sink = sink_slot >= 0 && sink_slot < nst ? sink_slot : -1;
     a.sink_cost = sink_cost;
     unsigned long long *d_tasks = nullptr, *d_off = nullptr, *d_arcs = nullptr, *d_agg = nullptr;
-    auto carve = [&](Carve<int> ci, Carve<unsigned long long> cu) {
+    rc = carve_scratch(s, [&](Carve<int>& ci, Carve<unsigned long long>& cu) {
         a.t_agg = ci.take((int64_t)k + 1);
         for (int** x : {&a.aflag, &a.a_off, &a.a_slot}) *x = ci.take(nst + 1);
         a.agg_cnt = cu.take(nst + 1);   // (first: the only u64 array that starts zeroed)
@@ -869,27 +849,15 @@ int Engine::add_tasks(const uint64_t* tasks, size_t k, const uint64_t* arc_off, 
         d_off = cu.take(k + 1);
         d_arcs = cu.take(2 * na);
         d_agg = cu.take(nu);
-        return std::make_pair(ci.n, cu.n);
-    };
-    const auto [n_i, n_u] = carve({nullptr}, {nullptr});
-    const int64_t nb = (nst + 4) & ~3LL;
-    KS_CHECK(s.cm_i.ensure(n_i));
-    KS_CHECK(s.cm_u.ensure(n_u));
-    KS_CHECK(s.cm_b.ensure(nb));
-    KS_CHECK(s.add_ctl.ensure(1));
-    carve({s.cm_i.p}, {s.cm_u.p});
+    }, nst + 1, true, err);
+    if (rc) return rc;
+    KS_CHECK(clear_ctl(s.add_ctl, st));
     a.fl = s.cm_b.p;
     a.ctl = s.add_ctl.p;
     a.tasks = d_tasks;
     a.arc_off = d_off;
     a.arcs = (const ks_task_arc*)d_arcs;
-    a.hkey = s.hkey.p;
-    a.hval = s.hval.p;
-    a.hmask = s.hcap ? (int)(s.hcap - 1) : -1;
-    KS_CHECK(hipMemsetAsync(s.cm_i.p, 0, n_i * sizeof(int), st));
-    KS_CHECK(hipMemsetAsync(a.agg_cnt, 0, (nst + 1) * 8, st));
-    KS_CHECK(hipMemsetAsync(s.cm_b.p, 0, nb, st));
-    KS_CHECK(hipMemsetAsync(s.add_ctl.p, 0, sizeof(AddCtl), st));
+    wire_hash(s, a);
     KS_CHECK(hipMemcpyAsync(d_tasks, tasks, k * 8, hipMemcpyHostToDevice, st));
     KS_CHECK(hipMemcpyAsync(d_off, arc_off, (k + 1) * 8, hipMemcpyHostToDevice, st));
     if (na) KS_CHECK(hipMemcpyAsync(d_arcs, arcs, na * sizeof(ks_task_arc), hipMemcpyHostToDevice, st));
@@ -907,12 +875,13 @@ int Engine::add_tasks(const uint64_t* tasks, size_t k, const uint64_t* arc_off, 
         return (size_t)(std::upper_bound(arc_off, arc_off + k, (uint64_t)j) - arc_off) - 1;
     };
     if (h.bad_head || h.bad_cost) {   // the first offending arc in input order; on one arc the head comes first
-        if (h.bad_head < 0 || h.bad_cost < 0 || (size_t)h.bad_head > na || (size_t)h.bad_cost > na) {
+        size_t jh, jc;
+        if (!first_bad(h.bad_head, na, &jh) || !first_bad(h.bad_cost, na, &jc)) {
             err = "inconsistent arc index";
             return KS_E_DEVICE;
         }
-        const bool head = h.bad_head >= h.bad_cost;
-        const size_t j = na - (size_t)(head ? h.bad_head : h.bad_cost);
+        const bool head = jh <= jc;
+        const size_t j = head ? jh : jc;
         const std::string who = "task " + std::to_string(tasks[task_of(j)]) + ": ";
         if (head) {
             err = who + "head " + std::to_string(arcs[j].dst) + " is not a node that was live before the call and is no "
@@ -923,12 +892,13 @@ int Engine::add_tasks(const uint64_t* tasks, size_t k, const uint64_t* arc_off, 
         return KS_E_RANGE;
     }
     if (h.bad_multi || h.bad_none) {
-        if (h.bad_multi < 0 || h.bad_none < 0 || (size_t)h.bad_multi > k || (size_t)h.bad_none > k) {
+        size_t im, in;
+        if (!first_bad(h.bad_multi, k, &im) || !first_bad(h.bad_none, k, &in)) {
             err = "inconsistent task index";
             return KS_E_DEVICE;
         }
-        const bool multi = h.bad_multi >= h.bad_none;
-        const uint64_t id = tasks[k - (size_t)(multi ? h.bad_multi : h.bad_none)];
+        const bool multi = im <= in;
+        const uint64_t id = tasks[multi ? im : in];
         err = multi ? "task " + std::to_string(id) + " has more than one arc into unscheduled aggregators: a task has one job"
                     : "task " + std::to_string(id) + " has no arc into a node with an arc into the sink; an aggregator "
                       "whose capacity fell to 0 has lost that arc: pass the aggregators' ids (unsched_ids)";
@@ -945,41 +915,29 @@ int Engine::add_tasks(const uint64_t* tasks, size_t k, const uint64_t* arc_off, 
     }
     // ---- 2. room for the new nodes and arcs; the host's node table follows
     const int64_t nrec = (int64_t)k + (int64_t)na + h.rec_agg;
-    int rc = ensure_nodes(s, std::max<int64_t>(nslots, 1), err);
+    rc = ensure_nodes(s, std::max<int64_t>(nslots, 1), err);
     if (rc == KS_OK) rc = ensure_arcs(s, (int64_t)s.hi() + (int64_t)na + h.rec_add, err);
     if (rc == KS_OK) rc = ensure_hash(s, (int64_t)na + h.rec_add, err);
+    if (rc == KS_OK) rc = size_stream(s, nrec, k, err);
     if (rc) return rc;
-    KS_CHECK(s.d_recs.ensure((size_t)nrec));
-    KS_CHECK(s.rec_ent.ensure((size_t)nrec));
-    KS_CHECK(s.d_edits.ensure(k));
     std::vector<NodeEdit> edits;
     make_edits(&edits);
     // from here on a failure leaves the device state unknown
     *dirty = true;
     s.nslots = std::max(s.nslots, nslots);
-    s.incremental = true;
     d = s.schd();   // (the node store and the arc table may have moved)
     const auto t2 = std::chrono::steady_clock::now();
     // ---- 3. the records, at their fixed positions, and the apply
-    if (!edits.empty())
-        KS_CHECK(hipMemcpyAsync(s.d_edits.p, edits.data(), edits.size() * sizeof(NodeEdit), hipMemcpyHostToDevice, st));
     KS_CHECK(sched_add_emit(d, a, s.d_recs.p, st));
-    rc = mark_cells(s, s.d_recs.p, (size_t)nrec, s.d_edits.p, edits.size(), err);
-    if (rc) return rc;
-    KS_CHECK(store_apply(s.sd(), s.d_recs.p, (int)nrec, s.rec_ent.p, s.d_edits.p, (int)edits.size(), st));
-    rc = read_sctl(s, err);
-    if (rc == KS_OK) rc = applied(s, err);
+    rc = apply_stream(s, nrec, edits, nrec > (int64_t)k, err);
     if (rc) return rc;
     if (log) {
         const auto t3 = std::chrono::steady_clock::now();
-        auto ms = [](auto x, auto y) { return std::chrono::duration<double, std::milli>(y - x).count(); };
         std::fprintf(stderr,
                      "add: %zu tasks, %zu arcs, %lld records, upload + checks + counts %.3f ms, node table + sizing "
                      "%.3f ms, emit + apply %.3f ms\n",
                      k, na, (long long)nrec, ms(t0, t1), ms(t1, t2), ms(t2, t3));
     }
-    s.solved = false;
-    if (nrec > (int64_t)k && s.cell_refused_values) s.cell_refused = s.cell_refused_values = false;   // (as run_apply)
     if (stats) {
         std::memset(stats, 0, sizeof(*stats));
         stats->tasks = (int64_t)k;
@@ -1030,29 +988,20 @@ int Engine::add_resources(const ks_res_node* nodes, size_t n, const ks_res_arc* 
     g.ntot = ntot;
     g.sink = sink_slot >= 0 && sink_slot < nst ? sink_slot : -1;
     unsigned long long *d_nodes = nullptr, *d_arcs = nullptr;
-    auto carve = [&](Carve<int> ci, Carve<unsigned long long> cu) {
+    int rc = carve_scratch(s, [&](Carve<int>& ci, Carve<unsigned long long>& cu) {
         for (int** x : {&g.newt, &g.par}) *x = ci.take(ntot + 1);
         for (int** x : {&g.nflag, &g.n_off}) *x = ci.take((int64_t)n + 1);
         for (int** x : {&g.eflag, &g.e_off, &g.e_slot}) *x = ci.take((int64_t)m + 1);
         g.S = cu.take(ntot + 1);   // (first: the only u64 array that starts zeroed)
         d_nodes = cu.take(4 * (int64_t)n);
         d_arcs = cu.take(4 * (int64_t)m);
-        return std::make_pair(ci.n, cu.n);
-    };
-    const auto [n_i, n_u] = carve({nullptr}, {nullptr});
-    KS_CHECK(s.cm_i.ensure(n_i));
-    KS_CHECK(s.cm_u.ensure(n_u));
-    KS_CHECK(s.grow_ctl.ensure(1));
-    carve({s.cm_i.p}, {s.cm_u.p});
+    }, ntot + 1, false, err);
+    if (rc) return rc;
+    KS_CHECK(clear_ctl(s.grow_ctl, st));
     g.ctl = s.grow_ctl.p;
     g.nodes = (const ks_res_node*)d_nodes;
     g.arcs = (const ks_res_arc*)d_arcs;
-    g.hkey = s.hkey.p;
-    g.hval = s.hval.p;
-    g.hmask = s.hcap ? (int)(s.hcap - 1) : -1;
-    KS_CHECK(hipMemsetAsync(s.cm_i.p, 0, n_i * sizeof(int), st));
-    KS_CHECK(hipMemsetAsync(g.S, 0, (ntot + 1) * 8, st));
-    KS_CHECK(hipMemsetAsync(s.grow_ctl.p, 0, sizeof(GrowCtl), st));
+    wire_hash(s, g);
     if (n) KS_CHECK(hipMemcpyAsync(d_nodes, nodes, n * sizeof(ks_res_node), hipMemcpyHostToDevice, st));
     if (m) KS_CHECK(hipMemcpyAsync(d_arcs, arcs, m * sizeof(ks_res_arc), hipMemcpyHostToDevice, st));
     SchedDev d = s.schd();
@@ -1066,11 +1015,11 @@ int Engine::add_resources(const ks_res_node* nodes, size_t n, const ks_res_arc* 
     KS_CHECK(hipStreamSynchronize(st));
     const auto t1 = std::chrono::steady_clock::now();
     if (h.bad_edge || first_pair < m) {   // the first offending edge in input order; on one edge the lowest class
-        if (h.bad_edge < 0 || (size_t)(h.bad_edge >> 3) > m || (h.bad_edge && ((h.bad_edge & 7) == 0 || h.bad_edge < 8))) {
+        size_t j;   // (the word: count − index, then 7 − class in the low three bits)
+        if (!first_bad(h.bad_edge >> 3, m, &j) || (h.bad_edge && ((h.bad_edge & 7) == 0 || h.bad_edge < 8))) {
             err = "inconsistent edge index";
             return KS_E_DEVICE;
         }
-        size_t j = h.bad_edge ? m - (size_t)(h.bad_edge >> 3) : m;
         int cls = h.bad_edge ? 7 - (h.bad_edge & 7) : 7;
         if (first_pair < j || (first_pair == j && cls == 6)) {   // (the repeated pair ranks before the second parent)
             j = first_pair;
@@ -1099,20 +1048,22 @@ int Engine::add_resources(const ks_res_node* nodes, size_t n, const ks_res_arc* 
         return KS_E_INVALID;
     }
     if (h.bad_depth) {
-        if (h.bad_depth < 0 || (size_t)h.bad_depth > n) {
+        size_t i;
+        if (!first_bad(h.bad_depth, n, &i)) {
             err = "inconsistent node index";
             return KS_E_DEVICE;
         }
-        err = "PU " + std::to_string(nodes[n - (size_t)h.bad_depth].id) + ": its tree edges do not end after " +
+        err = "PU " + std::to_string(nodes[i].id) + ": its tree edges do not end after " +
               std::to_string(KS_RES_MAX_DEPTH) + " steps (a cycle, or a topology too deep)";
         return KS_E_INVALID;
     }
     if (h.bad_cap) {
-        if (h.bad_cap < 0 || (size_t)h.bad_cap > m) {
+        size_t j;
+        if (!first_bad(h.bad_cap, m, &j)) {
             err = "inconsistent edge index";
             return KS_E_DEVICE;
         }
-        const ks_res_arc& e = arcs[m - (size_t)h.bad_cap];
+        const ks_res_arc& e = arcs[j];
         err = "edge " + std::to_string(e.parent) + " -> " + std::to_string(e.child) + ": the raised capacity is outside the "
               "supported range";
         return KS_E_RANGE;
@@ -1129,41 +1080,29 @@ int Engine::add_resources(const ks_res_node* nodes, size_t n, const ks_res_arc* 
     const int64_t nrec = (int64_t)n + h.rec_pu + h.rec_edge;
     if (!nrec) return KS_OK;   // chain edges alone with no new slot beneath them: nothing to write
     // ---- 2. room for the new nodes and arcs; the host's node table follows
-    int rc = ensure_nodes(s, std::max<int64_t>(nslots, 1), err);
+    rc = ensure_nodes(s, std::max<int64_t>(nslots, 1), err);
     if (rc == KS_OK) rc = ensure_arcs(s, (int64_t)s.hi() + h.rec_pu + h.rec_add, err);
     if (rc == KS_OK) rc = ensure_hash(s, (int64_t)h.rec_pu + h.rec_add, err);
+    if (rc == KS_OK) rc = size_stream(s, nrec, n, err);
     if (rc) return rc;
-    KS_CHECK(s.d_recs.ensure((size_t)nrec));
-    KS_CHECK(s.rec_ent.ensure((size_t)nrec));
-    KS_CHECK(s.d_edits.ensure(std::max<size_t>(n, 1)));
     std::vector<NodeEdit> edits;
     make_edits(&edits);
     // from here on a failure leaves the device state unknown
     *dirty = *changed = true;
     s.nslots = std::max(s.nslots, nslots);
-    s.incremental = true;
     d = s.schd();   // (the node store and the arc table may have moved)
     const auto t2 = std::chrono::steady_clock::now();
     // ---- 3. the records, at their fixed positions, and the apply
-    if (!edits.empty())
-        KS_CHECK(hipMemcpyAsync(s.d_edits.p, edits.data(), edits.size() * sizeof(NodeEdit), hipMemcpyHostToDevice, st));
     KS_CHECK(sched_grow_emit(d, g, h.rec_pu, s.d_recs.p, st));
-    rc = mark_cells(s, s.d_recs.p, (size_t)nrec, s.d_edits.p, edits.size(), err);
-    if (rc) return rc;
-    KS_CHECK(store_apply(s.sd(), s.d_recs.p, (int)nrec, s.rec_ent.p, s.d_edits.p, (int)edits.size(), st));
-    rc = read_sctl(s, err);
-    if (rc == KS_OK) rc = applied(s, err);
+    rc = apply_stream(s, nrec, edits, nrec > (int64_t)n, err);
     if (rc) return rc;
     if (log) {
         const auto t3 = std::chrono::steady_clock::now();
-        auto ms = [](auto x, auto y) { return std::chrono::duration<double, std::milli>(y - x).count(); };
         std::fprintf(stderr,
                      "grow: %zu nodes, %zu edges, %lld records, upload + checks + sums %.3f ms, node table + sizing "
                      "%.3f ms, emit + apply %.3f ms\n",
                      n, m, (long long)nrec, ms(t0, t1), ms(t1, t2), ms(t2, t3));
     }
-    s.solved = false;
-    if (nrec > (int64_t)n && s.cell_refused_values) s.cell_refused = s.cell_refused_values = false;   // (as run_apply)
     if (stats) {
         stats->nodes = (int64_t)n;
         stats->pus = pus;
@@ -1193,12 +1132,8 @@ int Engine::update_tasks(int flags, const uint64_t* tasks, size_t k, const uint6
     KS_CHECK(hipSetDevice(s.device));
     hipStream_t st = s.stream;
     const bool walk = !(flags & KS_UPDATE_KEEP_UNLISTED);
-    if (walk && !s.csr_valid) {   // the chunk items walk the residual CSR
-        int rc = build(s, err);
-        if (rc) return rc;
-        s.has_prev = false;
-        s.solved = false;
-    }
+    int rc = walk ? fresh_csr(s, err) : KS_OK;   // the chunk items walk the residual CSR
+    if (rc) return rc;
     const bool log = s.opts.log_cycles != 0;
     const auto t0 = std::chrono::steady_clock::now();
     const int64_t nst = s.nstore;
@@ -1208,11 +1143,8 @@ int Engine::update_tasks(int flags, const uint64_t* tasks, size_t k, const uint6
         err = "too many tasks, arcs or aggregator ids";
         return KS_E_RANGE;
     }
-    for (size_t i = 0; unsched_ids && i < nu; ++i)
-        if (unsched_ids[i] == 0 || (int64_t)unsched_ids[i] > nst) {
-            err = "unscheduled aggregator id beyond the graph";
-            return KS_E_INVALID;
-        }
+    rc = check_agg_ids(s, unsched_ids, nu, err);
+    if (rc) return rc;
     UpdDev u{};
     u.k = (int)k;
     u.na = (int)na;
@@ -1225,7 +1157,7 @@ int Engine::update_tasks(int flags, const uint64_t* tasks, size_t k, const uint6
     a.sink = sink_slot >= 0 && sink_slot < nst ? sink_slot : -1;
     a.sink_cost = sink_cost;
     unsigned long long *d_tasks = nullptr, *d_off = nullptr, *d_arcs = nullptr, *d_agg = nullptr;
-    auto carve = [&](Carve<int> ci, Carve<unsigned long long> cu) {
+    rc = carve_scratch(s, [&](Carve<int>& ci, Carve<unsigned long long>& cu) {
         for (int** x : {&u.t_own, &a.aflag, &a.a_off, &a.a_slot}) *x = ci.take(nst + 1);
         for (int** x : {&u.t_slot, &u.t_agg, &u.nch, &u.ch_off}) *x = ci.take((int64_t)k + 1);
         for (int** x : {&u.seen, &u.sflag, &u.s_off}) *x = ci.take((int64_t)hi + 1);
@@ -1235,16 +1167,10 @@ int Engine::update_tasks(int flags, const uint64_t* tasks, size_t k, const uint6
         d_off = cu.take(k + 1);
         d_arcs = cu.take(2 * na);
         d_agg = cu.take(nu);
-        return std::make_pair(ci.n, cu.n);
-    };
-    const auto [n_i, n_u] = carve({nullptr}, {nullptr});
-    const int64_t nb = (nst + 4) & ~3LL;
-    KS_CHECK(s.cm_i.ensure(n_i));
-    KS_CHECK(s.cm_u.ensure(n_u));
-    KS_CHECK(s.cm_b.ensure(nb));
-    KS_CHECK(s.upd_ctl.ensure(1));
-    KS_CHECK(s.add_ctl.ensure(1));
-    carve({s.cm_i.p}, {s.cm_u.p});
+    }, nst + 1, true, err);
+    if (rc) return rc;
+    KS_CHECK(clear_ctl(s.upd_ctl, st));
+    KS_CHECK(clear_ctl(s.add_ctl, st));
     u.fl = a.fl = s.cm_b.p;
     a.agg_cnt = u.agg_cnt;
     u.ctl = s.upd_ctl.p;
@@ -1252,14 +1178,8 @@ int Engine::update_tasks(int flags, const uint64_t* tasks, size_t k, const uint6
     u.tasks = d_tasks;
     u.arc_off = d_off;
     u.arcs = (const ks_task_arc*)d_arcs;
-    u.hkey = a.hkey = s.hkey.p;
-    u.hval = a.hval = s.hval.p;
-    u.hmask = a.hmask = s.hcap ? (int)(s.hcap - 1) : -1;
-    KS_CHECK(hipMemsetAsync(s.cm_i.p, 0, n_i * sizeof(int), st));
-    KS_CHECK(hipMemsetAsync(u.agg_cnt, 0, (nst + 1) * 8, st));
-    KS_CHECK(hipMemsetAsync(s.cm_b.p, 0, nb, st));
-    KS_CHECK(hipMemsetAsync(s.upd_ctl.p, 0, sizeof(UpdCtl), st));
-    KS_CHECK(hipMemsetAsync(s.add_ctl.p, 0, sizeof(AddCtl), st));
+    wire_hash(s, u);
+    wire_hash(s, a);
     KS_CHECK(hipMemcpyAsync(d_tasks, tasks, k * 8, hipMemcpyHostToDevice, st));
     KS_CHECK(hipMemcpyAsync(d_off, arc_off, (k + 1) * 8, hipMemcpyHostToDevice, st));
     if (na) KS_CHECK(hipMemcpyAsync(d_arcs, arcs, na * sizeof(ks_task_arc), hipMemcpyHostToDevice, st));
@@ -1282,11 +1202,12 @@ int Engine::update_tasks(int flags, const uint64_t* tasks, size_t k, const uint6
     KS_CHECK(hipStreamSynchronize(st));
     const auto t1 = std::chrono::steady_clock::now();
     if (h.bad_task) {
-        if (h.bad_task < 0 || (size_t)h.bad_task > k) {
+        size_t i;
+        if (!first_bad(h.bad_task, k, &i)) {
             err = "inconsistent task index";
             return KS_E_DEVICE;
         }
-        err = "task " + std::to_string(tasks[k - (size_t)h.bad_task]) + " is not a live task node listed once (0, beyond "
+        err = "task " + std::to_string(tasks[i]) + " is not a live task node listed once (0, beyond "
               "the graph, dead, of another type, or listed before)";
         return KS_E_INVALID;
     }
@@ -1295,11 +1216,11 @@ int Engine::update_tasks(int flags, const uint64_t* tasks, size_t k, const uint6
     };
     // the first offending arc in input order; on one arc the head, then the repeat, then the cost
     if (h.bad_head || h.bad_cost || first_pair < na) {
-        if (h.bad_head < 0 || h.bad_cost < 0 || (size_t)h.bad_head > na || (size_t)h.bad_cost > na) {
+        size_t jh, jc;
+        if (!first_bad(h.bad_head, na, &jh) || !first_bad(h.bad_cost, na, &jc)) {
             err = "inconsistent arc index";
             return KS_E_DEVICE;
         }
-        const size_t jh = h.bad_head ? na - (size_t)h.bad_head : na, jc = h.bad_cost ? na - (size_t)h.bad_cost : na;
         const size_t j = std::min({jh, first_pair, jc});
         const std::string who = "task " + std::to_string(tasks[task_of(j)]) + ": ";
         if (j == jh) {
@@ -1316,12 +1237,13 @@ int Engine::update_tasks(int flags, const uint64_t* tasks, size_t k, const uint6
         return KS_E_RANGE;
     }
     if (h.bad_multi || h.bad_none) {
-        if (h.bad_multi < 0 || h.bad_none < 0 || (size_t)h.bad_multi > k || (size_t)h.bad_none > k) {
+        size_t im, in;
+        if (!first_bad(h.bad_multi, k, &im) || !first_bad(h.bad_none, k, &in)) {
             err = "inconsistent task index";
             return KS_E_DEVICE;
         }
-        const bool multi = h.bad_multi >= h.bad_none;
-        const uint64_t id = tasks[k - (size_t)(multi ? h.bad_multi : h.bad_none)];
+        const bool multi = im <= in;
+        const uint64_t id = tasks[multi ? im : in];
         err = multi ? "task " + std::to_string(id) + " would have arcs into two unscheduled aggregators: a task does not "
                       "change its job"
                     : "task " + std::to_string(id) + " is unbound and would have no arc into a node with an arc into the "
@@ -1355,36 +1277,26 @@ int Engine::update_tasks(int flags, const uint64_t* tasks, size_t k, const uint6
     }
     if (!nrec) return KS_OK;   // every list is what the store holds: the solution stands
     // ---- 2. room for the new arcs
-    int rc = ensure_arcs(s, (int64_t)hi + h.rec_add + ha.rec_add, err);
+    rc = ensure_arcs(s, (int64_t)hi + h.rec_add + ha.rec_add, err);
     if (rc == KS_OK) rc = ensure_hash(s, (int64_t)h.rec_add + ha.rec_add, err);
+    if (rc == KS_OK) rc = size_stream(s, nrec, 0, err);
     if (rc) return rc;
-    KS_CHECK(s.d_recs.ensure((size_t)nrec));
-    KS_CHECK(s.rec_ent.ensure((size_t)nrec));
-    KS_CHECK(s.d_edits.ensure(1));
     // from here on a failure leaves the device state unknown
     *dirty = true;
-    s.incremental = true;
     d = s.schd();   // (the arc table may have moved)
     const auto t2 = std::chrono::steady_clock::now();
     // ---- 3. the records, at their fixed positions, and the apply
     KS_CHECK(sched_upd_emit(d, u, h.rec_held, s.d_recs.p, st));
     KS_CHECK(sched_add_emit_aggs(d, a, (int64_t)h.rec_held + h.rec_add, s.d_recs.p, st));
-    rc = mark_cells(s, s.d_recs.p, (size_t)nrec, s.d_edits.p, 0, err);
-    if (rc) return rc;
-    KS_CHECK(store_apply(s.sd(), s.d_recs.p, (int)nrec, s.rec_ent.p, s.d_edits.p, 0, st));
-    rc = read_sctl(s, err);
-    if (rc == KS_OK) rc = applied(s, err);
+    rc = apply_stream(s, nrec, {}, true, err);
     if (rc) return rc;
     if (log) {
         const auto t3 = std::chrono::steady_clock::now();
-        auto ms = [](auto x, auto y) { return std::chrono::duration<double, std::milli>(y - x).count(); };
         std::fprintf(stderr,
                      "update: %zu tasks, %zu arcs, %lld records, upload + checks + diff %.3f ms, sizing %.3f ms, "
                      "emit + apply %.3f ms\n",
                      k, na, (long long)nrec, ms(t0, t1), ms(t1, t2), ms(t2, t3));
     }
-    s.solved = false;
-    if (s.cell_refused_values) s.cell_refused = s.cell_refused_values = false;   // (as run_apply)
     *changed = true;
     return KS_OK;
 }

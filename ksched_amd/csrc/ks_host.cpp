@@ -238,6 +238,65 @@ struct NodeTxn {
     }
 };
 
+// ---- what the scheduler-side calls share: their argument checks and their epilogues
+
+// The slot of the graph's one sink, −1 with none or several; every_sink: a partition's one
+// sink per cell counts as Engine::kEverySink.
+int64_t sink_slot(const ks_ctx* c, bool every_sink = false) {
+    return c->n_sinks == 1                                    ? (int64_t)c->sink_id - 1
+           : (every_sink && c->every_sink && c->n_sinks > 1) ? ks::Engine::kEverySink
+                                                              : -1;
+}
+
+int check_aggregators(ks_ctx* c, const uint64_t* ids, size_t k) {
+    for (size_t i = 0; ids && i < k; ++i)
+        if (!node_alive(c, ids[i]))
+            return c->fail(KS_E_INVALID, "unscheduled aggregator " + std::to_string(ids[i]) + " is not a live node");
+    return KS_OK;
+}
+
+// The task lists of ks_add_tasks and ks_update_tasks (k > 0): offsets from 0 that never fall,
+// and an arc array where they name an arc.
+int check_task_lists(ks_ctx* c, const uint64_t* tasks, size_t k, const uint64_t* arc_off, const ks_task_arc* arcs) {
+    if (arc_off[0] != 0) return c->fail(KS_E_INVALID, "arc_off[0] must be 0");
+    for (size_t i = 0; i < k; ++i)
+        if (arc_off[i + 1] < arc_off[i])
+            return c->fail(KS_E_INVALID, "arc_off decreases at task " + std::to_string(tasks[i]));
+    if (arc_off[k] && !arcs) return c->fail(KS_E_INVALID, "null arc array");
+    return KS_OK;
+}
+
+int check_sink_cost(ks_ctx* c, int64_t cost) {
+    if (cost > (int64_t(1) << 40) || cost < -(int64_t(1) << 40))
+        return c->fail(KS_E_RANGE, "unscheduled sink cost outside the supported range");
+    return KS_OK;
+}
+
+// The graph changed (as after ks_apply_deltas): the solution no longer stands.
+void drop_solution(ks_ctx* c) {
+    c->have_solution = c->map_fresh = c->flows_fresh = false;
+}
+
+// A call that needed the residual CSR may have rebuilt it, and the solution in place went with it.
+void follow_rebuild(ks_ctx* c) {
+    if (!c->eng.solved()) drop_solution(c);
+}
+
+// A device delta call failed with rc. With a node transaction: its edits were made when dirty (the
+// stream may be half applied: reload first), else only the node table moved. Without one a dirty
+// store is marked bad. The stats of a call that may have written some read zero.
+int delta_failed(ks_ctx* c, int rc, NodeTxn* txn, bool dirty) {
+    if (txn && dirty) txn->rollback_applied();
+    else if (txn) txn->rollback_nodes();
+    else if (dirty) c->store_bad = true;
+    return rc;
+}
+template <class Stats>
+int delta_failed(ks_ctx* c, int rc, NodeTxn* txn, bool dirty, Stats* stats) {
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    return delta_failed(c, rc, txn, dirty);
+}
+
 }  // namespace
 
 extern "C" {
@@ -302,9 +361,7 @@ int ks_load_graph(ks_ctx* c, const ks_node* nodes, size_t n, const ks_arc* arcs,
     c->sum_others = c->n_sinks = c->n_tasks = 0;
     c->sink_id = 0;
     for (uint64_t id = 1; id <= maxid; ++id) account(c, id, c->nodes[id], 1);
-    c->have_solution = false;
-    c->map_fresh = false;
-    c->flows_fresh = false;
+    drop_solution(c);
     std::vector<int64_t> supply(maxid);
     std::vector<uint8_t> type(maxid), alive(maxid);
     for (uint64_t id = 1; id <= maxid; ++id) {
@@ -377,9 +434,7 @@ int ks_apply_deltas(ks_ctx* c, const ks_delta* d, size_t k) {
     }
     std::vector<ks::NodeEdit> edits;
     txn.edits(edits);
-    c->have_solution = false;
-    c->map_fresh = false;
-    c->flows_fresh = false;
+    drop_solution(c);
     const auto t_dev = std::chrono::steady_clock::now();
     rc = c->eng.apply(edits.data(), edits.size(), d, k, c->nslots(), c->err);
     if (c->opts.log_cycles) {   // (ks_opts.log_cycles: the host's and the device's share of an apply)
@@ -503,9 +558,7 @@ int ks_solve(ks_ctx* c, ks_result* out) {
     }
     ks_result r;
     std::memset(&r, 0, sizeof(r));
-    c->have_solution = false;
-    c->map_fresh = false;
-    c->flows_fresh = false;
+    drop_solution(c);
     int rc = KS_OK;
     // auto-sink: the sink absorbs every other supply (its demand drifts without a
     // message in the reference, graph_manager.go:640, 808)
@@ -647,16 +700,10 @@ int ks_update_unsched_costs(ks_ctx* c, const uint64_t* ids, size_t k, int32_t mo
     const int64_t lim = int64_t(1) << 40;
     if (unsched_cost > lim || unsched_cost < -lim || continuation_cost > lim || continuation_cost < -lim)
         return c->fail(KS_E_RANGE, "cost outside the supported range");
-    for (size_t i = 0; ids && i < k; ++i)
-        if (!node_alive(c, ids[i])) return c->fail(KS_E_INVALID, "unscheduled aggregator " + std::to_string(ids[i]) +
-                                                                     " is not a live node");
+    if (int rc = check_aggregators(c, ids, k)) return rc;
     size_t ch = 0;
     int rc = c->eng.unsched_costs(ids, ids ? k : 0, mode, unsched_cost, continuation_cost, &ch, c->err);
-    if (rc == KS_OK && ch) {
-        c->have_solution = false;
-        c->map_fresh = false;
-        c->flows_fresh = false;
-    }
+    if (rc == KS_OK && ch) drop_solution(c);
     if (changed) *changed = ch;
     return rc;
 }
@@ -673,10 +720,9 @@ int ks_topology_stats(ks_ctx* c, uint64_t max_tasks_per_pu, const uint64_t* pu_i
     for (size_t i = 0; pu_ids && i < k; ++i)
         if (!node_alive(c, pu_ids[i]) || c->nodes[pu_ids[i]].type != KS_NODE_PU)
             return c->fail(KS_E_INVALID, "running count for a node that is not a live PU");
-    const int64_t sink = c->n_sinks == 1 ? (int64_t)c->sink_id - 1 : -1;
-    int rc = c->eng.topology_stats(max_tasks_per_pu, pu_ids, pu_running, pu_ids ? k : 0, sink, slots_below,
+    int rc = c->eng.topology_stats(max_tasks_per_pu, pu_ids, pu_running, pu_ids ? k : 0, sink_slot(c), slots_below,
                                    running_below, c->err);
-    if (!c->eng.solved()) c->have_solution = c->flows_fresh = c->map_fresh = false;   // a pending CSR rebuild ran
+    follow_rebuild(c);
     return rc;
 }
 
@@ -693,29 +739,20 @@ static int commit_call(ks_ctx* c, int32_t flags, int64_t continuation_cost, int6
     const int64_t lim = int64_t(1) << 40;
     if (continuation_cost > lim || continuation_cost < -lim || preemption_cost > lim || preemption_cost < -lim)
         return c->fail(KS_E_RANGE, "cost outside the supported range");
-    for (size_t i = 0; ids && i < k; ++i)
-        if (!node_alive(c, ids[i])) return c->fail(KS_E_INVALID, "unscheduled aggregator " + std::to_string(ids[i]) +
-                                                                     " is not a live node");
+    if (int rc = check_aggregators(c, ids, k)) return rc;
     if (!out) {   // count only
         size_t n = 0;
         const int rc = c->eng.sched_deltas(0, nullptr, &n, c->n_tasks, c->err);
         *count = n;
         return rc;
     }
-    const int64_t sink = c->n_sinks == 1 ? (int64_t)c->sink_id - 1
-                         : (c->every_sink && c->n_sinks > 1) ? ks::Engine::kEverySink : -1;
     std::vector<ks_sched_delta> v;
     bool dirty = false;
-    const int rc = run(sink, &v, &dirty);
-    if (rc) {
-        if (dirty) c->store_bad = true;   // the stream may be half applied: reload first
-        return rc;
-    }
+    const int rc = run(sink_slot(c, true), &v, &dirty);
+    if (rc) return delta_failed(c, rc, nullptr, dirty);   // (the engine writes the stats on success only)
     if (!v.empty()) std::memcpy(out, v.data(), v.size() * sizeof(ks_sched_delta));
     *count = v.size();
-    c->have_solution = false;   // as after ks_apply_deltas
-    c->map_fresh = false;
-    c->flows_fresh = false;
+    drop_solution(c);
     return KS_OK;
 }
 }  // extern "C++"
@@ -757,8 +794,6 @@ int ks_remove_resources(ks_ctx* c, int32_t flags, const uint64_t* roots, size_t 
     const bool probe = !removed && !evicted;
     if (!probe && ((!removed && rcap) || (!evicted && ecap)))
         return c->fail(KS_E_INVALID, "a null output buffer with room in it");
-    const int64_t sink = c->n_sinks == 1 ? (int64_t)c->sink_id - 1
-                         : (c->every_sink && c->n_sinks > 1) ? ks::Engine::kEverySink : -1;
     std::optional<NodeTxn> txn;
     int64_t pus = 0;
     auto make_edits = [&](const uint64_t* ids, size_t n, std::vector<ks::NodeEdit>* edits, std::string& err) {
@@ -782,21 +817,17 @@ int ks_remove_resources(ks_ctx* c, int32_t flags, const uint64_t* roots, size_t 
     std::vector<uint64_t> rm;
     std::vector<ks_sched_delta> ev;
     bool dirty = false;
-    const int rc = c->eng.remove_resources(flags, roots, k, sink, probe, removed ? rcap : 0, evicted ? ecap : 0, &rm,
-                                           &ev, nremoved, nevicted, stats, make_edits, &dirty, c->err);
-    if (!c->eng.solved()) c->have_solution = c->flows_fresh = c->map_fresh = false;   // a pending CSR rebuild ran
-    if (rc) {
-        if (txn) txn->rollback_applied();   // (the edits were made: the stream may be half applied, reload first)
-        else if (dirty) c->store_bad = true;
-        return rc;
-    }
+    const int rc = c->eng.remove_resources(flags, roots, k, sink_slot(c, true), probe, removed ? rcap : 0,
+                                           evicted ? ecap : 0, &rm, &ev, nremoved, nevicted, stats, make_edits, &dirty,
+                                           c->err);
+    follow_rebuild(c);
+    // (a transaction was made only behind the device's checks, and the engine writes the stats on success only)
+    if (rc) return delta_failed(c, rc, txn ? &*txn : nullptr, dirty);
     if (probe) return KS_OK;
     if (!rm.empty()) std::memcpy(removed, rm.data(), rm.size() * sizeof(uint64_t));
     if (!ev.empty()) std::memcpy(evicted, ev.data(), ev.size() * sizeof(ks_sched_delta));
     if (stats) stats->pus_removed = pus;
-    c->have_solution = false;   // as after ks_apply_deltas
-    c->map_fresh = false;
-    c->flows_fresh = false;
+    drop_solution(c);
     return KS_OK;
 }
 
@@ -814,11 +845,7 @@ int ks_complete_tasks(ks_ctx* c, int32_t flags, const uint64_t* tasks, size_t k,
     if (flags & ~(KS_COMPLETE_RESOURCE_CAPS | KS_COMPLETE_PREEMPTIVE)) return c->fail(KS_E_INVALID, "unknown complete flag");
     if ((flags & KS_COMPLETE_PREEMPTIVE) && !(flags & KS_COMPLETE_RESOURCE_CAPS))
         return c->fail(KS_E_INVALID, "KS_COMPLETE_PREEMPTIVE selects a capacity rule: it needs KS_COMPLETE_RESOURCE_CAPS");
-    for (size_t i = 0; unsched_ids && i < nu; ++i)
-        if (!node_alive(c, unsched_ids[i]))
-            return c->fail(KS_E_INVALID, "unscheduled aggregator " + std::to_string(unsched_ids[i]) + " is not a live node");
-    const int64_t sink = c->n_sinks == 1 ? (int64_t)c->sink_id - 1
-                         : (c->every_sink && c->n_sinks > 1) ? ks::Engine::kEverySink : -1;
+    if (int rc = check_aggregators(c, unsched_ids, nu)) return rc;
     std::optional<NodeTxn> txn;
     auto make_edits = [&](const uint64_t* ids, size_t n, std::vector<ks::NodeEdit>* edits, std::string& err) {
         for (size_t i = 0; i < n; ++i) {
@@ -835,19 +862,11 @@ int ks_complete_tasks(ks_ctx* c, int32_t flags, const uint64_t* tasks, size_t k,
         return KS_OK;
     };
     bool dirty = false, changed = false;
-    const int rc = c->eng.complete_tasks(flags, tasks, k, unsched_ids, unsched_ids ? nu : 0, sink, left, stats, make_edits,
-                                         &dirty, &changed, c->err);
-    if (!c->eng.solved()) c->have_solution = c->flows_fresh = c->map_fresh = false;   // a pending CSR rebuild ran
-    if (rc) {
-        if (txn) txn->rollback_applied();   // (the edits were made: the stream may be half applied, reload first)
-        else if (dirty) c->store_bad = true;
-        return rc;
-    }
-    if (changed) {
-        c->have_solution = false;   // as after ks_apply_deltas
-        c->map_fresh = false;
-        c->flows_fresh = false;
-    }
+    const int rc = c->eng.complete_tasks(flags, tasks, k, unsched_ids, unsched_ids ? nu : 0, sink_slot(c, true), left,
+                                         stats, make_edits, &dirty, &changed, c->err);
+    follow_rebuild(c);
+    if (rc) return delta_failed(c, rc, txn ? &*txn : nullptr, dirty, stats);   // (as in ks_remove_resources)
+    if (changed) drop_solution(c);
     return KS_OK;
 }
 
@@ -863,19 +882,11 @@ int ks_add_tasks(ks_ctx* c, int32_t flags, const uint64_t* tasks, size_t k, cons
     if (int g = store_guard(c)) return g;
     if (flags) return c->fail(KS_E_INVALID, "unknown add flag (flags is reserved: pass 0)");
     if (k && (!tasks || !arc_off)) return c->fail(KS_E_INVALID, "null task or offset array");
-    if (unsched_sink_cost > (int64_t(1) << 40) || unsched_sink_cost < -(int64_t(1) << 40))
-        return c->fail(KS_E_RANGE, "unscheduled sink cost outside the supported range");
+    if (int rc = check_sink_cost(c, unsched_sink_cost)) return rc;
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (!k) return KS_OK;   // nothing arrives: the solution stands
-    if (arc_off[0] != 0) return c->fail(KS_E_INVALID, "arc_off[0] must be 0");
-    for (size_t i = 0; i < k; ++i)
-        if (arc_off[i + 1] < arc_off[i])
-            return c->fail(KS_E_INVALID, "arc_off decreases at task " + std::to_string(tasks[i]));
-    if (arc_off[k] && !arcs) return c->fail(KS_E_INVALID, "null arc array");
-    for (size_t i = 0; unsched_ids && i < nu; ++i)
-        if (!node_alive(c, unsched_ids[i]))
-            return c->fail(KS_E_INVALID, "unscheduled aggregator " + std::to_string(unsched_ids[i]) + " is not a live node");
-    const int64_t sink = c->n_sinks == 1 ? (int64_t)c->sink_id - 1 : -1;
+    if (int rc = check_task_lists(c, tasks, k, arc_off, arcs)) return rc;
+    if (int rc = check_aggregators(c, unsched_ids, nu)) return rc;
     NodeTxn txn(c);
     for (size_t i = 0; i < k; ++i)
         if (int rc = txn.add(tasks[i], 1, KS_NODE_TASK)) {
@@ -884,17 +895,10 @@ int ks_add_tasks(ks_ctx* c, int32_t flags, const uint64_t* tasks, size_t k, cons
         }
     bool dirty = false;
     auto make_edits = [&](std::vector<ks::NodeEdit>* edits) { txn.edits(*edits); };
-    const int rc = c->eng.add_tasks(tasks, k, arc_off, arcs, unsched_ids, unsched_ids ? nu : 0, sink, unsched_sink_cost,
-                                    c->nslots(), stats, make_edits, &dirty, c->err);
-    if (rc) {
-        if (dirty) txn.rollback_applied();   // (the edits were made: the stream may be half applied, reload first)
-        else txn.rollback_nodes();
-        if (stats) std::memset(stats, 0, sizeof(*stats));
-        return rc;
-    }
-    c->have_solution = false;   // as after ks_apply_deltas
-    c->map_fresh = false;
-    c->flows_fresh = false;
+    const int rc = c->eng.add_tasks(tasks, k, arc_off, arcs, unsched_ids, unsched_ids ? nu : 0, sink_slot(c),
+                                    unsched_sink_cost, c->nslots(), stats, make_edits, &dirty, c->err);
+    if (rc) return delta_failed(c, rc, &txn, dirty, stats);
+    drop_solution(c);
     return KS_OK;
 }
 
@@ -950,22 +954,12 @@ int ks_add_resources(ks_ctx* c, int32_t flags, const ks_res_node* nodes, size_t 
             if (arcs[order[q]].parent == arcs[order[q - 1]].parent && arcs[order[q]].child == arcs[order[q - 1]].child)
                 first_pair = std::min(first_pair, order[q]);
     }
-    const int64_t sink = c->n_sinks == 1 ? (int64_t)c->sink_id - 1 : -1;
     bool dirty = false, changed = false;
     auto make_edits = [&](std::vector<ks::NodeEdit>* edits) { txn.edits(*edits); };
-    const int rc = c->eng.add_resources(nodes, n, arcs, m, first_pair, sink, c->nslots(), stats, make_edits, &dirty,
-                                        &changed, c->err);
-    if (rc) {
-        if (dirty) txn.rollback_applied();   // (the edits were made: the stream may be half applied, reload first)
-        else txn.rollback_nodes();
-        if (stats) std::memset(stats, 0, sizeof(*stats));
-        return rc;
-    }
-    if (changed) {   // as after ks_apply_deltas
-        c->have_solution = false;
-        c->map_fresh = false;
-        c->flows_fresh = false;
-    }
+    const int rc = c->eng.add_resources(nodes, n, arcs, m, first_pair, sink_slot(c), c->nslots(), stats, make_edits,
+                                        &dirty, &changed, c->err);
+    if (rc) return delta_failed(c, rc, &txn, dirty, stats);
+    if (changed) drop_solution(c);
     return KS_OK;
 }
 
@@ -982,19 +976,12 @@ int ks_update_tasks(ks_ctx* c, int32_t flags, const uint64_t* tasks, size_t k, c
     if (int g = store_guard(c)) return g;
     if (flags & ~KS_UPDATE_KEEP_UNLISTED) return c->fail(KS_E_INVALID, "unknown update flag");
     if (k && (!tasks || !arc_off)) return c->fail(KS_E_INVALID, "null task or offset array");
-    if (unsched_sink_cost > (int64_t(1) << 40) || unsched_sink_cost < -(int64_t(1) << 40))
-        return c->fail(KS_E_RANGE, "unscheduled sink cost outside the supported range");
+    if (int rc = check_sink_cost(c, unsched_sink_cost)) return rc;
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (!k) return KS_OK;   // nothing is refreshed: the solution stands
-    if (arc_off[0] != 0) return c->fail(KS_E_INVALID, "arc_off[0] must be 0");
-    for (size_t i = 0; i < k; ++i)
-        if (arc_off[i + 1] < arc_off[i])
-            return c->fail(KS_E_INVALID, "arc_off decreases at task " + std::to_string(tasks[i]));
+    if (int rc = check_task_lists(c, tasks, k, arc_off, arcs)) return rc;
+    if (int rc = check_aggregators(c, unsched_ids, nu)) return rc;
     const size_t na = (size_t)arc_off[k];
-    if (na && !arcs) return c->fail(KS_E_INVALID, "null arc array");
-    for (size_t i = 0; unsched_ids && i < nu; ++i)
-        if (!node_alive(c, unsched_ids[i]))
-            return c->fail(KS_E_INVALID, "unscheduled aggregator " + std::to_string(unsched_ids[i]) + " is not a live node");
     size_t first_pair = na;   // the first arc in input order that repeats an earlier head of its own task
     {
         std::vector<std::pair<uint64_t, size_t>> heads;
@@ -1007,21 +994,12 @@ int ks_update_tasks(ks_ctx* c, int32_t flags, const uint64_t* tasks, size_t k, c
             if (first_pair < na) break;   // (a later task's arcs come later in input order)
         }
     }
-    const int64_t sink = c->n_sinks == 1 ? (int64_t)c->sink_id - 1 : -1;
     bool dirty = false, changed = false;
-    const int rc = c->eng.update_tasks(flags, tasks, k, arc_off, arcs, first_pair, unsched_ids, unsched_ids ? nu : 0, sink,
-                                       unsched_sink_cost, stats, &dirty, &changed, c->err);
-    if (!c->eng.solved()) c->have_solution = c->flows_fresh = c->map_fresh = false;   // a pending CSR rebuild ran
-    if (rc) {
-        if (dirty) c->store_bad = true;   // (the stream may be half applied: reload first)
-        if (stats) std::memset(stats, 0, sizeof(*stats));
-        return rc;
-    }
-    if (changed) {   // as after ks_apply_deltas
-        c->have_solution = false;
-        c->map_fresh = false;
-        c->flows_fresh = false;
-    }
+    const int rc = c->eng.update_tasks(flags, tasks, k, arc_off, arcs, first_pair, unsched_ids, unsched_ids ? nu : 0,
+                                       sink_slot(c), unsched_sink_cost, stats, &dirty, &changed, c->err);
+    follow_rebuild(c);
+    if (rc) return delta_failed(c, rc, nullptr, dirty, stats);
+    if (changed) drop_solution(c);
     return KS_OK;
 }
 
