@@ -14,7 +14,7 @@ SOURCES = [os.path.join(CSRC, f) for f in ("ks_engine.hip", "ks_engine_build.hip
                                            "ks_engine_sched.hip", "ks_cell.hip", "ks_store.hip", "ks_sched.hip",
                                            "ks_batch.hip", "ks_host.cpp")]
 DEPS = SOURCES + [os.path.join(CSRC, h) for h in ("ks_engine.h", "ks_engine_impl.h", "ks_cell.h", "ks_store.h",
-                                                  "ks_sched.h", "ks_ctx.h", "ks_pos.h")] + [
+                                                  "ks_sched.h", "ks_ctx.h", "ks_pos.h", "ks_len.h")] + [
     os.path.join(ROOT, "include", "ksmcmf.h")]
 
 

@@ -77,6 +77,7 @@
 #include <vector>
 
 #include "ks_engine_impl.h"
+#include "ks_len.h"
 
 namespace ks {
 namespace {
@@ -246,11 +247,6 @@ __device__ __forceinline__ long long g_sum(long long x) {
 #pragma unroll
     for (int o = G / 2; o > 0; o >>= 1) x += __shfl_xor(x, o, G);
     return x;
-}
-__device__ __forceinline__ long long floordiv(long long a, long long b) {  // b > 0
-    long long q = a / b;
-    if ((a % b) != 0 && a < 0) --q;
-    return q;
 }
 
 // Mark node w active in frontier f (idempotent plain stores).
@@ -1071,9 +1067,15 @@ __device__ __forceinline__ long long dkey(long long raw) { return PR == 2 ? pk_d
 template <int PR>
 __device__ __forceinline__ bool dless(long long a, long long b) { return PR == 2 ? (a >> PK_NB) < (b >> PK_NB) : a < b; }
 
+// ε of the running phase with its reciprocal (Ctl::eps, Ctl::inv): arc lengths
+// divide by ε without a division (ks_len.h).
+struct EpsR {
+    long long eps;
+    double inv;
+};
 template <int PR>
-__device__ __forceinline__ long long arc_len(long long pu, long long ca, long long pv, long long eps) {
-    long long len = floordiv(pu - ca - pv, eps) + 1;
+__device__ __forceinline__ long long arc_len(long long pu, long long ca, long long pv, const EpsR& er) {
+    long long len = ks_floordiv_inv(pu - ca - pv, er.eps, er.inv) + 1;
     if (!PR) len = len < 0 ? 0 : (len > LEN_CAP ? LEN_CAP : len);
     return len;
 }
@@ -1154,7 +1156,7 @@ constexpr int LEAF_REGS = KS_LEAF_REGS;
 // its distance dropped to du: a second hop inside the same round.
 template <int PR, bool CP>
 __device__ __forceinline__ void expand_leaf(const DG& g, const Front& nf, const BfQ& Q, int u, long long du, long long pu,
-                                            int b0, int b1, long long eps, long long B, long long* hub_min, int& out,
+                                            int b0, int b1, const EpsR& er, long long B, long long* hub_min, int& out,
                                             int& lscan) {
     lscan += b1 - b0;   // the second hop's in-arc positions examined (ks_result.gu_leaf_scans)
     // the records of the first LEAF_REGS arcs issued together; usually one in-arc
@@ -1178,7 +1180,7 @@ __device__ __forceinline__ void expand_leaf(const DG& g, const Front& nf, const 
         if (q.ucap - q.rcap > 0) {
             const int u2 = q.head;
             const long long pu2 = g.p0[ni(u2)];
-            long long cand = du + arc_len<PR>(pu2, q.cost, pu, eps);
+            long long cand = du + arc_len<PR>(pu2, q.cost, pu, er);
             if (PR == 2) cand = pk(cand, b);
             if (offer<PR>(g, nf, u2, cand, u2 < g.hub_base ? g.dist[ni(u2)] : INF64, B, hub_min, out) &&
                 !bf_enqueue(Q, u2, Q.cap ? (unsigned long long)g.p0[ni(u2) + ND_SEG] : 0ULL, dkey<PR>(cand), pu2)) {
@@ -1202,7 +1204,7 @@ __device__ __forceinline__ void expand_leaf(const DG& g, const Front& nf, const 
         const long long du2 = u2 < g.hub_base ? g.dist[ni(u2)] : INF64;
         // (continuation: the segment comes with the record, for the queue entry)
         const unsigned long long sg2 = Q.cap ? (unsigned long long)g.p0[ni(u2) + ND_SEG] : 0ULL;
-        long long cand = du + arc_len<PR>(pu2, c2, pu, eps);
+        long long cand = du + arc_len<PR>(pu2, c2, pu, er);
         if (PR == 2) cand = pk(cand, b0 + k);
         if (offer<PR>(g, nf, u2, cand, du2, B, hub_min, out) && !bf_enqueue(Q, u2, sg2, dkey<PR>(cand), pu2)) {
             nf.flag[u2] = 1;
@@ -1216,7 +1218,7 @@ __device__ __forceinline__ void expand_leaf(const DG& g, const Front& nf, const 
 // (relax_pos: the position record q of arc a already loaded)
 template <int PR, bool CP>
 __device__ __forceinline__ void relax_pos(const DG& g, const Front& nf, const BfQ& Q, const Pos& q, int a, long long dv,
-                                          long long pv, long long eps, long long B, long long* hub_min, int& out,
+                                          long long pv, const EpsR& er, long long B, long long* hub_min, int& out,
                                           int& lscan) {
     const long long rin = q.ucap - q.rcap;
     // an arc that cannot relax reads node 0's (hot) record instead of its head's
@@ -1231,12 +1233,12 @@ __device__ __forceinline__ void relax_pos(const DG& g, const Front& nf, const Bf
     unsigned long long sg = 0;
     if (leaf || (u >= Q.lo && u < Q.hi)) sg = (unsigned long long)g.p0[ni(u) + ND_SEG];   // same record line as pu, du
     if (rin <= 0) return;
-    const long long cand = dv + arc_len<PR>(pu, ca, pv, eps);   // (dv decoded: a distance in every mode)
+    const long long cand = dv + arc_len<PR>(pu, ca, pv, er);   // (dv decoded: a distance in every mode)
     const long long key = PR == 2 ? pk(cand, a) : cand;
     if (!offer<PR>(g, nf, u, key, du, B, hub_min, out)) return;
     if (leaf) {
         const int b0 = (int)(unsigned)(sg & 0xffffffffULL), b1 = (int)(unsigned)(sg >> 32);
-        expand_leaf<PR, CP>(g, nf, Q, u, cand, pu, b0, b1, eps, B, hub_min, out, lscan);   // tasks, PUs: two hops per round
+        expand_leaf<PR, CP>(g, nf, Q, u, cand, pu, b0, b1, er, B, hub_min, out, lscan);   // tasks, PUs: two hops per round
     } else if (!bf_enqueue(Q, u, sg, dkey<PR>(key), pu)) {
         nf.flag[u] = 1;
         out = 1;
@@ -1245,8 +1247,8 @@ __device__ __forceinline__ void relax_pos(const DG& g, const Front& nf, const Bf
 
 template <int PR, bool CP>
 __device__ __forceinline__ void relax_in(const DG& g, const Front& nf, const BfQ& Q, int v, int a, long long dv, long long pv,
-                                         long long eps, long long B, long long* hub_min, int& out, int& lscan) {
-    relax_pos<PR, CP>(g, nf, Q, PL<CP>::ld_nr(g, a), a, dv, pv, eps, B, hub_min, out, lscan);
+                                         const EpsR& er, long long B, long long* hub_min, int& out, int& lscan) {
+    relax_pos<PR, CP>(g, nf, Q, PL<CP>::ld_nr(g, a), a, dv, pv, er, B, hub_min, out, lscan);
 }
 
 // The continuation's second pass: the workgroup's 32-lane groups take the queued
@@ -1256,7 +1258,7 @@ __device__ __forceinline__ void relax_in(const DG& g, const Front& nf, const BfQ
 // the propagation, through its own entry or its flag. Nodes lowered here go to
 // Qn (the next level; cap 0: the frontier flags of the next launch).
 template <int PR, bool CP>
-__device__ __forceinline__ void bf_drain(const DG& g, const Front& nf, const QEnt* q, int n, const BfQ& Qn, long long eps,
+__device__ __forceinline__ void bf_drain(const DG& g, const Front& nf, const QEnt* q, int n, const BfQ& Qn, const EpsR& er,
                                          long long B, long long* hub_min, int& out, int& scans, int& lscan) {
     constexpr int QG = BFQ_GROUP;
     const int lig = threadIdx.x & (QG - 1);
@@ -1266,7 +1268,7 @@ __device__ __forceinline__ void bf_drain(const DG& g, const Front& nf, const QEn
         for (int a = e.b0 + lig; a < e.b1; a += QG) {
             Pos p = PL<CP>::ld_nr(g, a);
             if (dkey<PR>(cur) != e.d) p.rcap = p.ucap;   // stale entry: no residual (a select, the loads stay issued together)
-            relax_pos<PR, CP>(g, nf, Qn, p, a, e.d, e.pu, eps, B, hub_min, out, lscan);
+            relax_pos<PR, CP>(g, nf, Qn, p, a, e.d, e.pu, er, B, hub_min, out, lscan);
             scans++;
         }
     }
@@ -1274,7 +1276,7 @@ __device__ __forceinline__ void bf_drain(const DG& g, const Front& nf, const QEn
 
 template <int G, int PR, bool CP>
 __device__ __forceinline__ void bf_group_pre(const DG& g, const Front& nf, const BfQ& Q, int v, long long dv, long long pv, int b0,
-                                             int en, long long eps, long long B, long long* hub_min, int& out, int& scans, int& lscan) {
+                                             int en, const EpsR& er, long long B, long long* hub_min, int& out, int& scans, int& lscan) {
     const int lig = lane_id() & (G - 1);
     const bool act = v >= 0 && (PR || dv < INF64);
     if (!act) en = b0;
@@ -1282,7 +1284,7 @@ __device__ __forceinline__ void bf_group_pre(const DG& g, const Front& nf, const
     for (int it = 0; it < iters; ++it) {
         const int a = b0 + it * G + lig;
         if (a < en) {
-            relax_in<PR, CP>(g, nf, Q, v, a, dkey<PR>(dv), pv, eps, B, hub_min, out, lscan);
+            relax_in<PR, CP>(g, nf, Q, v, a, dkey<PR>(dv), pv, er, B, hub_min, out, lscan);
             scans++;
         }
     }
@@ -1291,7 +1293,7 @@ __device__ __forceinline__ void bf_group_pre(const DG& g, const Front& nf, const
 // Sparse Bellman-Ford pass over window w of class C (mask from window_mask).
 template <int C, int PR, bool CP>
 __device__ __forceinline__ void bf_win(const DG& g, const Front& N, const BfQ& Q, int w, unsigned long long mask, const WinFlag& f,
-                                       long long eps, long long B, long long* hub_min, int& out, int& scans, int& lscan) {
+                                       const EpsR& er, long long B, long long* hub_min, int& out, int& scans, int& lscan) {
     constexpr int G = class_lanes(C);
     constexpr int PER = 64 / G;
     constexpr int WS = win_slots(C);
@@ -1305,26 +1307,26 @@ __device__ __forceinline__ void bf_win(const DG& g, const Front& N, const BfQ& Q
         int b0 = 0, en = 0;
         window_node(f, v, base, d, pv, b0, en);
         if (v < 0) d = INF64;
-        bf_group_pre<G, PR, CP>(g, N, Q, v, d, pv, b0, en, eps, B, hub_min, out, scans, lscan);
+        bf_group_pre<G, PR, CP>(g, N, Q, v, d, pv, b0, en, er, B, hub_min, out, scans, lscan);
         for (int j = 0; j < PER; ++j) mask &= mask - 1;
     }
 }
 
 // One 64-arc chunk of a chunked-class node (its flag already tested).
 template <int PR, bool CP>
-__device__ __forceinline__ void bf_chunk(const DG& g, const Front& N, const BfQ& Q, const CItem& ci, long long eps,
+__device__ __forceinline__ void bf_chunk(const DG& g, const Front& N, const BfQ& Q, const CItem& ci, const EpsR& er,
                                          long long B, long long* hub_min, int& out, int& scans, int& lscan) {
     const long long dv = atom_load(&g.dist[ni(ci.node)]);
     if (!PR && dv >= INF64) return;
     const int a = ci.begin + lane_id();
     if (a < ci.end) {
-        relax_in<PR, CP>(g, N, Q, ci.node, a, dkey<PR>(dv), g.p0[ni(ci.node)], eps, B, hub_min, out, lscan);
+        relax_in<PR, CP>(g, N, Q, ci.node, a, dkey<PR>(dv), g.p0[ni(ci.node)], er, B, hub_min, out, lscan);
         scans++;
     }
 }
 
 template <int G, int PR, bool CP>
-__device__ __forceinline__ void bf_group(const DG& g, const Front& nf, const BfQ& Q, int v, long long eps, long long B, long long* hub_min,
+__device__ __forceinline__ void bf_group(const DG& g, const Front& nf, const BfQ& Q, int v, const EpsR& er, long long B, long long* hub_min,
                                          int& out, int& scans, int& lscan) {
     const int lig = lane_id() & (G - 1);
     long long dv = INF64;
@@ -1340,7 +1342,7 @@ __device__ __forceinline__ void bf_group(const DG& g, const Front& nf, const BfQ
     for (int it = 0; it < iters; ++it) {
         const int a = b0 + it * G + lig;
         if (a < en) {
-            relax_in<PR, CP>(g, nf, Q, v, a, dkey<PR>(dv), pv, eps, B, hub_min, out, lscan);
+            relax_in<PR, CP>(g, nf, Q, v, a, dkey<PR>(dv), pv, er, B, hub_min, out, lscan);
             scans++;
         }
     }
@@ -1380,7 +1382,7 @@ __global__ __launch_bounds__(BLK) void k_bf_round(DG g, int seq, int dense_arg) 
         done = __builtin_amdgcn_readfirstlane(done);
         any = __builtin_amdgcn_readfirstlane(any);
     };
-    const long long eps = uniform64(g.ctl->eps);
+    const EpsR er{uniform64(g.ctl->eps), __longlong_as_double(uniform64(__double_as_longlong(g.ctl->inv)))};
     // bounded update (tail): offers at or above the listed excess nodes' largest
     // tentative distance are dropped (that bound only falls, so a stale copy is safe)
     const long long B = (!PR && g.bound) ? uniform64(atom_load(&g.ctl->bf_bound)) : INF64;
@@ -1405,7 +1407,7 @@ __global__ __launch_bounds__(BLK) void k_bf_round(DG g, int seq, int dense_arg) 
                 for (int k = 0; k < BF_PER_T; ++k) {
                     const int a = it.begin + sub * (CHUNK / HSPLIT) + threadIdx.x * BF_PER_T + k;
                     if (a < it.end) {
-                        relax_in<PR, CP>(g, N, Q, it.node, a, dkey<PR>(dv), pv, eps, B, hub_min, out, lscan);
+                        relax_in<PR, CP>(g, N, Q, it.node, a, dkey<PR>(dv), pv, er, B, hub_min, out, lscan);
                         scans++;
                     }
                 }
@@ -1419,11 +1421,11 @@ __global__ __launch_bounds__(BLK) void k_bf_round(DG g, int seq, int dense_arg) 
             // the update already converged
         } else if (w < g.wbeg[CCLS]) {
             const Scan sc{F.flag, 1};
-#define KS_BF_CALL(C) bf_group<G_, PR, CP>(g, N, Q, v, eps, B, hub_min, out, scans, lscan)
+#define KS_BF_CALL(C) bf_group<G_, PR, CP>(g, N, Q, v, er, B, hub_min, out, scans, lscan)
             KS_BY_CLASS(w, sc, KS_BF_CALL)
 #undef KS_BF_CALL
         } else if (w - g.wbeg[CCLS] < g.ncitems) {
-            bf_chunk<PR, CP>(g, N, Q, g.citems[w - g.wbeg[CCLS]], eps, B, hub_min, out, scans, lscan);
+            bf_chunk<PR, CP>(g, N, Q, g.citems[w - g.wbeg[CCLS]], er, B, hub_min, out, scans, lscan);
         }
     } else {
         const int tw = ((int)gridDim.x - nhb) * WPB;
@@ -1456,15 +1458,15 @@ __global__ __launch_bounds__(BLK) void k_bf_round(DG g, int seq, int dense_arg) 
             if (!mk[j]) continue;
             const int w = w0 + j * tw;
             if (w >= g.wbeg[CCLS]) {
-                bf_chunk<PR, CP>(g, N, Q, g.citems[w - g.wbeg[CCLS]], eps, B, hub_min, out, scans, lscan);
+                bf_chunk<PR, CP>(g, N, Q, g.citems[w - g.wbeg[CCLS]], er, B, hub_min, out, scans, lscan);
                 continue;
             }
             switch (class_of_window(g, w)) {
-                case 0: bf_win<0, PR, CP>(g, N, Q, w, mk[j], wf[j], eps, B, hub_min, out, scans, lscan); break;
-                case 1: bf_win<1, PR, CP>(g, N, Q, w, mk[j], wf[j], eps, B, hub_min, out, scans, lscan); break;
-                case 2: bf_win<2, PR, CP>(g, N, Q, w, mk[j], wf[j], eps, B, hub_min, out, scans, lscan); break;
-                case 3: bf_win<3, PR, CP>(g, N, Q, w, mk[j], wf[j], eps, B, hub_min, out, scans, lscan); break;
-                default: bf_win<4, PR, CP>(g, N, Q, w, mk[j], wf[j], eps, B, hub_min, out, scans, lscan); break;
+                case 0: bf_win<0, PR, CP>(g, N, Q, w, mk[j], wf[j], er, B, hub_min, out, scans, lscan); break;
+                case 1: bf_win<1, PR, CP>(g, N, Q, w, mk[j], wf[j], er, B, hub_min, out, scans, lscan); break;
+                case 2: bf_win<2, PR, CP>(g, N, Q, w, mk[j], wf[j], er, B, hub_min, out, scans, lscan); break;
+                case 3: bf_win<3, PR, CP>(g, N, Q, w, mk[j], wf[j], er, B, hub_min, out, scans, lscan); break;
+                default: bf_win<4, PR, CP>(g, N, Q, w, mk[j], wf[j], er, B, hub_min, out, scans, lscan); break;
             }
         }
     }
@@ -1477,7 +1479,7 @@ __global__ __launch_bounds__(BLK) void k_bf_round(DG g, int seq, int dense_arg) 
             const int qn = min(bfq_n[l], qcap);
             const BfQ Qn{bfq[l + 1 < BF_DEPTH ? l + 1 : 0], &bfq_n[l + 1 < BF_DEPTH ? l + 1 : 0],
                          l + 1 < BF_DEPTH ? qcap : 0, l + 1 < BF_DEPTH ? qlo : 0, l + 1 < BF_DEPTH ? qhi : 0};
-            bf_drain<PR, CP>(g, N, bfq[l], qn, Qn, eps, B, hub_min, out, scans, lscan);
+            bf_drain<PR, CP>(g, N, bfq[l], qn, Qn, er, B, hub_min, out, scans, lscan);
             __syncthreads();   // the next level's entries and the hub minima
         }
     }
@@ -1643,8 +1645,10 @@ __global__ void k_cycle_end(DG g, Ctl* host, int fwd) {
 // frontiers and flags the apply step and the sweeps write.
 constexpr int SET_FWD = 1;   // k_set_eps: no forward search pending, its counters zeroed
 constexpr int SET_CYC = 2;   //            the finish's cycle counters zeroed
-__global__ void k_set_eps(DG g, long long eps, int flags) {
+__global__ void k_set_eps(DG g, long long eps, double inv, int flags) {
     g.ctl->eps = eps;
+    g.ctl->inv = inv;                  // 1 / ε, the host's bits (ks_len.h)
+    g.ctl->lim = (1LL << 60) / eps;    // the largest distance ε multiplies without overflowing a price
     if (flags & SET_FWD) {
         g.ctl->fs_pending = 0;
         g.ctl->fs_cnt[0] = g.ctl->fs_cnt[1] = g.ctl->fs_cnt[2] = 0;
@@ -1727,7 +1731,7 @@ __global__ void k_gu_max(DG g) {
 __global__ void k_gu_apply(DG g, int sseq) {
     if (!g.ctl->bf_done) return;
     const long long eps = g.ctl->eps;
-    const long long lim = (1LL << 60) / eps;
+    const long long lim = g.ctl->lim;
     long long L = g.ctl->gu_L;
     L = L < g.ctl->gu_B ? L : g.ctl->gu_B;   // bounded update: the cap
     {   // and at the farthest excess node's distance: min(d, X) keeps the triangle inequality
@@ -2076,14 +2080,14 @@ __global__ void k_fs_init(DG g, int seq0) {
 // non-hub, non-deficit head w was lowered and is not yet listed for the next round.
 template <bool CP>
 __device__ __forceinline__ int fs_relax(const DG& g, const Front& N, int a, long long du, long long pu, long long eps,
-                                        long long B, int& wout) {
+                                        double inv, long long B, int& wout) {
     const Pos q = PL<CP>::ld_nr(g, a);
     const int w = q.head;
     const long long pw = g.p0[ni(w)];
     const long long kw = atom_load(&g.dist[ni(w)]);
     const long long ew = atom_load(&g.excess[w]);
     if (q.rcap <= 0) return 0;
-    long long len = floordiv(q.cost + pu - pw, eps) + 1;
+    long long len = ks_floordiv_inv(q.cost + pu - pw, eps, inv) + 1;
     len = len < 0 ? 0 : (len > LEN_CAP ? LEN_CAP : len);
     const long long cand = du + len;
     if (cand > B || cand >= FS_DMAX || cand >= fs_dist(kw)) return 0;
@@ -2117,6 +2121,7 @@ __global__ __launch_bounds__(BLK) void k_fs_round(DG g, int seq) {
     const int cnt = g.ctl->fs_cnt[lin];
     const long long B = atom_load(&g.ctl->fs_D);
     const long long eps = g.ctl->eps;
+    const double inv = g.ctl->inv;
     if (blockIdx.x == 0 && threadIdx.x == 0 && !done) {
         int hub_any = 0;
         for (int h = 0; h < g.nheavy; ++h) hub_any += F.hub[h];
@@ -2152,7 +2157,7 @@ __global__ __launch_bounds__(BLK) void k_fs_round(DG g, int seq) {
         for (int k = 0; k < BF_PER_T; ++k) {
             const int a = it.begin + sub * (CHUNK / HSPLIT) + threadIdx.x * BF_PER_T + k;
             int w = -1;
-            const int add = a < it.end ? fs_relax<CP>(g, N, a, du, pu, eps, B, w) : 0;
+            const int add = a < it.end ? fs_relax<CP>(g, N, a, du, pu, eps, inv, B, w) : 0;
             scans += a < it.end;
             fs_append(g, lout, add, w);
         }
@@ -2176,7 +2181,7 @@ __global__ __launch_bounds__(BLK) void k_fs_round(DG g, int seq) {
         for (int base = b0; base < b1; base += WAVE) {
             const int a = base + lane;
             int w = -1;
-            const int add = a < b1 ? fs_relax<CP>(g, N, a, du, pu, eps, B, w) : 0;
+            const int add = a < b1 ? fs_relax<CP>(g, N, a, du, pu, eps, inv, B, w) : 0;
             scans += a < b1;
             fs_append(g, lout, add, w);
         }
@@ -2195,7 +2200,7 @@ __global__ void k_fs_apply(DG g) {
         return;
     }
     const long long eps = g.ctl->eps;
-    if (D > (1LL << 60) / eps) {   // ε·D would overflow the prices: a backward update instead
+    if (D > g.ctl->lim) {   // ε·D would overflow the prices: a backward update instead
         if (blockIdx.x == 0 && threadIdx.x == 0) g.ctl->fs_fail = 1;
         return;
     }
@@ -3461,7 +3466,7 @@ struct SolveRun {
     // one-thread kernel: a host-to-device copy is a copy kernel behind a staging gap,
     // and each memset another launch
     hipError_t set_eps(long long e, int flags = 0) {
-        hipLaunchKernelGGL(k_set_eps, dim3(1), dim3(1), 0, st, g, e, flags);
+        hipLaunchKernelGGL(k_set_eps, dim3(1), dim3(1), 0, st, g, e, 1.0 / (double)e, flags);
         return hipGetLastError();
     }
     // One Bellman-Ford round on the next frontier buffer.

@@ -59,6 +59,7 @@ constexpr int FWD_UPD = 4;         // forward updates per cycle once a search fi
 
 struct Ctl {
     long long eps;
+    double inv;            // 1.0 / eps, computed on the host (ks_len.h); every writer of eps sets inv and lim too
     long long gu_L;        // max finite distance of the current global update
     long long gu_X;        // max distance of a node holding excess (−1: none)
     int infeasible;
@@ -104,6 +105,7 @@ struct Ctl {
     unsigned long long t_end;       // k_cycle_end started (= the last sweep ended)
     unsigned long long t_srch;      // the finish's running parent-graph search started (0: none)
     unsigned long long srch_ticks;  // the finish's searches so far (subtracted from its batches' spans)
+    long long lim;         // (1 << 60) / eps: distances ε multiplies without overflowing a price (the applies)
 };
 
 struct HItem {
