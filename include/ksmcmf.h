@@ -1144,6 +1144,65 @@ int ks_batch_commit_schedule(ks_batch* b, int32_t flags, int64_t continuation_co
 int ks_batch_commit_preemptive(ks_batch* b, int32_t flags, int64_t continuation_cost, int64_t preemption_cost,
                                ks_batch_delta* out, size_t cap, size_t* count, ks_preempt_stats* stats);
 
+/* ---- batch rounds, the task side: arrivals, completions, refreshes --------
+ * The twins of ks_add_tasks, ks_complete_tasks, ks_update_tasks, ks_get_bindings and
+ * ks_update_unsched_costs on a batch. Every rank passes one list per graph (ngraphs ==
+ * the loaded graphs, else KS_E_INVALID) and applies those of the graphs it owns; every id
+ * in a list is in its graph's OWN numbering. Each call has the semantics of its lone twin
+ * applied to every listed graph, as ONE device call per local device: the lists of a
+ * device's graphs go up back to back, the heads are range-checked and moved into the
+ * union's ids by one kernel, the record stream is generated on the device, is all or
+ * nothing there and marks its cells for the next solve. An aggregator's capacity record
+ * ends at the sink of the aggregator's own cell (a per-cell sink table, rebuilt per
+ * call); a cell without exactly one sink refuses a gaining aggregator.
+ *
+ * Refused before any device changes: a null array where k > 0 (KS_E_INVALID), offsets
+ * that do not start at 0 or fall (KS_E_INVALID), and any id outside 1..span of its graph,
+ * a task, a head or an aggregator (KS_E_RANGE; span = the graph's highest id at the load
+ * plus the reserved ids). The device's refusals keep the lone call's status code. Every
+ * message names the graph and the graph-local id. unsched_ids is one mode per call:
+ * either every listed graph passes its aggregators or none does (the NULL rule), else
+ * KS_E_INVALID.
+ *
+ * With ks_opts.auto_sink, after ks_batch_add_tasks and ks_batch_complete_tasks every
+ * touched graph with exactly one sink has that sink's supply at −Σ of its other nodes'
+ * supplies, as after ks_batch_apply_deltas. stats (may be NULL) are summed over the local
+ * devices. No collective: a rank returns its own failure. The resource side of a round
+ * (ks_remove_resources, ks_add_resources) has no batch twin. */
+typedef struct ks_batch_task_list {   /* one graph's part of a call, in the graph's OWN ids */
+    const uint64_t*    tasks;       size_t k;     /* k == 0: the graph is untouched          */
+    const uint64_t*    arc_off;                   /* k + 1, as ks_add_tasks (unused by complete) */
+    const ks_task_arc* arcs;
+    const uint64_t*    unsched_ids; size_t nu;    /* NULL: the NULL rule of the lone call    */
+} ks_batch_task_list;
+
+/* ks_add_tasks per listed graph: AddOrUpdateJobNodes (flowmanager/graph_manager.go:166-208)
+ * → addTaskNode (:632-648), updateUnscheduledAggNode(+1) (:194, :1291-1305), updateTaskNode
+ * (:1183-1192). flags is reserved: pass 0. */
+int ks_batch_add_tasks(ks_batch* b, int32_t flags, size_t ngraphs, const ks_batch_task_list* lists,
+                       int64_t unsched_sink_cost, ks_add_stats* stats);
+/* ks_complete_tasks per listed graph: HandleTaskCompletion (flowscheduler/scheduler.go:106-132)
+ * → TaskCompleted (flowmanager/graph_manager.go:389-405) → removeTaskNode (:803-813). flags:
+ * KS_COMPLETE_*. left (may be NULL): left[g] (may be NULL) receives, for a graph this rank
+ * owns, the k bindings read before anything changed, graph-local, 0 = unbound; an id listed
+ * twice gets the same value twice. */
+int ks_batch_complete_tasks(ks_batch* b, int32_t flags, size_t ngraphs, const ks_batch_task_list* lists,
+                            uint64_t* const* left, ks_complete_stats* stats);
+/* ks_update_tasks per listed graph: UpdateTimeDependentCosts (flowmanager/graph_manager.go:211-213)
+ * → updateTaskNode (:1183-1192) with removeInvalidECPrefArcs / removeInvalidPrefResArcs
+ * (:732-790). flags: KS_UPDATE_*. */
+int ks_batch_update_tasks(ks_batch* b, int32_t flags, size_t ngraphs, const ks_batch_task_list* lists,
+                          int64_t unsched_sink_cost, ks_update_stats* stats);
+/* ks_get_bindings for graph g, graph-local ids both ways (the mirror of
+ * ks_batch_set_bindings; KS_E_INVALID when g is not local). */
+int ks_batch_get_bindings(ks_batch* b, size_t g, const uint64_t* task, uint64_t* pu, size_t k);
+/* ks_update_unsched_costs: UpdateAllCostsToUnscheduledAggs (flowmanager/graph_manager.go:462-475).
+ * lists == NULL: every aggregator of every local graph (the NULL rule). Else only
+ * unsched_ids / nu of each entry are read: the aggregators whose tasks are re-costed (a
+ * graph with nu == 0 is untouched). *changed (may be NULL): summed over the local devices. */
+int ks_batch_update_unsched_costs(ks_batch* b, size_t ngraphs, const ks_batch_task_list* lists, int32_t mode,
+                                  int64_t cost, int64_t continuation_cost, size_t* changed);
+
 #ifdef __cplusplus
 }
 #endif

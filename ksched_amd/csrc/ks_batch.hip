@@ -356,6 +356,143 @@ int batch_commit(ks_batch* b, ks_batch_delta* out, size_t cap, size_t* count, St
     return KS_OK;
 }
 
+// ---- the task side of a round: one device's part of ks_batch_add_tasks, _complete_tasks,
+// _update_tasks. Its graphs' lists lie back to back in graph order: the task and aggregator
+// ids in the union's numbering (the O(k) part, which the node table needs anyway), the arcs as
+// the caller wrote them: their heads leave the graph's numbering on the device (BatchView).
+struct UnionLists {
+    std::vector<uint64_t> tasks, arc_off, agg;
+    std::vector<uint64_t> task_goff, arc_goff;   // per graph of the device (+ total): its first task, its first arc
+    std::vector<ks_task_arc> arcs;
+    std::vector<size_t> touched;                 // the listed graphs, as indices into Local::graphs
+    bool explicit_ids = false;                   // the listed graphs pass their aggregators (else the NULL rule)
+    ks::BatchView view;
+    const uint64_t* agg_ptr() const {            // (an empty list names no aggregator: not NULL, which is the NULL rule)
+        static const uint64_t none = 0;
+        return !explicit_ids ? nullptr : agg.empty() ? &none : agg.data();
+    }
+};
+
+// What every rank can check of all the lists, before any device is asked: the arrays, the
+// offsets, and the one aggregator mode of the call.
+int check_lists(ks_batch* b, size_t ngraphs, const ks_batch_task_list* lists, bool with_arcs) {
+    if (ngraphs != b->ngraphs) return b->fail(KS_E_INVALID, "the list count differs from the loaded graphs");
+    if (ngraphs && !lists) return b->fail(KS_E_INVALID, "null list array");
+    int mode = -1;   // 1: the listed graphs pass unsched_ids, 0: none does
+    for (size_t g = 0; g < ngraphs; ++g) {
+        const ks_batch_task_list& L = lists[g];
+        if (!L.k) continue;
+        const std::string who = "graph " + std::to_string(g) + ": ";
+        if (!L.tasks) return b->fail(KS_E_INVALID, who + "null task array");
+        if (L.k > (size_t)INT32_MAX / 4) return b->fail(KS_E_RANGE, who + "too many tasks");
+        if (L.unsched_ids == nullptr && L.nu) return b->fail(KS_E_INVALID, who + "null aggregator array");
+        const int m = L.unsched_ids ? 1 : 0;
+        if (mode >= 0 && m != mode)
+            return b->fail(KS_E_INVALID, who + "either every listed graph passes unsched_ids or none does (one rule per call)");
+        mode = m;
+        if (!with_arcs) continue;
+        if (!L.arc_off) return b->fail(KS_E_INVALID, who + "null offset array");
+        if (L.arc_off[0] != 0) return b->fail(KS_E_INVALID, who + "arc_off[0] must be 0");
+        for (size_t i = 0; i < L.k; ++i)
+            if (L.arc_off[i + 1] < L.arc_off[i])
+                return b->fail(KS_E_INVALID, who + "arc_off decreases at task " + std::to_string(L.tasks[i]));
+        if (L.arc_off[L.k] && !L.arcs) return b->fail(KS_E_INVALID, who + "null arc array");
+        if (L.arc_off[L.k] > (uint64_t)INT32_MAX / 4) return b->fail(KS_E_RANGE, who + "too many arcs");
+    }
+    return KS_OK;
+}
+
+// The lists of l's graphs as one union input. A task or an aggregator outside 1..span of its
+// graph is KS_E_RANGE here (a head: on the device, before anything changes there).
+int build_union(ks_batch* b, const ks_batch::Local& l, const ks_batch_task_list* lists, bool with_arcs, UnionLists& u) {
+    u.task_goff.assign(1, 0);
+    u.arc_goff.assign(1, 0);
+    if (with_arcs) u.arc_off.assign(1, 0);
+    for (size_t i = 0; i < l.graphs.size(); ++i) {
+        const size_t g = (size_t)l.graphs[i];
+        const ks_batch_task_list& L = lists[g];
+        if (L.k) {
+            const uint64_t lo = (uint64_t)l.off[i], span = (uint64_t)(l.off[i + 1] - l.off[i]);
+            auto range = [&](const char* what, uint64_t id) {
+                return b->fail(KS_E_RANGE, "graph " + std::to_string(g) + ": " + what + " " + std::to_string(id) +
+                                               " is outside the graph's ids 1.." + std::to_string(span) +
+                                               " (its highest id at the load plus the reserved ids)");
+            };
+            for (size_t j = 0; j < L.k; ++j) {
+                if (L.tasks[j] == 0 || L.tasks[j] > span) return range("task", L.tasks[j]);
+                u.tasks.push_back(L.tasks[j] + lo);
+            }
+            for (size_t j = 0; L.unsched_ids && j < L.nu; ++j) {
+                if (L.unsched_ids[j] == 0 || L.unsched_ids[j] > span) return range("unscheduled aggregator", L.unsched_ids[j]);
+                u.agg.push_back(L.unsched_ids[j] + lo);
+            }
+            u.explicit_ids = L.unsched_ids != nullptr;
+            if (with_arcs) {
+                const uint64_t at = u.arc_off.back();
+                for (size_t j = 1; j <= L.k; ++j) u.arc_off.push_back(at + L.arc_off[j]);
+                if (L.arc_off[L.k]) u.arcs.insert(u.arcs.end(), L.arcs, L.arcs + L.arc_off[L.k]);
+                if (u.arcs.size() > (size_t)INT32_MAX / 4) return b->fail(KS_E_RANGE, "too many arcs on one device");
+            }
+            u.touched.push_back(i);
+        }
+        u.task_goff.push_back(u.tasks.size());
+        u.arc_goff.push_back(u.arcs.size());
+    }
+    u.view.ng = l.graphs.size();
+    u.view.off = l.off.data();
+    u.view.graph = l.graphs.data();
+    u.view.arc_goff = u.arc_goff.data();
+    return KS_OK;
+}
+
+// All three task calls: every list checked on every local device first, then ONE lone call
+// per device on its union input (call(ctx, lists, left of the union's tasks, stats)), under the
+// view that lets its messages name graphs. A device that changed gets its touched graphs'
+// auto-sink records (supplies: tasks arrived or left) and its gather rows recounted, and
+// the bindings it returned leave the union's numbering.
+template <class Stats, class Call>
+int batch_task_call(ks_batch* b, size_t ngraphs, const ks_batch_task_list* lists, bool with_arcs, bool supplies,
+                    uint64_t* const* left, Stats* stats, Call call) {
+    if (!b) return KS_E_INVALID;
+    if (int rc = check_lists(b, ngraphs, lists, with_arcs)) return rc;
+    std::vector<UnionLists> us(b->loc.size());
+    for (size_t li = 0; li < b->loc.size(); ++li)
+        if (int rc = build_union(b, b->loc[li], lists, with_arcs, us[li])) return rc;
+    Stats sum;
+    std::memset(&sum, 0, sizeof(sum));
+    static_assert(sizeof(Stats) % sizeof(int64_t) == 0, "task call stats are int64 counters");
+    if (stats) *stats = sum;
+    for (size_t li = 0; li < b->loc.size(); ++li) {
+        auto& l = b->loc[li];
+        const UnionLists& u = us[li];
+        if (u.touched.empty()) continue;
+        Stats st;
+        std::memset(&st, 0, sizeof(st));
+        std::vector<uint64_t> hl(u.tasks.size());
+        l.ctx->view = &u.view;
+        int rc = call(l.ctx, u, hl.data(), &st);
+        l.ctx->view = nullptr;
+        if (rc) return b->fail(rc, "rank " + std::to_string(l.grank) + ": " + ks_last_error(l.ctx));
+        for (size_t w = 0; w < sizeof(Stats) / sizeof(int64_t); ++w)
+            reinterpret_cast<int64_t*>(&sum)[w] += reinterpret_cast<const int64_t*>(&st)[w];
+        if (supplies && l.ctx->opts.auto_sink) {
+            std::vector<ks_delta> sinks;
+            for (size_t i : u.touched) append_auto_sink(l, i, sinks, sinks.size());
+            if (!sinks.empty()) rc = ks_apply_deltas(l.ctx, sinks.data(), sinks.size());
+            if (rc) return b->fail(rc, "rank " + std::to_string(l.grank) + ": " + ks_last_error(l.ctx));
+        }
+        if (supplies) recompute_toff(l);
+        for (size_t i : u.touched) {
+            uint64_t* out = left ? left[(size_t)l.graphs[i]] : nullptr;
+            if (!out) continue;
+            const uint64_t lo = (uint64_t)l.off[i];
+            for (uint64_t j = u.task_goff[i]; j < u.task_goff[i + 1]; ++j) out[j - u.task_goff[i]] = hl[j] ? hl[j] - lo : 0;
+        }
+    }
+    if (stats) *stats = sum;
+    return KS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -886,6 +1023,100 @@ int ks_batch_commit_preemptive(ks_batch* b, int32_t flags, int64_t continuation_
                             return ks_commit_preemptive(c, flags, continuation_cost, preemption_cost, nullptr, 0, o,
                                                         ocap, n, st);
                         });
+}
+
+// ---- batch rounds, the task side: arrivals, completions, refreshes, bindings, costs ----
+
+int ks_batch_add_tasks(ks_batch* b, int32_t flags, size_t ngraphs, const ks_batch_task_list* lists,
+                       int64_t unsched_sink_cost, ks_add_stats* stats) {
+    return batch_task_call(b, ngraphs, lists, true, true, nullptr, stats,
+                           [&](ks_ctx* c, const UnionLists& u, uint64_t*, ks_add_stats* st) {
+                               return ks_add_tasks(c, flags, u.tasks.data(), u.tasks.size(), u.arc_off.data(),
+                                                   u.arcs.data(), u.agg_ptr(), u.agg.size(), unsched_sink_cost, st);
+                           });
+}
+
+int ks_batch_complete_tasks(ks_batch* b, int32_t flags, size_t ngraphs, const ks_batch_task_list* lists,
+                            uint64_t* const* left, ks_complete_stats* stats) {
+    return batch_task_call(b, ngraphs, lists, false, true, left, stats,
+                           [&](ks_ctx* c, const UnionLists& u, uint64_t* hl, ks_complete_stats* st) {
+                               return ks_complete_tasks(c, flags, u.tasks.data(), u.tasks.size(), u.agg_ptr(),
+                                                        u.agg.size(), hl, st);
+                           });
+}
+
+int ks_batch_update_tasks(ks_batch* b, int32_t flags, size_t ngraphs, const ks_batch_task_list* lists,
+                          int64_t unsched_sink_cost, ks_update_stats* stats) {
+    return batch_task_call(b, ngraphs, lists, true, false, nullptr, stats,
+                           [&](ks_ctx* c, const UnionLists& u, uint64_t*, ks_update_stats* st) {
+                               return ks_update_tasks(c, flags, u.tasks.data(), u.tasks.size(), u.arc_off.data(),
+                                                      u.arcs.data(), u.agg_ptr(), u.agg.size(), unsched_sink_cost, st);
+                           });
+}
+
+int ks_batch_get_bindings(ks_batch* b, size_t g, const uint64_t* task, uint64_t* pu, size_t k) {
+    if (!b) return KS_E_INVALID;
+    if (k && (!task || !pu)) return b->fail(KS_E_INVALID, "null binding array");
+    size_t i = 0;
+    ks_batch::Local* l = owner_of(b, g, &i);
+    if (!l) return b->fail(KS_E_INVALID, "graph " + std::to_string(g) + " is not on this rank");
+    const uint64_t lo = (uint64_t)l->off[i], span = (uint64_t)(l->off[i + 1] - l->off[i]);
+    const std::vector<NodeRec>& nodes = l->ctx->nodes;
+    std::vector<uint64_t> t(k);
+    for (size_t j = 0; j < k; ++j) {
+        if (task[j] == 0 || task[j] > span)
+            return b->fail(KS_E_RANGE, "graph " + std::to_string(g) + ": binding outside the graph's ids");
+        t[j] = task[j] + lo;
+        if (t[j] >= nodes.size() || !nodes[t[j]].alive || nodes[t[j]].type != KS_NODE_TASK)
+            return b->fail(KS_E_INVALID, "graph " + std::to_string(g) + ": binding of a node that is not a live task: " +
+                                             std::to_string(task[j]));
+    }
+    const int rc = ks_get_bindings(l->ctx, t.data(), pu, k);
+    if (rc) return b->fail(rc, ks_last_error(l->ctx));
+    for (size_t j = 0; j < k; ++j)
+        if (pu[j]) pu[j] -= lo;
+    return KS_OK;
+}
+
+int ks_batch_update_unsched_costs(ks_batch* b, size_t ngraphs, const ks_batch_task_list* lists, int32_t mode,
+                                  int64_t cost, int64_t continuation_cost, size_t* changed) {
+    if (!b) return KS_E_INVALID;
+    if (changed) *changed = 0;
+    if (lists && ngraphs != b->ngraphs) return b->fail(KS_E_INVALID, "the list count differs from the loaded graphs");
+    // every local device's aggregators first (a bad id stops the call before any device changed)
+    std::vector<std::vector<uint64_t>> ids(b->loc.size());
+    for (size_t li = 0; lists && li < b->loc.size(); ++li) {
+        const auto& l = b->loc[li];
+        for (size_t i = 0; i < l.graphs.size(); ++i) {
+            const size_t g = (size_t)l.graphs[i];
+            const ks_batch_task_list& L = lists[g];
+            if (!L.nu) continue;
+            if (!L.unsched_ids) return b->fail(KS_E_INVALID, "graph " + std::to_string(g) + ": null aggregator array");
+            const uint64_t lo = (uint64_t)l.off[i], span = (uint64_t)(l.off[i + 1] - l.off[i]);
+            for (size_t j = 0; j < L.nu; ++j) {
+                const uint64_t id = L.unsched_ids[j];
+                if (id == 0 || id > span)
+                    return b->fail(KS_E_RANGE, "graph " + std::to_string(g) + ": unscheduled aggregator " + std::to_string(id) +
+                                                   " is outside the graph's ids 1.." + std::to_string(span));
+                if (id + lo >= l.ctx->nodes.size() || !l.ctx->nodes[id + lo].alive)
+                    return b->fail(KS_E_INVALID, "graph " + std::to_string(g) + ": unscheduled aggregator " +
+                                                     std::to_string(id) + " is not a live node");
+                ids[li].push_back(id + lo);
+            }
+        }
+    }
+    size_t total = 0;
+    for (size_t li = 0; li < b->loc.size(); ++li) {
+        auto& l = b->loc[li];
+        if (lists && ids[li].empty()) continue;
+        size_t ch = 0;
+        const int rc = ks_update_unsched_costs(l.ctx, lists ? ids[li].data() : nullptr, ids[li].size(), mode, cost,
+                                               continuation_cost, &ch);
+        if (rc) return b->fail(rc, "rank " + std::to_string(l.grank) + ": " + ks_last_error(l.ctx));
+        total += ch;
+    }
+    if (changed) *changed = total;
+    return KS_OK;
 }
 
 }  // extern "C"

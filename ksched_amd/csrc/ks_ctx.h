@@ -44,6 +44,7 @@ struct ks_ctx {
     bool store_bad = false;                // a load / apply failed on the device: reload first
     bool every_sink = false;               // a ks_batch union: one sink per graph, and a commit's capacity
                                            //   refresh starts from all of them (a lone context refuses that)
+    const ks::BatchView* view = nullptr;   // set by a ks_batch task call around its lone twin: the ids' graphs
     std::vector<ks_flow> flows;
 
     int fail(int code, const std::string& msg) {

@@ -20,6 +20,21 @@ namespace ks {
 struct EngineImpl;
 struct CommitCtl;   // ks_sched.h
 
+// A batch call's ids (ks_batch_add_tasks, ks_batch_complete_tasks, ks_batch_update_tasks): the
+// lists of a union's graphs lie back to back. The task and aggregator ids are already the
+// union's (the host's O(k) part); the arcs' heads are still in each graph's own numbering and
+// leave it on the device (sched_translate_heads). Messages name a node as its caller knows
+// it: the graph and the graph-local id.
+struct BatchView {
+    size_t ng = 0;                        // graphs of this device's union
+    const int64_t* off = nullptr;         // [ng + 1] graph i owns the union ids (off[i], off[i + 1]]
+    const int* graph = nullptr;           // [ng] the caller's number of graph i
+    const uint64_t* arc_goff = nullptr;   // [ng + 1] the first listed arc of graph i (calls with arcs)
+    uint64_t base_of(uint64_t id) const;  // the base of the graph that owns union id `id`
+};
+// "task 17" on a lone context, "graph 3: task 17" (graph-local) under a view; id: the context's own id.
+std::string id_name(const BatchView* bv, const char* what, uint64_t id);
+
 class Engine {
 public:
     Engine();
@@ -120,15 +135,18 @@ public:
     // invalid); a call with k == 0 whose refresh finds every capacity right changes nothing.
     int complete_tasks(int flags, const uint64_t* tasks, size_t k, const uint64_t* unsched_ids, size_t nu,
                        int64_t sink_slot, uint64_t* left, ks_complete_stats* stats, const RemoveEdits& make_edits,
-                       bool* dirty, bool* changed, std::string& err);
+                       bool* dirty, bool* changed, std::string& err, const BatchView* bv = nullptr);
     // ks_add_tasks (the k new task ids, checked and already entered in the host's node table,
     // with their arcs; the aggregators gain a unit per task). nslots: the node slots in use
     // with the new ids. Every refusal is found before make_edits is called, once, for the node
     // edits of the stream (the host's aggregates move there); *dirty is set from then on.
+    // sink_slot == kEverySink over a cell partition: every aggregator's record ends at the sink
+    // of its own cell. bv: the arcs' heads are graph-local (BatchView), also in update_tasks.
     using AddEdits = std::function<void(std::vector<NodeEdit>* edits)>;
     int add_tasks(const uint64_t* tasks, size_t k, const uint64_t* arc_off, const ks_task_arc* arcs,
                   const uint64_t* unsched_ids, size_t nu, int64_t sink_slot, int64_t sink_cost, int64_t nslots,
-                  ks_add_stats* stats, const AddEdits& make_edits, bool* dirty, std::string& err);
+                  ks_add_stats* stats, const AddEdits& make_edits, bool* dirty, std::string& err,
+                  const BatchView* bv = nullptr);
     // ks_add_resources (the n new resource nodes, checked and already entered in the host's node
     // table, and the m edges; first_pair: the first edge that repeats an earlier (parent, child),
     // m when none does). make_edits and *dirty as in add_tasks; *changed: records were applied.
@@ -141,7 +159,8 @@ public:
     // leaves the device state unknown); *changed: records were applied.
     int update_tasks(int flags, const uint64_t* tasks, size_t k, const uint64_t* arc_off, const ks_task_arc* arcs,
                      size_t first_pair, const uint64_t* unsched_ids, size_t nu, int64_t sink_slot, int64_t sink_cost,
-                     ks_update_stats* stats, bool* dirty, bool* changed, std::string& err);
+                     ks_update_stats* stats, bool* dirty, bool* changed, std::string& err,
+                     const BatchView* bv = nullptr);
     // ks_get_bindings: pu[i] = the device-kept binding of task[i] (ids checked by the caller).
     int get_bindings(const uint64_t* task, uint64_t* pu, size_t k, std::string& err);
     int device() const;

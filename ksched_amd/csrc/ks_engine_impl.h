@@ -354,6 +354,7 @@ struct EngineImpl {
     std::vector<int> h_cell_first;      // the cells' first node slots (k + 1: the last one ends the partition)
     bool cell_first_valid = false;      // cell_first / cell_dirty hold the current partition
     DBuf<int> cell_first, cell_dirty;
+    DBuf<int> cell_sink;                // a union's sink per cell (sched_cell_sinks), rebuilt by every call that reads it
     DBuf<int> cell_list;                // the cells of a partial launch
     std::vector<int> h_cell_dirty, h_cell_list;
     bool cells_kept = false;            // the last solve ended OK on the cell path and no build ran since:
@@ -538,6 +539,8 @@ int read_sctl(EngineImpl& s, std::string& err);
 int ensure_arcs(EngineImpl& s, int64_t need, std::string& err);
 int ensure_hash(EngineImpl& s, int64_t extra, std::string& err);
 int applied(EngineImpl& s, std::string& err);
+// cell_first / cell_dirty of the current partition on the device (a partition must exist)
+int ensure_cell_first(EngineImpl& s, std::string& err);
 // the cells a record stream (device memory) touches, before it reaches store_apply
 int mark_cells(EngineImpl& s, const ks_delta* recs, size_t k, const NodeEdit* edits, size_t ne, std::string& err);
 // the tail of a record stream generated on the device: room for nrec records in

@@ -200,6 +200,22 @@ __global__ void k_mark_cells(const ks_delta* __restrict__ recs, int k, const Nod
 
 }  // namespace
 
+// The partition's first slots and its cleared dirty flags reach the device once per partition.
+int impl::ensure_cell_first(EngineImpl& s, std::string& err) {
+    if (s.cell_first_valid) return KS_OK;
+    hipStream_t st = s.stream;
+    const int ncells = (int)s.cell_off.size() - 1;
+    s.h_cell_first.assign(s.cell_off.begin(), s.cell_off.end());   // cell i: slots [off[i], off[i+1])
+    KS_CHECK(s.cell_first.ensure(ncells + 1));
+    KS_CHECK(s.cell_dirty.ensure(ncells));
+    KS_CHECK(hipMemcpyAsync(s.cell_first.p, s.h_cell_first.data(), (ncells + 1) * sizeof(int), hipMemcpyHostToDevice,
+                            st));
+    KS_CHECK(hipMemsetAsync(s.cell_dirty.p, 0, ncells * sizeof(int), st));
+    KS_CHECK(hipStreamSynchronize(st));
+    s.cell_first_valid = true;
+    return KS_OK;
+}
+
 // The flags of k_mark_cells for a stream in device memory (the host's, uploaded by
 // run_apply, or a commit's, generated there). Without a partition there is nothing to mark.
 int impl::mark_cells(EngineImpl& s, const ks_delta* recs, size_t k, const NodeEdit* edits, size_t ne,
@@ -207,16 +223,7 @@ int impl::mark_cells(EngineImpl& s, const ks_delta* recs, size_t k, const NodeEd
     if (s.cell_off.size() < 2 || k + ne == 0) return KS_OK;
     hipStream_t st = s.stream;
     const int ncells = (int)s.cell_off.size() - 1;
-    if (!s.cell_first_valid) {
-        s.h_cell_first.assign(s.cell_off.begin(), s.cell_off.end());   // cell i: slots [off[i], off[i+1])
-        KS_CHECK(s.cell_first.ensure(ncells + 1));
-        KS_CHECK(s.cell_dirty.ensure(ncells));
-        KS_CHECK(hipMemcpyAsync(s.cell_first.p, s.h_cell_first.data(), (ncells + 1) * sizeof(int),
-                                hipMemcpyHostToDevice, st));
-        KS_CHECK(hipMemsetAsync(s.cell_dirty.p, 0, ncells * sizeof(int), st));
-        KS_CHECK(hipStreamSynchronize(st));
-        s.cell_first_valid = true;
-    }
+    if (int rc = ensure_cell_first(s, err)) return rc;
     hipLaunchKernelGGL(k_mark_cells, dim3(grid_for((long long)(k + ne), 1024)), dim3(BLK), 0, st, recs, (int)k, edits,
                        (int)ne, (const int*)s.cell_first.p, ncells, s.cell_dirty.p);
     KS_CHECK(hipGetLastError());

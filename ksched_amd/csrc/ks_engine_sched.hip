@@ -122,6 +122,58 @@ bool first_bad(int word, size_t n, size_t* idx) {
     return true;
 }
 
+// A union's sinks for the aggregator records of an arrival or a refresh (sink_slot == kEverySink
+// over a cell partition): the table is rebuilt on every call, one pass over the slot bytes.
+int wire_cell_sinks(EngineImpl& s, const SchedDev& d, AddDev& a, int64_t sink_slot, std::string& err) {
+    if (sink_slot != Engine::kEverySink || s.cell_off.size() < 2) return KS_OK;
+    const int ncells = (int)s.cell_off.size() - 1;
+    if (int rc = ensure_cell_first(s, err)) return rc;
+    KS_CHECK(s.cell_sink.ensure(ncells));
+    KS_CHECK(hipMemsetAsync(s.cell_sink.p, 0xff, ncells * sizeof(int), s.stream));
+    KS_CHECK(sched_cell_sinks(d, a.nst, s.cell_first.p, ncells, s.cell_sink.p, s.stream));
+    a.cell_sink = s.cell_sink.p;
+    a.cell_first = s.cell_first.p;
+    a.ncells = ncells;
+    return KS_OK;
+}
+
+// A batch call's heads leave their graphs' numbering on the device (d_goff, d_base: ng + 1 words each).
+int translate_heads(EngineImpl& s, const BatchView& bv, unsigned long long* d_goff, unsigned long long* d_base,
+                    unsigned long long* d_arcs, size_t na, AddCtl* ctl, std::string& err) {
+    KS_CHECK(hipMemcpyAsync(d_goff, bv.arc_goff, (bv.ng + 1) * 8, hipMemcpyHostToDevice, s.stream));
+    KS_CHECK(hipMemcpyAsync(d_base, bv.off, (bv.ng + 1) * 8, hipMemcpyHostToDevice, s.stream));
+    KS_CHECK(sched_translate_heads((ks_task_arc*)d_arcs, (int)na, d_goff, (const long long*)d_base, (int)bv.ng, ctl,
+                                   s.stream));
+    return KS_OK;
+}
+
+// The refusal of a head outside its graph's ids (word: AddCtl::bad_range).
+int range_refusal(const BatchView& bv, int word, const uint64_t* tasks, const uint64_t* arc_off, size_t k,
+                  const ks_task_arc* arcs, size_t na, std::string& err) {
+    size_t j;
+    if (!first_bad(word, na, &j) || j >= na) {
+        err = "inconsistent arc index";
+        return KS_E_DEVICE;
+    }
+    const size_t g = (size_t)(std::upper_bound(bv.arc_goff, bv.arc_goff + bv.ng, (uint64_t)j) - bv.arc_goff) - 1;
+    const size_t i = (size_t)(std::upper_bound(arc_off, arc_off + k, (uint64_t)j) - arc_off) - 1;
+    err = id_name(&bv, "task", tasks[i]) + ": head " + std::to_string(arcs[j].dst) + " is outside the graph's ids 1.." +
+          std::to_string(bv.off[g + 1] - bv.off[g]) + " (its highest id at the load plus the reserved ids)";
+    return KS_E_RANGE;
+}
+
+// The refusal of a gaining aggregator whose cell has no single sink (word: AddCtl::bad_sink).
+int sink_refusal(const BatchView* bv, int word, int64_t nst, std::string& err) {
+    size_t v;
+    if (!first_bad(word, (size_t)nst, &v)) {
+        err = "inconsistent aggregator slot";
+        return KS_E_DEVICE;
+    }
+    err = id_name(bv, "unscheduled aggregator", (uint64_t)v + 1) + " gains a unit, and its cell has no sink or several: "
+          "the capacity of its arc into the sink needs exactly one";
+    return KS_E_INVALID;
+}
+
 double ms(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
     return std::chrono::duration<double, std::milli>(b - a).count();
 }
@@ -141,6 +193,20 @@ __global__ void k_seed_sinks(int ncap, const unsigned char* __restrict__ alive, 
         }
 }
 }  // namespace
+
+uint64_t BatchView::base_of(uint64_t id) const {
+    // graph i owns the ids (off[i], off[i + 1]]
+    size_t i = (size_t)(std::lower_bound(off, off + ng + 1, (int64_t)id) - off);
+    i = i ? i - 1 : 0;
+    return (uint64_t)off[std::min(i, ng ? ng - 1 : 0)];
+}
+
+std::string id_name(const BatchView* bv, const char* what, uint64_t id) {
+    if (!bv || !bv->ng) return std::string(what) + " " + std::to_string(id);
+    size_t i = (size_t)(std::lower_bound(bv->off, bv->off + bv->ng + 1, (int64_t)id) - bv->off);
+    i = std::min(i ? i - 1 : 0, bv->ng - 1);
+    return "graph " + std::to_string(bv->graph[i]) + ": " + what + " " + std::to_string(id - (uint64_t)bv->off[i]);
+}
 
 // ------------------------------------------------- scheduler-side sweeps ---
 int Engine::set_bindings(const uint64_t* task, const uint64_t* pu, size_t k, std::string& err) {
@@ -664,7 +730,7 @@ int Engine::remove_resources(int flags, const uint64_t* roots, size_t k, int64_t
 // as one stream.
 int Engine::complete_tasks(int flags, const uint64_t* tasks, size_t k, const uint64_t* unsched_ids, size_t nu,
                            int64_t sink_slot, uint64_t* left, ks_complete_stats* stats, const RemoveEdits& make_edits,
-                           bool* dirty, bool* changed, std::string& err) {
+                           bool* dirty, bool* changed, std::string& err, const BatchView* bv) {
     EngineImpl& s = *p_;
     *dirty = *changed = false;
     if (stats) std::memset(stats, 0, sizeof(*stats));
@@ -724,7 +790,7 @@ int Engine::complete_tasks(int flags, const uint64_t* tasks, size_t k, const uin
         KS_CHECK(hipStreamSynchronize(st));
         if (h.bad_root) {
             const uint64_t id = tasks[k - (size_t)h.bad_root];
-            err = "task " + std::to_string(id) + " is not a live task node (0, beyond the graph, dead or of another type)";
+            err = id_name(bv, "task", id) + " is not a live task node (0, beyond the graph, dead or of another type)";
             return KS_E_INVALID;
         }
         np = h.nfront;
@@ -817,7 +883,8 @@ int Engine::complete_tasks(int flags, const uint64_t* tasks, size_t k, const uin
 // store_apply as one stream. Neither the residual CSR nor the topology BFS is needed.
 int Engine::add_tasks(const uint64_t* tasks, size_t k, const uint64_t* arc_off, const ks_task_arc* arcs,
                       const uint64_t* unsched_ids, size_t nu, int64_t sink_slot, int64_t sink_cost, int64_t nslots,
-                      ks_add_stats* stats, const AddEdits& make_edits, bool* dirty, std::string& err) {
+                      ks_add_stats* stats, const AddEdits& make_edits, bool* dirty, std::string& err,
+                      const BatchView* bv) {
     EngineImpl& s = *p_;
     *dirty = false;
     if (!k) return KS_OK;
@@ -841,6 +908,7 @@ int Engine::add_tasks(const uint64_t* tasks, size_t k, const uint64_t* arc_off, 
     a.sink = sink_slot >= 0 && sink_slot < nst ? sink_slot : -1;
     a.sink_cost = sink_cost;
     unsigned long long *d_tasks = nullptr, *d_off = nullptr, *d_arcs = nullptr, *d_agg = nullptr;
+    unsigned long long *d_goff = nullptr, *d_base = nullptr;
     rc = carve_scratch(s, [&](Carve<int>& ci, Carve<unsigned long long>& cu) {
         a.t_agg = ci.take((int64_t)k + 1);
         for (int** x : {&a.aflag, &a.a_off, &a.a_slot}) *x = ci.take(nst + 1);
@@ -849,6 +917,8 @@ int Engine::add_tasks(const uint64_t* tasks, size_t k, const uint64_t* arc_off, 
         d_off = cu.take(k + 1);
         d_arcs = cu.take(2 * na);
         d_agg = cu.take(nu);
+        d_goff = cu.take(bv ? bv->ng + 1 : 0);
+        d_base = cu.take(bv ? bv->ng + 1 : 0);
     }, nst + 1, true, err);
     if (rc) return rc;
     KS_CHECK(clear_ctl(s.add_ctl, st));
@@ -863,6 +933,9 @@ int Engine::add_tasks(const uint64_t* tasks, size_t k, const uint64_t* arc_off, 
     if (na) KS_CHECK(hipMemcpyAsync(d_arcs, arcs, na * sizeof(ks_task_arc), hipMemcpyHostToDevice, st));
     if (unsched_ids && nu) KS_CHECK(hipMemcpyAsync(d_agg, unsched_ids, nu * 8, hipMemcpyHostToDevice, st));
     SchedDev d = s.schd();
+    rc = wire_cell_sinks(s, d, a, sink_slot, err);
+    if (rc == KS_OK && bv && na) rc = translate_heads(s, *bv, d_goff, d_base, d_arcs, na, a.ctl, err);
+    if (rc) return rc;
     // ---- 1. heads, costs, the aggregators' gains and their arcs into the sink: one sync
     KS_CHECK(sched_add_check(d, a, unsched_ids ? d_agg : nullptr, (int)nu, st));
     KS_CHECK(exclusive_sum(s, (const int*)a.aflag, a.a_off, nst + 1, st));
@@ -874,6 +947,7 @@ int Engine::add_tasks(const uint64_t* tasks, size_t k, const uint64_t* arc_off, 
     auto task_of = [&](size_t j) {   // the last i with arc_off[i] ≤ j
         return (size_t)(std::upper_bound(arc_off, arc_off + k, (uint64_t)j) - arc_off) - 1;
     };
+    if (bv && h.bad_range) return range_refusal(*bv, h.bad_range, tasks, arc_off, k, arcs, na, err);
     if (h.bad_head || h.bad_cost) {   // the first offending arc in input order; on one arc the head comes first
         size_t jh, jc;
         if (!first_bad(h.bad_head, na, &jh) || !first_bad(h.bad_cost, na, &jc)) {
@@ -882,7 +956,7 @@ int Engine::add_tasks(const uint64_t* tasks, size_t k, const uint64_t* arc_off, 
         }
         const bool head = jh <= jc;
         const size_t j = head ? jh : jc;
-        const std::string who = "task " + std::to_string(tasks[task_of(j)]) + ": ";
+        const std::string who = id_name(bv, "task", tasks[task_of(j)]) + ": ";
         if (head) {
             err = who + "head " + std::to_string(arcs[j].dst) + " is not a node that was live before the call and is no "
                   "task (0, beyond the graph, dead, a task, or a task of this call)";
@@ -899,12 +973,13 @@ int Engine::add_tasks(const uint64_t* tasks, size_t k, const uint64_t* arc_off, 
         }
         const bool multi = im <= in;
         const uint64_t id = tasks[multi ? im : in];
-        err = multi ? "task " + std::to_string(id) + " has more than one arc into unscheduled aggregators: a task has one job"
-                    : "task " + std::to_string(id) + " has no arc into a node with an arc into the sink; an aggregator "
+        err = multi ? id_name(bv, "task", id) + " has more than one arc into unscheduled aggregators: a task has one job"
+                    : id_name(bv, "task", id) + " has no arc into a node with an arc into the sink; an aggregator "
                       "whose capacity fell to 0 has lost that arc: pass the aggregators' ids (unsched_ids)";
         return KS_E_INVALID;
     }
-    if (h.units && a.sink < 0) {
+    if (a.cell_sink && h.bad_sink) return sink_refusal(bv, h.bad_sink, nst, err);
+    if (h.units && a.sink < 0 && !a.cell_sink) {
         err = "an unscheduled aggregator's capacity needs exactly one sink";
         return KS_E_INVALID;
     }
@@ -1125,7 +1200,8 @@ int Engine::add_resources(const ks_res_node* nodes, size_t n, const ks_res_arc* 
 // and the aggregator records (ascending id) reach store_apply as one stream. No node is edited.
 int Engine::update_tasks(int flags, const uint64_t* tasks, size_t k, const uint64_t* arc_off, const ks_task_arc* arcs,
                          size_t first_pair, const uint64_t* unsched_ids, size_t nu, int64_t sink_slot,
-                         int64_t sink_cost, ks_update_stats* stats, bool* dirty, bool* changed, std::string& err) {
+                         int64_t sink_cost, ks_update_stats* stats, bool* dirty, bool* changed, std::string& err,
+                         const BatchView* bv) {
     EngineImpl& s = *p_;
     *dirty = *changed = false;
     if (!k) return KS_OK;
@@ -1157,6 +1233,7 @@ int Engine::update_tasks(int flags, const uint64_t* tasks, size_t k, const uint6
     a.sink = sink_slot >= 0 && sink_slot < nst ? sink_slot : -1;
     a.sink_cost = sink_cost;
     unsigned long long *d_tasks = nullptr, *d_off = nullptr, *d_arcs = nullptr, *d_agg = nullptr;
+    unsigned long long *d_goff = nullptr, *d_base = nullptr;
     rc = carve_scratch(s, [&](Carve<int>& ci, Carve<unsigned long long>& cu) {
         for (int** x : {&u.t_own, &a.aflag, &a.a_off, &a.a_slot}) *x = ci.take(nst + 1);
         for (int** x : {&u.t_slot, &u.t_agg, &u.nch, &u.ch_off}) *x = ci.take((int64_t)k + 1);
@@ -1167,6 +1244,8 @@ int Engine::update_tasks(int flags, const uint64_t* tasks, size_t k, const uint6
         d_off = cu.take(k + 1);
         d_arcs = cu.take(2 * na);
         d_agg = cu.take(nu);
+        d_goff = cu.take(bv ? bv->ng + 1 : 0);
+        d_base = cu.take(bv ? bv->ng + 1 : 0);
     }, nst + 1, true, err);
     if (rc) return rc;
     KS_CHECK(clear_ctl(s.upd_ctl, st));
@@ -1185,6 +1264,9 @@ int Engine::update_tasks(int flags, const uint64_t* tasks, size_t k, const uint6
     if (na) KS_CHECK(hipMemcpyAsync(d_arcs, arcs, na * sizeof(ks_task_arc), hipMemcpyHostToDevice, st));
     if (unsched_ids && nu) KS_CHECK(hipMemcpyAsync(d_agg, unsched_ids, nu * 8, hipMemcpyHostToDevice, st));
     SchedDev d = s.schd();
+    rc = wire_cell_sinks(s, d, a, sink_slot, err);
+    if (rc == KS_OK && bv && na) rc = translate_heads(s, *bv, d_goff, d_base, d_arcs, na, a.ctl, err);
+    if (rc) return rc;
     // ---- 1. ids, heads, costs, the diff, the aggregators' gains and their arcs into the sink: one sync
     KS_CHECK(sched_upd_check(d, u, unsched_ids ? d_agg : nullptr, (int)nu, walk, st));
     if (walk) KS_CHECK(exclusive_sum(s, (const int*)u.nch, u.ch_off, (int64_t)k + 1, st));
@@ -1201,13 +1283,14 @@ int Engine::update_tasks(int flags, const uint64_t* tasks, size_t k, const uint6
     KS_CHECK(hipMemcpyAsync(&ha, a.ctl, sizeof(AddCtl), hipMemcpyDeviceToHost, st));
     KS_CHECK(hipStreamSynchronize(st));
     const auto t1 = std::chrono::steady_clock::now();
+    if (bv && ha.bad_range) return range_refusal(*bv, ha.bad_range, tasks, arc_off, k, arcs, na, err);
     if (h.bad_task) {
         size_t i;
         if (!first_bad(h.bad_task, k, &i)) {
             err = "inconsistent task index";
             return KS_E_DEVICE;
         }
-        err = "task " + std::to_string(tasks[i]) + " is not a live task node listed once (0, beyond "
+        err = id_name(bv, "task", tasks[i]) + " is not a live task node listed once (0, beyond "
               "the graph, dead, of another type, or listed before)";
         return KS_E_INVALID;
     }
@@ -1222,7 +1305,7 @@ int Engine::update_tasks(int flags, const uint64_t* tasks, size_t k, const uint6
             return KS_E_DEVICE;
         }
         const size_t j = std::min({jh, first_pair, jc});
-        const std::string who = "task " + std::to_string(tasks[task_of(j)]) + ": ";
+        const std::string who = id_name(bv, "task", tasks[task_of(j)]) + ": ";
         if (j == jh) {
             err = who + "head " + std::to_string(arcs[j].dst) + " is not a live node that is no task (0, beyond the graph, "
                   "dead or a task)";
@@ -1244,14 +1327,15 @@ int Engine::update_tasks(int flags, const uint64_t* tasks, size_t k, const uint6
         }
         const bool multi = im <= in;
         const uint64_t id = tasks[multi ? im : in];
-        err = multi ? "task " + std::to_string(id) + " would have arcs into two unscheduled aggregators: a task does not "
+        err = multi ? id_name(bv, "task", id) + " would have arcs into two unscheduled aggregators: a task does not "
                       "change its job"
-                    : "task " + std::to_string(id) + " is unbound and would have no arc into a node with an arc into the "
+                    : id_name(bv, "task", id) + " is unbound and would have no arc into a node with an arc into the "
                       "sink; an aggregator whose capacity fell to 0 has lost that arc: pass the aggregators' ids "
                       "(unsched_ids)";
         return KS_E_INVALID;
     }
-    if (h.units && a.sink < 0) {
+    if (a.cell_sink && ha.bad_sink) return sink_refusal(bv, ha.bad_sink, nst, err);
+    if (h.units && a.sink < 0 && !a.cell_sink) {
         err = "an unscheduled aggregator's capacity needs exactly one sink";
         return KS_E_INVALID;
     }

@@ -192,8 +192,8 @@ struct NodeTxn {
     }
     // ADD_NODE (ks_apply_deltas, ks_add_tasks): the id in range and not a live node (graph.go:95-98)
     int add(uint64_t id, int64_t excess, int32_t type) {
-        if (id == 0 || id >= kMaxId) return c->fail(KS_E_RANGE, "node id " + std::to_string(id) + " out of range");
-        if (node_alive(c, id)) return c->fail(KS_E_INVALID, "node " + std::to_string(id) + " already present");
+        if (id == 0 || id >= kMaxId) return c->fail(KS_E_RANGE, ks::id_name(c->view, "node id", id) + " out of range");
+        if (node_alive(c, id)) return c->fail(KS_E_INVALID, ks::id_name(c->view, "node", id) + " already present");
         touch(id);
         c->nodes[id] = NodeRec{excess, type, true, true};
         return KS_OK;
@@ -251,7 +251,7 @@ int64_t sink_slot(const ks_ctx* c, bool every_sink = false) {
 int check_aggregators(ks_ctx* c, const uint64_t* ids, size_t k) {
     for (size_t i = 0; ids && i < k; ++i)
         if (!node_alive(c, ids[i]))
-            return c->fail(KS_E_INVALID, "unscheduled aggregator " + std::to_string(ids[i]) + " is not a live node");
+            return c->fail(KS_E_INVALID, ks::id_name(c->view, "unscheduled aggregator", ids[i]) + " is not a live node");
     return KS_OK;
 }
 
@@ -261,7 +261,7 @@ int check_task_lists(ks_ctx* c, const uint64_t* tasks, size_t k, const uint64_t*
     if (arc_off[0] != 0) return c->fail(KS_E_INVALID, "arc_off[0] must be 0");
     for (size_t i = 0; i < k; ++i)
         if (arc_off[i + 1] < arc_off[i])
-            return c->fail(KS_E_INVALID, "arc_off decreases at task " + std::to_string(tasks[i]));
+            return c->fail(KS_E_INVALID, "arc_off decreases at " + ks::id_name(c->view, "task", tasks[i]));
     if (arc_off[k] && !arcs) return c->fail(KS_E_INVALID, "null arc array");
     return KS_OK;
 }
@@ -863,7 +863,7 @@ int ks_complete_tasks(ks_ctx* c, int32_t flags, const uint64_t* tasks, size_t k,
     };
     bool dirty = false, changed = false;
     const int rc = c->eng.complete_tasks(flags, tasks, k, unsched_ids, unsched_ids ? nu : 0, sink_slot(c, true), left,
-                                         stats, make_edits, &dirty, &changed, c->err);
+                                         stats, make_edits, &dirty, &changed, c->err, c->view);
     follow_rebuild(c);
     if (rc) return delta_failed(c, rc, txn ? &*txn : nullptr, dirty, stats);   // (as in ks_remove_resources)
     if (changed) drop_solution(c);
@@ -895,8 +895,9 @@ int ks_add_tasks(ks_ctx* c, int32_t flags, const uint64_t* tasks, size_t k, cons
         }
     bool dirty = false;
     auto make_edits = [&](std::vector<ks::NodeEdit>* edits) { txn.edits(*edits); };
-    const int rc = c->eng.add_tasks(tasks, k, arc_off, arcs, unsched_ids, unsched_ids ? nu : 0, sink_slot(c),
-                                    unsched_sink_cost, c->nslots(), stats, make_edits, &dirty, c->err);
+    // (a union's aggregators gain on their own cells' sinks: kEverySink; a lone context with several refuses)
+    const int rc = c->eng.add_tasks(tasks, k, arc_off, arcs, unsched_ids, unsched_ids ? nu : 0, sink_slot(c, true),
+                                    unsched_sink_cost, c->nslots(), stats, make_edits, &dirty, c->err, c->view);
     if (rc) return delta_failed(c, rc, &txn, dirty, stats);
     drop_solution(c);
     return KS_OK;
@@ -996,7 +997,7 @@ int ks_update_tasks(ks_ctx* c, int32_t flags, const uint64_t* tasks, size_t k, c
     }
     bool dirty = false, changed = false;
     const int rc = c->eng.update_tasks(flags, tasks, k, arc_off, arcs, first_pair, unsched_ids, unsched_ids ? nu : 0,
-                                       sink_slot(c), unsched_sink_cost, stats, &dirty, &changed, c->err);
+                                       sink_slot(c, true), unsched_sink_cost, stats, &dirty, &changed, c->err, c->view);
     follow_rebuild(c);
     if (rc) return delta_failed(c, rc, nullptr, dirty, stats);
     if (changed) drop_solution(c);

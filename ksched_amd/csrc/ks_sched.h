@@ -222,7 +222,7 @@ hipError_t sched_gather_bindings(const SchedDev& d, const unsigned long long* id
 // stream positions for store_apply. Only the node store, the arc table and the index are
 // read: no residual CSR is needed and no BFS runs.
 
-// Device counters of one arrival; the host reads them in one 32-byte copy.
+// Device counters of one arrival; the host reads them in one copy.
 struct AddCtl {
     int bad_head;    // na − the index of the first arc whose head is 0, beyond the graph, dead or a task, 0 none
     int bad_cost;    // na − the index of the first arc whose cost is beyond ±2^40, 0 none
@@ -232,6 +232,8 @@ struct AddCtl {
     int rec_upd;     // gaining aggregators whose arc into the sink the store holds (UPDATE_ARC)
     int rec_add;     // gaining aggregators without it (ADD_ARC)
     int rec_agg;     // the scan's total: rec_upd + rec_add
+    int bad_sink;    // per-cell sinks: nst − the slot of the first gaining aggregator whose cell has no single sink, 0 none
+    int bad_range;   // batch ids: na − the index of the first arc whose head lies outside 1..span of its graph, 0 none
 };
 
 // Inputs and scratch of one arrival (device pointers; nst node slots before the call).
@@ -251,11 +253,27 @@ struct AddDev {
     int null_rule;                     // unsched_ids == NULL: a task without an aggregator arc is refused
     long long sink;                    // the sink's node slot, −1: other than one sink
     long long sink_cost;               // cost of a re-created aggregator → sink arc
+    const int* cell_sink;              // [ncells] a union's sinks (sched_cell_sinks): an aggregator's records end
+                                       //   at its own cell's sink, and sink is not read; nullptr: the one sink
+    const int* cell_first;             // [ncells + 1] the cells' first node slots
+    int ncells;
     const unsigned long long* hkey;    // the store's (src, dst) index (ks_store.h)
     const int* hval;
     int hmask;                         // capacity − 1, −1: no index yet
     AddCtl* ctl;
 };
+
+// A union's sinks: cell_sink[c] = the node slot of cell c's one live sink, negative when the
+// cell has none or several (cell_sink starts at −1 in every word; nst node slots are read, each
+// live sink finds its cell by bisection over cell_first).
+hipError_t sched_cell_sinks(const SchedDev& d, long long nst, const int* cell_first, int ncells, int* cell_sink,
+                            hipStream_t st);
+// A batch call's listed arcs, the graphs' lists back to back (graph g owns the arcs
+// [arc_goff[g], arc_goff[g + 1]) and the union ids (base[g], base[g + 1]]): one lane per arc
+// finds its graph by bisection, checks 1 ≤ dst ≤ span (else ctl->bad_range, and the head
+// becomes 0) and adds the graph's base in place.
+hipError_t sched_translate_heads(ks_task_arc* arcs, int na, const unsigned long long* arc_goff, const long long* base,
+                                 int ng, AddCtl* ctl, hipStream_t st);
 
 // The aggregator flags (ids: nu node ids, or nullptr for every type-0 node with an arc into the
 // sink) into a.fl; the head pass, one lane per arc (head and cost checks, t_agg, agg_cnt with one

@@ -781,6 +781,59 @@ __global__ void k_add_task_check(AddDev a) {
     }
 }
 
+// The cell of node slot v: the last one with first[cell] ≤ v (as k_mark_cells), −1 outside the partition.
+__device__ __forceinline__ int cell_of_slot(const int* __restrict__ first, int ncells, long long v) {
+    if (ncells < 1 || v < first[0] || v >= first[ncells]) return -1;
+    int lo = 0, hi = ncells;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (first[mid] <= v) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// A union's sink table (one word per cell, −1 before): the first live sink of a cell claims its
+// word, any further one turns it into −2. A union has one sink per graph, far apart in slot
+// space: each is its own atomic (nothing to combine per wave, as in k_seed_sinks).
+__global__ void k_cell_sinks(long long nst, const unsigned char* __restrict__ alive,
+                             const unsigned char* __restrict__ type, const int* __restrict__ first, int ncells,
+                             int* __restrict__ cell_sink) {
+    for (long long v = blockIdx.x * (long long)SB + threadIdx.x; v < nst; v += (long long)gridDim.x * SB) {
+        if (!alive[v] || type[v] != KS_NODE_SINK) continue;
+        const int c = cell_of_slot(first, ncells, v);
+        if (c < 0) continue;
+        if (atomicCAS(&cell_sink[c], -1, (int)v) != -1) atomicExch(&cell_sink[c], -2);
+    }
+}
+
+// The listed arcs of a batch call leave their graphs' own ids: arc j belongs to the last graph g
+// with arc_goff[g] ≤ j (a graph without arcs shares its offset with its successor, which owns
+// the arc). A head outside 1..span is reported (the first in input order wins) and becomes 0,
+// which the head pass refuses as well; every other head gets its graph's base.
+__global__ void k_translate_heads(ks_task_arc* __restrict__ arcs, int na, const unsigned long long* __restrict__ arc_goff,
+                                  const long long* __restrict__ base, int ng, AddCtl* __restrict__ ctl) {
+    for (long long j = blockIdx.x * (long long)SB + threadIdx.x; j < na; j += (long long)gridDim.x * SB) {
+        const int g = task_of_arc(arc_goff, ng, j);
+        const unsigned long long span = (unsigned long long)(base[g + 1] - base[g]);
+        const unsigned long long dst = arcs[j].dst;
+        if (dst < 1 || dst > span) {
+            atomicMax(&ctl->bad_range, (int)(na - j));
+            arcs[j].dst = 0;
+        } else {
+            arcs[j].dst = dst + (unsigned long long)base[g];
+        }
+    }
+}
+
+// The sink an aggregator's capacity record ends at: the one sink, or over a union's sink table
+// the sink of the aggregator's own cell; negative: there is no such sink.
+__device__ __forceinline__ long long add_sink_of(const AddDev& a, long long v) {
+    if (!a.cell_sink) return a.sink;
+    const int c = cell_of_slot(a.cell_first, a.ncells, v);
+    return c < 0 ? -1 : (long long)a.cell_sink[c];
+}
+
 // updateUnscheduledAggNode(+1) (:1291-1305): the store's (src, dst) index tells "raise the
 // capacity" (the arc is there) from "the arc is gone, re-create it" (:1300-1304).
 __global__ void k_add_agg_flags(SchedDev d, AddDev a) {
@@ -789,8 +842,10 @@ __global__ void k_add_agg_flags(SchedDev d, AddDev a) {
         int f = 0, slot = -1;
         if (v < a.nst && a.agg_cnt[v] > 0) {
             f = 1;
-            if (a.sink >= 0 && a.hmask >= 0) {
-                const int e = store_hfind(a.hkey, a.hmask, arc_hkey(v + 1, a.sink + 1));
+            const long long sink = add_sink_of(a, v);
+            if (a.cell_sink && sink < 0) atomicMax(&a.ctl->bad_sink, (int)(a.nst - v));
+            if (sink >= 0 && a.hmask >= 0) {
+                const int e = store_hfind(a.hkey, a.hmask, arc_hkey(v + 1, sink + 1));
                 const int s = e >= 0 ? a.hval[e] : -1;
                 if (s >= 0 && s < d.hi && d.a_alive[s]) slot = s;
             }
@@ -835,10 +890,11 @@ __global__ void k_add_emit_aggs(SchedDev d, AddDev a, long long base, ks_delta* 
         if (!a.aflag[v]) continue;
         const long long cnt = (long long)a.agg_cnt[v];
         const int s = a.a_slot[v];
+        const int sink = (int)add_sink_of(a, v);   // (≥ 0: the host refused the call otherwise)
         recs[base + a.a_off[v]] =
-            s >= 0 ? arc_record(KS_UPDATE_ARC, d.a_type[s], (int)v, (int)a.sink, d.a_low[s], d.a_cap[s] + cnt, d.a_cost[s],
+            s >= 0 ? arc_record(KS_UPDATE_ARC, d.a_type[s], (int)v, sink, d.a_low[s], d.a_cap[s] + cnt, d.a_cost[s],
                                 d.a_cost[s])
-                   : arc_record(KS_ADD_ARC, 0, (int)v, (int)a.sink, 0, cnt, a.sink_cost, 0);
+                   : arc_record(KS_ADD_ARC, 0, (int)v, sink, 0, cnt, a.sink_cost, 0);
     }
 }
 
@@ -1369,6 +1425,21 @@ hipError_t sched_add_check(const SchedDev& d, const AddDev& a, const unsigned lo
     if (a.na) hipLaunchKernelGGL(k_add_heads, dim3(grid(a.na)), dim3(SB), 0, st, d, a);
     if (a.k) hipLaunchKernelGGL(k_add_task_check, dim3(grid(a.k)), dim3(SB), 0, st, a);
     hipLaunchKernelGGL(k_add_agg_flags, dim3(grid(a.nst + 1)), dim3(SB), 0, st, d, a);
+    return hipGetLastError();
+}
+
+hipError_t sched_cell_sinks(const SchedDev& d, long long nst, const int* cell_first, int ncells, int* cell_sink,
+                            hipStream_t st) {
+    if (nst > 0 && ncells > 0)
+        hipLaunchKernelGGL(k_cell_sinks, dim3(grid(nst)), dim3(SB), 0, st, nst, d.n_alive, d.n_type, cell_first, ncells,
+                           cell_sink);
+    return hipGetLastError();
+}
+
+hipError_t sched_translate_heads(ks_task_arc* arcs, int na, const unsigned long long* arc_goff, const long long* base,
+                                 int ng, AddCtl* ctl, hipStream_t st) {
+    if (na > 0 && ng > 0)
+        hipLaunchKernelGGL(k_translate_heads, dim3(grid(na)), dim3(SB), 0, st, arcs, na, arc_goff, base, ng, ctl);
     return hipGetLastError();
 }
 

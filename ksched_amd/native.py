@@ -28,6 +28,8 @@ EXPORTED_SYMBOLS = (
     "ks_batch_slots", "ks_batch_owner", "ks_batch_block_len", "ks_batch_unpack",
     "ks_batch_node_offsets", "ks_batch_translate_deltas", "ks_batch_reserve", "ks_batch_apply_deltas",
     "ks_batch_get_graph", "ks_batch_set_bindings", "ks_batch_commit_schedule", "ks_batch_commit_preemptive",
+    "ks_batch_add_tasks", "ks_batch_complete_tasks", "ks_batch_update_tasks", "ks_batch_get_bindings",
+    "ks_batch_update_unsched_costs",
 )
 ABI_VERSION = 5
 KS_DELTA_PLACE, KS_DELTA_PREEMPT, KS_DELTA_MIGRATE, KS_DELTA_NOOP = 0, 1, 2, 3
@@ -173,6 +175,57 @@ class KsGrowStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
+class KsBatchTaskList(C.Structure):
+    """ks_batch_task_list (48 B): one graph's part of a batch task call, in the graph's own ids."""
+    _fields_ = [("tasks", C.c_void_p), ("k", C.c_size_t), ("arc_off", C.c_void_p), ("arcs", C.c_void_p),
+                ("unsched_ids", C.c_void_p), ("nu", C.c_size_t)]
+
+
+def pack_task_lists(ngraphs: int, lists, unsched_ids=None, with_arcs: bool = True):
+    """One ks_batch_task_list per graph. lists[g]: None (graph g untouched), or with_arcs
+    (tasks, arc_off, dst, cost) as Context.add_tasks takes them, else the task ids alone.
+    unsched_ids: None (the NULL rule) or one id array (or None) per graph. → (the ctypes
+    array, the numpy arrays it points into: per graph a dict with tasks, arc_off, arcs
+    (TASK_ARC_DT), unsched_ids, or None)."""
+    if lists is None:
+        lists = [None] * ngraphs
+    if len(lists) != ngraphs or (unsched_ids is not None and len(unsched_ids) != ngraphs):
+        raise ValueError("one entry (or None) per loaded graph")
+    out = (KsBatchTaskList * max(1, ngraphs))()
+    keep = []
+    for g in range(ngraphs):
+        e = lists[g]
+        agg = None if unsched_ids is None or unsched_ids[g] is None else \
+            np.ascontiguousarray(unsched_ids[g], np.uint64).reshape(-1)
+        if e is None and agg is None:
+            keep.append(None)
+            continue
+        a = {"tasks": None, "arc_off": None, "arcs": None, "unsched_ids": agg}
+        if e is not None:
+            a["tasks"] = np.ascontiguousarray(e[0] if with_arcs else e, np.uint64).reshape(-1)
+            if with_arcs:
+                _, off, dst, cost = e
+                a["arc_off"] = np.ascontiguousarray(off, np.uint64).reshape(-1)
+                if a["arc_off"].shape[0] != a["tasks"].shape[0] + 1:
+                    raise ValueError("arc_off has one entry more than tasks")
+                dst, cost = np.asarray(dst, np.uint64).reshape(-1), np.asarray(cost, np.int64).reshape(-1)
+                a["arcs"] = np.zeros(max(dst.size, 1), TASK_ARC_DT)
+                a["arcs"]["dst"][:dst.size] = dst
+                a["arcs"]["cost"][:cost.size] = cost
+            out[g].tasks = a["tasks"].ctypes.data
+            out[g].k = a["tasks"].shape[0]
+            if with_arcs:
+                out[g].arc_off = a["arc_off"].ctypes.data
+                out[g].arcs = a["arcs"].ctypes.data
+        if agg is not None:
+            if agg.shape[0] == 0:   # an empty list names no aggregator: not NULL, which is the NULL rule
+                a["unsched_ids"] = np.zeros(1, np.uint64)
+            out[g].unsched_ids = a["unsched_ids"].ctypes.data
+            out[g].nu = agg.shape[0]
+        keep.append(a)
+    return out, keep
+
+
 RES_NODE_DT = np.dtype({"names": ["id", "type", "slots", "sink_cost"], "formats": ["<u8", "<i4", "<u8", "<i8"],
                         "offsets": [0, 8, 16, 24], "itemsize": 32})
 RES_ARC_DT = np.dtype({"names": ["parent", "child", "cost", "kind"], "formats": ["<u8", "<u8", "<i8", "<i4"],
@@ -276,6 +329,12 @@ def _bind(path: str):
     L.ks_batch_commit_schedule.argtypes = [V, C.c_int32, C.c_int64, V, C.c_size_t, P(C.c_size_t), P(KsCommitStats)]
     L.ks_batch_commit_preemptive.argtypes = [V, C.c_int32, C.c_int64, C.c_int64, V, C.c_size_t, P(C.c_size_t),
                                              P(KsPreemptStats)]
+    L.ks_batch_add_tasks.argtypes = [V, C.c_int32, C.c_size_t, P(KsBatchTaskList), C.c_int64, P(KsAddStats)]
+    L.ks_batch_complete_tasks.argtypes = [V, C.c_int32, C.c_size_t, P(KsBatchTaskList), P(V), P(KsCompleteStats)]
+    L.ks_batch_update_tasks.argtypes = [V, C.c_int32, C.c_size_t, P(KsBatchTaskList), C.c_int64, P(KsUpdateStats)]
+    L.ks_batch_get_bindings.argtypes = [V, C.c_size_t, V, V, C.c_size_t]
+    L.ks_batch_update_unsched_costs.argtypes = [V, C.c_size_t, P(KsBatchTaskList), C.c_int32, C.c_int64, C.c_int64,
+                                                P(C.c_size_t)]
     L.ks_set_bindings.argtypes = [V, V, V, C.c_size_t]
     L.ks_scheduling_deltas.argtypes = [V, C.c_int, V, C.c_size_t, P(C.c_size_t)]
     L.ks_update_unsched_costs.argtypes = [V, V, C.c_size_t, C.c_int32, C.c_int64, C.c_int64, P(C.c_size_t)]
@@ -745,6 +804,57 @@ class Batch:
         self._check(self._L.ks_batch_commit_preemptive(self._h, flags, continuation, preemption, out.ctypes.data,
                                                        cnt.value, C.byref(cnt), C.byref(st)))
         return out[:cnt.value], st.as_dict()
+
+    # -- rounds, the task side: one entry per graph, None = untouched, graph-local ids --------
+    def add_tasks(self, lists, unsched_ids=None, unsched_sink_cost: int = 0) -> dict:
+        """ks_batch_add_tasks: lists[g] = None or (tasks, arc_off, dst, cost) as Context.add_tasks
+        takes them, in graph g's own ids; unsched_ids: None (the NULL rule) or one id array per
+        graph (every listed graph then passes one). → stats summed over the local devices."""
+        ls, keep = pack_task_lists(self.ngraphs, lists, unsched_ids, True)
+        st = KsAddStats()
+        self._check(self._L.ks_batch_add_tasks(self._h, 0, self.ngraphs, ls, int(unsched_sink_cost), C.byref(st)))
+        del keep
+        return st.as_dict()
+
+    def complete_tasks(self, tasks, resource_caps: bool = True, preemptive: bool = False, unsched_ids=None):
+        """ks_batch_complete_tasks: tasks[g] = None or the finished ids of graph g. → (left: per
+        graph None or the PU each id was bound to, graph-local, 0 = unbound; stats)."""
+        ls, keep = pack_task_lists(self.ngraphs, tasks, unsched_ids, False)
+        flags = (KS_COMPLETE_RESOURCE_CAPS if resource_caps else 0) | (KS_COMPLETE_PREEMPTIVE if preemptive else 0)
+        left = [None if a is None or a["tasks"] is None else np.zeros(max(a["tasks"].shape[0], 1), np.uint64)
+                for a in keep]
+        ptr = (C.c_void_p * max(1, self.ngraphs))(*[None if x is None else x.ctypes.data for x in left])
+        st = KsCompleteStats()
+        self._check(self._L.ks_batch_complete_tasks(self._h, flags, self.ngraphs, ls, ptr, C.byref(st)))
+        return [None if x is None else x[:a["tasks"].shape[0]] for x, a in zip(left, keep)], st.as_dict()
+
+    def update_tasks(self, lists, unsched_ids=None, unsched_sink_cost: int = 0, keep_unlisted: bool = False) -> dict:
+        """ks_batch_update_tasks: lists[g] = None or (tasks, arc_off, dst, cost) as
+        Context.update_tasks takes them, in graph g's own ids. → stats summed."""
+        ls, keep = pack_task_lists(self.ngraphs, lists, unsched_ids, True)
+        st = KsUpdateStats()
+        self._check(self._L.ks_batch_update_tasks(self._h, KS_UPDATE_KEEP_UNLISTED if keep_unlisted else 0,
+                                                  self.ngraphs, ls, int(unsched_sink_cost), C.byref(st)))
+        del keep
+        return st.as_dict()
+
+    def bindings(self, g: int, tasks) -> np.ndarray:
+        """ks_batch_get_bindings: the PU each task of graph g is bound to, graph-local, 0 = unbound."""
+        ids = np.ascontiguousarray(tasks, np.uint64).reshape(-1)
+        pu = np.zeros(max(ids.shape[0], 1), np.uint64)
+        self._check(self._L.ks_batch_get_bindings(self._h, g, ids.ctypes.data, pu.ctypes.data, ids.shape[0]))
+        return pu[:ids.shape[0]]
+
+    def update_unsched_costs(self, cost: int, mode: int = KS_COST_SET, continuation: int = 0, unsched_ids=None) -> int:
+        """ks_batch_update_unsched_costs: unsched_ids None = every aggregator of every graph, else
+        one id array (or None: untouched) per graph. → arcs whose cost changed."""
+        ls = None
+        if unsched_ids is not None:
+            ls, keep = pack_task_lists(self.ngraphs, None, unsched_ids, False)
+        ch = C.c_size_t()
+        self._check(self._L.ks_batch_update_unsched_costs(self._h, self.ngraphs, ls, mode, int(cost), int(continuation),
+                                                          C.byref(ch)))
+        return ch.value
 
     def solve(self) -> list[SolveResult]:
         rs = (KsResult * self.local)()
