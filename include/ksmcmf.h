@@ -936,7 +936,8 @@ typedef struct ks_grow_stats {        /* 96 B */
  * built CSR or a full segment takes the store's rebuild path (ks_store_stats.rebuilds). Every
  * refusal is found before anything changes on the device, and the host's node table is rolled
  * back. A device failure after the records were emitted leaves the store unusable until the
- * next ks_load_graph; the host's node table is rolled back. stats may be NULL. No batch twin.
+ * next ks_load_graph; the host's node table is rolled back. stats may be NULL. On a batch:
+ * ks_batch_add_resources.
  * UpdateResourceTopology (:217-236, a resource's slots change) is not covered. */
 int ks_add_resources(ks_ctx* ctx, int32_t flags /* must be 0 */,
                      const ks_res_node* nodes, size_t n,
@@ -1168,7 +1169,7 @@ int ks_batch_commit_preemptive(ks_batch* b, int32_t flags, int64_t continuation_
  * touched graph with exactly one sink has that sink's supply at −Σ of its other nodes'
  * supplies, as after ks_batch_apply_deltas. stats (may be NULL) are summed over the local
  * devices. No collective: a rank returns its own failure. The resource side of a round
- * (ks_remove_resources, ks_add_resources) has no batch twin. */
+ * (ks_batch_remove_resources, ks_batch_add_resources) follows the same contract, below. */
 typedef struct ks_batch_task_list {   /* one graph's part of a call, in the graph's OWN ids */
     const uint64_t*    tasks;       size_t k;     /* k == 0: the graph is untouched          */
     const uint64_t*    arc_off;                   /* k + 1, as ks_add_tasks (unused by complete) */
@@ -1185,7 +1186,9 @@ int ks_batch_add_tasks(ks_batch* b, int32_t flags, size_t ngraphs, const ks_batc
  * → TaskCompleted (flowmanager/graph_manager.go:389-405) → removeTaskNode (:803-813). flags:
  * KS_COMPLETE_*. left (may be NULL): left[g] (may be NULL) receives, for a graph this rank
  * owns, the k bindings read before anything changed, graph-local, 0 = unbound; an id listed
- * twice gets the same value twice. */
+ * twice gets the same value twice. With every k == 0 and KS_COMPLETE_RESOURCE_CAPS the call is
+ * the lone call's plain capacity refresh (k == 0) on every local device's union, under the NULL
+ * rule: what a round runs after ks_batch_add_resources. */
 int ks_batch_complete_tasks(ks_batch* b, int32_t flags, size_t ngraphs, const ks_batch_task_list* lists,
                             uint64_t* const* left, ks_complete_stats* stats);
 /* ks_update_tasks per listed graph: UpdateTimeDependentCosts (flowmanager/graph_manager.go:211-213)
@@ -1202,6 +1205,54 @@ int ks_batch_get_bindings(ks_batch* b, size_t g, const uint64_t* task, uint64_t*
  * graph with nu == 0 is untouched). *changed (may be NULL): summed over the local devices. */
 int ks_batch_update_unsched_costs(ks_batch* b, size_t ngraphs, const ks_batch_task_list* lists, int32_t mode,
                                   int64_t cost, int64_t continuation_cost, size_t* changed);
+
+/* ---- batch rounds, the resource side: machines and racks leave and join ----
+ * The twins of ks_remove_resources and ks_add_resources on a batch, under the contract
+ * written above ks_batch_task_list: one list per loaded graph on every rank (else
+ * KS_E_INVALID), every id in its graph's OWN numbering, ONE device call per local device on
+ * its union with one record stream that is all or nothing there and marks its cells for the
+ * next solve, stats (may be NULL) summed over the local devices, no collective, and every
+ * message names the graph and the graph-local id. No supply changes, so no sink's demand
+ * moves, and evicted tasks stay task nodes: the rows of ks_batch_gather keep their length.
+ * A live resource's slot count changing (UpdateResourceTopology) stays with
+ * ks_batch_apply_deltas. */
+typedef struct ks_batch_res_list {   /* one graph's part of a call, in the graph's OWN ids */
+    const uint64_t*    roots; size_t k;     /* ks_batch_remove_resources; k == 0: untouched        */
+    const ks_res_node* nodes; size_t n;     /* ks_batch_add_resources; n == 0 && m == 0: untouched */
+    const ks_res_arc*  arcs;  size_t m;
+} ks_batch_res_list;
+
+/* ks_remove_resources per listed graph (only roots / k of each entry are read). flags:
+ * KS_REMOVE_* with the lone call's rules; the capacity BFS starts from every cell's sink,
+ * as in the batch commits. A root that is 0 or beyond 1..span of its graph is KS_E_RANGE
+ * before any device is asked; a root that is dead, a task or a sink keeps the lone call's
+ * KS_E_INVALID. removed receives graph-local ids grouped by graph in ascending graph order
+ * and ascending within a graph; removed_off (ngraphs + 1 entries, may be NULL) delimits
+ * them: removed_off[g] .. removed_off[g + 1] is graph g's part, empty for a graph this rank
+ * does not own. evicted receives one KS_DELTA_PREEMPT per evicted task (graph, graph-local
+ * task, the graph-local PU it leaves), grouped by graph and in task order within a graph.
+ * removed == NULL && evicted == NULL: a probe, the counts only and nothing changes. With
+ * several local devices every device is probed first, so a buffer that is too small
+ * (KS_E_INVALID, both counts written) or a root that any device refuses changes no device. */
+int ks_batch_remove_resources(ks_batch* b, int32_t flags, size_t ngraphs, const ks_batch_res_list* lists,
+                              uint64_t* removed, size_t rcap, size_t* nremoved,
+                              size_t* removed_off /* ngraphs + 1, may be NULL */,
+                              ks_batch_delta* evicted, size_t ecap, size_t* nevicted,
+                              ks_remove_stats* stats);
+/* ks_add_resources per listed graph (only nodes / n and arcs / m of each entry are read).
+ * flags is reserved: pass 0. The two 32-byte arrays go up back to back in graph order, as
+ * the caller wrote them; one kernel range-checks every node id and both endpoints of every
+ * edge against 1..span of the record's graph and moves them into the union's ids, so an edge
+ * between two cells cannot be written. The first record in input order (nodes, then edges)
+ * with an id outside its graph is KS_E_RANGE naming the graph, what the id was (node, parent
+ * or child) and the id. A repeated (parent, child) pair is a repeat within one graph only.
+ * Every new PU's arc ends at the sink of the PU's own cell (the per-cell sink table of the
+ * task calls); a PU whose cell has no sink or several is KS_E_INVALID naming the graph, and
+ * nothing changes. A new id may be any dead id of 1..span: a reserved one or a freed one.
+ * After a growth with an edge, refresh the capacities as after ks_add_resources:
+ * ks_batch_complete_tasks with every k == 0 and KS_COMPLETE_RESOURCE_CAPS. */
+int ks_batch_add_resources(ks_batch* b, int32_t flags /* 0 */, size_t ngraphs, const ks_batch_res_list* lists,
+                           ks_grow_stats* stats);
 
 #ifdef __cplusplus
 }

@@ -450,9 +450,10 @@ int build_union(ks_batch* b, const ks_batch::Local& l, const ks_batch_task_list*
 // view that lets its messages name graphs. A device that changed gets its touched graphs'
 // auto-sink records (supplies: tasks arrived or left) and its gather rows recounted, and
 // the bindings it returned leave the union's numbering.
+// every_device: a device whose graphs list nothing is called as well (the plain capacity refresh).
 template <class Stats, class Call>
 int batch_task_call(ks_batch* b, size_t ngraphs, const ks_batch_task_list* lists, bool with_arcs, bool supplies,
-                    uint64_t* const* left, Stats* stats, Call call) {
+                    uint64_t* const* left, Stats* stats, Call call, bool every_device = false) {
     if (!b) return KS_E_INVALID;
     if (int rc = check_lists(b, ngraphs, lists, with_arcs)) return rc;
     std::vector<UnionLists> us(b->loc.size());
@@ -465,7 +466,7 @@ int batch_task_call(ks_batch* b, size_t ngraphs, const ks_batch_task_list* lists
     for (size_t li = 0; li < b->loc.size(); ++li) {
         auto& l = b->loc[li];
         const UnionLists& u = us[li];
-        if (u.touched.empty()) continue;
+        if (u.touched.empty() && !(every_device && !l.graphs.empty())) continue;
         Stats st;
         std::memset(&st, 0, sizeof(st));
         std::vector<uint64_t> hl(u.tasks.size());
@@ -491,6 +492,87 @@ int batch_task_call(ks_batch* b, size_t ngraphs, const ks_batch_task_list* lists
     }
     if (stats) *stats = sum;
     return KS_OK;
+}
+
+// ---- the resource side of a round: one device's part of ks_batch_remove_resources (the roots in
+// the union's numbering: O(k) on the host, which checks their range) and of ks_batch_add_resources
+// (the two record arrays as the caller wrote them: their ids leave the graphs' numbering on the
+// device, BatchView::node_goff / arc_goff).
+struct UnionRes {
+    std::vector<uint64_t> roots;
+    std::vector<ks_res_node> nodes;
+    std::vector<ks_res_arc> arcs;
+    std::vector<uint64_t> node_goff, arc_goff;   // per graph of the device (+ total): its first node, its first edge
+    bool touched = false;
+    ks::BatchView view;
+};
+
+int check_res_lists(ks_batch* b, size_t ngraphs, const ks_batch_res_list* lists, bool adding) {
+    if (ngraphs != b->ngraphs) return b->fail(KS_E_INVALID, "the list count differs from the loaded graphs");
+    if (ngraphs && !lists) return b->fail(KS_E_INVALID, "null list array");
+    for (size_t g = 0; g < ngraphs; ++g) {
+        const ks_batch_res_list& L = lists[g];
+        const std::string who = "graph " + std::to_string(g) + ": ";
+        if (!adding && L.k && !L.roots) return b->fail(KS_E_INVALID, who + "null root array");
+        if (adding && ((L.n && !L.nodes) || (L.m && !L.arcs))) return b->fail(KS_E_INVALID, who + "null node or edge array");
+        if (L.k > (size_t)INT32_MAX / 16 || L.n > (size_t)INT32_MAX / 16 || L.m > (size_t)INT32_MAX / 16)
+            return b->fail(KS_E_RANGE, who + "too many roots, resource nodes or edges");
+    }
+    return KS_OK;
+}
+
+// The lists of l's graphs as one union input. A root or a node id outside 1..span of its graph is
+// KS_E_RANGE here (an edge's endpoint: on the device, before anything changes there).
+int build_union_res(ks_batch* b, const ks_batch::Local& l, const ks_batch_res_list* lists, bool adding, UnionRes& u) {
+    u.node_goff.assign(1, 0);
+    u.arc_goff.assign(1, 0);
+    for (size_t i = 0; i < l.graphs.size(); ++i) {
+        const size_t g = (size_t)l.graphs[i];
+        const ks_batch_res_list& L = lists[g];
+        const uint64_t lo = (uint64_t)l.off[i], span = (uint64_t)(l.off[i + 1] - l.off[i]);
+        auto range = [&](const char* what, uint64_t id) {
+            return b->fail(KS_E_RANGE, "graph " + std::to_string(g) + ": " + what + " " + std::to_string(id) +
+                                           " is outside the graph's ids 1.." + std::to_string(span) +
+                                           " (its highest id at the load plus the reserved ids)");
+        };
+        if (!adding) {
+            for (size_t j = 0; j < L.k; ++j) {
+                if (L.roots[j] == 0 || L.roots[j] > span) return range("root", L.roots[j]);
+                u.roots.push_back(L.roots[j] + lo);
+            }
+            u.touched |= L.k != 0;
+        } else {
+            for (size_t j = 0; j < L.n; ++j)
+                if (L.nodes[j].id == 0 || L.nodes[j].id > span) return range("resource node id", L.nodes[j].id);
+            if (L.n) u.nodes.insert(u.nodes.end(), L.nodes, L.nodes + L.n);
+            if (L.m) u.arcs.insert(u.arcs.end(), L.arcs, L.arcs + L.m);
+            if (u.nodes.size() > (size_t)INT32_MAX / 16 || u.arcs.size() > (size_t)INT32_MAX / 16)
+                return b->fail(KS_E_RANGE, "too many resource nodes or edges on one device");
+            u.touched |= L.n || L.m;
+        }
+        u.node_goff.push_back(u.nodes.size());
+        u.arc_goff.push_back(u.arcs.size());
+    }
+    u.view.ng = l.graphs.size();
+    u.view.off = l.off.data();
+    u.view.graph = l.graphs.data();
+    u.view.arc_goff = u.arc_goff.data();
+    u.view.node_goff = u.node_goff.data();
+    return KS_OK;
+}
+
+// The index among l's graphs of the graph that owns union id `id`: graph i owns (off[i], off[i+1]].
+size_t graph_index(const ks_batch::Local& l, uint64_t id) {
+    size_t i = (size_t)(std::lower_bound(l.off.begin(), l.off.end(), (int64_t)id) - l.off.begin());
+    i = i ? i - 1 : 0;
+    return std::min(i, l.graphs.size() ? l.graphs.size() - 1 : 0);
+}
+
+template <class Stats>
+void add_stats(Stats& sum, const Stats& st) {
+    static_assert(sizeof(Stats) % sizeof(int64_t) == 0, "stats are int64 counters");
+    for (size_t w = 0; w < sizeof(Stats) / sizeof(int64_t); ++w)
+        reinterpret_cast<int64_t*>(&sum)[w] += reinterpret_cast<const int64_t*>(&st)[w];
 }
 
 }  // namespace
@@ -1038,11 +1120,15 @@ int ks_batch_add_tasks(ks_batch* b, int32_t flags, size_t ngraphs, const ks_batc
 
 int ks_batch_complete_tasks(ks_batch* b, int32_t flags, size_t ngraphs, const ks_batch_task_list* lists,
                             uint64_t* const* left, ks_complete_stats* stats) {
+    // every k == 0 with the caps flag is the lone call's plain capacity refresh (what a round runs
+    // after ks_batch_add_resources): it reaches every local device's union under the NULL rule
+    bool listed = false;
+    for (size_t g = 0; b && lists && ngraphs == b->ngraphs && g < ngraphs; ++g) listed |= lists[g].k != 0;
     return batch_task_call(b, ngraphs, lists, false, true, left, stats,
                            [&](ks_ctx* c, const UnionLists& u, uint64_t* hl, ks_complete_stats* st) {
                                return ks_complete_tasks(c, flags, u.tasks.data(), u.tasks.size(), u.agg_ptr(),
                                                         u.agg.size(), hl, st);
-                           });
+                           }, (flags & KS_COMPLETE_RESOURCE_CAPS) && !listed);
 }
 
 int ks_batch_update_tasks(ks_batch* b, int32_t flags, size_t ngraphs, const ks_batch_task_list* lists,
@@ -1116,6 +1202,119 @@ int ks_batch_update_unsched_costs(ks_batch* b, size_t ngraphs, const ks_batch_ta
         total += ch;
     }
     if (changed) *changed = total;
+    return KS_OK;
+}
+
+// ---- batch rounds, the resource side: machines and racks leave and join ----
+
+int ks_batch_remove_resources(ks_batch* b, int32_t flags, size_t ngraphs, const ks_batch_res_list* lists,
+                              uint64_t* removed, size_t rcap, size_t* nremoved, size_t* removed_off,
+                              ks_batch_delta* evicted, size_t ecap, size_t* nevicted, ks_remove_stats* stats) {
+    if (!b || !nremoved || !nevicted) return KS_E_INVALID;
+    *nremoved = *nevicted = 0;
+    if (flags & ~(KS_REMOVE_RESOURCE_CAPS | KS_REMOVE_PREEMPTIVE)) return b->fail(KS_E_INVALID, "unknown remove flag");
+    if ((flags & KS_REMOVE_PREEMPTIVE) && !(flags & KS_REMOVE_RESOURCE_CAPS))
+        return b->fail(KS_E_INVALID, "KS_REMOVE_PREEMPTIVE selects a capacity rule: it needs KS_REMOVE_RESOURCE_CAPS");
+    if (int rc = check_res_lists(b, ngraphs, lists, false)) return rc;
+    const bool probe = !removed && !evicted;
+    if (!probe && ((!removed && rcap) || (!evicted && ecap)))
+        return b->fail(KS_E_INVALID, "a null output buffer with room in it");
+    if (!removed) rcap = 0;
+    if (!evicted) ecap = 0;
+    // every local device's roots first (a root outside its graph stops the call before any device is asked)
+    const size_t nl = b->loc.size();
+    std::vector<UnionRes> us(nl);
+    for (size_t li = 0; li < nl; ++li)
+        if (int rc = build_union_res(b, b->loc[li], lists, false, us[li])) return rc;
+    std::vector<size_t> nr(nl, 0), ne(nl, 0);
+    auto call = [&](size_t li, uint64_t* rm, size_t rc_cap, ks_sched_delta* ev, size_t ev_cap, ks_remove_stats* st) {
+        auto& l = b->loc[li];
+        l.ctx->view = &us[li].view;
+        const int rc = ks_remove_resources(l.ctx, flags, us[li].roots.data(), us[li].roots.size(), rm, rc_cap, &nr[li], ev,
+                                           ev_cap, &ne[li], st);
+        l.ctx->view = nullptr;
+        return rc ? b->fail(rc, "rank " + std::to_string(l.grank) + ": " + ks_last_error(l.ctx)) : KS_OK;
+    };
+    auto totals = [&]() {
+        *nremoved = *nevicted = 0;
+        for (size_t li = 0; li < nl; ++li) *nremoved += nr[li], *nevicted += ne[li];
+    };
+    // a probe, and with several local devices the count of every device before any of them
+    // changes: a buffer that is too small or a root any device refuses changes none
+    if (probe || nl > 1) {
+        for (size_t li = 0; li < nl; ++li)
+            if (us[li].touched)
+                if (int rc = call(li, nullptr, 0, nullptr, 0, nullptr)) return rc;
+        totals();
+        if (probe) return KS_OK;
+        if (rcap < *nremoved || ecap < *nevicted)
+            return b->fail(KS_E_INVALID, rcap < *nremoved ? "removed buffer smaller than the removed nodes"
+                                                          : "evicted buffer smaller than the evicted tasks");
+    }
+    ks_remove_stats sum;
+    std::memset(&sum, 0, sizeof(sum));
+    std::vector<std::vector<uint64_t>> per_graph(ngraphs);
+    std::vector<ks_batch_delta> all;
+    for (size_t li = 0; li < nl; ++li) {
+        auto& l = b->loc[li];
+        if (!us[li].touched) continue;
+        // (one local device: its own call counts and checks the room; no removal exceeds the node table)
+        const size_t cap_r = nl > 1 ? nr[li] : std::min(rcap, l.ctx->nodes.size());
+        const size_t cap_e = nl > 1 ? ne[li] : std::min(ecap, l.ctx->nodes.size());
+        std::vector<uint64_t> rm(cap_r + 1);
+        std::vector<ks_sched_delta> ev(cap_e + 1);
+        ks_remove_stats st;
+        std::memset(&st, 0, sizeof(st));
+        const int rc = call(li, rm.data(), cap_r, ev.data(), cap_e, &st);
+        if (nl == 1) totals();
+        if (rc) return rc;
+        add_stats(sum, st);
+        for (size_t j = 0; j < nr[li]; ++j) {   // ascending in the union: ascending within each graph
+            const size_t i = graph_index(l, rm[j]);
+            per_graph[(size_t)l.graphs[i]].push_back(rm[j] - (uint64_t)l.off[i]);
+        }
+        ev.resize(ne[li]);
+        localize_deltas(l, ev, all);
+    }
+    size_t at = 0;
+    for (size_t g = 0; g < ngraphs; ++g) {
+        if (removed_off) removed_off[g] = at;
+        for (uint64_t id : per_graph[g]) removed[at++] = id;
+    }
+    if (removed_off) removed_off[ngraphs] = at;
+    // grouped by graph, ascending; within a graph in task order (a device's evictions come in slot order)
+    std::stable_sort(all.begin(), all.end(),
+                     [](const ks_batch_delta& x, const ks_batch_delta& y) { return x.graph < y.graph; });
+    if (!all.empty()) std::memcpy(evicted, all.data(), all.size() * sizeof(ks_batch_delta));
+    if (stats) *stats = sum;
+    return KS_OK;
+}
+
+int ks_batch_add_resources(ks_batch* b, int32_t flags, size_t ngraphs, const ks_batch_res_list* lists,
+                           ks_grow_stats* stats) {
+    if (!b) return KS_E_INVALID;
+    if (flags) return b->fail(KS_E_INVALID, "unknown flag (flags is reserved: pass 0)");
+    if (int rc = check_res_lists(b, ngraphs, lists, true)) return rc;
+    // every local device's records first (a node id outside its graph stops the call before any device changed)
+    std::vector<UnionRes> us(b->loc.size());
+    for (size_t li = 0; li < b->loc.size(); ++li)
+        if (int rc = build_union_res(b, b->loc[li], lists, true, us[li])) return rc;
+    ks_grow_stats sum;
+    std::memset(&sum, 0, sizeof(sum));
+    if (stats) *stats = sum;
+    for (size_t li = 0; li < b->loc.size(); ++li) {
+        auto& l = b->loc[li];
+        const UnionRes& u = us[li];
+        if (!u.touched) continue;
+        ks_grow_stats st;
+        std::memset(&st, 0, sizeof(st));
+        l.ctx->view = &u.view;
+        const int rc = ks_add_resources(l.ctx, 0, u.nodes.data(), u.nodes.size(), u.arcs.data(), u.arcs.size(), &st);
+        l.ctx->view = nullptr;
+        if (rc) return b->fail(rc, "rank " + std::to_string(l.grank) + ": " + ks_last_error(l.ctx));
+        add_stats(sum, st);
+    }
+    if (stats) *stats = sum;
     return KS_OK;
 }
 

@@ -30,6 +30,8 @@ struct BatchView {
     const int64_t* off = nullptr;         // [ng + 1] graph i owns the union ids (off[i], off[i + 1]]
     const int* graph = nullptr;           // [ng] the caller's number of graph i
     const uint64_t* arc_goff = nullptr;   // [ng + 1] the first listed arc of graph i (calls with arcs)
+    const uint64_t* node_goff = nullptr;  // [ng + 1] the first listed resource node of graph i (ks_batch_add_resources,
+                                          //   whose node ids and edges are all graph-local: arc_goff counts its edges)
     uint64_t base_of(uint64_t id) const;  // the base of the graph that owns union id `id`
 };
 // "task 17" on a lone context, "graph 3: task 17" (graph-local) under a view; id: the context's own id.
@@ -127,7 +129,7 @@ public:
     int remove_resources(int flags, const uint64_t* roots, size_t k, int64_t sink_slot, bool probe, size_t rcap,
                          size_t ecap, std::vector<uint64_t>* removed, std::vector<ks_sched_delta>* evicted,
                          size_t* nremoved, size_t* nevicted, ks_remove_stats* stats, const RemoveEdits& make_edits,
-                         bool* dirty, std::string& err);
+                         bool* dirty, std::string& err, const BatchView* bv = nullptr);
     // ks_complete_tasks (the k task ids leave the graph; the aggregators' and, with the caps
     // flag, the resource arcs' capacities follow). left (k entries, may be null) receives the
     // bindings read before anything changes. make_edits is called once with the distinct ids
@@ -150,9 +152,11 @@ public:
     // ks_add_resources (the n new resource nodes, checked and already entered in the host's node
     // table, and the m edges; first_pair: the first edge that repeats an earlier (parent, child),
     // m when none does). make_edits and *dirty as in add_tasks; *changed: records were applied.
+    // sink_slot == kEverySink over a cell partition: every new PU's arc ends at the sink of its own
+    // cell. bv: the node ids and the edges' endpoints are graph-local (BatchView::node_goff).
     int add_resources(const ks_res_node* nodes, size_t n, const ks_res_arc* arcs, size_t m, size_t first_pair,
                       int64_t sink_slot, int64_t nslots, ks_grow_stats* stats, const AddEdits& make_edits, bool* dirty,
-                      bool* changed, std::string& err);
+                      bool* changed, std::string& err, const BatchView* bv = nullptr);
     // ks_update_tasks (the k live task ids with the arcs each should have; offsets checked by the
     // caller). first_pair: the first arc that repeats an earlier head of its own task, arc_off[k]
     // when none does. No node is edited. *dirty: records were emitted (a failure from then on

@@ -122,9 +122,11 @@ bool first_bad(int word, size_t n, size_t* idx) {
     return true;
 }
 
-// A union's sinks for the aggregator records of an arrival or a refresh (sink_slot == kEverySink
-// over a cell partition): the table is rebuilt on every call, one pass over the slot bytes.
-int wire_cell_sinks(EngineImpl& s, const SchedDev& d, AddDev& a, int64_t sink_slot, std::string& err) {
+// A union's sinks for the aggregator records of an arrival or a refresh and for the new PUs of a
+// growth (sink_slot == kEverySink over a cell partition): the table is rebuilt on every call, one
+// pass over the slot bytes.
+template <class Dev>
+int wire_cell_sinks(EngineImpl& s, const SchedDev& d, Dev& a, int64_t sink_slot, std::string& err) {
     if (sink_slot != Engine::kEverySink || s.cell_off.size() < 2) return KS_OK;
     const int ncells = (int)s.cell_off.size() - 1;
     if (int rc = ensure_cell_first(s, err)) return rc;
@@ -574,7 +576,7 @@ int Engine::commit_preemptive(int flags, int64_t ccost, int64_t pcost, const uin
 int Engine::remove_resources(int flags, const uint64_t* roots, size_t k, int64_t sink_slot, bool probe, size_t rcap,
                              size_t ecap, std::vector<uint64_t>* removed, std::vector<ks_sched_delta>* evicted,
                              size_t* nremoved, size_t* nevicted, ks_remove_stats* stats, const RemoveEdits& make_edits,
-                             bool* dirty, std::string& err) {
+                             bool* dirty, std::string& err, const BatchView* bv) {
     EngineImpl& s = *p_;
     *dirty = false;
     *nremoved = *nevicted = 0;
@@ -623,7 +625,7 @@ int Engine::remove_resources(int flags, const uint64_t* roots, size_t k, int64_t
     KS_CHECK(hipStreamSynchronize(st));
     if (h.bad_root) {
         const uint64_t id = roots[k - (size_t)h.bad_root];
-        err = "root " + std::to_string(id) + " is not a live resource or type-0 node (dead, beyond the graph, a task or a sink)";
+        err = id_name(bv, "root", id) + " is not a live resource or type-0 node (dead, beyond the graph, a task or a sink)";
         return KS_E_INVALID;
     }
     const int64_t nroots = h.nfront;
@@ -1035,7 +1037,7 @@ int Engine::add_tasks(const uint64_t* tasks, size_t k, const uint64_t* arc_off, 
 // first_pair: the first edge that repeats an earlier (parent, child), m: none (the host's sort).
 int Engine::add_resources(const ks_res_node* nodes, size_t n, const ks_res_arc* arcs, size_t m, size_t first_pair,
                           int64_t sink_slot, int64_t nslots, ks_grow_stats* stats, const AddEdits& make_edits,
-                          bool* dirty, bool* changed, std::string& err) {
+                          bool* dirty, bool* changed, std::string& err, const BatchView* bv) {
     EngineImpl& s = *p_;
     *dirty = *changed = false;
     if (!n && !m) return KS_OK;
@@ -1048,9 +1050,16 @@ int Engine::add_resources(const ks_res_node* nodes, size_t n, const ks_res_arc* 
         err = "too many resource nodes or edges";
         return KS_E_RANGE;
     }
+    // under a view the records are graph-local: the graph of node i or edge j, and how a message names it
+    auto graph_of = [&](const uint64_t* goff, size_t j) {
+        return (size_t)(std::upper_bound(goff, goff + bv->ng, (uint64_t)j) - goff) - 1;
+    };
+    auto in_graph = [&](const uint64_t* goff, size_t j) {
+        return bv ? "graph " + std::to_string(bv->graph[graph_of(goff, j)]) + ": " : std::string();
+    };
     int64_t ntot = nst, pus = 0, slots = 0;
     for (size_t i = 0; i < n; ++i) {
-        ntot = std::max<int64_t>(ntot, (int64_t)nodes[i].id);
+        ntot = std::max<int64_t>(ntot, (int64_t)nodes[i].id + (bv ? bv->off[graph_of(bv->node_goff, i)] : 0));
         if (nodes[i].type == KS_NODE_PU) {
             ++pus;
             slots += (int64_t)nodes[i].slots;
@@ -1063,6 +1072,7 @@ int Engine::add_resources(const ks_res_node* nodes, size_t n, const ks_res_arc* 
     g.ntot = ntot;
     g.sink = sink_slot >= 0 && sink_slot < nst ? sink_slot : -1;
     unsigned long long *d_nodes = nullptr, *d_arcs = nullptr;
+    unsigned long long *d_ngoff = nullptr, *d_agoff = nullptr, *d_base = nullptr;
     int rc = carve_scratch(s, [&](Carve<int>& ci, Carve<unsigned long long>& cu) {
         for (int** x : {&g.newt, &g.par}) *x = ci.take(ntot + 1);
         for (int** x : {&g.nflag, &g.n_off}) *x = ci.take((int64_t)n + 1);
@@ -1070,6 +1080,7 @@ int Engine::add_resources(const ks_res_node* nodes, size_t n, const ks_res_arc* 
         g.S = cu.take(ntot + 1);   // (first: the only u64 array that starts zeroed)
         d_nodes = cu.take(4 * (int64_t)n);
         d_arcs = cu.take(4 * (int64_t)m);
+        for (unsigned long long** x : {&d_ngoff, &d_agoff, &d_base}) *x = cu.take(bv ? bv->ng + 1 : 0);
     }, ntot + 1, false, err);
     if (rc) return rc;
     KS_CHECK(clear_ctl(s.grow_ctl, st));
@@ -1080,6 +1091,19 @@ int Engine::add_resources(const ks_res_node* nodes, size_t n, const ks_res_arc* 
     if (n) KS_CHECK(hipMemcpyAsync(d_nodes, nodes, n * sizeof(ks_res_node), hipMemcpyHostToDevice, st));
     if (m) KS_CHECK(hipMemcpyAsync(d_arcs, arcs, m * sizeof(ks_res_arc), hipMemcpyHostToDevice, st));
     SchedDev d = s.schd();
+    rc = pus ? wire_cell_sinks(s, d, g, sink_slot, err) : KS_OK;
+    if (rc) return rc;
+    if (pus && g.sink < 0 && !g.cell_sink) {
+        err = "a new PU's arc into the sink needs exactly one sink";
+        return KS_E_INVALID;
+    }
+    if (bv) {   // the records leave their graphs' numbering on the device
+        KS_CHECK(hipMemcpyAsync(d_ngoff, bv->node_goff, (bv->ng + 1) * 8, hipMemcpyHostToDevice, st));
+        KS_CHECK(hipMemcpyAsync(d_agoff, bv->arc_goff, (bv->ng + 1) * 8, hipMemcpyHostToDevice, st));
+        KS_CHECK(hipMemcpyAsync(d_base, bv->off, (bv->ng + 1) * 8, hipMemcpyHostToDevice, st));
+        KS_CHECK(sched_translate_res((ks_res_node*)d_nodes, (int)n, (ks_res_arc*)d_arcs, (int)m, d_ngoff, d_agoff,
+                                     (const long long*)d_base, (int)bv->ng, g.ctl, st));
+    }
     // ---- 1. the edges, the sums and the arcs the store still holds: one sync
     KS_CHECK(sched_grow_check(d, g, st));
     KS_CHECK(exclusive_sum(s, (const int*)g.nflag, g.n_off, (int64_t)n + 1, st));
@@ -1089,6 +1113,24 @@ int Engine::add_resources(const ks_res_node* nodes, size_t n, const ks_res_arc* 
     KS_CHECK(hipMemcpyAsync(&h, g.ctl, sizeof(GrowCtl), hipMemcpyDeviceToHost, st));
     KS_CHECK(hipStreamSynchronize(st));
     const auto t1 = std::chrono::steady_clock::now();
+    if (bv && h.bad_range) {   // the first record in input order (nodes, then edges) with an id outside its graph
+        size_t i;
+        if (!first_bad(h.bad_range, n + m, &i) || i >= n + m) {
+            err = "inconsistent record index";
+            return KS_E_DEVICE;
+        }
+        const bool node = i < n;
+        const size_t j = node ? i : i - n;
+        const size_t gi = graph_of(node ? bv->node_goff : bv->arc_goff, j);
+        const uint64_t span = (uint64_t)(bv->off[gi + 1] - bv->off[gi]);
+        const bool parent = !node && (arcs[j].parent < 1 || arcs[j].parent > span);
+        err = "graph " + std::to_string(bv->graph[gi]) + ": " +
+              (node ? "resource node id " + std::to_string(nodes[j].id)
+                    : "edge " + std::to_string(arcs[j].parent) + " -> " + std::to_string(arcs[j].child) + ": " +
+                          (parent ? "parent " + std::to_string(arcs[j].parent) : "child " + std::to_string(arcs[j].child))) +
+              " is outside the graph's ids 1.." + std::to_string(span) + " (its highest id at the load plus the reserved ids)";
+        return KS_E_RANGE;
+    }
     if (h.bad_edge || first_pair < m) {   // the first offending edge in input order; on one edge the lowest class
         size_t j;   // (the word: count − index, then 7 − class in the low three bits)
         if (!first_bad(h.bad_edge >> 3, m, &j) || (h.bad_edge && ((h.bad_edge & 7) == 0 || h.bad_edge < 8))) {
@@ -1101,7 +1143,8 @@ int Engine::add_resources(const ks_res_node* nodes, size_t n, const ks_res_arc* 
             cls = 7;
         }
         const ks_res_arc& e = arcs[j];
-        const std::string who = "edge " + std::to_string(e.parent) + " -> " + std::to_string(e.child) + ": ";
+        const std::string who = in_graph(bv ? bv->arc_goff : nullptr, j) + "edge " + std::to_string(e.parent) + " -> " +
+                                std::to_string(e.child) + ": ";
         switch (cls) {
             case 0:
                 err = who + "parent " + std::to_string(e.parent) + " is not a node of this call or a live node that is no task, "
@@ -1128,7 +1171,7 @@ int Engine::add_resources(const ks_res_node* nodes, size_t n, const ks_res_arc* 
             err = "inconsistent node index";
             return KS_E_DEVICE;
         }
-        err = "PU " + std::to_string(nodes[i].id) + ": its tree edges do not end after " +
+        err = in_graph(bv ? bv->node_goff : nullptr, i) + "PU " + std::to_string(nodes[i].id) + ": its tree edges do not end after " +
               std::to_string(KS_RES_MAX_DEPTH) + " steps (a cycle, or a topology too deep)";
         return KS_E_INVALID;
     }
@@ -1139,9 +1182,19 @@ int Engine::add_resources(const ks_res_node* nodes, size_t n, const ks_res_arc* 
             return KS_E_DEVICE;
         }
         const ks_res_arc& e = arcs[j];
-        err = "edge " + std::to_string(e.parent) + " -> " + std::to_string(e.child) + ": the raised capacity is outside the "
-              "supported range";
+        err = in_graph(bv ? bv->arc_goff : nullptr, j) + "edge " + std::to_string(e.parent) + " -> " + std::to_string(e.child) +
+              ": the raised capacity is outside the supported range";
         return KS_E_RANGE;
+    }
+    if (g.cell_sink && h.bad_sink) {   // the first new PU in input order whose cell has no single sink
+        size_t i;
+        if (!first_bad(h.bad_sink, n, &i) || i >= n) {
+            err = "inconsistent node index";
+            return KS_E_DEVICE;
+        }
+        err = in_graph(bv ? bv->node_goff : nullptr, i) + "PU " + std::to_string(nodes[i].id) +
+              ": its cell has no sink or several, and a new PU's arc into the sink needs exactly one";
+        return KS_E_INVALID;
     }
     if (h.rec_upd < 0 || h.rec_add < 0 || h.skipped < 0 || h.rec_upd + h.rec_add != h.rec_edge ||
         (int64_t)h.rec_edge + h.skipped != (int64_t)m || h.rec_pu != pus) {

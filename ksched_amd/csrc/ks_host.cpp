@@ -801,7 +801,7 @@ int ks_remove_resources(ks_ctx* c, int32_t flags, const uint64_t* roots, size_t 
             const uint64_t id = ids[i];
             if (!node_alive(c, id) || c->nodes[id].type == KS_NODE_TASK || c->nodes[id].type == KS_NODE_SINK ||
                 (i && ids[i - 1] >= id)) {
-                err = "the device removes node " + std::to_string(id) + ", which the host's node table does not hold as a "
+                err = "the device removes " + ks::id_name(c->view, "node", id) + ", which the host's node table does not hold as a "
                       "live resource";
                 return KS_E_DEVICE;
             }
@@ -819,7 +819,7 @@ int ks_remove_resources(ks_ctx* c, int32_t flags, const uint64_t* roots, size_t 
     bool dirty = false;
     const int rc = c->eng.remove_resources(flags, roots, k, sink_slot(c, true), probe, removed ? rcap : 0,
                                            evicted ? ecap : 0, &rm, &ev, nremoved, nevicted, stats, make_edits, &dirty,
-                                           c->err);
+                                           c->err, c->view);
     follow_rebuild(c);
     // (a transaction was made only behind the device's checks, and the engine writes the stats on success only)
     if (rc) return delta_failed(c, rc, txn ? &*txn : nullptr, dirty);
@@ -921,15 +921,31 @@ int ks_add_resources(ks_ctx* c, int32_t flags, const ks_res_node* nodes, size_t 
         txn.rollback_nodes();
         return c->fail(code, msg);
     };
+    // under a batch view the records are graph-local (node i belongs to the last graph whose
+    // node_goff is ≤ i); the node table takes the union's id
+    const ks::BatchView* bv = c->view;
+    auto graph_of = [&](const uint64_t* goff, size_t j) {
+        return (size_t)(std::upper_bound(goff, goff + bv->ng, (uint64_t)j) - goff) - 1;
+    };
     uint64_t total = 0;
     bool pu = false;
     for (size_t i = 0; i < n; ++i) {
         const ks_res_node& x = nodes[i];
-        if (int rc = txn.add(x.id, 0, x.type)) {
+        uint64_t id = x.id;
+        std::string who = "resource node " + std::to_string(x.id);
+        if (bv) {
+            const size_t gi = graph_of(bv->node_goff, i);
+            const uint64_t span = (uint64_t)(bv->off[gi + 1] - bv->off[gi]);
+            who = "graph " + std::to_string(bv->graph[gi]) + ": " + who;
+            if (x.id == 0 || x.id > span)
+                return refuse(KS_E_RANGE, who + " is outside the graph's ids 1.." + std::to_string(span) +
+                                              " (its highest id at the load plus the reserved ids)");
+            id += (uint64_t)bv->off[gi];
+        }
+        if (int rc = txn.add(id, 0, x.type)) {
             txn.rollback_nodes();
             return rc;
         }
-        const std::string who = "resource node " + std::to_string(x.id);
         if (x.type != KS_NODE_PU && x.type != KS_NODE_MACHINE && x.type != KS_NODE_INTERMEDIATE && x.type != KS_NODE_OTHER)
             return refuse(KS_E_INVALID, who + " has type " + std::to_string(x.type) + ": not a resource type");
         if (x.type == KS_NODE_PU ? x.slots == 0 : (x.slots != 0 || x.sink_cost != 0))
@@ -941,24 +957,33 @@ int ks_add_resources(ks_ctx* c, int32_t flags, const ks_res_node* nodes, size_t 
         if (total > (uint64_t(1) << 53)) return refuse(KS_E_RANGE, who + ": the new slots summed exceed the supported range");
         pu |= x.type == KS_NODE_PU;
     }
-    if (pu && c->n_sinks != 1) return refuse(KS_E_INVALID, "a new PU's arc into the sink needs exactly one sink");
+    // (a union's PUs join their own cells' sinks: kEverySink, and the device refuses a cell without
+    // exactly one; a lone context with several sinks refuses here)
+    const bool every_sink = c->every_sink && c->n_sinks >= 1;
+    if (pu && c->n_sinks != 1 && !every_sink)
+        return refuse(KS_E_INVALID, "a new PU's arc into the sink needs exactly one sink");
     size_t first_pair = m;   // the first edge in input order that repeats an earlier (parent, child)
     {
-        std::vector<size_t> order(m);
+        // (graph-local pairs: equal ones in two graphs are no repeat, so the graph leads the key)
+        std::vector<size_t> order(m), eg(bv ? m : 0);
         for (size_t j = 0; j < m; ++j) order[j] = j;
+        for (size_t j = 0; j < eg.size(); ++j) eg[j] = graph_of(bv->arc_goff, j);
         std::sort(order.begin(), order.end(), [&](size_t a, size_t b) {
+            if (bv && eg[a] != eg[b]) return eg[a] < eg[b];
             if (arcs[a].parent != arcs[b].parent) return arcs[a].parent < arcs[b].parent;
             if (arcs[a].child != arcs[b].child) return arcs[a].child < arcs[b].child;
             return a < b;
         });
         for (size_t q = 1; q < m; ++q)
-            if (arcs[order[q]].parent == arcs[order[q - 1]].parent && arcs[order[q]].child == arcs[order[q - 1]].child)
+            if (arcs[order[q]].parent == arcs[order[q - 1]].parent && arcs[order[q]].child == arcs[order[q - 1]].child &&
+                (!bv || eg[order[q]] == eg[order[q - 1]]))
                 first_pair = std::min(first_pair, order[q]);
     }
     bool dirty = false, changed = false;
     auto make_edits = [&](std::vector<ks::NodeEdit>* edits) { txn.edits(*edits); };
-    const int rc = c->eng.add_resources(nodes, n, arcs, m, first_pair, sink_slot(c), c->nslots(), stats, make_edits,
-                                        &dirty, &changed, c->err);
+    const int rc = c->eng.add_resources(nodes, n, arcs, m, first_pair,
+                                        every_sink ? ks::Engine::kEverySink : sink_slot(c), c->nslots(), stats, make_edits,
+                                        &dirty, &changed, c->err, bv);
     if (rc) return delta_failed(c, rc, &txn, dirty, stats);
     if (changed) drop_solution(c);
     return KS_OK;

@@ -296,7 +296,7 @@ hipError_t sched_add_emit(const SchedDev& d, const AddDev& a, ks_delta* recs, hi
 // ADD_NODE, PU → sink and edge records at fixed stream positions for store_apply. Only the node
 // store, the arc table and the index are read: no residual CSR is needed and no BFS runs.
 
-// Device counters of one growth; the host reads them in one 32-byte copy.
+// Device counters of one growth; the host reads them in one 40-byte copy.
 struct GrowCtl {
     int bad_edge;    // 8·(m − j) + (7 − class) of the first offending edge j, lowest class first; 0 none.
                      // class 0 parent, 1 child, 2 parent == child, 3 kind, 4 a live node would move,
@@ -309,6 +309,9 @@ struct GrowCtl {
     int skipped;     // edges without a record (no new slot beneath the head)
     int rec_pu;      // the node scan's total: PU → sink records
     int rec_edge;    // the edge scan's total: rec_upd + rec_add
+    int bad_sink;    // per-cell sinks: n − the index of the first new PU whose cell has no single sink, 0 none
+    int bad_range;   // batch ids: n + m − the index (nodes, then edges) of the first record with an id outside
+                     // 1..span of its graph, 0 none
 };
 
 // Inputs and scratch of one growth (device pointers). nst node slots before the call, ntot ≥
@@ -330,11 +333,25 @@ struct GrowDev {
     int* e_off;                        // [m + 1]
     int* e_slot;                       // [m + 1] arc slot of parent → child, −1: the store does not hold it
     long long sink;                    // the sink's node slot, −1: other than one sink
+    const int* cell_sink;              // [ncells] a union's sinks (sched_cell_sinks): a new PU's arc ends at its
+                                       //   own cell's sink, and sink is not read; nullptr: the one sink
+    const int* cell_first;             // [ncells + 1] the cells' first node slots (they cover every id of a
+                                       //   graph's span, also ids beyond the store's slots)
+    int ncells;
     const unsigned long long* hkey;    // the store's (src, dst) index (ks_store.h)
     const int* hval;
     int hmask;                         // capacity − 1, −1: no index yet
     GrowCtl* ctl;
 };
+
+// A batch call's resource records, the graphs' lists back to back (graph g owns the nodes
+// [node_goff[g], node_goff[g + 1]), the edges [arc_goff[g], arc_goff[g + 1]) and the union ids
+// (base[g], base[g + 1]]): one lane per node record and one per edge record finds its graph by
+// bisection, checks 1 ≤ id ≤ span for the node id and for both endpoints (else ctl->bad_range,
+// and the id becomes 0, which every later pass refuses or skips) and adds the graph's base in place.
+hipError_t sched_translate_res(ks_res_node* nodes, int n, ks_res_arc* arcs, int m, const unsigned long long* node_goff,
+                               const unsigned long long* arc_goff, const long long* base, int ng, GrowCtl* ctl,
+                               hipStream_t st);
 
 // The new nodes into the per-slot scratch (newt, S of the PUs, nflag); the edge pass, one lane
 // per edge (endpoints, kind, cost, the claim of par); the second-parent check; the sums, one

@@ -941,16 +941,61 @@ __device__ __forceinline__ int grow_type(const SchedDev& d, const GrowDev& g, un
     return v < g.nst && d.n_alive[v] ? (int)d.n_type[v] : -1;
 }
 
+// A batch call's resource records leave their graphs' own ids: record i (the nodes, then the
+// edges) belongs to the last graph g whose offset is ≤ its index (a graph without records shares
+// its offset with its successor, which owns the record). An id outside 1..span is reported (the
+// first record in input order wins, nodes before edges) and becomes 0, which the node pass skips
+// and the edge pass refuses as well; every other id gets its graph's base. Translating per graph
+// is what makes an edge between two cells unrepresentable.
+__global__ void k_translate_res(ks_res_node* __restrict__ nodes, int n, ks_res_arc* __restrict__ arcs, int m,
+                                const unsigned long long* __restrict__ node_goff,
+                                const unsigned long long* __restrict__ arc_goff, const long long* __restrict__ base, int ng,
+                                GrowCtl* __restrict__ ctl) {
+    const long long tot = (long long)n + m;
+    for (long long i = blockIdx.x * (long long)SB + threadIdx.x; i < tot; i += (long long)gridDim.x * SB) {
+        const bool node = i < n;
+        const long long j = node ? i : i - n;
+        const int g = task_of_arc(node ? node_goff : arc_goff, ng, j);
+        const unsigned long long lo = (unsigned long long)base[g], span = (unsigned long long)(base[g + 1] - base[g]);
+        bool bad = false;
+        if (node) {
+            const unsigned long long id = nodes[j].id;
+            bad = id < 1 || id > span;
+            nodes[j].id = bad ? 0 : id + lo;
+        } else {
+            const unsigned long long p = arcs[j].parent, c = arcs[j].child;
+            const bool bp = p < 1 || p > span, bc = c < 1 || c > span;
+            bad = bp || bc;
+            arcs[j].parent = bp ? 0 : p + lo;
+            arcs[j].child = bc ? 0 : c + lo;
+        }
+        if (bad) atomicMax(&ctl->bad_range, (int)(tot - i));
+    }
+}
+
+// The sink a new PU's arc ends at: the one sink, or over a union's sink table the sink of the PU's
+// own cell (the cells' first slots cover a graph's whole span, so an id beyond the store's slots
+// finds its cell too); negative: there is no such sink.
+__device__ __forceinline__ long long grow_sink_of(const GrowDev& g, long long v) {
+    if (!g.cell_sink) return g.sink;
+    const int c = cell_of_slot(g.cell_first, g.ncells, v);
+    return c < 0 ? -1 : (long long)g.cell_sink[c];
+}
+
 // addResourceNode (:528-551): the new nodes into the per-slot scratch. The host checked the
-// ids (in range, distinct), so every lane owns its slot's words.
+// ids (in range, distinct), so every lane owns its slot's words; an id the translation refused
+// is 0 and owns nothing. Over a union's sink table a PU whose cell has no sink or several is
+// reported, the first in input order.
 __global__ void k_grow_nodes(GrowDev g) {
     for (long long i = blockIdx.x * (long long)SB + threadIdx.x; i < g.n; i += (long long)gridDim.x * SB) {
         const ks_res_node x = g.nodes[i];
-        const long long v = (long long)x.id - 1;
         const int pu = x.type == KS_NODE_PU;
-        g.newt[v] = 1 + x.type;
         g.nflag[i] = pu;
+        if (x.id < 1 || x.id > (unsigned long long)g.ntot) continue;
+        const long long v = (long long)x.id - 1;
+        g.newt[v] = 1 + x.type;
         if (pu) g.S[v] = x.slots;
+        if (pu && g.cell_sink && grow_sink_of(g, v) < 0) atomicMax(&g.ctl->bad_sink, (int)(g.n - i));
     }
 }
 
@@ -998,7 +1043,7 @@ __global__ void k_grow_sums(GrowDev g) {
         unsigned long long w = 0;
         if (i < g.n) {
             const ks_res_node x = g.nodes[i];
-            if (x.type == KS_NODE_PU) {
+            if (x.type == KS_NODE_PU && x.id >= 1 && x.id <= (unsigned long long)g.ntot) {
                 cur = (long long)x.id - 1;
                 w = x.slots;
             }
@@ -1065,9 +1110,9 @@ __global__ void k_grow_emit(SchedDev d, GrowDev g, int rec_pu, ks_delta* __restr
             r.type = x.type;
             r.id = x.id;
             recs[i] = r;
-            if (g.nflag[i])
-                recs[g.n + g.n_off[i]] =
-                    arc_record(KS_ADD_ARC, 0, (int)(x.id - 1), (int)g.sink, 0, (long long)x.slots, x.sink_cost, 0);
+            if (g.nflag[i])   // (its sink is ≥ 0: the host refused the call otherwise)
+                recs[g.n + g.n_off[i]] = arc_record(KS_ADD_ARC, 0, (int)(x.id - 1), (int)grow_sink_of(g, (long long)x.id - 1),
+                                                    0, (long long)x.slots, x.sink_cost, 0);
         } else {
             const long long j = i - g.n;
             if (!g.eflag[j]) continue;
@@ -1487,6 +1532,15 @@ hipError_t sched_upd_totals(const UpdDev& u, hipStream_t st) {
 hipError_t sched_upd_emit(const SchedDev& d, const UpdDev& u, int rec_held, ks_delta* recs, hipStream_t st) {
     if (u.hi) hipLaunchKernelGGL(k_upd_emit_held, dim3(grid(u.hi)), dim3(SB), 0, st, d, u, recs);
     if (u.na) hipLaunchKernelGGL(k_upd_emit_adds, dim3(grid(u.na)), dim3(SB), 0, st, u, rec_held, recs);
+    return hipGetLastError();
+}
+
+hipError_t sched_translate_res(ks_res_node* nodes, int n, ks_res_arc* arcs, int m, const unsigned long long* node_goff,
+                               const unsigned long long* arc_goff, const long long* base, int ng, GrowCtl* ctl,
+                               hipStream_t st) {
+    if (n + m > 0 && ng > 0)
+        hipLaunchKernelGGL(k_translate_res, dim3(grid((long long)n + m)), dim3(SB), 0, st, nodes, n, arcs, m, node_goff,
+                           arc_goff, base, ng, ctl);
     return hipGetLastError();
 }
 

@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = (
     "ks_batch_get_graph", "ks_batch_set_bindings", "ks_batch_commit_schedule", "ks_batch_commit_preemptive",
     "ks_batch_add_tasks", "ks_batch_complete_tasks", "ks_batch_update_tasks", "ks_batch_get_bindings",
     "ks_batch_update_unsched_costs",
+    "ks_batch_remove_resources", "ks_batch_add_resources",
 )
 ABI_VERSION = 5
 KS_DELTA_PLACE, KS_DELTA_PREEMPT, KS_DELTA_MIGRATE, KS_DELTA_NOOP = 0, 1, 2, 3
@@ -233,6 +234,22 @@ RES_ARC_DT = np.dtype({"names": ["parent", "child", "cost", "kind"], "formats": 
 KS_RES_TREE, KS_RES_EXTRA, KS_RES_MAX_DEPTH = 0, 1, 32
 
 
+class KsBatchResList(C.Structure):
+    """ks_batch_res_list (48 B): one graph's part of a batch resource call, in the graph's own ids."""
+    _fields_ = [("roots", C.c_void_p), ("k", C.c_size_t), ("nodes", C.c_void_p), ("n", C.c_size_t),
+                ("arcs", C.c_void_p), ("m", C.c_size_t)]
+
+
+def res_rows(x, dt):
+    """RES_NODE_DT / RES_ARC_DT rows from an array of that dtype or from tuples in field order."""
+    if isinstance(x, np.ndarray) and x.dtype == dt:
+        return np.ascontiguousarray(x).reshape(-1)
+    out = np.zeros(len(x), dt)
+    for name, col in zip(dt.names, zip(*x)):
+        out[name] = np.asarray(col, dtype=dt[name])
+    return out
+
+
 class KsError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"ksmcmf error {code}: {msg}")
@@ -335,6 +352,9 @@ def _bind(path: str):
     L.ks_batch_get_bindings.argtypes = [V, C.c_size_t, V, V, C.c_size_t]
     L.ks_batch_update_unsched_costs.argtypes = [V, C.c_size_t, P(KsBatchTaskList), C.c_int32, C.c_int64, C.c_int64,
                                                 P(C.c_size_t)]
+    L.ks_batch_remove_resources.argtypes = [V, C.c_int32, C.c_size_t, P(KsBatchResList), V, C.c_size_t, P(C.c_size_t),
+                                            V, V, C.c_size_t, P(C.c_size_t), P(KsRemoveStats)]
+    L.ks_batch_add_resources.argtypes = [V, C.c_int32, C.c_size_t, P(KsBatchResList), P(KsGrowStats)]
     L.ks_set_bindings.argtypes = [V, V, V, C.c_size_t]
     L.ks_scheduling_deltas.argtypes = [V, C.c_int, V, C.c_size_t, P(C.c_size_t)]
     L.ks_update_unsched_costs.argtypes = [V, V, C.c_size_t, C.c_int32, C.c_int64, C.c_int64, P(C.c_size_t)]
@@ -617,14 +637,7 @@ class Context:
         into nodes of the call. An edge whose head has S new slots beneath it is created with
         capacity S or, where the store still holds it, has its capacity raised by S. -> stats
         dict. Needs no solve; invalidates the solution when a record is applied."""
-        def rows(x, dt):
-            if isinstance(x, np.ndarray) and x.dtype == dt:
-                return np.ascontiguousarray(x).reshape(-1)
-            out = np.zeros(len(x), dt)
-            for name, col in zip(dt.names, zip(*x)):
-                out[name] = np.asarray(col, dtype=dt[name])
-            return out
-        nd, ar = rows(nodes, RES_NODE_DT), rows(arcs, RES_ARC_DT)
+        nd, ar = res_rows(nodes, RES_NODE_DT), res_rows(arcs, RES_ARC_DT)
         st = KsGrowStats()
         self._check(self._L.ks_add_resources(self._h, 0, nd.ctypes.data if nd.shape[0] else None, nd.shape[0],
                                              ar.ctypes.data if ar.shape[0] else None, ar.shape[0], C.byref(st)))
@@ -835,6 +848,57 @@ class Batch:
         st = KsUpdateStats()
         self._check(self._L.ks_batch_update_tasks(self._h, KS_UPDATE_KEEP_UNLISTED if keep_unlisted else 0,
                                                   self.ngraphs, ls, int(unsched_sink_cost), C.byref(st)))
+        del keep
+        return st.as_dict()
+
+    # -- rounds, the resource side: one entry per graph, None = untouched, graph-local ids ----
+    def remove_resources(self, roots_per_graph, resource_caps: bool = True, preemptive: bool = False, flags=None):
+        """ks_batch_remove_resources: roots_per_graph[g] = None or the root ids of graph g, as
+        Context.remove_resources takes them. → (removed: per graph the removed ids ascending
+        uint64, empty for an untouched graph; evicted BATCH_DELTA_DT PREEMPTs grouped by graph
+        in task order; stats summed over the local devices). flags: the raw KS_REMOVE_* word
+        instead of the two switches."""
+        if len(roots_per_graph) != self.ngraphs:
+            raise ValueError("one root list (or None) per loaded graph")
+        if flags is None:
+            flags = (KS_REMOVE_RESOURCE_CAPS if resource_caps else 0) | (KS_REMOVE_PREEMPTIVE if preemptive else 0)
+        ls = (KsBatchResList * max(1, self.ngraphs))()
+        keep = [None if r is None else np.ascontiguousarray(r, np.uint64).reshape(-1) for r in roots_per_graph]
+        for g, r in enumerate(keep):
+            if r is not None and r.shape[0]:
+                ls[g].roots, ls[g].k = r.ctypes.data, r.shape[0]
+        nr, ne = C.c_size_t(), C.c_size_t()
+        self._check(self._L.ks_batch_remove_resources(self._h, flags, self.ngraphs, ls, None, 0, C.byref(nr), None,
+                                                      None, 0, C.byref(ne), None))
+        removed = np.zeros(max(nr.value, 1), np.uint64)
+        evicted = np.zeros(max(ne.value, 1), BATCH_DELTA_DT)
+        off = np.zeros(self.ngraphs + 1, np.uintp)
+        st = KsRemoveStats()
+        self._check(self._L.ks_batch_remove_resources(self._h, flags, self.ngraphs, ls, removed.ctypes.data, nr.value,
+                                                      C.byref(nr), off.ctypes.data, evicted.ctypes.data, ne.value,
+                                                      C.byref(ne), C.byref(st)))
+        del keep
+        per = [removed[int(off[g]):int(off[g + 1])].copy() for g in range(self.ngraphs)]
+        return per, evicted[:ne.value], st.as_dict()
+
+    def add_resources(self, per_graph) -> dict:
+        """ks_batch_add_resources: per_graph[g] = None or (nodes, arcs) as Context.add_resources
+        takes them, in graph g's own ids. → stats summed over the local devices."""
+        if len(per_graph) != self.ngraphs:
+            raise ValueError("one (nodes, arcs) pair (or None) per loaded graph")
+        ls = (KsBatchResList * max(1, self.ngraphs))()
+        keep = []
+        for g, e in enumerate(per_graph):
+            if e is None:
+                continue
+            nd, ar = res_rows(e[0], RES_NODE_DT), res_rows(e[1], RES_ARC_DT)
+            keep.append((nd, ar))
+            if nd.shape[0]:
+                ls[g].nodes, ls[g].n = nd.ctypes.data, nd.shape[0]
+            if ar.shape[0]:
+                ls[g].arcs, ls[g].m = ar.ctypes.data, ar.shape[0]
+        st = KsGrowStats()
+        self._check(self._L.ks_batch_add_resources(self._h, 0, self.ngraphs, ls, C.byref(st)))
         del keep
         return st.as_dict()
 
