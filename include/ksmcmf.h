@@ -46,6 +46,11 @@
  *                            (:1183-1192) for tasks that have their node: arcs added, re-costed
  *                            and dropped as the cost model lists them, generated and applied on
  *                            device
+ *   ks_update_nodes          the rest of that sweep, updateFlowGraph (graph_manager.go:1012-1033):
+ *                            updateEquivClassNode (:931-1010) and updateResourceNode →
+ *                            updateResOutgoingArcs (:1094-1111), updateResToSinkArc (:1116-1129):
+ *                            class and resource arcs added, re-costed, re-sized and dropped,
+ *                            generated and applied on device
  *   ks_get_bindings          the TaskBindings the device keeps (ks_set_bindings, the commits)
  *   ks_last_error           the panics of solver.go:97-108, 148-153, 175-178, 223-225
  *                            become status codes + a message
@@ -111,6 +116,8 @@ extern "C" {
                                   structs were added).
                                   ks_update_tasks (still 5: one entry point and one
                                   struct were added, nothing was resized).
+                                  ks_update_nodes (still 5: one entry point and two
+                                  structs were added, nothing was resized).
                                   ks_opts (96 B) CHANGED SIZE in ABI 2 and ks_result in
                                   ABI 2, 3 and 5: a caller must check
                                   ks_abi_version() == KSMCMF_ABI_VERSION before ks_create. */
@@ -549,7 +556,7 @@ typedef struct ks_commit_stats {
  *     only changed arcs get a record). Type-0 heads count as resources exactly as
  *     ks_topology_stats counts them (the coordinator, an equivalence class above
  *     machines): a cost model with arcs between equivalence classes leaves the
- *     flag off and sends those capacities itself.
+ *     flag off and sends those capacities itself (ks_update_nodes).
  *   - A capacity that would fall below its arc's lower bound: KS_E_VERIFY, nothing
  *     changes.
  * Requires a successful solve on the context (KS_E_INVALID otherwise) and, on
@@ -938,7 +945,9 @@ typedef struct ks_grow_stats {        /* 96 B */
  * back. A device failure after the records were emitted leaves the store unusable until the
  * next ks_load_graph; the host's node table is rolled back. stats may be NULL. On a batch:
  * ks_batch_add_resources.
- * UpdateResourceTopology (:217-236, a resource's slots change) is not covered. */
+ * UpdateResourceTopology (:217-236, a live resource's slots change): ks_update_nodes with the
+ * PU → sink arc listed at its new slot count, then ks_complete_tasks(k = 0,
+ * KS_COMPLETE_RESOURCE_CAPS [| KS_COMPLETE_PREEMPTIVE]) for the capacities above it. */
 int ks_add_resources(ks_ctx* ctx, int32_t flags /* must be 0 */,
                      const ks_res_node* nodes, size_t n,
                      const ks_res_arc* arcs, size_t m,
@@ -1028,12 +1037,106 @@ typedef struct ks_update_stats {      /* 96 B */
  * anything changes on the device. A device failure after the records were emitted leaves the
  * store unusable until the next ks_load_graph. stats may be NULL; records == arcs_added +
  * cost_updates + arcs_removed + unsched_updates + unsched_added. No batch twin.
- * UpdateResourceTopology (:217-236) stays with ks_apply_deltas. */
+ * The class and resource nodes' arcs are ks_update_nodes; UpdateResourceTopology (:217-236) is
+ * ks_update_nodes on the PU → sink arc, then ks_complete_tasks(k = 0, KS_COMPLETE_RESOURCE_CAPS
+ * [| KS_COMPLETE_PREEMPTIVE]). */
 int ks_update_tasks(ks_ctx* ctx, int32_t flags,
                     const uint64_t* tasks, size_t k,
                     const uint64_t* arc_off /* k + 1 */, const ks_task_arc* arcs,
                     const uint64_t* unsched_ids, size_t nu, int64_t unsched_sink_cost,
                     ks_update_stats* stats /* may be NULL */);
+
+#define KS_CAP_KEEP UINT64_MAX        /* listed arc: keep the held arc's capacity (ChangeArcCost) */
+#define KS_NODES_KEEP_UNLISTED 1      /* no arc is deleted for being unlisted */
+
+typedef struct ks_node_arc { uint64_t dst; int64_t cost; uint64_t cap; } ks_node_arc;   /* 24 B */
+
+typedef struct ks_node_stats {        /* 96 B */
+    int64_t nodes;           /* tails listed                                                  */
+    int64_t arcs_added;      /* listed, not held, cap > 0 (ADD_ARC)                           */
+    int64_t arcs_updated;    /* listed, held, cost or capacity differs (UPDATE_ARC)           */
+    int64_t arcs_unchanged;  /* listed, held, same cost and capacity: no record               */
+    int64_t arcs_skipped;    /* listed, not held, cap == 0: no record                         */
+    int64_t arcs_zeroed;     /* listed, held, cap == 0: deleted (UPDATE_ARC 0/0)              */
+    int64_t arcs_removed;    /* held, unlisted, deleted (UPDATE_ARC 0/0)                      */
+    int64_t records;         /* arcs_added + arcs_updated + arcs_zeroed + arcs_removed        */
+    int64_t reserved[4];
+} ks_node_stats;
+
+/* Class and resource arcs follow the cost model, on device: the part of AddOrUpdateJobNodes →
+ * updateFlowGraph (flowmanager/graph_manager.go:1012-1033) that ks_update_tasks leaves out. The
+ * sweep walks on from the task nodes through every equivalence-class node and every resource
+ * node it reaches. updateEquivClassNode (:931-1010): per class, EquivClassToEquivClass and
+ * EquivClassToResourceNode each give a cost AND a capacity; an absent arc gets AddArc(0, cap,
+ * cost), a held one ChangeArc(low kept, cap, cost), and removeInvalidECPrefArcs /
+ * removeInvalidPrefResArcs (:732-790) drop what is no longer preferred. updateResourceNode →
+ * updateResOutgoingArcs (:1094-1111): ChangeArcCost on every resource → resource arc, and
+ * updateResToSinkArc (:1116-1129) on PU → sink. The caller lists, per tail, the out-arcs it
+ * should have with their costs and capacities; the device diffs each list against the arcs the
+ * store holds, so the caller keeps no shadow of those arcs (which the commits,
+ * ks_remove_resources, ks_complete_tasks and ks_add_resources rewrite or delete on the device
+ * alone). The records are generated in device memory and applied as ONE stream with the
+ * semantics of ks_apply_deltas (all or nothing, in place, store counters, warm-start bookkeeping,
+ * the dirty-cell marks of a partition). The stream's order is that of ks_update_tasks, so a host
+ * restatement produces the identical stream: the records on held arcs in ascending arc-slot
+ * order, the order in which ks_get_graph lists arcs; then the ADD_ARC records in input order.
+ * No (src, dst) appears twice (ks_store_stats.superseded stays 0). Only the ids, the offsets and
+ * the 24-byte arcs cross PCIe.
+ *   - Tails: every nodes[i] must be a live node of type 0, a machine, an intermediate node or a
+ *     PU. The first id in input order that is 0, beyond the graph, dead, a task, a sink or
+ *     listed a second time: KS_E_INVALID, the error names the id, nothing changes. No node is
+ *     added or removed; the host's node table is only read.
+ *   - Listed arcs: tail i's list is arcs[arc_off[i] .. arc_off[i + 1]), the offsets as in
+ *     ks_add_tasks (arc_off[0] == 0, never decreasing, else KS_E_INVALID); an empty list is
+ *     legal. The head must be a live node that is no task and not the tail itself; a PU's only
+ *     legal head is a sink, and a sink head is legal only from a PU or a type-0 tail: else
+ *     KS_E_INVALID, the error names the tail and the head. A head listed twice for one tail:
+ *     KS_E_INVALID. |cost| > 2^40: KS_E_RANGE. A cap other than KS_CAP_KEEP above 2^53:
+ *     KS_E_RANGE. The first offending arc in input order is the one reported; on one arc the
+ *     head comes before the repeat, the repeat before the cost, the cost before the capacity.
+ *     Only when every arc passes these is the store consulted, and again the first offending
+ *     arc in input order is reported (the two cases below that refuse). Per listed arc (u, h):
+ *       the store does not hold it, cap > 0         ADD_ARC (low 0, cap, the listed cost, type 0)
+ *       the store does not hold it, cap == 0        no record (arcs_skipped): a capacity of 0 is
+ *                                                   an absent arc, as everywhere in this library
+ *       the store does not hold it, KS_CAP_KEEP     KS_E_INVALID naming tail and head (there is
+ *                                                   nothing to keep)
+ *       held; c = cap, or under KS_CAP_KEEP the held capacity:
+ *         c == 0 and the held lower bound is 0      UPDATE_ARC 0/0, a deletion (arcs_zeroed)
+ *         c below the held lower bound              KS_E_VERIFY, nothing changes, as in the commits
+ *         cost and capacity both unchanged          no record (ChangeArc logs nothing then)
+ *         otherwise                                 UPDATE_ARC: low and type kept, cap c, the
+ *                                                   listed cost, old_cost the cost it had
+ *   - Held arcs of a listed tail that its list does not name: a type-0 tail's are deleted
+ *     (UPDATE_ARC with low == cap == 0), except an arc into a sink, which stays: removeInvalid*
+ *     never looks at the sink, and an unscheduled aggregator's arc into the sink belongs to the
+ *     unit accounting of the task calls. So an empty list is "no preferences" (:942-945,
+ *     :980-983) and drops every non-sink arc of the class. A machine, an intermediate node or a
+ *     PU never loses an arc: updateResOutgoingArcs deletes nothing. With KS_NODES_KEEP_UNLISTED
+ *     nothing at all is deleted for being unlisted.
+ *   - flags: KS_NODES_KEEP_UNLISTED or 0; any other bit is KS_E_INVALID.
+ * Needs no previous solve. Without the flag the type-0 tails' segments of the residual CSR are
+ * walked (a pending rebuild runs first, as in ks_update_tasks); with it only the node store, the
+ * arc table and the (src, dst) index are read. k == 0 does nothing and keeps the solution, as
+ * does a call that generates no record (the solution and the mapping stay valid); a call that
+ * generates any record invalidates them, exactly as ks_apply_deltas does. A full segment takes
+ * the store's rebuild path (ks_store_stats.rebuilds). Every refusal is found before anything
+ * changes on the device. A device failure after the records were emitted leaves the store
+ * unusable until the next ks_load_graph. stats may be NULL. No batch twin.
+ * What the call does not do:
+ *   - It does not purge a class that lost its last in-arc: the reference declares
+ *     PurgeUnconnectedEquivClassNodes (:347-357) and never calls it. ks_remove_resources with
+ *     the class as a root removes one.
+ *   - A capacity written here is overwritten by any later call that runs the capacity rule
+ *     (KS_COMMIT_RESOURCE_CAPS, KS_REMOVE_RESOURCE_CAPS, KS_COMPLETE_RESOURCE_CAPS) on an arc
+ *     that rule counts as a resource arc: the caveat the commits already carry.
+ *   - UpdateResourceTopology (:217-236): list PU → sink with the new slot count here, then run
+ *     ks_complete_tasks(k = 0, KS_COMPLETE_RESOURCE_CAPS [| KS_COMPLETE_PREEMPTIVE]), which
+ *     carries the new slots up the chain. */
+int ks_update_nodes(ks_ctx* ctx, int32_t flags,
+                    const uint64_t* nodes, size_t k,
+                    const uint64_t* arc_off /* k + 1 */, const ks_node_arc* arcs,
+                    ks_node_stats* stats /* may be NULL */);
 
 /* pu[i] = the PU task[i] is bound to on the device (ks_set_bindings, the commits), 0 =
  * unbound: for the pinned recipe above and for checkpoints. A task id that is not a live
@@ -1214,8 +1317,9 @@ int ks_batch_update_unsched_costs(ks_batch* b, size_t ngraphs, const ks_batch_ta
  * next solve, stats (may be NULL) summed over the local devices, no collective, and every
  * message names the graph and the graph-local id. No supply changes, so no sink's demand
  * moves, and evicted tasks stay task nodes: the rows of ks_batch_gather keep their length.
- * A live resource's slot count changing (UpdateResourceTopology) stays with
- * ks_batch_apply_deltas. */
+ * A live resource's slot count changing (UpdateResourceTopology) is, on a single context,
+ * ks_update_nodes on the PU → sink arc followed by the capacity refresh of ks_complete_tasks;
+ * ks_update_nodes has no batch twin, so on a batch it goes through ks_batch_apply_deltas. */
 typedef struct ks_batch_res_list {   /* one graph's part of a call, in the graph's OWN ids */
     const uint64_t*    roots; size_t k;     /* ks_batch_remove_resources; k == 0: untouched        */
     const ks_res_node* nodes; size_t n;     /* ks_batch_add_resources; n == 0 && m == 0: untouched */

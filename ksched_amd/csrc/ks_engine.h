@@ -165,6 +165,13 @@ public:
                      size_t first_pair, const uint64_t* unsched_ids, size_t nu, int64_t sink_slot, int64_t sink_cost,
                      ks_update_stats* stats, bool* dirty, bool* changed, std::string& err,
                      const BatchView* bv = nullptr);
+    // ks_update_nodes (the k tails with the arcs each should have; offsets checked by the caller).
+    // first_pair, first_cost, first_cap: the first arc that repeats an earlier head of its own
+    // tail, whose cost and whose capacity is out of range, arc_off[k] when none does or is. No
+    // node is edited. *dirty, *changed: as in update_tasks.
+    int update_nodes(int flags, const uint64_t* nodes, size_t k, const uint64_t* arc_off, const ks_node_arc* arcs,
+                     size_t first_pair, size_t first_cost, size_t first_cap, ks_node_stats* stats, bool* dirty,
+                     bool* changed, std::string& err);
     // ks_get_bindings: pu[i] = the device-kept binding of task[i] (ids checked by the caller).
     int get_bindings(const uint64_t* task, uint64_t* pu, size_t k, std::string& err);
     int device() const;

@@ -372,6 +372,7 @@ struct EngineImpl {
     DBuf<AddCtl> add_ctl;               // ks_add_tasks: its counters (the scratch is the commit's)
     DBuf<GrowCtl> grow_ctl;             // ks_add_resources: its counters (the scratch is the commit's)
     DBuf<UpdCtl> upd_ctl;               // ks_update_tasks: its counters (the scratch is the commit's)
+    DBuf<NodCtl> nod_ctl;               // ks_update_nodes: its counters (the scratch is the commit's)
 
     SchedDev schd() const {
         SchedDev d{};

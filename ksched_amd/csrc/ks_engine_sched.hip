@@ -1,7 +1,7 @@
 // ks_engine_sched.hip — the engine's scheduler glue: bindings, scheduling deltas,
 // unscheduled costs, topology statistics, ks_commit_schedule and ks_commit_preemptive,
-// ks_remove_resources, ks_complete_tasks, ks_add_tasks, ks_add_resources, ks_update_tasks and
-// ks_get_bindings. It launches the kernels of ks_sched.hip and ks_store.hip through their
+// ks_remove_resources, ks_complete_tasks, ks_add_tasks, ks_add_resources, ks_update_tasks,
+// ks_update_nodes and ks_get_bindings. It launches the kernels of ks_sched.hip and ks_store.hip through their
 // launchers, none of the engine's.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -19,6 +19,10 @@ namespace ks {
 namespace {
 struct NonZero {
     __host__ __device__ int operator()(int x) const { return x != 0; }
+};
+// ks_update_nodes: an arc slot whose flag carries a record (NOD_RECORD, NOD_UNLISTED).
+struct NodRecord {
+    __host__ __device__ int operator()(int x) const { return x >= NOD_RECORD; }
 };
 
 // out[i] = in[0] + … + in[i − 1] for i < n, on st; hipcub's scratch is map_tmp.
@@ -1431,6 +1435,173 @@ int Engine::update_tasks(int flags, const uint64_t* tasks, size_t k, const uint6
         const auto t3 = std::chrono::steady_clock::now();
         std::fprintf(stderr,
                      "update: %zu tasks, %zu arcs, %lld records, upload + checks + diff %.3f ms, sizing %.3f ms, "
+                     "emit + apply %.3f ms\n",
+                     k, na, (long long)nrec, ms(t0, t1), ms(t1, t2), ms(t2, t3));
+    }
+    *changed = true;
+    return KS_OK;
+}
+
+// ks_update_nodes: the eighth body. The ids, the offsets and the 24-byte arcs go up; one lane per
+// id checks and claims it, one lane per listed arc checks its head against its tail's type, asks
+// the store's index for the arc's slot and takes its row of the table, the type-0 tails' segments
+// give the held arcs nobody listed (with KS_NODES_KEEP_UNLISTED no segment is read and no CSR is
+// needed), and ONE host sync brings every refusal and the record counts (no step before it writes
+// anything but scratch). Over the arc slots there is one flag array and its scan; everything else
+// is per tail, per listed arc or per chunk position. Then the sizing of the arc table and the
+// index, and the records on held arcs (ascending arc slot) and the new arcs (input order) reach
+// store_apply as one stream. No node is edited.
+int Engine::update_nodes(int flags, const uint64_t* nodes, size_t k, const uint64_t* arc_off, const ks_node_arc* arcs,
+                         size_t first_pair, size_t first_cost, size_t first_cap, ks_node_stats* stats, bool* dirty,
+                         bool* changed, std::string& err) {
+    EngineImpl& s = *p_;
+    *dirty = *changed = false;
+    if (!k) return KS_OK;
+    KS_CHECK(hipSetDevice(s.device));
+    hipStream_t st = s.stream;
+    const bool walk = !(flags & KS_NODES_KEEP_UNLISTED);
+    int rc = walk ? fresh_csr(s, err) : KS_OK;   // the chunk items walk the residual CSR
+    if (rc) return rc;
+    const bool log = s.opts.log_cycles != 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int64_t nst = s.nstore;
+    const int hi = s.hi();
+    const size_t na = (size_t)arc_off[k];
+    if (k > (size_t)INT32_MAX / 4 || na > (size_t)INT32_MAX / 4) {
+        err = "too many nodes or arcs";
+        return KS_E_RANGE;
+    }
+    NodDev u{};
+    u.k = (int)k;
+    u.na = (int)na;
+    u.hi = hi;
+    u.keep = walk ? 0 : 1;
+    u.nst = nst;
+    unsigned long long *d_nodes = nullptr, *d_off = nullptr, *d_arcs = nullptr;
+    rc = carve_scratch(s, [&](Carve<int>& ci, Carve<unsigned long long>& cu) {
+        u.n_own = ci.take(nst + 1);
+        for (int** x : {&u.n_slot, &u.nch, &u.ch_off}) *x = ci.take((int64_t)k + 1);
+        for (int** x : {&u.l_slot, &u.lflag, &u.l_off}) *x = ci.take((int64_t)na + 1);
+        for (int** x : {&u.sflag, &u.s_off}) *x = ci.take((int64_t)hi + 1);
+        d_nodes = cu.take(k);
+        d_off = cu.take(k + 1);
+        d_arcs = cu.take(3 * na);
+    }, 0, false, err);
+    if (rc) return rc;
+    KS_CHECK(clear_ctl(s.nod_ctl, st));
+    u.ctl = s.nod_ctl.p;
+    u.nodes = d_nodes;
+    u.arc_off = d_off;
+    u.arcs = (const ks_node_arc*)d_arcs;
+    wire_hash(s, u);
+    KS_CHECK(hipMemcpyAsync(d_nodes, nodes, k * 8, hipMemcpyHostToDevice, st));
+    KS_CHECK(hipMemcpyAsync(d_off, arc_off, (k + 1) * 8, hipMemcpyHostToDevice, st));
+    if (na) KS_CHECK(hipMemcpyAsync(d_arcs, arcs, na * sizeof(ks_node_arc), hipMemcpyHostToDevice, st));
+    SchedDev d = s.schd();
+    const int ni_max = (int)(k + s.m2cap / 64 + 1);
+    // ---- 1. ids, heads, the diff and the unlisted arcs: one sync
+    KS_CHECK(sched_nod_check(d, u, walk, st));
+    if (walk) {
+        KS_CHECK(exclusive_sum(s, (const int*)u.nch, u.ch_off, (int64_t)k + 1, st));
+        KS_CHECK(sched_nod_unlisted(d, u, ni_max, st));
+    }
+    hipcub::TransformInputIterator<int, NodRecord, const int*> is_rec(u.sflag, NodRecord());
+    KS_CHECK(exclusive_sum(s, is_rec, u.s_off, (int64_t)hi + 1, st));
+    KS_CHECK(exclusive_sum(s, (const int*)u.lflag, u.l_off, (int64_t)na + 1, st));
+    KS_CHECK(sched_nod_totals(u, st));
+    NodCtl h{};
+    KS_CHECK(hipMemcpyAsync(&h, u.ctl, sizeof(NodCtl), hipMemcpyDeviceToHost, st));
+    KS_CHECK(hipStreamSynchronize(st));
+    const auto t1 = std::chrono::steady_clock::now();
+    if (h.bad_node) {
+        size_t i;
+        if (!first_bad(h.bad_node, k, &i)) {
+            err = "inconsistent node index";
+            return KS_E_DEVICE;
+        }
+        err = "node " + std::to_string(nodes[i]) + " is not a live class, machine, intermediate or PU node listed once "
+              "(0, beyond the graph, dead, a task, a sink, or listed before)";
+        return KS_E_INVALID;
+    }
+    auto tail_of = [&](size_t j) {   // the last i with arc_off[i] ≤ j
+        return (size_t)(std::upper_bound(arc_off, arc_off + k, (uint64_t)j) - arc_off) - 1;
+    };
+    // the first offending arc in input order; on one arc the head, the repeat, the cost, then the capacity
+    if (h.bad_head || std::min({first_pair, first_cost, first_cap}) < na) {
+        size_t jh;
+        if (!first_bad(h.bad_head, na, &jh)) {
+            err = "inconsistent arc index";
+            return KS_E_DEVICE;
+        }
+        const size_t j = std::min({jh, first_pair, first_cost, first_cap});
+        const std::string who = "node " + std::to_string(nodes[tail_of(j)]) + ": ";
+        const std::string head = std::to_string(arcs[j].dst);
+        if (j == jh) {
+            err = who + "head " + head + " is not a legal head (0, beyond the graph, dead, a task or the tail itself; a "
+                  "PU's only head is a sink, and only a PU or a type-0 node has an arc into a sink)";
+            return KS_E_INVALID;
+        }
+        if (j == first_pair) {
+            err = who + "head " + head + " is listed twice: the list is the set of arcs the node should have";
+            return KS_E_INVALID;
+        }
+        err = who + (j == first_cost ? "the cost" : "the capacity") + " of its arc into " + head +
+              " is outside the supported range";
+        return KS_E_RANGE;
+    }
+    // then the store's answers: KS_CAP_KEEP on an arc it does not hold, a capacity below a lower bound
+    if (h.bad_keep || h.bad_low) {
+        size_t jk, jl;
+        if (!first_bad(h.bad_keep, na, &jk) || !first_bad(h.bad_low, na, &jl)) {
+            err = "inconsistent arc index";
+            return KS_E_DEVICE;
+        }
+        const size_t j = std::min(jk, jl);
+        const std::string who = "node " + std::to_string(nodes[tail_of(j)]) + ": ";
+        if (j == jk) {
+            err = who + "KS_CAP_KEEP on its arc into " + std::to_string(arcs[j].dst) + ", which the store does not hold: "
+                  "there is no capacity to keep";
+            return KS_E_INVALID;
+        }
+        err = who + "the capacity of its arc into " + std::to_string(arcs[j].dst) + " would fall below the arc's lower bound";
+        return KS_E_VERIFY;
+    }
+    if (h.n_add < 0 || h.n_upd < 0 || h.n_same < 0 || h.n_skip < 0 || h.n_zero < 0 || h.n_del < 0 ||
+        (int64_t)h.n_add + h.n_upd + h.n_same + h.n_skip + h.n_zero != (int64_t)na || h.rec_add != h.n_add ||
+        h.n_upd + h.n_zero + h.n_del != h.rec_held || h.rec_held > hi || (!walk && h.n_del)) {
+        err = "inconsistent record counts";
+        return KS_E_DEVICE;
+    }
+    const int64_t nrec = (int64_t)h.rec_held + h.rec_add;
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        stats->nodes = (int64_t)k;
+        stats->arcs_added = h.n_add;
+        stats->arcs_updated = h.n_upd;
+        stats->arcs_unchanged = h.n_same;
+        stats->arcs_skipped = h.n_skip;
+        stats->arcs_zeroed = h.n_zero;
+        stats->arcs_removed = h.n_del;
+        stats->records = nrec;
+    }
+    if (!nrec) return KS_OK;   // every list is what the store holds: the solution stands
+    // ---- 2. room for the new arcs
+    rc = ensure_arcs(s, (int64_t)hi + h.rec_add, err);
+    if (rc == KS_OK) rc = ensure_hash(s, (int64_t)h.rec_add, err);
+    if (rc == KS_OK) rc = size_stream(s, nrec, 0, err);
+    if (rc) return rc;
+    // from here on a failure leaves the device state unknown
+    *dirty = true;
+    d = s.schd();   // (the arc table may have moved)
+    const auto t2 = std::chrono::steady_clock::now();
+    // ---- 3. the records, at their fixed positions, and the apply
+    KS_CHECK(sched_nod_emit(d, u, walk && h.n_del, ni_max, h.rec_held, s.d_recs.p, st));
+    rc = apply_stream(s, nrec, {}, true, err);
+    if (rc) return rc;
+    if (log) {
+        const auto t3 = std::chrono::steady_clock::now();
+        std::fprintf(stderr,
+                     "nodes: %zu nodes, %zu arcs, %lld records, upload + checks + diff %.3f ms, sizing %.3f ms, "
                      "emit + apply %.3f ms\n",
                      k, na, (long long)nrec, ms(t0, t1), ms(t1, t2), ms(t2, t3));
     }

@@ -1029,6 +1029,52 @@ int ks_update_tasks(ks_ctx* c, int32_t flags, const uint64_t* tasks, size_t k, c
     return KS_OK;
 }
 
+// The rest of updateFlowGraph (flowmanager/graph_manager.go:1012-1033): updateEquivClassNode
+// (:931-1010) and updateResourceNode (:1094-1129). No node is edited, so there is no NodeTxn: the
+// host's part is the argument and flag checks, the offsets, the two range checks and a head
+// listed twice for one tail (a sort of each tail's heads, as in ks_update_tasks). The device
+// checks the ids and the heads and generates the records.
+int ks_update_nodes(ks_ctx* c, int32_t flags, const uint64_t* nodes, size_t k, const uint64_t* arc_off,
+                    const ks_node_arc* arcs, ks_node_stats* stats) {
+    if (!c) return KS_E_INVALID;
+    if (int g = store_guard(c)) return g;
+    if (flags & ~KS_NODES_KEEP_UNLISTED) return c->fail(KS_E_INVALID, "unknown update flag");
+    if (k && (!nodes || !arc_off)) return c->fail(KS_E_INVALID, "null node or offset array");
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (!k) return KS_OK;   // nothing is refreshed: the solution stands
+    if (arc_off[0] != 0) return c->fail(KS_E_INVALID, "arc_off[0] must be 0");
+    for (size_t i = 0; i < k; ++i)
+        if (arc_off[i + 1] < arc_off[i])
+            return c->fail(KS_E_INVALID, "arc_off decreases at node " + std::to_string(nodes[i]));
+    if (arc_off[k] && !arcs) return c->fail(KS_E_INVALID, "null arc array");
+    const size_t na = (size_t)arc_off[k];
+    // the first arc in input order that repeats an earlier head of its own tail, and the first
+    // whose cost and whose capacity leave the range
+    size_t first_pair = na, first_cost = na, first_cap = na;
+    for (size_t j = 0; j < na && (first_cost == na || first_cap == na); ++j) {
+        if (first_cost == na && (arcs[j].cost > (int64_t(1) << 40) || arcs[j].cost < -(int64_t(1) << 40))) first_cost = j;
+        if (first_cap == na && arcs[j].cap != KS_CAP_KEEP && arcs[j].cap > (uint64_t(1) << 53)) first_cap = j;
+    }
+    {
+        std::vector<std::pair<uint64_t, size_t>> heads;
+        for (size_t i = 0; i < k; ++i) {
+            heads.clear();
+            for (size_t j = (size_t)arc_off[i]; j < (size_t)arc_off[i + 1]; ++j) heads.emplace_back(arcs[j].dst, j);
+            std::sort(heads.begin(), heads.end());
+            for (size_t q = 1; q < heads.size(); ++q)
+                if (heads[q].first == heads[q - 1].first) first_pair = std::min(first_pair, heads[q].second);
+            if (first_pair < na) break;   // (a later tail's arcs come later in input order)
+        }
+    }
+    bool dirty = false, changed = false;
+    const int rc = c->eng.update_nodes(flags, nodes, k, arc_off, arcs, first_pair, first_cost, first_cap, stats, &dirty,
+                                       &changed, c->err);
+    follow_rebuild(c);
+    if (rc) return delta_failed(c, rc, nullptr, dirty, stats);
+    if (changed) drop_solution(c);
+    return KS_OK;
+}
+
 int ks_get_bindings(ks_ctx* c, const uint64_t* task, uint64_t* pu, size_t k) {
     if (!c) return KS_E_INVALID;
     if (int g = store_guard(c)) return g;

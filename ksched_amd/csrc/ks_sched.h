@@ -447,4 +447,81 @@ hipError_t sched_upd_emit(const SchedDev& d, const UpdDev& u, int rec_held, ks_d
 hipError_t sched_add_agg_flags(const SchedDev& d, const AddDev& a, hipStream_t st);
 hipError_t sched_add_emit_aggs(const SchedDev& d, const AddDev& a, long long base, ks_delta* recs, hipStream_t st);
 
+// ---- ks_update_nodes: class and resource arcs follow the cost model. The rest of the sweep of
+// AddOrUpdateJobNodes → updateFlowGraph (flowmanager/graph_manager.go:1012-1033):
+// updateEquivClassNode (:931-1010), each AddArc or ChangeArc with a cost and a capacity, then
+// removeInvalidECPrefArcs / removeInvalidPrefResArcs (:732-790); updateResourceNode →
+// updateResOutgoingArcs (:1094-1111) with updateResToSinkArc (:1116-1129). The tails are few and
+// wide, so the scratch is per listed arc and per chunk position: a listed arc finds its slot
+// through the store's (src, dst) index, a type-0 tail's held arcs nobody listed are found in its
+// residual segment. One array over the arc slots (sflag) and its scan give the held records
+// their ascending-slot order.
+
+// sflag of an arc slot: what the call found for it.
+constexpr int NOD_LISTED = 1;     // a listed arc names it, no record (same cost and capacity)
+constexpr int NOD_RECORD = 2;     // a listed arc names it and it gets a record (an update or the 0/0 of a zeroed arc)
+constexpr int NOD_UNLISTED = 3;   // a type-0 tail's arc nobody listed: deleted
+
+// Device counters of one refresh; the host reads them in one 64-byte copy.
+struct NodCtl {
+    int bad_node;    // k − the index of the first id that is 0, beyond the graph, dead, a task, a sink or listed before, 0 none
+    int bad_head;    // na − the index of the first arc whose head is illegal for its tail, 0 none
+    int bad_keep;    // na − the index of the first KS_CAP_KEEP arc the store does not hold, 0 none
+    int bad_low;     // na − the index of the first held arc whose new capacity is below its lower bound, 0 none
+    int n_add;       // listed, not held, cap > 0 (ADD_ARC)
+    int n_upd;       // listed, held, another cost or capacity (UPDATE_ARC)
+    int n_same;      // listed, held, the same cost and capacity
+    int n_skip;      // listed, not held, cap == 0
+    int n_zero;      // listed, held, cap == 0: deleted
+    int n_del;       // held, unlisted, deleted
+    int rec_held;    // the arc-slot scan's total: n_upd + n_zero + n_del
+    int rec_add;     // the listed-arc scan's total: n_add
+    int reserved[4];
+};
+
+// Inputs and scratch of one refresh (device pointers; nst node slots, hi arc slots).
+struct NodDev {
+    int k;                             // tails
+    int na;                            // listed arcs
+    int hi;                            // arc slots handed out when the call began
+    int keep;                          // KS_NODES_KEEP_UNLISTED: nothing is deleted, no segment is walked
+    const unsigned long long* nodes;   // [k] unchecked
+    const unsigned long long* arc_off; // [k + 1] checked by the host: 0 first, never decreasing, na last
+    const ks_node_arc* arcs;           // [na] costs, capacities and repeats checked by the host, heads unchecked
+    long long nst;                     // node slots the passes may read
+    int* n_own;                        // [nst + 1] per node slot: k − i of the first listing i of the tail, 0: not
+                                       //   listed (claimed with atomicMax, so the array starts zeroed)
+    int* n_slot;                       // [k + 1] node slot of tail i, −1: the id is refused
+    int* nch;                          // [k + 1] 64-position chunks of a type-0 tail's segment, 0 for a resource
+                                       //   tail and under keep; ch_off its scan
+    int* ch_off;                       // [k + 1]
+    int* l_slot;                       // [na + 1] 1 + the arc slot listed arc j names, 0: the store does not hold it
+    int* lflag;                        // [na + 1] 1: listed arc j is an ADD_ARC; l_off its scan
+    int* l_off;                        // [na + 1]
+    int* sflag;                        // [hi + 1] NOD_* of the arc slot, 0: untouched; s_off the scan of its records
+    int* s_off;                        // [hi + 1]
+    const unsigned long long* hkey;    // the store's (src, dst) index (ks_store.h)
+    const int* hval;
+    int hmask;                         // capacity − 1, −1: no index yet
+    NodCtl* ctl;
+};
+
+// The tail seed, one lane per id (liveness, type, the claim of n_own, n_slot, nch; walk: the id
+// must lie in the built CSR, whose segments are walked), then the listed-arc pass, one lane per
+// arc (the head against its tail's type, the index lookup, the table's row: l_slot, lflag, sflag
+// and the counters). Nothing outside the scratch is written. The caller scans nch → ch_off when
+// it walks.
+hipError_t sched_nod_check(const SchedDev& d, const NodDev& u, bool walk, hipStream_t st);
+// The held arcs of the type-0 tails that nobody listed, one wave per 64-position chunk item of
+// their segments (ni_max bounds the items); an arc into a sink stays. The caller scans
+// sflag → s_off (records only) and lflag → l_off.
+hipError_t sched_nod_unlisted(const SchedDev& d, const NodDev& u, int ni_max, hipStream_t st);
+// ctl->rec_held and ctl->rec_add after the scans.
+hipError_t sched_nod_totals(const NodDev& u, hipStream_t st);
+// The records on held arcs at s_off (ascending arc slot: the listed ones by their lane, the
+// unlisted by the chunk items again), the ADD_ARC records at rec_held + l_off (input order);
+// d: the arc table as it is now, after any growth.
+hipError_t sched_nod_emit(const SchedDev& d, const NodDev& u, bool walk, int ni_max, int rec_held, ks_delta* recs,
+                          hipStream_t st);
+
 }  // namespace ks

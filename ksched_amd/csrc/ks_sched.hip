@@ -1139,8 +1139,9 @@ __global__ void k_grow_emit(SchedDev d, GrowDev g, int rec_pu, ks_delta* __restr
 // delete, only the aggregator counts to complete) by a pass over the arc table. Three record
 // families at fixed positions: held arcs by slot, new arcs in input order, aggregators by id.
 
-// The arc slot of src → dst (node slots), −1: the store does not hold it.
-__device__ __forceinline__ int upd_held_slot(const SchedDev& d, const UpdDev& u, int src, int dst) {
+// The arc slot of src → dst (node slots), −1: the store does not hold it (u: UpdDev or NodDev).
+template <class Dev>
+__device__ __forceinline__ int upd_held_slot(const SchedDev& d, const Dev& u, int src, int dst) {
     if (u.hmask < 0) return -1;
     const int e = store_hfind(u.hkey, u.hmask, arc_hkey((long long)src + 1, (long long)dst + 1));
     const int s = e >= 0 ? u.hval[e] : -1;
@@ -1304,6 +1305,169 @@ __global__ void k_upd_emit_adds(UpdDev u, int rec_held, ks_delta* __restrict__ r
         const ks_task_arc x = u.arcs[j];
         recs[(long long)rec_held + u.l_off[j]] =
             arc_record(KS_ADD_ARC, 0, u.t_slot[task_of_arc(u.arc_off, u.k, j)], (int)(x.dst - 1), 0, 1, x.cost, 0);
+    }
+}
+
+// ----------------------------------------------------------------- update nodes ---
+// The other two thirds of updateFlowGraph (graph_manager.go:1012-1033). updateEquivClassNode
+// (:931-1010) gives every class arc a cost and a capacity, AddArc(0, cap, cost) where the graph
+// lacks it and ChangeArc(low kept, cap, cost) where it holds it, and then drops what is no longer
+// preferred (:732-790); updateResOutgoingArcs (:1094-1111) and updateResToSinkArc (:1116-1129)
+// re-cost the resource arcs and delete nothing. The diff is that of the tasks' refresh with a
+// narrower scratch: a listed arc keeps the slot it found (l_slot), so the one array over the arc
+// slots is sflag; the unlisted walk covers the type-0 tails' segments only, one wave per
+// 64-position chunk item (a cluster aggregator's segment also holds the reverse positions of
+// every task that points at it: no lane walks it).
+
+// An id must be a live class, machine, intermediate node or PU and listed once (the claim of
+// k_upd_seed). Only a type-0 tail loses unlisted arcs: every other chunk count is 0.
+__global__ void k_nod_seed(SchedDev d, NodDev u, int walk) {
+    const unsigned long long lim = walk ? (unsigned long long)d.ncap : (unsigned long long)u.nst;
+    for (long long i = blockIdx.x * (long long)SB + threadIdx.x; i < u.k; i += (long long)gridDim.x * SB) {
+        const unsigned long long id = u.nodes[i];
+        bool ok = id >= 1 && id <= lim;
+        int v = -1, nch = 0;
+        unsigned char ty = 0;
+        if (ok) {
+            v = (int)(id - 1);
+            ty = d.n_type[v];
+            ok = d.n_alive[v] && (!walk || d.perm[v] >= 0) &&
+                 (ty == KS_NODE_OTHER || ty == KS_NODE_MACHINE || ty == KS_NODE_INTERMEDIATE || ty == KS_NODE_PU);
+        }
+        if (ok) {
+            const int mine = (int)(u.k - i);
+            const int old = atomicMax(&u.n_own[v], mine);
+            if (old) atomicMax(&u.ctl->bad_node, min(old, mine));
+            if (walk && ty == KS_NODE_OTHER) nch = (remove_seg_len(d, d.perm[v]) + 63) >> 6;
+        } else {
+            v = -1;
+            atomicMax(&u.ctl->bad_node, (int)(u.k - i));
+        }
+        u.n_slot[i] = v;
+        u.nch[i] = nch;
+    }
+}
+
+// The capacity a listed arc asks for on the held slot s.
+__device__ __forceinline__ long long nod_cap(const SchedDev& d, const ks_node_arc& x, int s) {
+    return x.cap == KS_CAP_KEEP ? d.a_cap[s] : (long long)x.cap;
+}
+
+// One lane per listed arc: the head against its tail's type, then the table's row. The costs,
+// the capacities and the repeats are the host's checks, so no two lanes name one slot.
+__global__ void k_nod_heads(SchedDev d, NodDev u) {
+    for (long long j0 = blockIdx.x * (long long)SB; j0 < u.na; j0 += (long long)gridDim.x * SB) {   // (uniform per workgroup)
+        const long long j = j0 + threadIdx.x;
+        bool add = false, upd = false, same = false, skip = false, zero = false;
+        const int t = j < u.na ? u.n_slot[task_of_arc(u.arc_off, u.k, j)] : -1;
+        if (t >= 0) {   // (a refused tail is reported before any arc)
+            const ks_node_arc x = u.arcs[j];
+            bool ok = x.dst >= 1 && x.dst <= (unsigned long long)u.nst;
+            int v = 0;
+            if (ok) {
+                v = (int)(x.dst - 1);
+                const unsigned char tt = d.n_type[t], ht = d.n_type[v];
+                ok = d.n_alive[v] && ht != KS_NODE_TASK && v != t &&
+                     (ht == KS_NODE_SINK ? (tt == KS_NODE_PU || tt == KS_NODE_OTHER) : tt != KS_NODE_PU);
+            }
+            if (!ok) {
+                atomicMax(&u.ctl->bad_head, (int)(u.na - j));
+            } else {
+                const int s = upd_held_slot(d, u, t, v);
+                if (s < 0) {
+                    if (x.cap == KS_CAP_KEEP) atomicMax(&u.ctl->bad_keep, (int)(u.na - j));
+                    else if (x.cap == 0) skip = true;
+                    else u.lflag[j] = 1, add = true;
+                } else {
+                    u.l_slot[j] = s + 1;
+                    const long long c = nod_cap(d, x, s);
+                    if (c < d.a_low[s]) {
+                        u.sflag[s] = NOD_LISTED;
+                        atomicMax(&u.ctl->bad_low, (int)(u.na - j));
+                    } else {
+                        zero = c == 0;
+                        same = !zero && c == d.a_cap[s] && x.cost == d.a_cost[s];
+                        upd = !zero && !same;
+                        u.sflag[s] = same ? NOD_LISTED : NOD_RECORD;
+                    }
+                }
+            }
+        }
+        wave_count(&u.ctl->n_add, add);
+        wave_count(&u.ctl->n_upd, upd);
+        wave_count(&u.ctl->n_same, same);
+        wave_count(&u.ctl->n_skip, skip);
+        wave_count(&u.ctl->n_zero, zero);
+    }
+}
+
+// The arc slot of a type-0 tail's held arc that no listed arc named, −1 for every other
+// position: forward positions only, and an arc into a sink stays (removeInvalid* never looks at
+// the sink, and an unscheduled aggregator's arc into it belongs to the task calls).
+__device__ __forceinline__ int nod_unlisted_slot(const SchedDev& d, const NodDev& u, int w, int lane) {
+    RemoveDev r{};   // (the chunk items of remove_item_pos: the tails' node slots and their chunk scan)
+    r.front = u.n_slot;
+    r.ch_off = u.ch_off;
+    const int p = remove_item_pos(d, r, u.k, w, lane);
+    const int e = p >= 0 ? d.ent[p] : -1;
+    if (e < 0 || (e & 1) || (e >> 1) >= u.hi) return -1;
+    const int s = e >> 1;
+    if (!d.a_alive[s] || d.n_type[d.a_dst[s]] == KS_NODE_SINK) return -1;
+    return s;
+}
+
+__global__ void k_nod_walk(SchedDev d, NodDev u, int ni_max) {
+    const int lane = threadIdx.x & 63;
+    const int wave = (blockIdx.x * SB + threadIdx.x) >> 6;
+    const int nwaves = (gridDim.x * SB) >> 6;
+    const int ni = min(u.ch_off[u.k], ni_max);
+    for (int w = wave; w < ni; w += nwaves) {
+        const int s = nod_unlisted_slot(d, u, w, lane);
+        const bool del = s >= 0 && u.sflag[s] == 0;
+        if (del) u.sflag[s] = NOD_UNLISTED;
+        wave_count(&u.ctl->n_del, del);
+    }
+}
+
+__global__ void k_nod_totals(NodDev u) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        u.ctl->rec_held = u.s_off[u.hi];
+        u.ctl->rec_add = u.l_off[u.na];
+    }
+}
+
+// One lane per listed arc. A held one with a record writes it at its slot's place in stream part
+// 1: ChangeArc (low and type kept, the new capacity, the listed cost), or the delete (UPDATE_ARC
+// 0/0, as the commit writes it) of a zeroed arc. One the store lacks is stream part 2, input
+// order: AddArc(tail, head, 0, cap, cost, ArcTypeOther).
+__global__ void k_nod_emit_listed(SchedDev d, NodDev u, int rec_held, ks_delta* __restrict__ recs) {
+    for (long long j = blockIdx.x * (long long)SB + threadIdx.x; j < u.na; j += (long long)gridDim.x * SB) {
+        const ks_node_arc x = u.arcs[j];
+        if (u.lflag[j]) {
+            recs[(long long)rec_held + u.l_off[j]] =
+                arc_record(KS_ADD_ARC, 0, u.n_slot[task_of_arc(u.arc_off, u.k, j)], (int)(x.dst - 1), 0, (long long)x.cap,
+                           x.cost, 0);
+            continue;
+        }
+        const int s = u.l_slot[j] - 1;
+        if (s < 0 || u.sflag[s] != NOD_RECORD) continue;
+        const long long c = nod_cap(d, x, s), co = d.a_cost[s];
+        recs[u.s_off[s]] = c ? arc_record(KS_UPDATE_ARC, d.a_type[s], d.a_src[s], d.a_dst[s], d.a_low[s], c, x.cost, co)
+                             : arc_record(KS_UPDATE_ARC, d.a_type[s], d.a_src[s], d.a_dst[s], 0, 0, co, co);
+    }
+}
+
+// The deletes of the unlisted arcs, found by the chunk items as k_nod_walk found them.
+__global__ void k_nod_emit_unlisted(SchedDev d, NodDev u, int ni_max, ks_delta* __restrict__ recs) {
+    const int lane = threadIdx.x & 63;
+    const int wave = (blockIdx.x * SB + threadIdx.x) >> 6;
+    const int nwaves = (gridDim.x * SB) >> 6;
+    const int ni = min(u.ch_off[u.k], ni_max);
+    for (int w = wave; w < ni; w += nwaves) {
+        const int s = nod_unlisted_slot(d, u, w, lane);
+        if (s < 0 || u.sflag[s] != NOD_UNLISTED) continue;
+        const long long co = d.a_cost[s];
+        recs[u.s_off[s]] = arc_record(KS_UPDATE_ARC, d.a_type[s], d.a_src[s], d.a_dst[s], 0, 0, co, co);
     }
 }
 
@@ -1532,6 +1696,29 @@ hipError_t sched_upd_totals(const UpdDev& u, hipStream_t st) {
 hipError_t sched_upd_emit(const SchedDev& d, const UpdDev& u, int rec_held, ks_delta* recs, hipStream_t st) {
     if (u.hi) hipLaunchKernelGGL(k_upd_emit_held, dim3(grid(u.hi)), dim3(SB), 0, st, d, u, recs);
     if (u.na) hipLaunchKernelGGL(k_upd_emit_adds, dim3(grid(u.na)), dim3(SB), 0, st, u, rec_held, recs);
+    return hipGetLastError();
+}
+
+hipError_t sched_nod_check(const SchedDev& d, const NodDev& u, bool walk, hipStream_t st) {
+    hipLaunchKernelGGL(k_nod_seed, dim3(grid(u.k)), dim3(SB), 0, st, d, u, walk ? 1 : 0);
+    if (u.na) hipLaunchKernelGGL(k_nod_heads, dim3(grid(u.na)), dim3(SB), 0, st, d, u);
+    return hipGetLastError();
+}
+
+hipError_t sched_nod_unlisted(const SchedDev& d, const NodDev& u, int ni_max, hipStream_t st) {
+    hipLaunchKernelGGL(k_nod_walk, dim3(grid(64LL * ni_max)), dim3(SB), 0, st, d, u, ni_max);
+    return hipGetLastError();
+}
+
+hipError_t sched_nod_totals(const NodDev& u, hipStream_t st) {
+    hipLaunchKernelGGL(k_nod_totals, dim3(1), dim3(64), 0, st, u);
+    return hipGetLastError();
+}
+
+hipError_t sched_nod_emit(const SchedDev& d, const NodDev& u, bool walk, int ni_max, int rec_held, ks_delta* recs,
+                          hipStream_t st) {
+    if (u.na) hipLaunchKernelGGL(k_nod_emit_listed, dim3(grid(u.na)), dim3(SB), 0, st, d, u, rec_held, recs);
+    if (walk) hipLaunchKernelGGL(k_nod_emit_unlisted, dim3(grid(64LL * ni_max)), dim3(SB), 0, st, d, u, ni_max, recs);
     return hipGetLastError();
 }
 

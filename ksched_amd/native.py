@@ -22,7 +22,7 @@ EXPORTED_SYMBOLS = (
     "ks_coalesce_deltas", "ks_get_store_stats", "ks_set_bindings", "ks_scheduling_deltas",
     "ks_update_unsched_costs", "ks_topology_stats", "ks_get_graph", "ks_commit_schedule",
     "ks_commit_preemptive", "ks_remove_resources", "ks_complete_tasks", "ks_get_bindings",
-    "ks_add_tasks", "ks_add_resources", "ks_update_tasks",
+    "ks_add_tasks", "ks_add_resources", "ks_update_tasks", "ks_update_nodes",
     "ks_batch_create", "ks_batch_create_rank", "ks_batch_unique_id", "ks_batch_destroy", "ks_batch_last_error",
     "ks_batch_load", "ks_batch_solve", "ks_batch_gather",
     "ks_batch_slots", "ks_batch_owner", "ks_batch_block_len", "ks_batch_unpack",
@@ -39,6 +39,8 @@ KS_COMMIT_RESOURCE_CAPS = 1
 KS_REMOVE_RESOURCE_CAPS, KS_REMOVE_PREEMPTIVE = 1, 2
 KS_COMPLETE_RESOURCE_CAPS, KS_COMPLETE_PREEMPTIVE = 1, 2
 KS_UPDATE_KEEP_UNLISTED = 1
+KS_NODES_KEEP_UNLISTED = 1
+KS_CAP_KEEP = (1 << 64) - 1   # a listed arc of ks_update_nodes keeps the held arc's capacity
 
 NODE_DT = np.dtype({"names": ["id", "excess", "type", "_pad"],
                     "formats": ["<u8", "<i8", "<i4", "<i4"], "offsets": [0, 8, 16, 20], "itemsize": 24})
@@ -164,6 +166,20 @@ class KsUpdateStats(C.Structure):
 
 
 TASK_ARC_DT = np.dtype({"names": ["dst", "cost"], "formats": ["<u8", "<i8"], "offsets": [0, 8], "itemsize": 16})
+
+
+class KsNodeStats(C.Structure):
+    """ks_node_stats: what one ks_update_nodes found and generated on device."""
+    _fields_ = [("nodes", C.c_int64), ("arcs_added", C.c_int64), ("arcs_updated", C.c_int64),
+                ("arcs_unchanged", C.c_int64), ("arcs_skipped", C.c_int64), ("arcs_zeroed", C.c_int64),
+                ("arcs_removed", C.c_int64), ("records", C.c_int64), ("reserved", C.c_int64 * 4)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+NODE_ARC_DT = np.dtype({"names": ["dst", "cost", "cap"], "formats": ["<u8", "<i8", "<u8"], "offsets": [0, 8, 16],
+                        "itemsize": 24})
 
 
 class KsGrowStats(C.Structure):
@@ -369,6 +385,7 @@ def _bind(path: str):
     L.ks_add_tasks.argtypes = [V, C.c_int32, V, C.c_size_t, V, V, V, C.c_size_t, C.c_int64, P(KsAddStats)]
     L.ks_add_resources.argtypes = [V, C.c_int32, V, C.c_size_t, V, C.c_size_t, P(KsGrowStats)]
     L.ks_update_tasks.argtypes = [V, C.c_int32, V, C.c_size_t, V, V, V, C.c_size_t, C.c_int64, P(KsUpdateStats)]
+    L.ks_update_nodes.argtypes = [V, C.c_int32, V, C.c_size_t, V, V, P(KsNodeStats)]
     L.ks_get_bindings.argtypes = [V, V, V, C.c_size_t]
     return L
 
@@ -672,6 +689,32 @@ class Context:
                                             ids.shape[0], off.ctypes.data, arcs.ctypes.data,
                                             None if agg is None else agg.ctypes.data, nu, int(unsched_sink_cost),
                                             C.byref(st)))
+        return st.as_dict()
+
+    def update_nodes(self, nodes, arc_off, dst, cost, cap, keep_unlisted: bool = False) -> dict:
+        """ks_update_nodes: the live class, machine, intermediate and PU ids get the out-arcs
+        their lists name. Tail i's list is (dst[j], cost[j], cap[j]) for arc_off[i] <= j <
+        arc_off[i + 1]: an arc the store does not hold is added (low 0, type 0) unless its cap is
+        0, a held one whose cost or capacity differs is updated with its lower bound and type
+        kept, a held one listed with cap 0 is deleted; cap KS_CAP_KEEP keeps the held capacity. A
+        type-0 tail's held arcs that its list does not name are deleted, except an arc into a
+        sink; every other tail keeps them (keep_unlisted: nothing is deleted, and no residual
+        CSR is needed). → stats dict. Needs no solve; invalidates the solution when a record is
+        applied."""
+        ids = np.ascontiguousarray(nodes, np.uint64).reshape(-1)
+        off = np.ascontiguousarray(arc_off, np.uint64).reshape(-1)
+        if off.shape[0] != ids.shape[0] + 1:
+            raise ValueError("arc_off has one entry more than nodes")
+        n = np.asarray(dst).size
+        if np.asarray(cost).size != n or np.asarray(cap).size != n:
+            raise ValueError("dst, cost and cap have one entry per listed arc")
+        arcs = np.zeros(max(n, 1), NODE_ARC_DT)
+        arcs["dst"][:n] = np.asarray(dst, np.uint64).reshape(-1)
+        arcs["cost"][:n] = np.asarray(cost, np.int64).reshape(-1)
+        arcs["cap"][:n] = np.asarray(cap, np.uint64).reshape(-1)
+        st = KsNodeStats()
+        self._check(self._L.ks_update_nodes(self._h, KS_NODES_KEEP_UNLISTED if keep_unlisted else 0, ids.ctypes.data,
+                                            ids.shape[0], off.ctypes.data, arcs.ctypes.data, C.byref(st)))
         return st.as_dict()
 
     def bindings(self, tasks) -> np.ndarray:
