@@ -1132,7 +1132,23 @@ typedef struct ks_node_stats {        /* 96 B */
  *     that rule counts as a resource arc: the caveat the commits already carry.
  *   - UpdateResourceTopology (:217-236): list PU → sink with the new slot count here, then run
  *     ks_complete_tasks(k = 0, KS_COMPLETE_RESOURCE_CAPS [| KS_COMPLETE_PREEMPTIVE]), which
- *     carries the new slots up the chain. */
+ *     carries the new slots up the chain. Under the pinned rule (slots − running) a PU that
+ *     was FULL has no arc from its machine, and neither has any ancestor that was full with it:
+ *     the refresh writes only arcs that exist, so the new slot would stay cut off. List those
+ *     chain arcs (machine → PU and upwards as far as the heads were full) in the same call with
+ *     any positive capacity: they are ADD_ARC, and the refresh sets them. It is the parent-chain
+ *     recipe of ks_complete_tasks, through this call.
+ * What a caller without a shadow can list (tests/round_ref.py plays it over whole rounds):
+ *   - KS_CAP_KEEP only on an arc it knows the store to hold. The capacity rule deletes every arc
+ *     into a head with no room (pinned: a full PU, a machine or rack of full PUs) and counts a
+ *     class → machine arc as a resource arc, so after a pinned commit a class has no arc into a
+ *     full machine and KS_CAP_KEEP on it is refused. Class arcs are therefore listed with an
+ *     explicit capacity (the machine's room, or less): 0 while the machine is full (skipped or
+ *     zeroed), positive once a completion freed a slot (ADD_ARC: the arc comes back here, not
+ *     with the completion's parent-chain upserts, which name the resource tree only).
+ *   - The arc into a rack with no slot beneath it is the one whose presence cannot be known
+ *     (the rule leaves it as it was, absent or stale): list it with capacity 0.
+ *     ks_add_resources re-creates it when a machine joins. */
 int ks_update_nodes(ks_ctx* ctx, int32_t flags,
                     const uint64_t* nodes, size_t k,
                     const uint64_t* arc_off /* k + 1 */, const ks_node_arc* arcs,

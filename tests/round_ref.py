@@ -1,14 +1,35 @@
 """A caller that keeps no shadow, and the graph it expects: whole scheduling rounds (INTEGRATION
-§2.1: solve → mapping → commit → ks_remove_resources → ks_complete_tasks → ks_add_resources →
-ks_add_tasks → ks_update_tasks → ks_update_unsched_costs → solve) on the host only.
+§2.1: commit → ks_remove_resources → ks_complete_tasks → ks_add_resources → the capacity refresh →
+ks_add_tasks → ks_update_tasks → ks_update_nodes → ks_update_unsched_costs → solve, and the mapping
+read after it: the ten-call round) on the host only.
 
 RoundModel plays ksched's side of the C-ABI and holds the expected graph. The graph evolves only
 through the rules the single-call suites already restate (commit_reference, preempt_reference,
 remove_reference, complete_reference, grow_reference, arrive_reference, refresh_reference,
-sched_ref.scheduling_deltas / apply_deltas) and one new one, unsched_costs_reference. What the
+nodes_reference, sched_ref.scheduling_deltas / apply_deltas) and one new one, unsched_costs_reference. What the
 model knows beside the graph is what a real caller knows: the resource tree, the slots of every
 PU, each live task's job and preference list, the bindings and an id allocator. The recipes of
 include/ksmcmf.h are issued from that knowledge.
+
+With classes = True (off by default: without it no case draws or adds anything more) every job has
+an equivalence class between its tasks and a few preferred machines, and a cost model that moves:
+class → machine costs and capacities follow the bindings and the slots, the resource tree's arcs
+are re-costed with KS_CAP_KEEP, two rounds change a PU's slot count, and ks_update_nodes carries
+all of it each round. The arcs it lists are those the caller KNOWS the store to hold or to lack:
+  - class → machine: always with an explicit capacity (the room the capacity rule gives the arc,
+    capped at 1 for the classes with an odd index). The pinned rule deletes the arc into a full
+    machine, so KS_CAP_KEEP on a class arc is not the caller's to use: an explicit capacity adds
+    the arc back once a completion freed a slot, and 0 drops or skips it while the machine is full.
+  - a resource arc with KS_CAP_KEEP only into a head that is not blocked(): the rule holds exactly
+    those. The arc into a rack with NO slot beneath it is the one whose presence the caller cannot
+    know (the rule leaves it as it was: absent if the rack had filled up before it emptied, stale
+    otherwise), so it is listed with capacity 0: zeroed when held, skipped when not. No flow could
+    use it, and ks_add_resources re-creates it with the right capacity when a machine joins.
+  - pinned, a FULL PU that gains a slot: the rule had deleted the arcs into it and into every
+    ancestor that was blocked with it, and the capacity refresh that follows the slot change only
+    writes arcs that exist. So the caller lists those chain arcs with an explicit positive capacity
+    in the same call (ADD_ARC), as the completion recipe does with its upserts; the refresh then
+    sets them.
 
 THE RULE: nothing read from ctx.graph() ever becomes an input of the model or of a later call.
 A backend (the oracle here, the device in test_gpu_rounds.py) answers the solve; its cost, flow,
@@ -28,6 +49,7 @@ from arrive_ref import arrive_reference
 from commit_ref import MACHINE, OTHER, PU, SINK, TASK, commit_reference
 from complete_ref import chain_upserts, complete_reference, parent_chains
 from grow_ref import TREE, chain, grow_reference
+from nodes_ref import CAP_KEEP, nodes_reference
 from oracle import ko, sched_ref
 from preempt_ref import preempt_reference, table_graph
 from refresh_ref import refresh_reference
@@ -41,8 +63,12 @@ UNSCHED, WILDCARD, PREEMPTION, AGE, SINK_COST = 1000, 500, 300, 3, 0
 CONTINUATION, RAISED_CONTINUATION, LURE = 0, 40, -5000
 # ResourceNodeToResourceNodeCost by the child's type: an arc the device re-creates must carry its edge's cost
 TREE_COST = {OTHER: 3, MACHINE: 2, PU: 1}
+# with classes: task → class at a fixed cost, class → machine at a base drawn once + SPREAD × the tasks bound there
+CLASS_COST, SPREAD = 200, 7
 COUNTERS = ("evictions", "bound_id_reused", "pu_id_reused", "aggregator_recreated", "ancestor_recreated",
-            "migrations", "preemptions", "new_jobs", "superseded", "running_kept", "recipe_upserts", "stale_caps_repaired")
+            "migrations", "preemptions", "new_jobs", "superseded", "running_kept", "recipe_upserts", "stale_caps_repaired",
+            "class_arcs_added", "class_arcs_removed", "class_arcs_zeroed", "class_arc_recreated", "cap_overwritten",
+            "resource_recosted", "resource_unchanged", "slots_raised", "slots_lowered", "chain_relisted", "class_tail_over_64")
 
 
 def unsched_costs_reference(ntype, arcs: dict, aggs, mode: int, unsched_cost: int, continuation: int):
@@ -97,12 +123,20 @@ class RoundModel:
         self.had_sink_arc = {a for a in self.aggs if (a, self.sink) in self.arcs}   # to tell "re-created" from "new"
         self._held_before: set = set()
         self.log: list = []
+        # the classes (empty without the option): what the caller knows of them
+        self.cls: dict = {}                            # job (its aggregator) → the job's class node
+        self.classes: list = []                        # in the order they were made: the index decides the cap-1 limit
+        self.pref: dict = {}                           # class → its preferred machines
+        self.base: dict = {}                           # (class, machine) → the base cost, drawn once
+        self.caps_from = "rule"                        # who wrote the class arcs' capacities last: "rule" or "model"
+        self.commit_dropped: set = set()               # class arcs a commit deleted (into a full machine)
+        self.held_down: set = set()                    # cap-1 arcs the last ks_update_nodes wrote below the rule's value
 
     # ---------------------------------------------------------------- the cluster ---
     @classmethod
-    def cluster(cls, preemptive, seed, racks=2, mpr=3, pus=1, slots=2, job_sizes=(8, 8, 8)):
+    def cluster(cls, preemptive, seed, racks=2, mpr=3, pus=1, slots=2, job_sizes=(8, 8, 8), classes=False):
         """SINK 1, X 2, the racks, the machines (machine k in rack k // mpr), their PUs, one
-        unscheduled aggregator per job, the tasks."""
+        unscheduled aggregator per job, [one class per job,] the tasks."""
         rng = np.random.default_rng(seed)
         ntype, supply = [SINK, OTHER], [0, 0]
 
@@ -115,6 +149,7 @@ class RoundModel:
         ms = [node(MACHINE) for _ in range(racks * mpr)]
         ps = [node(PU) for _ in range(racks * mpr * pus)]
         ag = [node(OTHER) for _ in job_sizes]
+        cl = [node(OTHER) for _ in job_sizes] if classes else []
         arcs, parent, slot = {}, {}, {}
         for r in rk:
             arcs[(X, r)], parent[r] = (0, mpr * pus * slots, TREE_COST[OTHER], 0), X
@@ -124,17 +159,23 @@ class RoundModel:
             arcs[(ms[k // pus], p)], parent[p], slot[p] = (0, slots, TREE_COST[PU], 0), ms[k // pus], slots
             arcs[(p, 1)] = (0, slots, SINK_COST, 0)
         job, prefs = {}, {}
-        for a, size in zip(ag, job_sizes):
+        for k, (a, size) in enumerate(zip(ag, job_sizes)):
             arcs[(a, 1)] = (0, size, SINK_COST, 0)
             for _ in range(size):
                 t = node(TASK, 1)
                 job[t] = a
                 prefs[t] = [(int(m), int(c)) for m, c in zip(rng.choice(ms, 2, replace=False), rng.integers(1, 100, 2))]
-                for d, c in prefs[t] + [(X, WILDCARD), (a, UNSCHED)]:
+                for d, c in prefs[t] + ([(cl[k], CLASS_COST)] if cl else []) + [(X, WILDCARD), (a, UNSCHED)]:
                     arcs[(t, d)] = (0, 1, c, 0)
         supply[0] = -len(job)
         m = cls(preemptive, ntype, supply, arcs, parent, slot, job, prefs, wildcard=X, seed=seed)
         m.rng = rng
+        for a, c in zip(ag, cl):                         # the graph is loaded with the cost model's arcs of an idle cluster
+            m.add_class(a, c)
+            for x, co, cap in m.class_list(c, m.draw_class_set(c)):
+                m.arcs[(c, x)] = (0, cap, co, 0)
+        if cl:
+            m.caps_from = "model"
         return m
 
     # -------------------------------------------------------------------- views ---
@@ -185,8 +226,76 @@ class RoundModel:
         """The caller's own resource tree as an arc table (any positive capacity)."""
         return {(p, c): (0, 1, self.tree_cost.get(c, 0), 0) for c, p in self.parent.items()}
 
+    # ------------------------------------------------- the cost model that moves ---
+    def add_class(self, job, c):
+        self.cls[job] = c
+        self.classes.append(c)
+        self.pref[c] = []
+
+    def limited(self, c) -> bool:
+        """A per-job, per-machine limit of one task: the classes with an odd index."""
+        return self.classes.index(c) % 2 == 1
+
+    def draw_class_set(self, c) -> list:
+        ms = self.of_type(MACHINE)
+        self.pref[c] = sorted(int(x) for x in self.rng.choice(ms, min(3, len(ms)), replace=False)) if ms else []
+        return self.pref[c]
+
+    def bound_beneath(self, v, load=None) -> int:
+        load = self.load() if load is None else load
+        return sum(load.get(p, 0) for p in self.subtree(v) if p in self.slots)
+
+    def room(self, v, load=None) -> int:
+        """What the capacity rule gives an arc into v: the slots beneath it, minus the bound tasks in pinned mode."""
+        load = self.load() if load is None else load
+        return sum(self.slots[p] - (0 if self.preemptive else load.get(p, 0)) for p in self.subtree(v) if p in self.slots)
+
+    def class_list(self, c, machines, load=None) -> list:
+        """(machine, cost, cap) of the class's arcs; a base cost is drawn when a pair is first priced."""
+        load = self.load() if load is None else load
+        out = []
+        for x in machines:
+            if (c, x) not in self.base:
+                self.base[(c, x)] = int(self.rng.integers(1, 50))
+            room = self.room(x, load)
+            out.append((x, self.base[(c, x)] + SPREAD * self.bound_beneath(x, load), min(room, 1) if self.limited(c) else room))
+        return out
+
+    def resource_lists(self, was_blocked=(), resized=None) -> tuple:
+        """→ (tails, lists) of X, the racks, the machines and the PUs: every arc the caller knows
+        the store to hold, re-costed with KS_CAP_KEEP (the edge's cost + the tasks bound beneath
+        the head; machine → PU and PU → sink move at every second task only); X → a rack with no
+        slot beneath it with capacity 0; the arcs into was_blocked (a full PU that gained a slot,
+        and its ancestors that were blocked with it) with an explicit capacity; the resized PU's
+        arc into the sink with its new slot count."""
+        load = self.load()
+        tails, lists = [], []
+        for u in [self.wildcard] + self.of_type(OTHER) + self.of_type(MACHINE):
+            lst = []
+            for v in self.children(u):
+                n = self.bound_beneath(v, load)
+                cost = self.tree_cost.get(v, 0) + (n // 2 if v in self.slots else n)
+                if not any(p in self.slots for p in self.subtree(v)):
+                    lst.append((v, cost, 0))
+                elif v in was_blocked:
+                    lst.append((v, cost, 1))
+                elif not self.blocked(v, load):
+                    lst.append((v, cost, CAP_KEEP))
+            tails.append(u)
+            lists.append(lst)
+        for p in sorted(self.slots):
+            tails.append(p)
+            lists.append([(self.sink, SINK_COST + load.get(p, 0) // 2, self.slots[p] if p == resized else CAP_KEEP)])
+        return tails, lists
+
+    def set_slots(self, p, n):
+        self.count["slots_raised" if n > self.slots[p] else "slots_lowered"] += 1
+        self.slots[p] = n
+
     def full_list(self, t, with_agg: bool) -> list:
         out = list(self.prefs[t])
+        if self.cls:
+            out.append((self.cls[self.job[t]], CLASS_COST))
         if self.wildcard:
             out.append((self.wildcard, WILDCARD))
         if with_agg:
@@ -262,6 +371,8 @@ class RoundModel:
                       unsched_updates=sum(1 for k in before if k[0] in self.aggs and k[1] == self.sink and changed(k)),
                       cap_updates=sum(1 for k in before if self.ntype[k[0] - 1] != TASK and k[1] != self.sink and changed(k)))
             st["records"] = sum(v for k, v in st.items() if k != "placed")
+        self.commit_dropped |= {k for k in before if k[0] in self.pref and k not in arcs}
+        self.caps_from = "rule"
         self.arcs, self.bindings = arcs, {t: p for t, p in bind.items() if p}
         self.count["migrations"] += sum(1 for k, _, _ in deltas if k == MIGRATE)
         self.count["preemptions"] += sum(1 for k, _, _ in deltas if k == PREEMPT)
@@ -278,6 +389,8 @@ class RoundModel:
         ref = remove_reference(self.graph(), named, self.bindings, True, self.preemptive, alive=self.alive)
         assert ref.removed == tree, ("the rule's subtree is the caller's", ref.removed, tree)
         self.arcs, self.bindings = dict(ref.arcs), dict(ref.bindings)
+        self.caps_from = "rule"
+        self.pref = {c: [x for x in ms if x not in tree] for c, ms in self.pref.items()}   # the caller's own knowledge
         self.freed_pus |= {v for v in tree if v in self.slots}
         for v in tree:
             self.parent.pop(v, None)
@@ -315,6 +428,7 @@ class RoundModel:
         ref = complete_reference(self.graph(), tasks, self.bindings, caps, False, self.aggs, alive=self.alive)
         self.freed_bound |= {t for t in ref.removed if t in self.bindings}
         self.arcs, self.bindings = dict(ref.arcs), dict(ref.bindings)
+        self.caps_from = "rule" if caps else self.caps_from
         for t in ref.removed:
             del self.job[t], self.prefs[t]
         self.returning = [t for t in self.returning if t in self.job]
@@ -348,6 +462,7 @@ class RoundModel:
         """ks_complete_tasks(k = 0, KS_COMPLETE_RESOURCE_CAPS[ | _PREEMPTIVE]): the plain refresh."""
         ref = complete_reference(self.graph(), [], self.bindings, True, self.preemptive, self.aggs, alive=self.alive)
         self.arcs = dict(ref.arcs)
+        self.caps_from = "rule"
         self.count["stale_caps_repaired"] += ref.stats["cap_updates"]
         self.record("refresh_caps")
         return dict(preemptive=self.preemptive, aggs=list(self.aggs)), dict(left=[], stats=ref.stats)
@@ -385,6 +500,38 @@ class RoundModel:
         self.record("refresh", tasks=list(tasks), lists=lists)
         return dict(tasks=list(tasks), lists=lists, aggs=list(self.aggs)), dict(stats=ref.stats)
 
+    def nodes(self, tails, lists):
+        """ks_update_nodes with the classes' and the resources' lists. A refusal of the rule
+        (InvalidNodes, BelowLowerBound) leaves the model as it was."""
+        table = dict(sorted(self.arcs.items()))           # any fixed order: the record order is not compared
+        ref = nodes_reference(self.ntype, table, tails, lists, 0, alive=self.alive)
+        n, before, down = self.count, self.arcs, set()
+        for u, lst in zip(tails, lists):
+            named = {d for d, _, _ in lst}
+            if u not in self.pref:
+                n["resource_recosted"] += sum(1 for d, c, _ in lst if (u, d) in before and before[(u, d)][2] != c)
+                n["resource_unchanged"] += sum(1 for d, c, cap in lst if cap == CAP_KEEP and (u, d) in before and before[(u, d)][2] == c)
+                n["chain_relisted"] += sum(1 for d, _, cap in lst if d != self.sink and cap not in (0, CAP_KEEP) and (u, d) not in before)
+                continue
+            if sum(1 for k in before if u in k) > 64:     # its residual segment holds its out-arcs and its in-arcs: more than one chunk
+                n["class_tail_over_64"] += 1
+            n["class_arcs_removed"] += sum(1 for (s, d) in before if s == u and d not in named and d != self.sink)
+            for d, _, cap in lst:
+                if (u, d) not in before:
+                    n["class_arcs_added"] += cap > 0
+                    n["class_arc_recreated"] += cap > 0 and (u, d) in self.commit_dropped
+                else:
+                    n["class_arcs_zeroed"] += cap == 0
+                    n["cap_overwritten"] += 0 < cap < before[(u, d)][1] and (u, d) in self.held_down
+                if self.limited(u) and 0 < cap < self.room(d):
+                    down.add((u, d))
+        self.commit_dropped -= {(u, d) for u, lst in zip(tails, lists) for d, _, cap in lst if cap}
+        self.held_down = down
+        self.arcs = dict(ref.arcs)
+        self.caps_from = "model"
+        self.record("nodes", tails=list(tails), lists=lists)
+        return dict(tails=list(tails), lists=lists), dict(stats=ref.stats)
+
     def age(self, mode, cost, continuation=None):
         self.cont = self.cont if continuation is None else continuation
         self.arcs, changed = unsched_costs_reference(self.ntype, self.arcs, self.aggs, mode, cost, self.cont)
@@ -404,7 +551,21 @@ class RoundModel:
             assert (arc is None) == (into.get(a, 0) == 0) and (arc is None or arc[1] == into[a]), ("aggregator", a, arc, into.get(a))
         if caps:
             ref = complete_reference(self.graph(), [], self.bindings, True, self.preemptive, self.aggs, alive=self.alive)
-            assert ref.stats["records"] == 0, ("resource capacities are not the rule's", ref.stream)
+            if not self.classes or self.caps_from == "rule":
+                assert ref.stats["records"] == 0, ("resource capacities are not the rule's", ref.stream)
+            else:                                          # ks_update_nodes wrote last: the cap-1 classes' arcs are the cost model's
+                odd = {c for c in self.classes if self.limited(c)}
+                assert all(int(x["src"]) in odd for x in ref.stream), ("resource capacities are not the rule's", ref.stream)
+                load = self.load()
+                for (s, d), a in self.arcs.items():
+                    assert s not in odd or d == self.sink or a[1] == min(self.room(d, load), 1), ("a cap-1 arc", s, d, a)
+        if caps:                                           # no free slot is cut off: the tree's arc leads into every head with room
+            load = self.load()
+            for v, p in self.parent.items():
+                assert self.blocked(v, load) or (p, v) in self.arcs, ("no arc into a resource with room", p, v)
+        for (s, d) in self.arcs:                           # (no class: nothing to look at)
+            if s in self.pref:
+                assert self.ntype[d - 1] == MACHINE and d in self.pref[s], ("a class arc outside the class's set", s, d)
         for t, p in self.bindings.items():
             assert t in self.job and p in self.slots and self.arcs[(t, p)][3] == 1, ("binding", t, p)
         for (s, d), a in self.arcs.items():
@@ -461,9 +622,13 @@ class Script:
     """The seeded event generator and the scripted events of a run. It draws from the model's
     rng over the model's sorted state only."""
 
-    def __init__(self, model, rounds, arrivals=(2, 5), completions=(1, 3), burst=None, grow_rack=None, hub=None):
+    def __init__(self, model, rounds, arrivals=(2, 5), completions=(1, 3), burst=None, grow_rack=None, hub=None,
+                 classes=False, wide=None):
         self.m, self.rounds, self.arrivals, self.completions = model, rounds, arrivals, completions
         self.burst, self.grow_rack, self.hub = burst, grow_rack, hub
+        self.classes, self.wide = classes, wide   # wide: the class that prefers every machine of the growing rack ("round 4": that round's new job's)
+        self.fresh: list = []                 # (job, class) of the jobs ks_add_resources brought in this round
+        self.resized = False                  # a PU's slot count changed in this round's ks_update_nodes
         self.frozen: set = set()              # tasks a scripted event still needs
         self.guard: set = set()               # resources a scripted event still needs
         self.drain = None                     # the job drained for the re-created aggregator
@@ -555,6 +720,12 @@ class Script:
             a = m.alloc()
             nodes.append((a, OTHER, 0, 0))
             jobs.append(a)
+            if self.classes:                  # … and its class no arc at all: ks_add_tasks and ks_update_nodes give it them
+                c = m.alloc()
+                nodes.append((c, OTHER, 0, 0))
+                self.fresh.append((a, c))
+                if self.wide == "round 4" and rnd == 4:
+                    self.wide = c
         return nodes, edges, jobs
 
     def draw_prefs(self):
@@ -644,6 +815,56 @@ class Script:
                 lists.append(lst)
         return (tasks, lists) if tasks else None
 
+    def node_lists(self, rnd):
+        """→ (tails, lists) of this round's ks_update_nodes, or None without the option: a slot
+        change in rounds 2 and 6, every class's set with one machine gone and one other in it, the
+        classes' and the resources' arcs as the cost model prices them now."""
+        self.resized = False
+        if not self.classes:
+            return None
+        m, rng = self.m, self.m.rng
+        load = m.load()
+        was_blocked, resized = set(), None
+        free = [p for p in sorted(m.slots) if m.parent[p] not in self.guard]
+        if rnd == 6:                          # a PU with a bound task gains a slot (pinned: a full one first)
+            cand = sorted((p for p in free if load.get(p, 0)), key=lambda p: (load[p] < m.slots[p], p))
+            if cand:
+                v = resized = cand[0]
+                while v in m.parent and m.blocked(v, load):    # the arcs into these went with the pinned rule
+                    was_blocked.add(v)
+                    v = m.parent[v]
+                m.set_slots(resized, m.slots[resized] + 1)
+        if rnd == 2:                          # a PU with room loses a slot, never below its bound tasks
+            down = lambda p: load[p] if not m.preemptive and load.get(p, 0) else m.slots[p] - 1
+            held = lambda p: any(m.parent[p] in s for s in m.pref.values())     # listed last round, with room: a class holds the arc
+            cand = sorted((p for p in free if m.slots[p] - 1 >= max(load.get(p, 0), 1)),
+                          key=lambda p: (down(p) != load.get(p, 0), len(m.children(m.parent[p])), not held(p), p))
+            if cand:                          # pinned: down to exactly that count, the only PU of a machine a class prefers first:
+                resized = cand[0]             # the PU is full, and the class arc into its machine is listed with capacity 0
+                m.set_slots(resized, down(resized))
+        self.resized = resized is not None
+        ms = m.of_type(MACHINE)
+        tails, lists = [], []
+        for c in m.classes:
+            mine = list(m.pref[c])
+            if c == self.wide:                # every machine of the growing rack but one, another one each round
+                mine = m.children(m.of_type(OTHER)[0]) if m.of_type(OTHER) else []
+                mine = [x for k, x in enumerate(mine) if len(mine) <= 3 or k != rnd % len(mine)]
+            elif not mine:                    # a new class (or one whose machines all left)
+                mine = m.draw_class_set(c)
+            else:                             # one leaves, one other joins; then up to three again after removals
+                others = [x for x in ms if x not in mine]
+                if others:                    # (the machine of a PU resized in this call stays: its arc is re-sized, not dropped)
+                    mine.remove(int(rng.choice([x for x in mine if resized is None or x != m.parent[resized]] or mine)))
+                    mine.append(int(rng.choice(others)))
+                while len(mine) < 3 and len(mine) < len(ms):
+                    mine.append(int(rng.choice([x for x in ms if x not in mine])))
+            m.pref[c] = sorted(mine)
+            tails.append(c)
+            lists.append(m.class_list(c, m.pref[c], load))
+        rt, rl = m.resource_lists(was_blocked, resized)
+        return tails + rt, lists + rl
+
     def ageing(self, rnd):
         if rnd == 7:                          # once per run: a SET, with a raised continuation cost
             return COST_SET, UNSCHED + 50, RAISED_CONTINUATION
@@ -682,6 +903,8 @@ def run_round(model, script, dev, rnd):
         step("grow", m.grow(nodes, edges), caps=not edges)
         m.aggs = sorted(m.aggs + jobs)
         m.count["new_jobs"] += len(jobs)
+        while script.fresh:
+            m.add_class(*script.fresh.pop(0))
         if edges:                             # a stale capacity into a rack that had no free slot beneath it was raised, not set
             step("refresh_caps", m.refresh_caps())
     tasks, jobs, prefs, lists = script.arrival(rnd)
@@ -691,6 +914,11 @@ def run_round(model, script, dev, rnd):
     if upd:
         step("refresh", m.refresh(*upd))
     assert not m.returning, "an evicted task did not come back in its round"
+    lists = script.node_lists(rnd)
+    if lists:
+        step("nodes", m.nodes(*lists), caps=not script.resized)
+        if script.resized:                    # UpdateResourceTopology: the new slot count goes up the chain
+            step("refresh_caps", m.refresh_caps())
     step("age", m.age(*script.ageing(rnd)))
 
 
@@ -711,16 +939,20 @@ def run(model, script, dev, rounds, tmp_path=None):
 
 
 # ------------------------------------------------------- the cases of both suites ---
-def small_case(preemptive, seed, rounds):
-    m = RoundModel.cluster(preemptive, seed)
-    return m, Script(m, rounds), rounds
+def small_case(preemptive, seed, rounds, classes=False):
+    m = RoundModel.cluster(preemptive, seed, classes=classes, slots=6 if classes else 2)
+    return m, Script(m, rounds, classes=classes), rounds
 
 
-def wave_case(preemptive):
+def wave_case(preemptive, classes=False):
     """One job of 150 tasks, 65 arrivals and 65 completions in round 2, one rack that gains 12
-    machines in each of rounds 1 to 5."""
-    m = RoundModel.cluster(preemptive, 7, job_sizes=(150, 8, 8))
-    return m, Script(m, 6, burst=(2, 65), grow_rack=((1, 2, 3, 4, 5), 12)), 6
+    machines in each of rounds 1 to 5. With classes: the 150-task job's class holds more than 64
+    arcs (its tasks' and its machines': its segment is walked in chunks), and the class of the job
+    that round 4 brings prefers every machine of the growing rack from its first call on: some
+    fifty arcs (pinned: the dozen into machines with room) into the segment of a node the store
+    has just sized for the one or two tasks pointing at it, whatever the solves chose before."""
+    m = RoundModel.cluster(preemptive, 7, job_sizes=(150, 8, 8), classes=classes)
+    return m, Script(m, 6, burst=(2, 65), grow_rack=((1, 2, 3, 4, 5), 12), classes=classes, wide="round 4" if classes else None), 6
 
 
 def hub_case(preemptive):

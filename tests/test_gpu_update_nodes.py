@@ -288,6 +288,37 @@ def test_the_update_resource_topology_recipe(state, preemptive, slots):
         resolve_and_check(ctx)
 
 
+@pytest.mark.parametrize("state", ["cell", "engine", "warm"])
+def test_a_full_pu_gains_a_slot_under_the_pinned_rule(state):
+    """Pinned, one slot per PU, tasks running on machines 0 and 1: rack 0 is full, and the commit's
+    capacity rule has deleted M0 → P0, R0 → M0, M1 → P1, R0 → M1 and X → R0. P0 goes to 2 slots.
+    PU → sink and the refresh alone (the recipe as the header first gave it) leave the new slot cut
+    off: the refresh writes only arcs that exist. KS_CAP_KEEP on the chain is refused, there is
+    nothing to keep. The completed recipe lists the chain arcs the rule had deleted with an explicit
+    positive capacity in the same call (ADD_ARC), and the refresh then sets them: the new slot can
+    be reached from X again."""
+    spec = Jobs(2, 2, 1, 1, [(0, 0, 0, False), (0, 1, 0, False), (0, None, 1, False)])
+    X, R, M, P, SINK = spec.X, spec.R0, spec.M0, spec.P0, spec.SINK
+    chain = [(X, R), (R, M), (M, P)]
+    with native.Context(0, **STATES[state]) as ctx:
+        prepare(ctx, spec, state, False)
+        before = Snapshot(ctx)
+        assert bound(ctx) == {spec.task(0): P, spec.task(1): P + 1, spec.task(2): 0}
+        assert not [k for k in chain + [(R, M + 1), (M + 1, P + 1)] if k in before.table]
+        other = (R + 1, 0, CAP_KEEP)                                    # X is a type-0 tail: its arc into rack 1 stays listed
+        rc, msg, _ = raw_call(ctx, [P, M, R, X], [[(SINK, 0, 2)], [(P, 0, CAP_KEEP)], [(M, 0, CAP_KEEP)], [(R, 0, CAP_KEEP), other]])
+        assert rc == native.KS_E_INVALID and "KS_CAP_KEEP" in msg and f"node {M}" in msg and Snapshot(ctx).table == before.table
+        ref, stats, after, _ = nodes_and_check(ctx, [P, M, R, X], [[(SINK, 0, 2)], [(P, 0, 1)], [(M, 0, 1)], [(R, 0, 1), other]],
+                                               solve=False)
+        assert (stats["arcs_updated"], stats["arcs_added"], stats["arcs_unchanged"], stats["records"]) == (1, 3, 1, 4)
+        want = complete_reference(after.graph(), [], bound(ctx), True, False, alive=after.alive)
+        _, cstats = ctx.complete_tasks([], resource_caps=True, preemptive=False)
+        done = Snapshot(ctx)
+        assert done.table == want.arcs and cstats["cap_updates"] == 0       # 2 slots − 1 running: the 1 it was listed with
+        assert [done.table[k][1] for k in chain] == [1, 1, 1] and (R, M + 1) not in done.table
+        resolve_and_check(ctx)
+
+
 # -------------------------------------------------------------- load spreading ---
 SPREAD_PREEMPTION = 150
 
