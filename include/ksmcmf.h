@@ -118,6 +118,8 @@ extern "C" {
                                   struct were added, nothing was resized).
                                   ks_update_nodes (still 5: one entry point and two
                                   structs were added, nothing was resized).
+                                  ks_batch_update_nodes (still 5: one entry point and one
+                                  struct were added, nothing was resized).
                                   ks_opts (96 B) CHANGED SIZE in ABI 2 and ks_result in
                                   ABI 2, 3 and 5: a caller must check
                                   ks_abi_version() == KSMCMF_ABI_VERSION before ks_create. */
@@ -1036,7 +1038,7 @@ typedef struct ks_update_stats {      /* 96 B */
  * segment takes the store's rebuild path (ks_store_stats.rebuilds). Every refusal is found before
  * anything changes on the device. A device failure after the records were emitted leaves the
  * store unusable until the next ks_load_graph. stats may be NULL; records == arcs_added +
- * cost_updates + arcs_removed + unsched_updates + unsched_added. No batch twin.
+ * cost_updates + arcs_removed + unsched_updates + unsched_added.
  * The class and resource nodes' arcs are ks_update_nodes; UpdateResourceTopology (:217-236) is
  * ks_update_nodes on the PU → sink arc, then ks_complete_tasks(k = 0, KS_COMPLETE_RESOURCE_CAPS
  * [| KS_COMPLETE_PREEMPTIVE]). */
@@ -1122,7 +1124,7 @@ typedef struct ks_node_stats {        /* 96 B */
  * generates any record invalidates them, exactly as ks_apply_deltas does. A full segment takes
  * the store's rebuild path (ks_store_stats.rebuilds). Every refusal is found before anything
  * changes on the device. A device failure after the records were emitted leaves the store
- * unusable until the next ks_load_graph. stats may be NULL. No batch twin.
+ * unusable until the next ks_load_graph. stats may be NULL. On a batch: ks_batch_update_nodes.
  * What the call does not do:
  *   - It does not purge a class that lost its last in-arc: the reference declares
  *     PurgeUnconnectedEquivClassNodes (:347-357) and never calls it. ks_remove_resources with
@@ -1333,9 +1335,10 @@ int ks_batch_update_unsched_costs(ks_batch* b, size_t ngraphs, const ks_batch_ta
  * next solve, stats (may be NULL) summed over the local devices, no collective, and every
  * message names the graph and the graph-local id. No supply changes, so no sink's demand
  * moves, and evicted tasks stay task nodes: the rows of ks_batch_gather keep their length.
- * A live resource's slot count changing (UpdateResourceTopology) is, on a single context,
- * ks_update_nodes on the PU → sink arc followed by the capacity refresh of ks_complete_tasks;
- * ks_update_nodes has no batch twin, so on a batch it goes through ks_batch_apply_deltas. */
+ * A live resource's slot count changing (UpdateResourceTopology) is, on a batch,
+ * ks_batch_update_nodes on the PU → sink arc followed by ks_batch_complete_tasks with every
+ * k == 0 and KS_COMPLETE_RESOURCE_CAPS [| KS_COMPLETE_PREEMPTIVE]: the lone recipe of
+ * ks_update_nodes, call for call. */
 typedef struct ks_batch_res_list {   /* one graph's part of a call, in the graph's OWN ids */
     const uint64_t*    roots; size_t k;     /* ks_batch_remove_resources; k == 0: untouched        */
     const ks_res_node* nodes; size_t n;     /* ks_batch_add_resources; n == 0 && m == 0: untouched */
@@ -1373,6 +1376,49 @@ int ks_batch_remove_resources(ks_batch* b, int32_t flags, size_t ngraphs, const 
  * ks_batch_complete_tasks with every k == 0 and KS_COMPLETE_RESOURCE_CAPS. */
 int ks_batch_add_resources(ks_batch* b, int32_t flags /* 0 */, size_t ngraphs, const ks_batch_res_list* lists,
                            ks_grow_stats* stats);
+
+/* ---- batch rounds, class and resource arcs: the cost model's sweep ----------
+ * The twin of ks_update_nodes on a batch, under the contract written above
+ * ks_batch_task_list: one list per loaded graph on every rank (else KS_E_INVALID), every id
+ * in its graph's OWN numbering, ONE device call per local device on its union with one record
+ * stream that is all or nothing there and marks its cells for the next solve, stats (may be
+ * NULL) summed over the local devices, no collective, and every message names the graph and
+ * the graph-local id. With it the ten calls of a round (commit, remove, complete, add
+ * resources, refresh, add tasks, update tasks, update nodes, costs, solve) all run on a batch,
+ * and a caller whose class, rack or PU → sink costs move, or whose PUs change their slot
+ * count, keeps no shadow of any cell's arcs.
+ *
+ * Refused on the host before any device is asked: a list count other than the loaded graphs,
+ * an unknown flag bit, a null array where k > 0, arc_off[0] != 0, falling offsets, a null
+ * arcs with arc_off[k] > 0 (all KS_E_INVALID); more than INT32_MAX / 4 tails or arcs per
+ * graph or per device (KS_E_RANGE); and any tail outside 1..span of its graph (KS_E_RANGE),
+ * which is checked for every local device first.
+ *
+ * The tails go into the union's ids on the host (O(k)). The 24-byte arcs go up as the caller
+ * wrote them: one kernel range-checks every head against 1..span of the arc's graph and moves
+ * it into the union's ids in place, so an arc from one cell into another cannot be written.
+ * The first head in input order outside its graph is KS_E_RANGE naming the graph, the tail,
+ * the head and the span; it is reported before the device's other refusals, as in
+ * ks_batch_update_tasks, and nothing changes. Every other refusal (a dead tail, a task or
+ * sink tail, a tail listed twice, an illegal head, a repeated head for one tail, a cost or a
+ * capacity out of range, KS_CAP_KEEP on an arc the store does not hold, a capacity below a
+ * lower bound) keeps the lone call's status code and the lone call's order within a device.
+ * A tail listed twice is twice within one graph: the same local id in two graphs is two tails.
+ *
+ * With several local devices the call is all or nothing PER DEVICE, as in
+ * ks_batch_update_tasks: the devices are asked in order, and a later device's refusal does
+ * not undo the stream an earlier device has applied. No supply moves, so no auto-sink record
+ * follows and the rows of ks_batch_gather keep their length. A call whose lists are all empty,
+ * or that generates no record on a device, keeps that device's solution and mapping and marks
+ * no cell. */
+typedef struct ks_batch_node_list {   /* one graph's part of the call, in the graph's OWN ids */
+    const uint64_t*    nodes;  size_t k;    /* the tails; k == 0: the graph is untouched */
+    const uint64_t*    arc_off;             /* k + 1, as ks_update_nodes                 */
+    const ks_node_arc* arcs;
+} ks_batch_node_list;
+
+int ks_batch_update_nodes(ks_batch* b, int32_t flags /* KS_NODES_KEEP_UNLISTED or 0 */,
+                          size_t ngraphs, const ks_batch_node_list* lists, ks_node_stats* stats);
 
 #ifdef __cplusplus
 }

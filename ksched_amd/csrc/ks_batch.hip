@@ -561,6 +561,67 @@ int build_union_res(ks_batch* b, const ks_batch::Local& l, const ks_batch_res_li
     return KS_OK;
 }
 
+// ---- class and resource arcs: one device's part of ks_batch_update_nodes. The tails in the
+// union's numbering (O(k) on the host, which checks their range), the offsets rebased, the
+// 24-byte arcs as the caller wrote them: their heads leave the graph's numbering on the device.
+struct UnionNodes {
+    std::vector<uint64_t> nodes, arc_off;
+    std::vector<uint64_t> arc_goff;   // per graph of the device (+ total): its first arc
+    std::vector<ks_node_arc> arcs;
+    ks::BatchView view;
+};
+
+int check_node_lists(ks_batch* b, size_t ngraphs, const ks_batch_node_list* lists) {
+    if (ngraphs != b->ngraphs) return b->fail(KS_E_INVALID, "the list count differs from the loaded graphs");
+    if (ngraphs && !lists) return b->fail(KS_E_INVALID, "null list array");
+    for (size_t g = 0; g < ngraphs; ++g) {
+        const ks_batch_node_list& L = lists[g];
+        if (!L.k) continue;
+        const std::string who = "graph " + std::to_string(g) + ": ";
+        if (!L.nodes || !L.arc_off) return b->fail(KS_E_INVALID, who + "null node or offset array");
+        if (L.k > (size_t)INT32_MAX / 4) return b->fail(KS_E_RANGE, who + "too many nodes");
+        if (L.arc_off[0] != 0) return b->fail(KS_E_INVALID, who + "arc_off[0] must be 0");
+        for (size_t i = 0; i < L.k; ++i)
+            if (L.arc_off[i + 1] < L.arc_off[i])
+                return b->fail(KS_E_INVALID, who + "arc_off decreases at node " + std::to_string(L.nodes[i]));
+        if (L.arc_off[L.k] && !L.arcs) return b->fail(KS_E_INVALID, who + "null arc array");
+        if (L.arc_off[L.k] > (uint64_t)INT32_MAX / 4) return b->fail(KS_E_RANGE, who + "too many arcs");
+    }
+    return KS_OK;
+}
+
+// The lists of l's graphs as one union input. A tail outside 1..span of its graph is KS_E_RANGE
+// here (a head: on the device, before anything changes there).
+int build_union_nodes(ks_batch* b, const ks_batch::Local& l, const ks_batch_node_list* lists, UnionNodes& u) {
+    u.arc_goff.assign(1, 0);
+    u.arc_off.assign(1, 0);
+    for (size_t i = 0; i < l.graphs.size(); ++i) {
+        const size_t g = (size_t)l.graphs[i];
+        const ks_batch_node_list& L = lists[g];
+        const uint64_t lo = (uint64_t)l.off[i], span = (uint64_t)(l.off[i + 1] - l.off[i]);
+        for (size_t j = 0; j < L.k; ++j) {
+            if (L.nodes[j] == 0 || L.nodes[j] > span)
+                return b->fail(KS_E_RANGE, "graph " + std::to_string(g) + ": node " + std::to_string(L.nodes[j]) +
+                                               " is outside the graph's ids 1.." + std::to_string(span) +
+                                               " (its highest id at the load plus the reserved ids)");
+            u.nodes.push_back(L.nodes[j] + lo);
+        }
+        if (L.k) {
+            const uint64_t at = u.arc_off.back();
+            for (size_t j = 1; j <= L.k; ++j) u.arc_off.push_back(at + L.arc_off[j]);
+            if (L.arc_off[L.k]) u.arcs.insert(u.arcs.end(), L.arcs, L.arcs + L.arc_off[L.k]);
+            if (u.nodes.size() > (size_t)INT32_MAX / 4 || u.arcs.size() > (size_t)INT32_MAX / 4)
+                return b->fail(KS_E_RANGE, "too many nodes or arcs on one device");
+        }
+        u.arc_goff.push_back(u.arcs.size());
+    }
+    u.view.ng = l.graphs.size();
+    u.view.off = l.off.data();
+    u.view.graph = l.graphs.data();
+    u.view.arc_goff = u.arc_goff.data();
+    return KS_OK;
+}
+
 // The index among l's graphs of the graph that owns union id `id`: graph i owns (off[i], off[i+1]].
 size_t graph_index(const ks_batch::Local& l, uint64_t id) {
     size_t i = (size_t)(std::lower_bound(l.off.begin(), l.off.end(), (int64_t)id) - l.off.begin());
@@ -1310,6 +1371,36 @@ int ks_batch_add_resources(ks_batch* b, int32_t flags, size_t ngraphs, const ks_
         std::memset(&st, 0, sizeof(st));
         l.ctx->view = &u.view;
         const int rc = ks_add_resources(l.ctx, 0, u.nodes.data(), u.nodes.size(), u.arcs.data(), u.arcs.size(), &st);
+        l.ctx->view = nullptr;
+        if (rc) return b->fail(rc, "rank " + std::to_string(l.grank) + ": " + ks_last_error(l.ctx));
+        add_stats(sum, st);
+    }
+    if (stats) *stats = sum;
+    return KS_OK;
+}
+
+// ---- batch rounds, class and resource arcs: the rest of the cost model's sweep ----
+
+int ks_batch_update_nodes(ks_batch* b, int32_t flags, size_t ngraphs, const ks_batch_node_list* lists,
+                          ks_node_stats* stats) {
+    if (!b) return KS_E_INVALID;
+    if (flags & ~KS_NODES_KEEP_UNLISTED) return b->fail(KS_E_INVALID, "unknown update flag");
+    if (int rc = check_node_lists(b, ngraphs, lists)) return rc;
+    // every local device's tails first (a tail outside its graph stops the call before any device is asked)
+    std::vector<UnionNodes> us(b->loc.size());
+    for (size_t li = 0; li < b->loc.size(); ++li)
+        if (int rc = build_union_nodes(b, b->loc[li], lists, us[li])) return rc;
+    ks_node_stats sum;
+    std::memset(&sum, 0, sizeof(sum));
+    if (stats) *stats = sum;
+    for (size_t li = 0; li < b->loc.size(); ++li) {
+        auto& l = b->loc[li];
+        const UnionNodes& u = us[li];
+        if (u.nodes.empty()) continue;
+        ks_node_stats st;
+        std::memset(&st, 0, sizeof(st));
+        l.ctx->view = &u.view;
+        const int rc = ks_update_nodes(l.ctx, flags, u.nodes.data(), u.nodes.size(), u.arc_off.data(), u.arcs.data(), &st);
         l.ctx->view = nullptr;
         if (rc) return b->fail(rc, "rank " + std::to_string(l.grank) + ": " + ks_last_error(l.ctx));
         add_stats(sum, st);

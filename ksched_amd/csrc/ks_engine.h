@@ -20,8 +20,9 @@ namespace ks {
 struct EngineImpl;
 struct CommitCtl;   // ks_sched.h
 
-// A batch call's ids (ks_batch_add_tasks, ks_batch_complete_tasks, ks_batch_update_tasks): the
-// lists of a union's graphs lie back to back. The task and aggregator ids are already the
+// A batch call's ids (ks_batch_add_tasks, ks_batch_complete_tasks, ks_batch_update_tasks,
+// ks_batch_update_nodes): the lists of a union's graphs lie back to back. The task, tail and
+// aggregator ids are already the
 // union's (the host's O(k) part); the arcs' heads are still in each graph's own numbering and
 // leave it on the device (sched_translate_heads). Messages name a node as its caller knows
 // it: the graph and the graph-local id.
@@ -168,10 +169,11 @@ public:
     // ks_update_nodes (the k tails with the arcs each should have; offsets checked by the caller).
     // first_pair, first_cost, first_cap: the first arc that repeats an earlier head of its own
     // tail, whose cost and whose capacity is out of range, arc_off[k] when none does or is. No
-    // node is edited. *dirty, *changed: as in update_tasks.
+    // node is edited. *dirty, *changed: as in update_tasks. bv: the tails are the union's, the
+    // arcs' heads are graph-local (BatchView).
     int update_nodes(int flags, const uint64_t* nodes, size_t k, const uint64_t* arc_off, const ks_node_arc* arcs,
                      size_t first_pair, size_t first_cost, size_t first_cap, ks_node_stats* stats, bool* dirty,
-                     bool* changed, std::string& err);
+                     bool* changed, std::string& err, const BatchView* bv = nullptr);
     // ks_get_bindings: pu[i] = the device-kept binding of task[i] (ids checked by the caller).
     int get_bindings(const uint64_t* task, uint64_t* pu, size_t k, std::string& err);
     int device() const;

@@ -1450,10 +1450,11 @@ int Engine::update_tasks(int flags, const uint64_t* tasks, size_t k, const uint6
 // anything but scratch). Over the arc slots there is one flag array and its scan; everything else
 // is per tail, per listed arc or per chunk position. Then the sizing of the arc table and the
 // index, and the records on held arcs (ascending arc slot) and the new arcs (input order) reach
-// store_apply as one stream. No node is edited.
+// store_apply as one stream. No node is edited. Under a view (ks_batch_update_nodes) the tails are
+// the union's already and the heads leave their graphs' numbering in one launch before the checks.
 int Engine::update_nodes(int flags, const uint64_t* nodes, size_t k, const uint64_t* arc_off, const ks_node_arc* arcs,
                          size_t first_pair, size_t first_cost, size_t first_cap, ks_node_stats* stats, bool* dirty,
-                         bool* changed, std::string& err) {
+                         bool* changed, std::string& err, const BatchView* bv) {
     EngineImpl& s = *p_;
     *dirty = *changed = false;
     if (!k) return KS_OK;
@@ -1478,6 +1479,7 @@ int Engine::update_nodes(int flags, const uint64_t* nodes, size_t k, const uint6
     u.keep = walk ? 0 : 1;
     u.nst = nst;
     unsigned long long *d_nodes = nullptr, *d_off = nullptr, *d_arcs = nullptr;
+    unsigned long long *d_goff = nullptr, *d_base = nullptr;
     rc = carve_scratch(s, [&](Carve<int>& ci, Carve<unsigned long long>& cu) {
         u.n_own = ci.take(nst + 1);
         for (int** x : {&u.n_slot, &u.nch, &u.ch_off}) *x = ci.take((int64_t)k + 1);
@@ -1486,6 +1488,8 @@ int Engine::update_nodes(int flags, const uint64_t* nodes, size_t k, const uint6
         d_nodes = cu.take(k);
         d_off = cu.take(k + 1);
         d_arcs = cu.take(3 * na);
+        d_goff = cu.take(bv ? bv->ng + 1 : 0);
+        d_base = cu.take(bv ? bv->ng + 1 : 0);
     }, 0, false, err);
     if (rc) return rc;
     KS_CHECK(clear_ctl(s.nod_ctl, st));
@@ -1499,6 +1503,12 @@ int Engine::update_nodes(int flags, const uint64_t* nodes, size_t k, const uint6
     if (na) KS_CHECK(hipMemcpyAsync(d_arcs, arcs, na * sizeof(ks_node_arc), hipMemcpyHostToDevice, st));
     SchedDev d = s.schd();
     const int ni_max = (int)(k + s.m2cap / 64 + 1);
+    if (bv && na) {   // the heads leave their graphs' numbering, as in translate_heads
+        KS_CHECK(hipMemcpyAsync(d_goff, bv->arc_goff, (bv->ng + 1) * 8, hipMemcpyHostToDevice, st));
+        KS_CHECK(hipMemcpyAsync(d_base, bv->off, (bv->ng + 1) * 8, hipMemcpyHostToDevice, st));
+        KS_CHECK(sched_translate_node_heads((ks_node_arc*)d_arcs, (int)na, d_goff, (const long long*)d_base, (int)bv->ng,
+                                            u.ctl, st));
+    }
     // ---- 1. ids, heads, the diff and the unlisted arcs: one sync
     KS_CHECK(sched_nod_check(d, u, walk, st));
     if (walk) {
@@ -1513,19 +1523,31 @@ int Engine::update_nodes(int flags, const uint64_t* nodes, size_t k, const uint6
     KS_CHECK(hipMemcpyAsync(&h, u.ctl, sizeof(NodCtl), hipMemcpyDeviceToHost, st));
     KS_CHECK(hipStreamSynchronize(st));
     const auto t1 = std::chrono::steady_clock::now();
+    auto tail_of = [&](size_t j) {   // the last i with arc_off[i] ≤ j
+        return (size_t)(std::upper_bound(arc_off, arc_off + k, (uint64_t)j) - arc_off) - 1;
+    };
+    if (bv && h.bad_range) {   // (the host's arcs are still graph-local: the device translated its own copy)
+        size_t j;
+        if (!first_bad(h.bad_range, na, &j) || j >= na) {
+            err = "inconsistent arc index";
+            return KS_E_DEVICE;
+        }
+        const size_t g = (size_t)(std::upper_bound(bv->arc_goff, bv->arc_goff + bv->ng, (uint64_t)j) - bv->arc_goff) - 1;
+        err = id_name(bv, "node", nodes[tail_of(j)]) + ": head " + std::to_string(arcs[j].dst) +
+              " is outside the graph's ids 1.." + std::to_string(bv->off[g + 1] - bv->off[g]) +
+              " (its highest id at the load plus the reserved ids)";
+        return KS_E_RANGE;
+    }
     if (h.bad_node) {
         size_t i;
         if (!first_bad(h.bad_node, k, &i)) {
             err = "inconsistent node index";
             return KS_E_DEVICE;
         }
-        err = "node " + std::to_string(nodes[i]) + " is not a live class, machine, intermediate or PU node listed once "
+        err = id_name(bv, "node", nodes[i]) + " is not a live class, machine, intermediate or PU node listed once "
               "(0, beyond the graph, dead, a task, a sink, or listed before)";
         return KS_E_INVALID;
     }
-    auto tail_of = [&](size_t j) {   // the last i with arc_off[i] ≤ j
-        return (size_t)(std::upper_bound(arc_off, arc_off + k, (uint64_t)j) - arc_off) - 1;
-    };
     // the first offending arc in input order; on one arc the head, the repeat, the cost, then the capacity
     if (h.bad_head || std::min({first_pair, first_cost, first_cap}) < na) {
         size_t jh;
@@ -1534,7 +1556,7 @@ int Engine::update_nodes(int flags, const uint64_t* nodes, size_t k, const uint6
             return KS_E_DEVICE;
         }
         const size_t j = std::min({jh, first_pair, first_cost, first_cap});
-        const std::string who = "node " + std::to_string(nodes[tail_of(j)]) + ": ";
+        const std::string who = id_name(bv, "node", nodes[tail_of(j)]) + ": ";
         const std::string head = std::to_string(arcs[j].dst);
         if (j == jh) {
             err = who + "head " + head + " is not a legal head (0, beyond the graph, dead, a task or the tail itself; a "
@@ -1557,7 +1579,7 @@ int Engine::update_nodes(int flags, const uint64_t* nodes, size_t k, const uint6
             return KS_E_DEVICE;
         }
         const size_t j = std::min(jk, jl);
-        const std::string who = "node " + std::to_string(nodes[tail_of(j)]) + ": ";
+        const std::string who = id_name(bv, "node", nodes[tail_of(j)]) + ": ";
         if (j == jk) {
             err = who + "KS_CAP_KEEP on its arc into " + std::to_string(arcs[j].dst) + ", which the store does not hold: "
                   "there is no capacity to keep";

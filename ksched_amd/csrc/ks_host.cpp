@@ -1068,7 +1068,7 @@ int ks_update_nodes(ks_ctx* c, int32_t flags, const uint64_t* nodes, size_t k, c
     }
     bool dirty = false, changed = false;
     const int rc = c->eng.update_nodes(flags, nodes, k, arc_off, arcs, first_pair, first_cost, first_cap, stats, &dirty,
-                                       &changed, c->err);
+                                       &changed, c->err, c->view);
     follow_rebuild(c);
     if (rc) return delta_failed(c, rc, nullptr, dirty, stats);
     if (changed) drop_solution(c);

@@ -476,7 +476,8 @@ struct NodCtl {
     int n_del;       // held, unlisted, deleted
     int rec_held;    // the arc-slot scan's total: n_upd + n_zero + n_del
     int rec_add;     // the listed-arc scan's total: n_add
-    int reserved[4];
+    int bad_range;   // batch ids: na − the index of the first arc whose head lies outside 1..span of its graph, 0 none
+    int reserved[3];
 };
 
 // Inputs and scratch of one refresh (device pointers; nst node slots, hi arc slots).
@@ -506,6 +507,10 @@ struct NodDev {
     NodCtl* ctl;
 };
 
+// sched_translate_heads for the 24-byte arcs of a batch call's node lists: only the dst word of
+// each record is read and written (ctl->bad_range, and an offending head becomes 0).
+hipError_t sched_translate_node_heads(ks_node_arc* arcs, int na, const unsigned long long* arc_goff, const long long* base,
+                                      int ng, NodCtl* ctl, hipStream_t st);
 // The tail seed, one lane per id (liveness, type, the claim of n_own, n_slot, nch; walk: the id
 // must lie in the built CSR, whose segments are walked), then the listed-arc pass, one lane per
 // arc (the head against its tail's type, the index lookup, the table's row: l_slot, lflag, sflag

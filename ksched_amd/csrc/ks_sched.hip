@@ -826,6 +826,25 @@ __global__ void k_translate_heads(ks_task_arc* __restrict__ arcs, int na, const 
     }
 }
 
+// The same for the 24-byte arcs of ks_batch_update_nodes: only the dst word of a record is read
+// and written (its cost and capacity are the host's to check), and only an offending lane
+// touches the control word.
+__global__ void k_translate_node_heads(ks_node_arc* __restrict__ arcs, int na,
+                                       const unsigned long long* __restrict__ arc_goff,
+                                       const long long* __restrict__ base, int ng, NodCtl* __restrict__ ctl) {
+    for (long long j = blockIdx.x * (long long)SB + threadIdx.x; j < na; j += (long long)gridDim.x * SB) {
+        const int g = task_of_arc(arc_goff, ng, j);
+        const unsigned long long span = (unsigned long long)(base[g + 1] - base[g]);
+        const unsigned long long dst = arcs[j].dst;
+        if (dst < 1 || dst > span) {
+            atomicMax(&ctl->bad_range, (int)(na - j));
+            arcs[j].dst = 0;
+        } else {
+            arcs[j].dst = dst + (unsigned long long)base[g];
+        }
+    }
+}
+
 // The sink an aggregator's capacity record ends at: the one sink, or over a union's sink table
 // the sink of the aggregator's own cell; negative: there is no such sink.
 __device__ __forceinline__ long long add_sink_of(const AddDev& a, long long v) {
@@ -1649,6 +1668,13 @@ hipError_t sched_translate_heads(ks_task_arc* arcs, int na, const unsigned long 
                                  int ng, AddCtl* ctl, hipStream_t st) {
     if (na > 0 && ng > 0)
         hipLaunchKernelGGL(k_translate_heads, dim3(grid(na)), dim3(SB), 0, st, arcs, na, arc_goff, base, ng, ctl);
+    return hipGetLastError();
+}
+
+hipError_t sched_translate_node_heads(ks_node_arc* arcs, int na, const unsigned long long* arc_goff, const long long* base,
+                                      int ng, NodCtl* ctl, hipStream_t st) {
+    if (na > 0 && ng > 0)
+        hipLaunchKernelGGL(k_translate_node_heads, dim3(grid(na)), dim3(SB), 0, st, arcs, na, arc_goff, base, ng, ctl);
     return hipGetLastError();
 }
 

@@ -30,7 +30,7 @@ EXPORTED_SYMBOLS = (
     "ks_batch_get_graph", "ks_batch_set_bindings", "ks_batch_commit_schedule", "ks_batch_commit_preemptive",
     "ks_batch_add_tasks", "ks_batch_complete_tasks", "ks_batch_update_tasks", "ks_batch_get_bindings",
     "ks_batch_update_unsched_costs",
-    "ks_batch_remove_resources", "ks_batch_add_resources",
+    "ks_batch_remove_resources", "ks_batch_add_resources", "ks_batch_update_nodes",
 )
 ABI_VERSION = 5
 KS_DELTA_PLACE, KS_DELTA_PREEMPT, KS_DELTA_MIGRATE, KS_DELTA_NOOP = 0, 1, 2, 3
@@ -180,6 +180,45 @@ class KsNodeStats(C.Structure):
 
 NODE_ARC_DT = np.dtype({"names": ["dst", "cost", "cap"], "formats": ["<u8", "<i8", "<u8"], "offsets": [0, 8, 16],
                         "itemsize": 24})
+
+
+class KsBatchNodeList(C.Structure):
+    """ks_batch_node_list (32 B): one graph's part of ks_batch_update_nodes, in the graph's own ids."""
+    _fields_ = [("nodes", C.c_void_p), ("k", C.c_size_t), ("arc_off", C.c_void_p), ("arcs", C.c_void_p)]
+
+
+def pack_node_lists(ngraphs: int, lists):
+    """One ks_batch_node_list per graph. lists[g]: None (graph g untouched) or (nodes, arc_off,
+    dst, cost, cap) as Context.update_nodes takes them. → (the ctypes array, the numpy arrays it
+    points into: per graph a dict with nodes, arc_off, arcs (NODE_ARC_DT), or None)."""
+    if lists is None:
+        lists = [None] * ngraphs
+    if len(lists) != ngraphs:
+        raise ValueError("one entry (or None) per loaded graph")
+    out = (KsBatchNodeList * max(1, ngraphs))()
+    keep = []
+    for g in range(ngraphs):
+        if lists[g] is None:
+            keep.append(None)
+            continue
+        nodes, off, dst, cost, cap = lists[g]
+        a = {"nodes": np.ascontiguousarray(nodes, np.uint64).reshape(-1),
+             "arc_off": np.ascontiguousarray(off, np.uint64).reshape(-1)}
+        if a["arc_off"].shape[0] != a["nodes"].shape[0] + 1:
+            raise ValueError("arc_off has one entry more than nodes")
+        n = np.asarray(dst).size
+        if np.asarray(cost).size != n or np.asarray(cap).size != n:
+            raise ValueError("dst, cost and cap have one entry per listed arc")
+        a["arcs"] = np.zeros(max(n, 1), NODE_ARC_DT)
+        a["arcs"]["dst"][:n] = np.asarray(dst, np.uint64).reshape(-1)
+        a["arcs"]["cost"][:n] = np.asarray(cost, np.int64).reshape(-1)
+        a["arcs"]["cap"][:n] = np.asarray(cap, np.uint64).reshape(-1)
+        out[g].nodes = a["nodes"].ctypes.data
+        out[g].k = a["nodes"].shape[0]
+        out[g].arc_off = a["arc_off"].ctypes.data
+        out[g].arcs = a["arcs"].ctypes.data
+        keep.append(a)
+    return out, keep
 
 
 class KsGrowStats(C.Structure):
@@ -371,6 +410,7 @@ def _bind(path: str):
     L.ks_batch_remove_resources.argtypes = [V, C.c_int32, C.c_size_t, P(KsBatchResList), V, C.c_size_t, P(C.c_size_t),
                                             V, V, C.c_size_t, P(C.c_size_t), P(KsRemoveStats)]
     L.ks_batch_add_resources.argtypes = [V, C.c_int32, C.c_size_t, P(KsBatchResList), P(KsGrowStats)]
+    L.ks_batch_update_nodes.argtypes = [V, C.c_int32, C.c_size_t, P(KsBatchNodeList), P(KsNodeStats)]
     L.ks_set_bindings.argtypes = [V, V, V, C.c_size_t]
     L.ks_scheduling_deltas.argtypes = [V, C.c_int, V, C.c_size_t, P(C.c_size_t)]
     L.ks_update_unsched_costs.argtypes = [V, V, C.c_size_t, C.c_int32, C.c_int64, C.c_int64, P(C.c_size_t)]
@@ -942,6 +982,18 @@ class Batch:
                 ls[g].arcs, ls[g].m = ar.ctypes.data, ar.shape[0]
         st = KsGrowStats()
         self._check(self._L.ks_batch_add_resources(self._h, 0, self.ngraphs, ls, C.byref(st)))
+        del keep
+        return st.as_dict()
+
+    def update_nodes(self, lists, keep_unlisted: bool = False, flags=None) -> dict:
+        """ks_batch_update_nodes: lists[g] = None or (nodes, arc_off, dst, cost, cap) as
+        Context.update_nodes takes them, in graph g's own ids. → stats summed over the local
+        devices. flags: the raw KS_NODES_* word instead of the switch."""
+        ls, keep = pack_node_lists(self.ngraphs, lists)
+        if flags is None:
+            flags = KS_NODES_KEEP_UNLISTED if keep_unlisted else 0
+        st = KsNodeStats()
+        self._check(self._L.ks_batch_update_nodes(self._h, flags, self.ngraphs, ls, C.byref(st)))
         del keep
         return st.as_dict()
 
