@@ -301,14 +301,26 @@ void append_auto_sink(const ks_batch::Local& l, size_t i, std::vector<ks_delta>&
     u.push_back(d);
 }
 
+// The index among l's graphs of the graph that owns union id `id`: graph i owns (off[i], off[i+1]]
+// (an id past the last graph is the last graph's; 0 when off holds no graph).
+size_t graph_index(const ks_batch::Local& l, uint64_t id) {
+    size_t i = (size_t)(std::lower_bound(l.off.begin(), l.off.end(), (int64_t)id) - l.off.begin());
+    i = i ? i - 1 : 0;
+    return std::min(i, l.off.size() >= 2 ? l.off.size() - 2 : 0);
+}
+
+template <class Stats>
+void add_stats(Stats& sum, const Stats& st) {
+    static_assert(sizeof(Stats) % sizeof(int64_t) == 0, "stats are int64 counters");
+    for (size_t w = 0; w < sizeof(Stats) / sizeof(int64_t); ++w)
+        reinterpret_cast<int64_t*>(&sum)[w] += reinterpret_cast<const int64_t*>(&st)[w];
+}
+
 // A commit's deltas of one device (union ids, the order of ks_scheduling_deltas) as
 // ks_batch_delta records in graph-local ids.
 void localize_deltas(const ks_batch::Local& l, const std::vector<ks_sched_delta>& v, std::vector<ks_batch_delta>& out) {
     for (const ks_sched_delta& x : v) {
-        // graph i owns the ids (off[i], off[i+1]]
-        size_t i = (size_t)(std::lower_bound(l.off.begin(), l.off.end(), (int64_t)x.task) - l.off.begin());
-        i = i ? i - 1 : 0;
-        if (i + 1 >= l.off.size()) i = l.off.size() >= 2 ? l.off.size() - 2 : 0;
+        const size_t i = graph_index(l, x.task);
         const uint64_t base = (uint64_t)l.off[i];
         out.push_back(ks_batch_delta{x.type, l.graphs.empty() ? 0 : l.graphs[i], x.task - base, x.pu ? x.pu - base : 0});
     }
@@ -331,7 +343,6 @@ int batch_commit(ks_batch* b, ks_batch_delta* out, size_t cap, size_t* count, St
     if (cap < total) return b->fail(KS_E_INVALID, "output buffer smaller than the delta count");
     Stats sum;
     std::memset(&sum, 0, sizeof(sum));
-    static_assert(sizeof(Stats) % sizeof(int64_t) == 0, "commit stats are int64 counters");
     std::vector<ks_batch_delta> all;
     for (size_t li = 0; li < b->loc.size(); ++li) {
         auto& l = b->loc[li];
@@ -343,8 +354,7 @@ int batch_commit(ks_batch* b, ks_batch_delta* out, size_t cap, size_t* count, St
         if (rc) return b->fail(rc, ks_last_error(l.ctx));
         v.resize(got);
         localize_deltas(l, v, all);
-        for (size_t w = 0; w < sizeof(Stats) / sizeof(int64_t); ++w)
-            reinterpret_cast<int64_t*>(&sum)[w] += reinterpret_cast<const int64_t*>(&st)[w];
+        add_stats(sum, st);
         recompute_toff(l);
     }
     // grouped by graph, ascending; within a graph the order of ks_scheduling_deltas
@@ -355,6 +365,97 @@ int batch_commit(ks_batch* b, ks_batch_delta* out, size_t cap, size_t* count, St
     if (stats) *stats = sum;
     return KS_OK;
 }
+
+// ---- what the round calls share: the checks of the per-graph lists, a graph's ids into the
+// union's numbering, a device's view of its union, and the one lone call per device ----
+
+// One list per loaded graph.
+int check_list_array(ks_batch* b, size_t ngraphs, const void* lists) {
+    if (ngraphs != b->ngraphs) return b->fail(KS_E_INVALID, "the list count differs from the loaded graphs");
+    if (ngraphs && !lists) return b->fail(KS_E_INVALID, "null list array");
+    return KS_OK;
+}
+
+std::string in_graph(size_t g) { return "graph " + std::to_string(g) + ": "; }
+
+// Graph g's list of k ids (what: their noun) with arc_off[k + 1] into its arcs.
+int check_offsets(ks_batch* b, size_t g, size_t k, const uint64_t* arc_off, const uint64_t* ids, bool null_arcs,
+                  const char* what) {
+    if (arc_off[0] != 0) return b->fail(KS_E_INVALID, in_graph(g) + "arc_off[0] must be 0");
+    for (size_t i = 0; i < k; ++i)
+        if (arc_off[i + 1] < arc_off[i])
+            return b->fail(KS_E_INVALID, in_graph(g) + "arc_off decreases at " + what + " " + std::to_string(ids[i]));
+    if (arc_off[k] && null_arcs) return b->fail(KS_E_INVALID, in_graph(g) + "null arc array");
+    if (arc_off[k] > (uint64_t)INT32_MAX / 4) return b->fail(KS_E_RANGE, in_graph(g) + "too many arcs");
+    return KS_OK;
+}
+
+int outside_ids(ks_batch* b, size_t g, const char* what, uint64_t id, uint64_t span) {
+    return b->fail(KS_E_RANGE, in_graph(g) + what + " " + std::to_string(id) + " is outside the graph's ids 1.." +
+                                   std::to_string(span) + " (its highest id at the load plus the reserved ids)");
+}
+
+uint64_t span_of(const ks_batch::Local& l, size_t i) { return (uint64_t)(l.off[i + 1] - l.off[i]); }
+
+// k ids of l's graph i (what: their noun) in the union's numbering, appended to out: the O(k) part
+// of a call, which the node table needs anyway. One outside 1..span of its graph is KS_E_RANGE.
+int to_union(ks_batch* b, const ks_batch::Local& l, size_t i, const char* what, const uint64_t* ids, size_t k,
+             std::vector<uint64_t>& out) {
+    const uint64_t lo = (uint64_t)l.off[i], span = span_of(l, i);
+    for (size_t j = 0; j < k; ++j) {
+        if (ids[j] == 0 || ids[j] > span) return outside_ids(b, (size_t)l.graphs[i], what, ids[j], span);
+        out.push_back(ids[j] + lo);
+    }
+    return KS_OK;
+}
+
+// A graph's k offsets and the arcs behind them appended to a union's: the offsets rebased, the
+// arcs as the caller wrote them.
+template <class Arc>
+void append_arcs(std::vector<uint64_t>& union_off, std::vector<Arc>& union_arcs, size_t k, const uint64_t* arc_off,
+                 const Arc* arcs) {
+    const uint64_t at = union_off.back();
+    for (size_t j = 1; j <= k; ++j) union_off.push_back(at + arc_off[j]);
+    if (arc_off[k]) union_arcs.insert(union_arcs.end(), arcs, arcs + arc_off[k]);
+}
+
+// How the lone call addresses l's graphs: arc_goff (and node_goff, where the call has one) hold
+// the first listed record of each graph (+ the total).
+void wire_view(ks::BatchView& v, const ks_batch::Local& l, const std::vector<uint64_t>& arc_goff,
+               const std::vector<uint64_t>* node_goff = nullptr) {
+    v.ng = l.graphs.size();
+    v.off = l.off.data();
+    v.graph = l.graphs.data();
+    v.arc_goff = arc_goff.data();
+    v.node_goff = node_goff ? node_goff->data() : nullptr;
+}
+
+// ONE lone call per local device on its union input us[li], after every list passed the checks of
+// every local device. want(l, u): whether the device is called at all; call(l, u, &st): the lone
+// call, under the view that lets its messages name graphs; after(l, u): what follows a call that
+// succeeded. A failure of either is the rank's, with the device's message. stats: the sum over
+// the devices, zero from the start and whole at the end.
+template <class Stats, class Union, class Want, class Call, class After>
+int each_device(ks_batch* b, std::vector<Union>& us, Stats* stats, Want want, Call call, After after) {
+    Stats sum;
+    std::memset(&sum, 0, sizeof(sum));
+    if (stats) *stats = sum;
+    for (size_t li = 0; li < b->loc.size(); ++li) {
+        ks_batch::Local& l = b->loc[li];
+        if (!want(l, us[li])) continue;
+        Stats st;
+        std::memset(&st, 0, sizeof(st));
+        l.ctx->view = &us[li].view;
+        int rc = call(l, us[li], &st);
+        l.ctx->view = nullptr;
+        if (rc == KS_OK) rc = after(l, us[li]);
+        if (rc) return b->fail(rc, "rank " + std::to_string(l.grank) + ": " + ks_last_error(l.ctx));
+        add_stats(sum, st);
+    }
+    if (stats) *stats = sum;
+    return KS_OK;
+}
+const auto nothing_after = [](ks_batch::Local&, const auto&) { return (int)KS_OK; };
 
 // ---- the task side of a round: one device's part of ks_batch_add_tasks, _complete_tasks,
 // _update_tasks. Its graphs' lists lie back to back in graph order: the task and aggregator
@@ -376,13 +477,12 @@ struct UnionLists {
 // What every rank can check of all the lists, before any device is asked: the arrays, the
 // offsets, and the one aggregator mode of the call.
 int check_lists(ks_batch* b, size_t ngraphs, const ks_batch_task_list* lists, bool with_arcs) {
-    if (ngraphs != b->ngraphs) return b->fail(KS_E_INVALID, "the list count differs from the loaded graphs");
-    if (ngraphs && !lists) return b->fail(KS_E_INVALID, "null list array");
+    if (int rc = check_list_array(b, ngraphs, lists)) return rc;
     int mode = -1;   // 1: the listed graphs pass unsched_ids, 0: none does
     for (size_t g = 0; g < ngraphs; ++g) {
         const ks_batch_task_list& L = lists[g];
         if (!L.k) continue;
-        const std::string who = "graph " + std::to_string(g) + ": ";
+        const std::string who = in_graph(g);
         if (!L.tasks) return b->fail(KS_E_INVALID, who + "null task array");
         if (L.k > (size_t)INT32_MAX / 4) return b->fail(KS_E_RANGE, who + "too many tasks");
         if (L.unsched_ids == nullptr && L.nu) return b->fail(KS_E_INVALID, who + "null aggregator array");
@@ -392,12 +492,7 @@ int check_lists(ks_batch* b, size_t ngraphs, const ks_batch_task_list* lists, bo
         mode = m;
         if (!with_arcs) continue;
         if (!L.arc_off) return b->fail(KS_E_INVALID, who + "null offset array");
-        if (L.arc_off[0] != 0) return b->fail(KS_E_INVALID, who + "arc_off[0] must be 0");
-        for (size_t i = 0; i < L.k; ++i)
-            if (L.arc_off[i + 1] < L.arc_off[i])
-                return b->fail(KS_E_INVALID, who + "arc_off decreases at task " + std::to_string(L.tasks[i]));
-        if (L.arc_off[L.k] && !L.arcs) return b->fail(KS_E_INVALID, who + "null arc array");
-        if (L.arc_off[L.k] > (uint64_t)INT32_MAX / 4) return b->fail(KS_E_RANGE, who + "too many arcs");
+        if (int rc = check_offsets(b, g, L.k, L.arc_off, L.tasks, !L.arcs, "task")) return rc;
     }
     return KS_OK;
 }
@@ -409,28 +504,13 @@ int build_union(ks_batch* b, const ks_batch::Local& l, const ks_batch_task_list*
     u.arc_goff.assign(1, 0);
     if (with_arcs) u.arc_off.assign(1, 0);
     for (size_t i = 0; i < l.graphs.size(); ++i) {
-        const size_t g = (size_t)l.graphs[i];
-        const ks_batch_task_list& L = lists[g];
+        const ks_batch_task_list& L = lists[(size_t)l.graphs[i]];
         if (L.k) {
-            const uint64_t lo = (uint64_t)l.off[i], span = (uint64_t)(l.off[i + 1] - l.off[i]);
-            auto range = [&](const char* what, uint64_t id) {
-                return b->fail(KS_E_RANGE, "graph " + std::to_string(g) + ": " + what + " " + std::to_string(id) +
-                                               " is outside the graph's ids 1.." + std::to_string(span) +
-                                               " (its highest id at the load plus the reserved ids)");
-            };
-            for (size_t j = 0; j < L.k; ++j) {
-                if (L.tasks[j] == 0 || L.tasks[j] > span) return range("task", L.tasks[j]);
-                u.tasks.push_back(L.tasks[j] + lo);
-            }
-            for (size_t j = 0; L.unsched_ids && j < L.nu; ++j) {
-                if (L.unsched_ids[j] == 0 || L.unsched_ids[j] > span) return range("unscheduled aggregator", L.unsched_ids[j]);
-                u.agg.push_back(L.unsched_ids[j] + lo);
-            }
+            if (int rc = to_union(b, l, i, "task", L.tasks, L.k, u.tasks)) return rc;
+            if (int rc = to_union(b, l, i, "unscheduled aggregator", L.unsched_ids, L.unsched_ids ? L.nu : 0, u.agg)) return rc;
             u.explicit_ids = L.unsched_ids != nullptr;
             if (with_arcs) {
-                const uint64_t at = u.arc_off.back();
-                for (size_t j = 1; j <= L.k; ++j) u.arc_off.push_back(at + L.arc_off[j]);
-                if (L.arc_off[L.k]) u.arcs.insert(u.arcs.end(), L.arcs, L.arcs + L.arc_off[L.k]);
+                append_arcs(u.arc_off, u.arcs, L.k, L.arc_off, L.arcs);
                 if (u.arcs.size() > (size_t)INT32_MAX / 4) return b->fail(KS_E_RANGE, "too many arcs on one device");
             }
             u.touched.push_back(i);
@@ -438,10 +518,7 @@ int build_union(ks_batch* b, const ks_batch::Local& l, const ks_batch_task_list*
         u.task_goff.push_back(u.tasks.size());
         u.arc_goff.push_back(u.arcs.size());
     }
-    u.view.ng = l.graphs.size();
-    u.view.off = l.off.data();
-    u.view.graph = l.graphs.data();
-    u.view.arc_goff = u.arc_goff.data();
+    wire_view(u.view, l, u.arc_goff);
     return KS_OK;
 }
 
@@ -459,60 +536,54 @@ int batch_task_call(ks_batch* b, size_t ngraphs, const ks_batch_task_list* lists
     std::vector<UnionLists> us(b->loc.size());
     for (size_t li = 0; li < b->loc.size(); ++li)
         if (int rc = build_union(b, b->loc[li], lists, with_arcs, us[li])) return rc;
-    Stats sum;
-    std::memset(&sum, 0, sizeof(sum));
-    static_assert(sizeof(Stats) % sizeof(int64_t) == 0, "task call stats are int64 counters");
-    if (stats) *stats = sum;
-    for (size_t li = 0; li < b->loc.size(); ++li) {
-        auto& l = b->loc[li];
-        const UnionLists& u = us[li];
-        if (u.touched.empty() && !(every_device && !l.graphs.empty())) continue;
-        Stats st;
-        std::memset(&st, 0, sizeof(st));
-        std::vector<uint64_t> hl(u.tasks.size());
-        l.ctx->view = &u.view;
-        int rc = call(l.ctx, u, hl.data(), &st);
-        l.ctx->view = nullptr;
-        if (rc) return b->fail(rc, "rank " + std::to_string(l.grank) + ": " + ks_last_error(l.ctx));
-        for (size_t w = 0; w < sizeof(Stats) / sizeof(int64_t); ++w)
-            reinterpret_cast<int64_t*>(&sum)[w] += reinterpret_cast<const int64_t*>(&st)[w];
-        if (supplies && l.ctx->opts.auto_sink) {
-            std::vector<ks_delta> sinks;
-            for (size_t i : u.touched) append_auto_sink(l, i, sinks, sinks.size());
-            if (!sinks.empty()) rc = ks_apply_deltas(l.ctx, sinks.data(), sinks.size());
-            if (rc) return b->fail(rc, "rank " + std::to_string(l.grank) + ": " + ks_last_error(l.ctx));
-        }
-        if (supplies) recompute_toff(l);
-        for (size_t i : u.touched) {
-            uint64_t* out = left ? left[(size_t)l.graphs[i]] : nullptr;
-            if (!out) continue;
-            const uint64_t lo = (uint64_t)l.off[i];
-            for (uint64_t j = u.task_goff[i]; j < u.task_goff[i + 1]; ++j) out[j - u.task_goff[i]] = hl[j] ? hl[j] - lo : 0;
-        }
-    }
-    if (stats) *stats = sum;
-    return KS_OK;
+    // the bindings the device being called returns, in the union's numbering: filled by a device's
+    // call, read by its after-step, then reused for the next device (valid only between the two)
+    std::vector<uint64_t> hl;
+    return each_device(
+        b, us, stats,
+        [&](const ks_batch::Local& l, const UnionLists& u) { return !u.touched.empty() || (every_device && !l.graphs.empty()); },
+        [&](ks_batch::Local& l, const UnionLists& u, Stats* st) {
+            hl.assign(u.tasks.size(), 0);
+            return call(l.ctx, u, hl.data(), st);
+        },
+        [&](ks_batch::Local& l, const UnionLists& u) {
+            if (supplies && l.ctx->opts.auto_sink) {
+                std::vector<ks_delta> sinks;
+                for (size_t i : u.touched) append_auto_sink(l, i, sinks, sinks.size());
+                if (!sinks.empty())
+                    if (int rc = ks_apply_deltas(l.ctx, sinks.data(), sinks.size())) return rc;
+            }
+            if (supplies) recompute_toff(l);
+            for (size_t i : u.touched) {
+                uint64_t* out = left ? left[(size_t)l.graphs[i]] : nullptr;
+                if (!out) continue;
+                const uint64_t lo = (uint64_t)l.off[i];
+                for (uint64_t j = u.task_goff[i]; j < u.task_goff[i + 1]; ++j) out[j - u.task_goff[i]] = hl[j] ? hl[j] - lo : 0;
+            }
+            return (int)KS_OK;
+        });
 }
 
 // ---- the resource side of a round: one device's part of ks_batch_remove_resources (the roots in
 // the union's numbering: O(k) on the host, which checks their range) and of ks_batch_add_resources
 // (the two record arrays as the caller wrote them: their ids leave the graphs' numbering on the
-// device, BatchView::node_goff / arc_goff).
+// device, BatchView::node_goff / arc_goff). Everything is the call's input but nr and ne, which a
+// removal's device call writes: its counts, kept here between the probing pass and the removing one.
 struct UnionRes {
     std::vector<uint64_t> roots;
     std::vector<ks_res_node> nodes;
     std::vector<ks_res_arc> arcs;
     std::vector<uint64_t> node_goff, arc_goff;   // per graph of the device (+ total): its first node, its first edge
     bool touched = false;
+    size_t nr = 0, ne = 0;                       // a removal: the nodes and the evictions the device counted
     ks::BatchView view;
 };
 
 int check_res_lists(ks_batch* b, size_t ngraphs, const ks_batch_res_list* lists, bool adding) {
-    if (ngraphs != b->ngraphs) return b->fail(KS_E_INVALID, "the list count differs from the loaded graphs");
-    if (ngraphs && !lists) return b->fail(KS_E_INVALID, "null list array");
+    if (int rc = check_list_array(b, ngraphs, lists)) return rc;
     for (size_t g = 0; g < ngraphs; ++g) {
         const ks_batch_res_list& L = lists[g];
-        const std::string who = "graph " + std::to_string(g) + ": ";
+        const std::string who = in_graph(g);
         if (!adding && L.k && !L.roots) return b->fail(KS_E_INVALID, who + "null root array");
         if (adding && ((L.n && !L.nodes) || (L.m && !L.arcs))) return b->fail(KS_E_INVALID, who + "null node or edge array");
         if (L.k > (size_t)INT32_MAX / 16 || L.n > (size_t)INT32_MAX / 16 || L.m > (size_t)INT32_MAX / 16)
@@ -529,21 +600,13 @@ int build_union_res(ks_batch* b, const ks_batch::Local& l, const ks_batch_res_li
     for (size_t i = 0; i < l.graphs.size(); ++i) {
         const size_t g = (size_t)l.graphs[i];
         const ks_batch_res_list& L = lists[g];
-        const uint64_t lo = (uint64_t)l.off[i], span = (uint64_t)(l.off[i + 1] - l.off[i]);
-        auto range = [&](const char* what, uint64_t id) {
-            return b->fail(KS_E_RANGE, "graph " + std::to_string(g) + ": " + what + " " + std::to_string(id) +
-                                           " is outside the graph's ids 1.." + std::to_string(span) +
-                                           " (its highest id at the load plus the reserved ids)");
-        };
         if (!adding) {
-            for (size_t j = 0; j < L.k; ++j) {
-                if (L.roots[j] == 0 || L.roots[j] > span) return range("root", L.roots[j]);
-                u.roots.push_back(L.roots[j] + lo);
-            }
+            if (int rc = to_union(b, l, i, "root", L.roots, L.k, u.roots)) return rc;
             u.touched |= L.k != 0;
         } else {
             for (size_t j = 0; j < L.n; ++j)
-                if (L.nodes[j].id == 0 || L.nodes[j].id > span) return range("resource node id", L.nodes[j].id);
+                if (L.nodes[j].id == 0 || L.nodes[j].id > span_of(l, i))
+                    return outside_ids(b, g, "resource node id", L.nodes[j].id, span_of(l, i));
             if (L.n) u.nodes.insert(u.nodes.end(), L.nodes, L.nodes + L.n);
             if (L.m) u.arcs.insert(u.arcs.end(), L.arcs, L.arcs + L.m);
             if (u.nodes.size() > (size_t)INT32_MAX / 16 || u.arcs.size() > (size_t)INT32_MAX / 16)
@@ -553,11 +616,7 @@ int build_union_res(ks_batch* b, const ks_batch::Local& l, const ks_batch_res_li
         u.node_goff.push_back(u.nodes.size());
         u.arc_goff.push_back(u.arcs.size());
     }
-    u.view.ng = l.graphs.size();
-    u.view.off = l.off.data();
-    u.view.graph = l.graphs.data();
-    u.view.arc_goff = u.arc_goff.data();
-    u.view.node_goff = u.node_goff.data();
+    wire_view(u.view, l, u.arc_goff, &u.node_goff);
     return KS_OK;
 }
 
@@ -572,20 +631,13 @@ struct UnionNodes {
 };
 
 int check_node_lists(ks_batch* b, size_t ngraphs, const ks_batch_node_list* lists) {
-    if (ngraphs != b->ngraphs) return b->fail(KS_E_INVALID, "the list count differs from the loaded graphs");
-    if (ngraphs && !lists) return b->fail(KS_E_INVALID, "null list array");
+    if (int rc = check_list_array(b, ngraphs, lists)) return rc;
     for (size_t g = 0; g < ngraphs; ++g) {
         const ks_batch_node_list& L = lists[g];
         if (!L.k) continue;
-        const std::string who = "graph " + std::to_string(g) + ": ";
-        if (!L.nodes || !L.arc_off) return b->fail(KS_E_INVALID, who + "null node or offset array");
-        if (L.k > (size_t)INT32_MAX / 4) return b->fail(KS_E_RANGE, who + "too many nodes");
-        if (L.arc_off[0] != 0) return b->fail(KS_E_INVALID, who + "arc_off[0] must be 0");
-        for (size_t i = 0; i < L.k; ++i)
-            if (L.arc_off[i + 1] < L.arc_off[i])
-                return b->fail(KS_E_INVALID, who + "arc_off decreases at node " + std::to_string(L.nodes[i]));
-        if (L.arc_off[L.k] && !L.arcs) return b->fail(KS_E_INVALID, who + "null arc array");
-        if (L.arc_off[L.k] > (uint64_t)INT32_MAX / 4) return b->fail(KS_E_RANGE, who + "too many arcs");
+        if (!L.nodes || !L.arc_off) return b->fail(KS_E_INVALID, in_graph(g) + "null node or offset array");
+        if (L.k > (size_t)INT32_MAX / 4) return b->fail(KS_E_RANGE, in_graph(g) + "too many nodes");
+        if (int rc = check_offsets(b, g, L.k, L.arc_off, L.nodes, !L.arcs, "node")) return rc;
     }
     return KS_OK;
 }
@@ -596,44 +648,17 @@ int build_union_nodes(ks_batch* b, const ks_batch::Local& l, const ks_batch_node
     u.arc_goff.assign(1, 0);
     u.arc_off.assign(1, 0);
     for (size_t i = 0; i < l.graphs.size(); ++i) {
-        const size_t g = (size_t)l.graphs[i];
-        const ks_batch_node_list& L = lists[g];
-        const uint64_t lo = (uint64_t)l.off[i], span = (uint64_t)(l.off[i + 1] - l.off[i]);
-        for (size_t j = 0; j < L.k; ++j) {
-            if (L.nodes[j] == 0 || L.nodes[j] > span)
-                return b->fail(KS_E_RANGE, "graph " + std::to_string(g) + ": node " + std::to_string(L.nodes[j]) +
-                                               " is outside the graph's ids 1.." + std::to_string(span) +
-                                               " (its highest id at the load plus the reserved ids)");
-            u.nodes.push_back(L.nodes[j] + lo);
-        }
+        const ks_batch_node_list& L = lists[(size_t)l.graphs[i]];
         if (L.k) {
-            const uint64_t at = u.arc_off.back();
-            for (size_t j = 1; j <= L.k; ++j) u.arc_off.push_back(at + L.arc_off[j]);
-            if (L.arc_off[L.k]) u.arcs.insert(u.arcs.end(), L.arcs, L.arcs + L.arc_off[L.k]);
+            if (int rc = to_union(b, l, i, "node", L.nodes, L.k, u.nodes)) return rc;
+            append_arcs(u.arc_off, u.arcs, L.k, L.arc_off, L.arcs);
             if (u.nodes.size() > (size_t)INT32_MAX / 4 || u.arcs.size() > (size_t)INT32_MAX / 4)
                 return b->fail(KS_E_RANGE, "too many nodes or arcs on one device");
         }
         u.arc_goff.push_back(u.arcs.size());
     }
-    u.view.ng = l.graphs.size();
-    u.view.off = l.off.data();
-    u.view.graph = l.graphs.data();
-    u.view.arc_goff = u.arc_goff.data();
+    wire_view(u.view, l, u.arc_goff);
     return KS_OK;
-}
-
-// The index among l's graphs of the graph that owns union id `id`: graph i owns (off[i], off[i+1]].
-size_t graph_index(const ks_batch::Local& l, uint64_t id) {
-    size_t i = (size_t)(std::lower_bound(l.off.begin(), l.off.end(), (int64_t)id) - l.off.begin());
-    i = i ? i - 1 : 0;
-    return std::min(i, l.graphs.size() ? l.graphs.size() - 1 : 0);
-}
-
-template <class Stats>
-void add_stats(Stats& sum, const Stats& st) {
-    static_assert(sizeof(Stats) % sizeof(int64_t) == 0, "stats are int64 counters");
-    for (size_t w = 0; w < sizeof(Stats) / sizeof(int64_t); ++w)
-        reinterpret_cast<int64_t*>(&sum)[w] += reinterpret_cast<const int64_t*>(&st)[w];
 }
 
 }  // namespace
@@ -1287,25 +1312,20 @@ int ks_batch_remove_resources(ks_batch* b, int32_t flags, size_t ngraphs, const 
     std::vector<UnionRes> us(nl);
     for (size_t li = 0; li < nl; ++li)
         if (int rc = build_union_res(b, b->loc[li], lists, false, us[li])) return rc;
-    std::vector<size_t> nr(nl, 0), ne(nl, 0);
-    auto call = [&](size_t li, uint64_t* rm, size_t rc_cap, ks_sched_delta* ev, size_t ev_cap, ks_remove_stats* st) {
-        auto& l = b->loc[li];
-        l.ctx->view = &us[li].view;
-        const int rc = ks_remove_resources(l.ctx, flags, us[li].roots.data(), us[li].roots.size(), rm, rc_cap, &nr[li], ev,
-                                           ev_cap, &ne[li], st);
-        l.ctx->view = nullptr;
-        return rc ? b->fail(rc, "rank " + std::to_string(l.grank) + ": " + ks_last_error(l.ctx)) : KS_OK;
-    };
+    auto touched = [](const ks_batch::Local&, const UnionRes& u) { return u.touched; };
     auto totals = [&]() {
         *nremoved = *nevicted = 0;
-        for (size_t li = 0; li < nl; ++li) *nremoved += nr[li], *nevicted += ne[li];
+        for (const UnionRes& u : us) *nremoved += u.nr, *nevicted += u.ne;
     };
     // a probe, and with several local devices the count of every device before any of them
     // changes: a buffer that is too small or a root any device refuses changes none
     if (probe || nl > 1) {
-        for (size_t li = 0; li < nl; ++li)
-            if (us[li].touched)
-                if (int rc = call(li, nullptr, 0, nullptr, 0, nullptr)) return rc;
+        const int rc = each_device(b, us, (ks_remove_stats*)nullptr, touched,
+                                   [&](ks_batch::Local& l, UnionRes& u, ks_remove_stats*) {
+                                       return ks_remove_resources(l.ctx, flags, u.roots.data(), u.roots.size(), nullptr, 0,
+                                                                  &u.nr, nullptr, 0, &u.ne, nullptr);
+                                   }, nothing_after);
+        if (rc) return rc;
         totals();
         if (probe) return KS_OK;
         if (rcap < *nremoved || ecap < *nevicted)
@@ -1313,30 +1333,35 @@ int ks_batch_remove_resources(ks_batch* b, int32_t flags, size_t ngraphs, const 
                                                           : "evicted buffer smaller than the evicted tasks");
     }
     ks_remove_stats sum;
-    std::memset(&sum, 0, sizeof(sum));
     std::vector<std::vector<uint64_t>> per_graph(ngraphs);
     std::vector<ks_batch_delta> all;
-    for (size_t li = 0; li < nl; ++li) {
-        auto& l = b->loc[li];
-        if (!us[li].touched) continue;
-        // (one local device: its own call counts and checks the room; no removal exceeds the node table)
-        const size_t cap_r = nl > 1 ? nr[li] : std::min(rcap, l.ctx->nodes.size());
-        const size_t cap_e = nl > 1 ? ne[li] : std::min(ecap, l.ctx->nodes.size());
-        std::vector<uint64_t> rm(cap_r + 1);
-        std::vector<ks_sched_delta> ev(cap_e + 1);
-        ks_remove_stats st;
-        std::memset(&st, 0, sizeof(st));
-        const int rc = call(li, rm.data(), cap_r, ev.data(), cap_e, &st);
-        if (nl == 1) totals();
-        if (rc) return rc;
-        add_stats(sum, st);
-        for (size_t j = 0; j < nr[li]; ++j) {   // ascending in the union: ascending within each graph
-            const size_t i = graph_index(l, rm[j]);
-            per_graph[(size_t)l.graphs[i]].push_back(rm[j] - (uint64_t)l.off[i]);
-        }
-        ev.resize(ne[li]);
-        localize_deltas(l, ev, all);
-    }
+    // what the device being called removed and evicted, in the union's numbering: filled by a device's
+    // call, read by its after-step, then reused for the next device (valid only between the two)
+    std::vector<uint64_t> rm;
+    std::vector<ks_sched_delta> ev;
+    const int rc = each_device(
+        b, us, &sum, touched,
+        [&](ks_batch::Local& l, UnionRes& u, ks_remove_stats* st) {
+            // (one local device: its own call counts and checks the room; no removal exceeds the node table)
+            const size_t cap_r = nl > 1 ? u.nr : std::min(rcap, l.ctx->nodes.size());
+            const size_t cap_e = nl > 1 ? u.ne : std::min(ecap, l.ctx->nodes.size());
+            rm.assign(cap_r + 1, 0);
+            ev.assign(cap_e + 1, ks_sched_delta{});
+            const int rc = ks_remove_resources(l.ctx, flags, u.roots.data(), u.roots.size(), rm.data(), cap_r, &u.nr,
+                                               ev.data(), cap_e, &u.ne, st);
+            if (nl == 1) totals();
+            return rc;
+        },
+        [&](ks_batch::Local& l, UnionRes& u) {
+            for (size_t j = 0; j < u.nr; ++j) {   // ascending in the union: ascending within each graph
+                const size_t i = graph_index(l, rm[j]);
+                per_graph[(size_t)l.graphs[i]].push_back(rm[j] - (uint64_t)l.off[i]);
+            }
+            ev.resize(u.ne);
+            localize_deltas(l, ev, all);
+            return (int)KS_OK;
+        });
+    if (rc) return rc;
     size_t at = 0;
     for (size_t g = 0; g < ngraphs; ++g) {
         if (removed_off) removed_off[g] = at;
@@ -1360,23 +1385,10 @@ int ks_batch_add_resources(ks_batch* b, int32_t flags, size_t ngraphs, const ks_
     std::vector<UnionRes> us(b->loc.size());
     for (size_t li = 0; li < b->loc.size(); ++li)
         if (int rc = build_union_res(b, b->loc[li], lists, true, us[li])) return rc;
-    ks_grow_stats sum;
-    std::memset(&sum, 0, sizeof(sum));
-    if (stats) *stats = sum;
-    for (size_t li = 0; li < b->loc.size(); ++li) {
-        auto& l = b->loc[li];
-        const UnionRes& u = us[li];
-        if (!u.touched) continue;
-        ks_grow_stats st;
-        std::memset(&st, 0, sizeof(st));
-        l.ctx->view = &u.view;
-        const int rc = ks_add_resources(l.ctx, 0, u.nodes.data(), u.nodes.size(), u.arcs.data(), u.arcs.size(), &st);
-        l.ctx->view = nullptr;
-        if (rc) return b->fail(rc, "rank " + std::to_string(l.grank) + ": " + ks_last_error(l.ctx));
-        add_stats(sum, st);
-    }
-    if (stats) *stats = sum;
-    return KS_OK;
+    return each_device(b, us, stats, [](const ks_batch::Local&, const UnionRes& u) { return u.touched; },
+                       [&](ks_batch::Local& l, const UnionRes& u, ks_grow_stats* st) {
+                           return ks_add_resources(l.ctx, 0, u.nodes.data(), u.nodes.size(), u.arcs.data(), u.arcs.size(), st);
+                       }, nothing_after);
 }
 
 // ---- batch rounds, class and resource arcs: the rest of the cost model's sweep ----
@@ -1390,23 +1402,11 @@ int ks_batch_update_nodes(ks_batch* b, int32_t flags, size_t ngraphs, const ks_b
     std::vector<UnionNodes> us(b->loc.size());
     for (size_t li = 0; li < b->loc.size(); ++li)
         if (int rc = build_union_nodes(b, b->loc[li], lists, us[li])) return rc;
-    ks_node_stats sum;
-    std::memset(&sum, 0, sizeof(sum));
-    if (stats) *stats = sum;
-    for (size_t li = 0; li < b->loc.size(); ++li) {
-        auto& l = b->loc[li];
-        const UnionNodes& u = us[li];
-        if (u.nodes.empty()) continue;
-        ks_node_stats st;
-        std::memset(&st, 0, sizeof(st));
-        l.ctx->view = &u.view;
-        const int rc = ks_update_nodes(l.ctx, flags, u.nodes.data(), u.nodes.size(), u.arc_off.data(), u.arcs.data(), &st);
-        l.ctx->view = nullptr;
-        if (rc) return b->fail(rc, "rank " + std::to_string(l.grank) + ": " + ks_last_error(l.ctx));
-        add_stats(sum, st);
-    }
-    if (stats) *stats = sum;
-    return KS_OK;
+    return each_device(b, us, stats, [](const ks_batch::Local&, const UnionNodes& u) { return !u.nodes.empty(); },
+                       [&](ks_batch::Local& l, const UnionNodes& u, ks_node_stats* st) {
+                           return ks_update_nodes(l.ctx, flags, u.nodes.data(), u.nodes.size(), u.arc_off.data(),
+                                                  u.arcs.data(), st);
+                       }, nothing_after);
 }
 
 }  // extern "C"

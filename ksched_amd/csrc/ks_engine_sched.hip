@@ -143,19 +143,29 @@ int wire_cell_sinks(EngineImpl& s, const SchedDev& d, Dev& a, int64_t sink_slot,
     return KS_OK;
 }
 
-// A batch call's heads leave their graphs' numbering on the device (d_goff, d_base: ng + 1 words each).
+// A batch call's heads leave their graphs' numbering on the device (d_goff, d_base: ng + 1 words
+// each; Arc: ks_task_arc or ks_node_arc; bad_range: that word of the call's control struct).
+template <class Arc>
 int translate_heads(EngineImpl& s, const BatchView& bv, unsigned long long* d_goff, unsigned long long* d_base,
-                    unsigned long long* d_arcs, size_t na, AddCtl* ctl, std::string& err) {
+                    unsigned long long* d_arcs, size_t na, int* bad_range, std::string& err) {
     KS_CHECK(hipMemcpyAsync(d_goff, bv.arc_goff, (bv.ng + 1) * 8, hipMemcpyHostToDevice, s.stream));
     KS_CHECK(hipMemcpyAsync(d_base, bv.off, (bv.ng + 1) * 8, hipMemcpyHostToDevice, s.stream));
-    KS_CHECK(sched_translate_heads((ks_task_arc*)d_arcs, (int)na, d_goff, (const long long*)d_base, (int)bv.ng, ctl,
+    KS_CHECK(sched_translate_heads((Arc*)d_arcs, (int)na, d_goff, (const long long*)d_base, (int)bv.ng, bad_range,
                                    s.stream));
     return KS_OK;
 }
 
-// The refusal of a head outside its graph's ids (word: AddCtl::bad_range).
-int range_refusal(const BatchView& bv, int word, const uint64_t* tasks, const uint64_t* arc_off, size_t k,
-                  const ks_task_arc* arcs, size_t na, std::string& err) {
+// What every range refusal of a batch call ends with (span: the ids of the offender's graph).
+std::string outside_ids_tail(int64_t span) {
+    return " is outside the graph's ids 1.." + std::to_string(span) + " (its highest id at the load plus the reserved ids)";
+}
+
+// The refusal of a head outside its graph's ids (word: the control struct's bad_range; what: the
+// noun of the k listed ids, "task" or "node"; the host's arcs are still graph-local: the device
+// translated its own copy).
+template <class Arc>
+int range_refusal(const BatchView& bv, int word, const char* what, const uint64_t* ids, const uint64_t* arc_off,
+                  size_t k, const Arc* arcs, size_t na, std::string& err) {
     size_t j;
     if (!first_bad(word, na, &j) || j >= na) {
         err = "inconsistent arc index";
@@ -163,8 +173,7 @@ int range_refusal(const BatchView& bv, int word, const uint64_t* tasks, const ui
     }
     const size_t g = (size_t)(std::upper_bound(bv.arc_goff, bv.arc_goff + bv.ng, (uint64_t)j) - bv.arc_goff) - 1;
     const size_t i = (size_t)(std::upper_bound(arc_off, arc_off + k, (uint64_t)j) - arc_off) - 1;
-    err = id_name(&bv, "task", tasks[i]) + ": head " + std::to_string(arcs[j].dst) + " is outside the graph's ids 1.." +
-          std::to_string(bv.off[g + 1] - bv.off[g]) + " (its highest id at the load plus the reserved ids)";
+    err = id_name(&bv, what, ids[i]) + ": head " + std::to_string(arcs[j].dst) + outside_ids_tail(bv.off[g + 1] - bv.off[g]);
     return KS_E_RANGE;
 }
 
@@ -940,7 +949,7 @@ int Engine::add_tasks(const uint64_t* tasks, size_t k, const uint64_t* arc_off, 
     if (unsched_ids && nu) KS_CHECK(hipMemcpyAsync(d_agg, unsched_ids, nu * 8, hipMemcpyHostToDevice, st));
     SchedDev d = s.schd();
     rc = wire_cell_sinks(s, d, a, sink_slot, err);
-    if (rc == KS_OK && bv && na) rc = translate_heads(s, *bv, d_goff, d_base, d_arcs, na, a.ctl, err);
+    if (rc == KS_OK && bv && na) rc = translate_heads<ks_task_arc>(s, *bv, d_goff, d_base, d_arcs, na, &a.ctl->bad_range, err);
     if (rc) return rc;
     // ---- 1. heads, costs, the aggregators' gains and their arcs into the sink: one sync
     KS_CHECK(sched_add_check(d, a, unsched_ids ? d_agg : nullptr, (int)nu, st));
@@ -953,7 +962,7 @@ int Engine::add_tasks(const uint64_t* tasks, size_t k, const uint64_t* arc_off, 
     auto task_of = [&](size_t j) {   // the last i with arc_off[i] ≤ j
         return (size_t)(std::upper_bound(arc_off, arc_off + k, (uint64_t)j) - arc_off) - 1;
     };
-    if (bv && h.bad_range) return range_refusal(*bv, h.bad_range, tasks, arc_off, k, arcs, na, err);
+    if (bv && h.bad_range) return range_refusal(*bv, h.bad_range, "task", tasks, arc_off, k, arcs, na, err);
     if (h.bad_head || h.bad_cost) {   // the first offending arc in input order; on one arc the head comes first
         size_t jh, jc;
         if (!first_bad(h.bad_head, na, &jh) || !first_bad(h.bad_cost, na, &jc)) {
@@ -1132,7 +1141,7 @@ int Engine::add_resources(const ks_res_node* nodes, size_t n, const ks_res_arc* 
               (node ? "resource node id " + std::to_string(nodes[j].id)
                     : "edge " + std::to_string(arcs[j].parent) + " -> " + std::to_string(arcs[j].child) + ": " +
                           (parent ? "parent " + std::to_string(arcs[j].parent) : "child " + std::to_string(arcs[j].child))) +
-              " is outside the graph's ids 1.." + std::to_string(span) + " (its highest id at the load plus the reserved ids)";
+              outside_ids_tail((int64_t)span);
         return KS_E_RANGE;
     }
     if (h.bad_edge || first_pair < m) {   // the first offending edge in input order; on one edge the lowest class
@@ -1322,7 +1331,7 @@ int Engine::update_tasks(int flags, const uint64_t* tasks, size_t k, const uint6
     if (unsched_ids && nu) KS_CHECK(hipMemcpyAsync(d_agg, unsched_ids, nu * 8, hipMemcpyHostToDevice, st));
     SchedDev d = s.schd();
     rc = wire_cell_sinks(s, d, a, sink_slot, err);
-    if (rc == KS_OK && bv && na) rc = translate_heads(s, *bv, d_goff, d_base, d_arcs, na, a.ctl, err);
+    if (rc == KS_OK && bv && na) rc = translate_heads<ks_task_arc>(s, *bv, d_goff, d_base, d_arcs, na, &a.ctl->bad_range, err);
     if (rc) return rc;
     // ---- 1. ids, heads, costs, the diff, the aggregators' gains and their arcs into the sink: one sync
     KS_CHECK(sched_upd_check(d, u, unsched_ids ? d_agg : nullptr, (int)nu, walk, st));
@@ -1340,7 +1349,7 @@ int Engine::update_tasks(int flags, const uint64_t* tasks, size_t k, const uint6
     KS_CHECK(hipMemcpyAsync(&ha, a.ctl, sizeof(AddCtl), hipMemcpyDeviceToHost, st));
     KS_CHECK(hipStreamSynchronize(st));
     const auto t1 = std::chrono::steady_clock::now();
-    if (bv && ha.bad_range) return range_refusal(*bv, ha.bad_range, tasks, arc_off, k, arcs, na, err);
+    if (bv && ha.bad_range) return range_refusal(*bv, ha.bad_range, "task", tasks, arc_off, k, arcs, na, err);
     if (h.bad_task) {
         size_t i;
         if (!first_bad(h.bad_task, k, &i)) {
@@ -1503,12 +1512,8 @@ int Engine::update_nodes(int flags, const uint64_t* nodes, size_t k, const uint6
     if (na) KS_CHECK(hipMemcpyAsync(d_arcs, arcs, na * sizeof(ks_node_arc), hipMemcpyHostToDevice, st));
     SchedDev d = s.schd();
     const int ni_max = (int)(k + s.m2cap / 64 + 1);
-    if (bv && na) {   // the heads leave their graphs' numbering, as in translate_heads
-        KS_CHECK(hipMemcpyAsync(d_goff, bv->arc_goff, (bv->ng + 1) * 8, hipMemcpyHostToDevice, st));
-        KS_CHECK(hipMemcpyAsync(d_base, bv->off, (bv->ng + 1) * 8, hipMemcpyHostToDevice, st));
-        KS_CHECK(sched_translate_node_heads((ks_node_arc*)d_arcs, (int)na, d_goff, (const long long*)d_base, (int)bv->ng,
-                                            u.ctl, st));
-    }
+    rc = bv && na ? translate_heads<ks_node_arc>(s, *bv, d_goff, d_base, d_arcs, na, &u.ctl->bad_range, err) : KS_OK;
+    if (rc) return rc;
     // ---- 1. ids, heads, the diff and the unlisted arcs: one sync
     KS_CHECK(sched_nod_check(d, u, walk, st));
     if (walk) {
@@ -1526,18 +1531,7 @@ int Engine::update_nodes(int flags, const uint64_t* nodes, size_t k, const uint6
     auto tail_of = [&](size_t j) {   // the last i with arc_off[i] ≤ j
         return (size_t)(std::upper_bound(arc_off, arc_off + k, (uint64_t)j) - arc_off) - 1;
     };
-    if (bv && h.bad_range) {   // (the host's arcs are still graph-local: the device translated its own copy)
-        size_t j;
-        if (!first_bad(h.bad_range, na, &j) || j >= na) {
-            err = "inconsistent arc index";
-            return KS_E_DEVICE;
-        }
-        const size_t g = (size_t)(std::upper_bound(bv->arc_goff, bv->arc_goff + bv->ng, (uint64_t)j) - bv->arc_goff) - 1;
-        err = id_name(bv, "node", nodes[tail_of(j)]) + ": head " + std::to_string(arcs[j].dst) +
-              " is outside the graph's ids 1.." + std::to_string(bv->off[g + 1] - bv->off[g]) +
-              " (its highest id at the load plus the reserved ids)";
-        return KS_E_RANGE;
-    }
+    if (bv && h.bad_range) return range_refusal(*bv, h.bad_range, "node", nodes, arc_off, k, arcs, na, err);
     if (h.bad_node) {
         size_t i;
         if (!first_bad(h.bad_node, k, &i)) {

@@ -270,10 +270,14 @@ hipError_t sched_cell_sinks(const SchedDev& d, long long nst, const int* cell_fi
                             hipStream_t st);
 // A batch call's listed arcs, the graphs' lists back to back (graph g owns the arcs
 // [arc_goff[g], arc_goff[g + 1]) and the union ids (base[g], base[g + 1]]): one lane per arc
-// finds its graph by bisection, checks 1 ≤ dst ≤ span (else ctl->bad_range, and the head
-// becomes 0) and adds the graph's base in place.
-hipError_t sched_translate_heads(ks_task_arc* arcs, int na, const unsigned long long* arc_goff, const long long* base,
-                                 int ng, AddCtl* ctl, hipStream_t st);
+// finds its graph by bisection, checks 1 ≤ dst ≤ span (else *bad_range, the call's control word
+// of that name, and the head becomes 0) and adds the graph's base in place. Only the dst word of a
+// record is read and written: the 16-byte arcs of the task lists and the 24-byte arcs of the
+// node lists (whose cost and capacity are the host's to check) go through the same kernel
+// (Arc: ks_task_arc or ks_node_arc, instantiated in ks_sched.hip).
+template <class Arc>
+hipError_t sched_translate_heads(Arc* arcs, int na, const unsigned long long* arc_goff, const long long* base, int ng,
+                                 int* bad_range, hipStream_t st);
 
 // The aggregator flags (ids: nu node ids, or nullptr for every type-0 node with an arc into the
 // sink) into a.fl; the head pass, one lane per arc (head and cost checks, t_agg, agg_cnt with one
@@ -507,10 +511,6 @@ struct NodDev {
     NodCtl* ctl;
 };
 
-// sched_translate_heads for the 24-byte arcs of a batch call's node lists: only the dst word of
-// each record is read and written (ctl->bad_range, and an offending head becomes 0).
-hipError_t sched_translate_node_heads(ks_node_arc* arcs, int na, const unsigned long long* arc_goff, const long long* base,
-                                      int ng, NodCtl* ctl, hipStream_t st);
 // The tail seed, one lane per id (liveness, type, the claim of n_own, n_slot, nch; walk: the id
 // must lie in the built CSR, whose segments are walked), then the listed-arc pass, one lane per
 // arc (the head against its tail's type, the index lookup, the table's row: l_slot, lflag, sflag

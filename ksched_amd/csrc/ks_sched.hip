@@ -810,34 +810,18 @@ __global__ void k_cell_sinks(long long nst, const unsigned char* __restrict__ al
 // The listed arcs of a batch call leave their graphs' own ids: arc j belongs to the last graph g
 // with arc_goff[g] ≤ j (a graph without arcs shares its offset with its successor, which owns
 // the arc). A head outside 1..span is reported (the first in input order wins) and becomes 0,
-// which the head pass refuses as well; every other head gets its graph's base.
-__global__ void k_translate_heads(ks_task_arc* __restrict__ arcs, int na, const unsigned long long* __restrict__ arc_goff,
-                                  const long long* __restrict__ base, int ng, AddCtl* __restrict__ ctl) {
+// which the head pass refuses as well; every other head gets its graph's base. Arc: ks_task_arc
+// or the 24-byte ks_node_arc of ks_batch_update_nodes; only the dst word of a record is read and
+// written, and only an offending lane touches the call's control word.
+template <class Arc>
+__global__ void k_translate_heads(Arc* __restrict__ arcs, int na, const unsigned long long* __restrict__ arc_goff,
+                                  const long long* __restrict__ base, int ng, int* __restrict__ bad_range) {
     for (long long j = blockIdx.x * (long long)SB + threadIdx.x; j < na; j += (long long)gridDim.x * SB) {
         const int g = task_of_arc(arc_goff, ng, j);
         const unsigned long long span = (unsigned long long)(base[g + 1] - base[g]);
         const unsigned long long dst = arcs[j].dst;
         if (dst < 1 || dst > span) {
-            atomicMax(&ctl->bad_range, (int)(na - j));
-            arcs[j].dst = 0;
-        } else {
-            arcs[j].dst = dst + (unsigned long long)base[g];
-        }
-    }
-}
-
-// The same for the 24-byte arcs of ks_batch_update_nodes: only the dst word of a record is read
-// and written (its cost and capacity are the host's to check), and only an offending lane
-// touches the control word.
-__global__ void k_translate_node_heads(ks_node_arc* __restrict__ arcs, int na,
-                                       const unsigned long long* __restrict__ arc_goff,
-                                       const long long* __restrict__ base, int ng, NodCtl* __restrict__ ctl) {
-    for (long long j = blockIdx.x * (long long)SB + threadIdx.x; j < na; j += (long long)gridDim.x * SB) {
-        const int g = task_of_arc(arc_goff, ng, j);
-        const unsigned long long span = (unsigned long long)(base[g + 1] - base[g]);
-        const unsigned long long dst = arcs[j].dst;
-        if (dst < 1 || dst > span) {
-            atomicMax(&ctl->bad_range, (int)(na - j));
+            atomicMax(bad_range, (int)(na - j));
             arcs[j].dst = 0;
         } else {
             arcs[j].dst = dst + (unsigned long long)base[g];
@@ -1664,19 +1648,16 @@ hipError_t sched_cell_sinks(const SchedDev& d, long long nst, const int* cell_fi
     return hipGetLastError();
 }
 
-hipError_t sched_translate_heads(ks_task_arc* arcs, int na, const unsigned long long* arc_goff, const long long* base,
-                                 int ng, AddCtl* ctl, hipStream_t st) {
+template <class Arc>
+hipError_t sched_translate_heads(Arc* arcs, int na, const unsigned long long* arc_goff, const long long* base, int ng,
+                                 int* bad_range, hipStream_t st) {
     if (na > 0 && ng > 0)
-        hipLaunchKernelGGL(k_translate_heads, dim3(grid(na)), dim3(SB), 0, st, arcs, na, arc_goff, base, ng, ctl);
+        hipLaunchKernelGGL(k_translate_heads<Arc>, dim3(grid(na)), dim3(SB), 0, st, arcs, na, arc_goff, base, ng,
+                           bad_range);
     return hipGetLastError();
 }
-
-hipError_t sched_translate_node_heads(ks_node_arc* arcs, int na, const unsigned long long* arc_goff, const long long* base,
-                                      int ng, NodCtl* ctl, hipStream_t st) {
-    if (na > 0 && ng > 0)
-        hipLaunchKernelGGL(k_translate_node_heads, dim3(grid(na)), dim3(SB), 0, st, arcs, na, arc_goff, base, ng, ctl);
-    return hipGetLastError();
-}
+template hipError_t sched_translate_heads(ks_task_arc*, int, const unsigned long long*, const long long*, int, int*, hipStream_t);
+template hipError_t sched_translate_heads(ks_node_arc*, int, const unsigned long long*, const long long*, int, int*, hipStream_t);
 
 hipError_t sched_add_totals(const AddDev& a, hipStream_t st) {
     hipLaunchKernelGGL(k_add_totals, dim3(1), dim3(64), 0, st, a);
