@@ -45,6 +45,8 @@ def solve_and_check(ctx, g, cost, flow, check_flows=True):
     # recovery may run unless a test injects the fault
     if not ctx.opts.fault_inject:
         assert r.raw["recoveries"] == 0, "the optimality certificate needed a repair"
+        # nor may a cell that gave up be re-solved on the engine behind a KS_OK with solver == 1
+        assert r.raw["cell_fallbacks"] == 0, "a cell did not converge and the engine re-solved it"
     if check_flows:
         fl = flows_by_arc(ctx, g)
         st, c2, _ = ko.verify(g, fl)
