@@ -23,9 +23,9 @@ class block):
   * general digraphs without a hub and without a chunked node, and one with
     several hubs.
 """
-import numpy as np
 import pytest
 
+from engine_shapes import WPB, WPW, layout as engine_layout   # the rules, restated beside their source lines
 from graphs import random_graphs, random_hub_graphs
 from ksched_amd import gen, native
 from oracle import ko
@@ -36,18 +36,13 @@ pytestmark = pytest.mark.gpu
 QUINCY = [(600, 100, 5, 10), (2000, 200, 10, 20), (2000, 100, 5, 20), (1000, 100, 5, 10), (3300, 50, 50, 500)]
 OPTS = [{"compact_pos": cp, "two_hop": th} for cp in (0, -1) for th in (1, 2)]
 
-HEAVY_MIN = 4096        # ks_engine_impl.h: degree above → hub
-WIN_SLOTS = (32, 16, 8, 4, 1)   # node slots per window of the 4-, 8-, 16-, 32- and 64-lane classes
-WINDOWS_PER_BLOCK = 8   # WPW · WPB
+WINDOWS_PER_BLOCK = WPW * WPB   # 8
 
 
 def layout(g):
-    """(class windows, chunked nodes, hubs) of g by the engine's class rules."""
-    deg = np.bincount(g.src - 1, minlength=g.n) + np.bincount(g.dst - 1, minlength=g.n)
-    cls = np.searchsorted([4, 8, 16, 32, 64, HEAVY_MIN], deg, side="left")   # degree_class
-    ncls = np.bincount(cls, minlength=7)
-    windows = sum(-(-int(ncls[c]) // WIN_SLOTS[c]) for c in range(5))
-    return windows, int(ncls[5]), int(ncls[6])
+    """(class windows that hold a node, chunked nodes, hubs) of g by the engine's class rules."""
+    L = engine_layout(g)
+    return sum(L.occupied), L.ncls[5], L.nheavy
 
 
 @pytest.fixture(scope="module")
@@ -86,6 +81,10 @@ def test_the_shapes_sit_on_the_boundaries(corpus):
     assert by["quincy(1000, 100, 5, 10)"][0] % WINDOWS_PER_BLOCK != 0
     w, chunked, hubs = by["quincy(3300, 50, 50, 500)"]
     assert chunked > -(-w // WINDOWS_PER_BLOCK) and hubs == 0
+    # the same two with the windows build() lays out (every class padded to whole 64-node blocks)
+    full = {name: engine_layout(g) for name, g, _, _, _ in corpus}
+    assert full["quincy(1000, 100, 5, 10)"].class_windows % WINDOWS_PER_BLOCK != 0
+    assert full["quincy(3300, 50, 50, 500)"].ncls[5] > full["quincy(3300, 50, 50, 500)"].sweep_cls_blocks
     assert by["random-small"][2] == 0      # no hub
     assert by["random-large"][1] == 0      # no chunked node
     assert by["random-hubs"][2] >= 2
